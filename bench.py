@@ -21,6 +21,9 @@ Extra objects in that line:
                  recipe that recomputes every number from profiles/r3_*.
   cpu_baseline - the CPU oracle (torch-CPU restatement of the reference step,
                  oracle/) timed on the host cores of this box on a bounded sample.
+
+--dump-outputs DIR writes what the last timed step handed its caller, as float32 .npy files (rank 0; see dump_outputs).
+The inputs (weights, batch, labels) are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -378,6 +381,50 @@ def cpu_baseline(counts, sample_bs, steps, device=None):
     return out
 
 
+DUMP_SAMPLE = 4 << 20            # elements kept of each flattened whole-network array (parameters, momentum)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _seeded_sample(flat, k, seed=0):
+    """A fixed sample of ``k`` elements of a 1-d tensor, in index order (the whole tensor if it has at most ``k``): the same
+    indices for the same length on every run."""
+    n = flat.numel()
+    if n <= k:
+        return flat
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, net, loss, logits):
+    """What the timed step returns or leaves behind, after the last timed step, as float32 .npy files under ``path``:
+        loss.npy         the step's loss (1 element)
+        logits.npy       the step's logits, [batch, classes]
+        params.npy       the parameters after the fused SGD update, flattened in parameters() order (reference shapes)
+        momentum.npy     the SGD momentum buffers, same order and indices as params.npy
+        bn_running.npy   every BN running mean / variance, concatenated in state_dict() order
+    params / momentum hold a fixed seeded sample of DUMP_SAMPLE elements when the network has more parameters."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    with torch.no_grad():
+        params = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+        mom = torch.cat([s["momentum_buffer"].reshape(-1) for _, s in sorted(net.optimizer_state_dict(0.0)["state"].items())])
+        running = [v.reshape(-1) for k, v in net.state_dict().items() if "running_" in k and v.is_floating_point()]
+        arrays = {
+            "loss": loss.detach().reshape(1),
+            "logits": logits.detach(),
+            "params": _seeded_sample(params, DUMP_SAMPLE),
+            "momentum": _seeded_sample(mom, DUMP_SAMPLE),
+            "bn_running": torch.cat(running) if running else torch.zeros(0),
+        }
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB (limit %d MB)" % (total / 2.0 ** 20, DUMP_LIMIT_BYTES >> 20))
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return total
+
+
 def _self_launch(args):
     """Parent of a multi-GPU run started without torchrun: checks that the GPUs are there, spawns
     ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N bench.py <same arguments>`` as a child process, passes its
@@ -432,7 +479,11 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the measured path); gloo only to rehearse N ranks on one GPU")
     ap.add_argument("--device-index", type=int, default=None, help="put every rank on this GPU (rehearsal only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as the driver types it: start the N ranks as a CHILD torch.distributed.run and relay rank
@@ -512,11 +563,11 @@ def main():
 
     def step(it):
         lr = 0.1 * (1e-3 * (1 - min(it, 1000) / 1000.0) + min(it, 1000) / 1000.0)      # train.py:52-56 warm-up
-        loss, _ = net.loss_and_backward(x, y, crit, reducer=reducer)
+        loss, logits = net.loss_and_backward(x, y, crit, reducer=reducer)
         net.sgd_step(lr, 0.9, 1e-4, grad_scale=scale)
         if args.trace_loss:
             trace.append(loss.clone())
-        return loss
+        return loss, logits
 
     def note(msg):
         if rank == 0:
@@ -555,7 +606,7 @@ def main():
         if timer is not None:
             timer.active = it % max(args.event_every, 1) == 0
             timer.sampled_steps += 1 if timer.active else 0
-        loss = step(args.warmup + it)
+        loss, logits = step(args.warmup + it)
     t_enq = time.perf_counter() - t0          # the host is done enqueueing (close to dt: the step is bound by the host's launch rate)
     torch.cuda.synchronize()
     if world > 1:
@@ -572,6 +623,9 @@ def main():
     note("timed region: %.3f s for %d steps" % (dt, args.steps))
     if trace:
         note("loss trace: " + " ".join("%.4f" % t.item() for t in trace))
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, net, loss, logits)
+        note("outputs of the last timed step: %.1f MB -> %s" % (nbytes / 2.0 ** 20, args.dump_outputs))
 
     if rank == 0:
         out = {
