@@ -1,6 +1,7 @@
-"""IIF classifier loss and mixup — host-side mirror of the reference's
-``classification/custom.py`` (IIFLoss :6-39, Mixup :91-117) over the fused
-gfx950 kernel ``iif_ce_fwd_bwd``.
+"""IIF classifier loss, sigmoid BCE / focal loss and mixup — host-side mirror of
+the reference's ``classification/custom.py`` (IIFLoss :6-39, FocalLoss :42-89,
+Mixup :91-117) over the fused gfx950 kernels ``iif_ce_fwd_bwd`` and
+``iif_sigmoid_focal_fwd_bwd``.
 
 Same constructor, attributes (``.iif`` dict of float32 ``[1, C]`` tables,
 ``.variant``, ``.reduction``) and call signature as the reference, so
@@ -253,13 +254,114 @@ def scale_logits(pred, table):
     return out
 
 
+def _launch_focal(pred, ta, tb, lam, weights, gamma, alpha, scale, want_grad):
+    """One launch of the fused sigmoid BCE / focal kernel.  Returns (loss, dlogits-or-None)."""
+    _lib.require_gpu(pred, ta, tb, weights)
+    if pred.dim() != 2:
+        raise ValueError("logits must be [B, C], got %s" % (tuple(pred.shape),))
+    if pred.stride(1) != 1:
+        pred = pred.contiguous()
+    B, C = pred.shape
+    if weights is not None and weights.numel() != C:
+        raise ValueError("class weights have %d entries, logits have %d classes" % (weights.numel(), C))
+    dlogits = torch.empty((B, C), dtype=pred.dtype, device=pred.device) if want_grad else None
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)          # written by the kernel (0 for B == 0)
+    rows, ticket, status = _workspace(pred.device, B, False)
+    ta = ta.to(torch.int64).contiguous()
+    tb = None if tb is None else tb.to(torch.int64).contiguous()
+    cw = None if weights is None else weights.to(torch.float32).reshape(-1).contiguous()
+    rc = _lib.lib().iif_sigmoid_focal_fwd_bwd(
+        _lib.ptr(pred), _lib.dtype_code(pred), pred.stride(0) if B else C, _lib.ptr(ta), _lib.ptr(tb), float(lam),
+        _lib.ptr(cw), float(gamma), 1 if alpha else 0, float(alpha or 0.0), float(scale), B, C, _lib.ptr(rows),
+        _lib.ptr(loss), _lib.ptr(dlogits), C, _lib.ptr(status), _lib.ptr(ticket), _lib.stream_ptr())
+    _lib.check(rc, "iif_sigmoid_focal_fwd_bwd", ticket[:1])
+    return loss, dlogits
+
+
+class _FusedSigmoidFocal(torch.autograd.Function):
+    """Scalar sigmoid BCE / focal loss from ONE launch; d(loss)/d(logits) comes out of the same launch and backward
+    only multiplies it by the upstream scalar (device-side, no host sync)."""
+
+    @staticmethod
+    def forward(ctx, pred, ta, tb, lam, weights, gamma, alpha, scale):
+        loss, dlogits = _launch_focal(pred, ta, tb, lam, weights, gamma, alpha, scale, ctx.needs_input_grad[0])
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        (dlogits,) = ctx.saved_tensors
+        if dlogits is None:
+            return (None,) * 8
+        g = g_loss.to(torch.float32).contiguous()
+        out = torch.empty_like(dlogits)           # the saved gradient stays intact: backward may run twice
+        rc = _lib.lib().iif_scale_by_device_scalar(_lib.ptr(dlogits), _lib.dtype_code(dlogits), dlogits.numel(),
+                                                   _lib.ptr(g), _lib.ptr(out), _lib.stream_ptr())
+        _lib.check(rc, "iif_scale_by_device_scalar")
+        return (out,) + (None,) * 7
+
+
+class FocalLoss(nn.Module):
+    """Drop-in for ``custom.FocalLoss`` (classification/custom.py:42-89) over one launch of
+    ``iif_sigmoid_focal_fwd_bwd``.
+
+    ``gamma == 0`` is sigmoid BCE with logits (``alpha`` ignored, as in the reference); ``gamma > 0`` is the focal
+    loss, with ``alpha_t`` when ``alpha`` is truthy (0 and None mean off).  ``weights`` (per class, ``[C]``) multiply
+    the columns.  ``reduction='sum'`` divides the sum by the batch size; every other value, 'none' included, is the
+    mean over all B*C elements.  Unlike the reference, the loss is exact where sigmoid(x) rounds to 1 in fp32
+    (|x| above ~16.6): nn.BCELoss clamps log(s) at -100 there and its gradient becomes 0 ("Sigmoid BCE /
+    focal head").  The constructor does no device work; tensors must live on the MI355X.
+    """
+
+    def __init__(self, gamma, alpha=None, reduction="mean", device="cuda", weights=None):
+        super().__init__()
+        if gamma < 0:
+            raise ValueError("gamma must be >= 0, got %r" % (gamma,))
+        self.weights = weights.unsqueeze(0) if weights is not None else 1
+        self.gamma = gamma
+        self.alpha = alpha
+        self.reduction = reduction
+
+    def set_weights(self, weights):
+        self.weights = weights.unsqueeze(0)
+
+    def _weights(self, like):
+        w = self.weights
+        if not torch.is_tensor(w):
+            return None
+        if w.device != like.device:
+            w = w.to(like.device)
+            self.weights = w
+        return w
+
+    def scale(self, B, C):
+        """Reduction factor: 1/B for 'sum' (custom.py:68-69, 81-83), 1/(B*C) for everything else."""
+        return 1.0 / B if self.reduction == "sum" else 1.0 / (B * C)
+
+    def _loss(self, pred, ta, tb, lam):
+        _lib.require_gpu(pred)
+        B, C = pred.shape
+        loss = _FusedSigmoidFocal.apply(pred, ta, tb, lam, self._weights(pred), self.gamma, self.alpha,
+                                        self.scale(max(B, 1), C))
+        if B == 0:
+            return loss * float("nan")          # torch: mean (or sum / 0) of an empty batch
+        return loss
+
+    def forward(self, pred, targets):
+        return self._loss(pred, targets, None, 1.0)
+
+    def mixup_loss(self, pred, y_a, y_b, lam):
+        """``lam*L(pred,y_a) + (1-lam)*L(pred,y_b)`` from a single launch."""
+        return self._loss(pred, y_a, y_b, lam)
+
+
 class Mixup(object):
     """Mirror of ``custom.Mixup`` (classification/custom.py:91-117).
 
     ``__call__`` draws ``lam ~ Beta(alpha, alpha)`` from numpy's global RNG and a
     device permutation, as the reference does, and blends the images with one
     native pass.  ``mixup_criterion`` uses the fused two-target kernel when the
-    criterion is an :class:`IIFLoss`.
+    criterion is an :class:`IIFLoss` or a :class:`FocalLoss`.
     """
 
     def __init__(self, criterion, alpha=1):
@@ -274,6 +376,8 @@ class Mixup(object):
 
     def mixup_criterion(self, pred, y_a, y_b, lam):
         if isinstance(self.criterion, IIFLoss):
+            return self.criterion.mixup_loss(pred, y_a, y_b, lam)
+        if isinstance(self.criterion, FocalLoss):
             return self.criterion.mixup_loss(pred, y_a, y_b, lam)
         return lam * self.criterion(pred, y_a) + (1 - lam) * self.criterion(pred, y_b)
 

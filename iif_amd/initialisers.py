@@ -23,8 +23,14 @@ class _UniformTable(object):
 
 def get_criterion(args, dataset, model, num_classes):
     """initialisers.py:22-48.  'iif' -> fused IIFLoss; 'ce' -> the same fused kernel
-    with an all-ones table built by hand (plain softmax cross-entropy); the focal / BCE
-    branches of the reference are outside the hot path."""
+    with an all-ones table built by hand (plain softmax cross-entropy); 'bce' ->
+    FocalLoss(gamma=0) (sigmoid BCE with logits); 'focal_loss' ->
+    FocalLoss(gamma=args.gamma, alpha=args.alpha).  In every branch the class weights
+    are get_weights(dataset) under --deffered and None otherwise.
+
+    The reference's 'focal_loss' branch also passes ``feat_select=args.feat_select``,
+    which neither its parser nor its FocalLoss defines, so it crashes there; this
+    builds the evident intent instead."""
     device = getattr(args, "device", "cuda")
     weight = get_weights(dataset, device) if getattr(args, "deffered", False) else None
     if args.classif == "iif":
@@ -39,8 +45,12 @@ def get_criterion(args, dataset, model, num_classes):
         # (initialisers.py:43-46), unlike IIFLoss whose .mean() divides by the batch size (custom.py:32-33)
         crit.weighted_mean = weight is not None and args.reduction == "mean"
         return crit
-    raise NotImplementedError("criterion %r is outside the IIF hot path (SURVEY §2a: FocalLoss hard-codes CUDA tensors "
-                              "and is used by no config)" % (args.classif,))
+    if args.classif == "bce":
+        return custom.FocalLoss(gamma=0, reduction=args.reduction, device=device, weights=weight)
+    if args.classif == "focal_loss":
+        return custom.FocalLoss(gamma=args.gamma, alpha=args.alpha, reduction=args.reduction, device=device,
+                                weights=weight)
+    raise NotImplementedError("unknown criterion %r (iif, ce, bce, focal_loss)" % (args.classif,))
 
 
 def get_data(args):

@@ -569,13 +569,15 @@ class NativeResNet(nn.Module):
         return {"stem": 0, "blocks": blocks, "head": first(self._head)}
 
     def loss_and_backward(self, x, targets, criterion, targets_b=None, lam=1.0, reducer=None):
-        """forward -> fused IIF loss (writes dlogits in the same pass) -> backward.
+        """forward -> fused IIF loss, or fused sigmoid BCE / focal loss (writes dlogits in the same pass) -> backward.
         Returns (loss 0-dim tensor, logits view).  No autograd involved.  With a
         ``reducer`` the gradient all-reduce is launched bucket by bucket while
         backward is still running."""
-        from .custom import IIFLoss
+        from .custom import FocalLoss, IIFLoss
+        if isinstance(criterion, FocalLoss):
+            return self._focal_loss_and_backward(x, targets, criterion, targets_b, lam, reducer)
         if not isinstance(criterion, IIFLoss):
-            raise TypeError("loss_and_backward needs an iif_amd.custom.IIFLoss criterion")
+            raise TypeError("loss_and_backward needs an iif_amd.custom.IIFLoss or FocalLoss criterion")
         logits = self.run_forward(x, True)
         plan = self._saved
         B, C = x.shape[0], self.num_classes
@@ -603,6 +605,24 @@ class NativeResNet(nn.Module):
             _lib.check(_lib.lib().iif_scale_by_device_scalar(_lib.ptr(plan.dlogits), _lib.IIF_F32, plan.dlogits.numel(),
                                                              _lib.ptr(plan.loss_rescale), _lib.ptr(plan.dlogits),
                                                              _lib.stream_ptr()), "iif_scale_by_device_scalar")
+        plan.backward(reducer)
+        return plan.loss, logits
+
+    def _focal_loss_and_backward(self, x, targets, criterion, targets_b, lam, reducer):
+        """loss_and_backward for a FocalLoss: one launch of iif_sigmoid_focal_fwd_bwd into the plan's loss buffers."""
+        logits = self.run_forward(x, True)
+        plan = self._saved
+        B, C = x.shape[0], self.num_classes
+        cw = criterion._weights(plan.logits)
+        if cw is not None:
+            cw = cw.to(torch.float32).reshape(-1).contiguous()
+        a = criterion.alpha
+        rc = _lib.lib().iif_sigmoid_focal_fwd_bwd(
+            _lib.ptr(plan.logits), _lib.IIF_F32, plan.logits.stride(0), _lib.ptr(targets), _lib.ptr(targets_b),
+            float(lam), _lib.ptr(cw), float(criterion.gamma), 1 if a else 0, float(a or 0.0), criterion.scale(B, C), B, C,
+            _lib.ptr(plan.loss_rows), _lib.ptr(plan.loss), _lib.ptr(plan.dlogits), plan.dlogits.stride(0),
+            _lib.ptr(plan.label_status), _lib.ptr(plan.loss_ticket), _lib.stream_ptr())
+        _lib.check(rc, "iif_sigmoid_focal_fwd_bwd", plan.loss_ticket[:1])
         plan.backward(reducer)
         return plan.loss, logits
 

@@ -91,6 +91,39 @@ int iif_ce_fwd_bwd(const void* logits, int dtype, int64_t ld_logits,
                    void* dlogits, int64_t ld_dlogits, int32_t* d_status, void* d_workspace, void* stream);
 #define IIF_CE_WORKSPACE_BYTES (4 * (1 + 2048))
 
+/* Fused sigmoid BCE / focal loss, forward + gradient in ONE pass over logits.
+ * Replaces classification/custom.py:42-89 (FocalLoss: one-hot targets, sigmoid,
+ * BCELoss / BCEWithLogitsLoss, modulating factor, class weights, alpha_t, reduction)
+ * and custom.py:116-117 (mixup criterion: pass targets_b and lam).
+ *
+ *   y        = one-hot of the row's target,  s = sigmoid(x),  w_c = class_weight[c] (1 if NULL)
+ *   gamma==0: l(x,y) = softplus(x) - x*y                      (alpha ignored, as the reference)
+ *   gamma >0: l(x,y) = BCE(s,y) * (1-p_t)^gamma * alpha_t,   p_t = s*y + (1-s)*(1-y),
+ *             alpha_t = alpha*y + (1-alpha)*(1-y) if use_alpha, else 1
+ *   r_i      = sum_c w_c * ( lam*l(x_ic, [c==ta_i]) + (1-lam)*l(x_ic, [c==tb_i]) )
+ *   loss     = scale * sum_i r_i   (scale = 1/(B*C) for 'mean' / 'none', 1/B for 'sum')
+ *   dlogits[i,c] = scale * d r_i / d logits[i,c]
+ *
+ * The function is evaluated exactly at every |x| (stable softplus forms); the
+ * reference's nn.BCELoss path saturates once sigmoid(x) rounds to 1 in fp32.
+ * logits/dlogits: [B, C] row-major with leading dimensions ld_logits / ld_dlogits
+ * (elements), dtype IIF_F32 or IIF_BF16 (math is fp32; dlogits in the logits'
+ * dtype); both pointers element-aligned.  targets_b == NULL means no mixup (lam
+ * ignored).  class_weight: float[C] or NULL.  gamma >= 0 and finite; 1 and 2 are
+ * evaluated as multiplies.  loss_per_row: float[B] (required; receives r_i).
+ * loss_out: float[1] or NULL.  dlogits may be NULL (loss only).  d_status: int32[1]
+ * or NULL; set to 1 if any target is outside [0,C) (such rows contribute 0; there
+ * is no ignore index).  d_workspace: IIF_CE_WORKSPACE_BYTES with the same contract
+ * as iif_ce_fwd_bwd's (ticket zero on entry and exit, one workspace per stream);
+ * with it the scalar loss comes out of the same launch.  Deterministic (fixed-order
+ * sums, no float atomics).  B == 0 writes a zero loss. */
+int iif_sigmoid_focal_fwd_bwd(const void* logits, int dtype, int64_t ld_logits,
+                              const int64_t* targets_a, const int64_t* targets_b, float lam,
+                              const float* class_weight, float gamma, int use_alpha, float alpha,
+                              float scale, int B, int C, float* loss_per_row, float* loss_out,
+                              void* dlogits, int64_t ld_dlogits, int32_t* d_status, void* d_workspace,
+                              void* stream);
+
 /* out = logits * table.  Replaces classification/custom.py:37-39 (infer=True). */
 int iif_scale_logits(const void* logits, int dtype, int64_t ld_logits, const float* table,
                      int B, int C, void* out, int64_t ld_out, void* stream);
