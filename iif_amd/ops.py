@@ -270,6 +270,20 @@ def sgd_step(params, grads, bufs, lr, momentum, weight_decay, nesterov=False, gr
                              float(weight_decay), 1 if nesterov else 0, float(grad_scale), stream_ptr()), "iif_sgd_step")
 
 
+def rmsprop_step(params, grads, square_avg, lr, alpha, eps, weight_decay, momentum, momentum_buf=None, grad_avg=None,
+                 grad_scale=1.0, d_lr=None):
+    """torch.optim.RMSprop over flat fp32 buffers in one launch.  ``momentum_buf`` is needed iff momentum > 0, and
+    ``grad_avg`` (centered RMSprop) selects the centered variant."""
+    require_gpu(params, grads, square_avg, momentum_buf, grad_avg, d_lr)
+    for t in (params, grads, square_avg, momentum_buf if momentum > 0 else None, grad_avg):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != params.numel()):
+            raise ValueError("rmsprop_step: every buffer must be a contiguous fp32 tensor of params.numel() elements")
+    check(lib().iif_rmsprop_step(ptr(params), ptr(grads), ptr(square_avg), ptr(momentum_buf) if momentum > 0 else 0,
+                                 ptr(grad_avg), params.numel(), float(lr), ptr(d_lr), float(alpha), float(eps),
+                                 float(weight_decay), float(momentum), 1 if grad_avg is not None else 0, float(grad_scale),
+                                 stream_ptr()), "iif_rmsprop_step")
+
+
 # ------------------------------------------------------- cosine / normed heads
 def rowmap_forward(x, mode, scale, out, norms=None, eps=1e-12):
     rows, cols = x.shape

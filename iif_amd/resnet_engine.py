@@ -329,6 +329,11 @@ class NativeResNet(nn.Module):
         self._arena = arena
         self._grad_arena = torch.zeros_like(arena)
         self._mom_arena = torch.zeros_like(arena)
+        # RMSprop state: allocated by the first rmsprop_step (or a loaded RMSprop state); steps per region (whole arena, head)
+        self._sq_arena = None
+        self._gavg_arena = None
+        self._rms_steps = [0, 0]
+        self._optimizer_kind = None     # "sgd" / "rmsprop" once one of them has stepped: the momentum arena means one thing
         # running statistics / counters: flat buffers too
         bns = [m for m in self.modules() if isinstance(m, BNParam)]
         ctot = sum(_round_up(b.num_features, 16) for b in bns)
@@ -477,15 +482,51 @@ class NativeResNet(nn.Module):
         frozen backbone only the classifier's slice (the tail of the arena) is stepped, as
         torch.optim.SGD skips parameters without gradients."""
         self._join_side_work()
+        self._claim_optimizer("sgd")
         lo = self.block_offsets()["head"] if self._head_only else 0
         ops.sgd_step(self._arena[lo:], self._grad_arena[lo:], self._mom_arena[lo:], lr, momentum, weight_decay, nesterov,
                      grad_scale)
+
+    def rmsprop_step(self, lr, alpha=0.9, eps=0.0316, weight_decay=1e-4, momentum=0.9, centered=False, grad_scale=1.0):
+        """torch.optim.RMSprop (classification/train.py:205-207) in ONE launch over the parameter arena, or over the
+        classifier's tail of it with a frozen backbone.  The momentum buffer is the momentum arena; square_avg (and grad_avg
+        when ``centered``) are allocated on the first call, so an SGD run carries none of them."""
+        if not eps > 0:
+            raise ValueError("rmsprop_step: eps must be > 0 (the arena's zero padding lanes would divide 0 by 0), got %r" % (eps,))
+        self._join_side_work()
+        self._claim_optimizer("rmsprop")
+        self._alloc_rmsprop_state(centered)
+        lo = self.block_offsets()["head"] if self._head_only else 0
+        ops.rmsprop_step(self._arena[lo:], self._grad_arena[lo:], self._sq_arena[lo:], lr, alpha, eps, weight_decay, momentum,
+                         momentum_buf=self._mom_arena[lo:],
+                         grad_avg=self._gavg_arena[lo:] if centered else None, grad_scale=grad_scale)
+        self._rms_steps[1 if self._head_only else 0] += 1
+
+    def _claim_optimizer(self, kind):
+        if self._optimizer_kind not in (None, kind):
+            raise RuntimeError("this engine's optimizer state belongs to %s: a %s step would reuse its momentum arena with "
+                               "another meaning (one NativeResNet serves one optimizer)" % (self._optimizer_kind, kind))
+        self._optimizer_kind = kind
+
+    def _alloc_rmsprop_state(self, centered):
+        if self._sq_arena is None:
+            self._sq_arena = torch.zeros_like(self._arena)
+        if centered and self._gavg_arena is None:
+            self._gavg_arena = torch.zeros_like(self._arena)
+
+    def _rmsprop_param_steps(self):
+        """RMSprop steps each parameter (parameters() order) has taken: whole-arena steps, plus head-only ones for the head."""
+        head = self.block_offsets()["head"]
+        return [self._rms_steps[0] + (self._rms_steps[1] if self._offsets[(id(m), attr)][0] >= head else 0)
+                for (m, attr, _, _) in self._param_specs()]
 
     # ------------------------------------------------ optimizer-state interop
     def optimizer_state_dict(self, lr, momentum=0.9, weight_decay=1e-4, nesterov=False, initial_lr=None):
         """The ``torch.optim.SGD.state_dict()`` the reference would have saved (classification/train.py:266-271):
         one param group over ``model.parameters()`` order, ``momentum_buffer`` per parameter taken from the momentum
         arena (as OIHW / reference-shaped tensors), so a reference run can resume from a native checkpoint."""
+        if self._optimizer_kind == "rmsprop":
+            raise RuntimeError("this engine has stepped with RMSprop: its state is rmsprop_state_dict(), not SGD's")
         views = self._arena_views(self._mom_arena)
         state = {i: {"momentum_buffer": v.detach().clone().contiguous().cpu()} for i, v in enumerate(views)}
         group = {"lr": lr, "momentum": momentum, "dampening": 0, "weight_decay": weight_decay, "nesterov": nesterov,
@@ -495,10 +536,62 @@ class NativeResNet(nn.Module):
             group["initial_lr"] = initial_lr
         return {"state": state, "param_groups": [group]}
 
-    def load_optimizer_state_dict(self, sd):
+    def rmsprop_state_dict(self, lr, alpha=0.9, eps=0.0316, weight_decay=1e-4, momentum=0.9, centered=False, initial_lr=None):
+        """The ``torch.optim.RMSprop.state_dict()`` of the same run: one param group over ``model.parameters()`` order; per
+        parameter that has stepped, ``step`` (0-dim float tensor), ``square_avg``, ``momentum_buffer`` (momentum > 0) and
+        ``grad_avg`` (centered) as reference-shaped tensors.  A parameter that never stepped (the backbone after
+        ``select_training_param``) has no entry, as in torch."""
+        if self._optimizer_kind == "sgd":
+            raise RuntimeError("this engine has stepped with SGD: its state is optimizer_state_dict(), not RMSprop's")
+        steps = self._rmsprop_param_steps()
+        if any(steps) and centered and self._gavg_arena is None:
+            raise RuntimeError("rmsprop_state_dict(centered=True) for an engine that stepped without centering")
+        take = lambda a: [v.detach().clone().contiguous().cpu() for v in self._arena_views(a)] if any(steps) else None  # noqa: E731
+        sq = take(self._sq_arena)
+        mom = take(self._mom_arena) if momentum > 0 else None
+        gavg = take(self._gavg_arena) if centered else None
+        state = {}
+        for i, k in enumerate(steps):
+            if k == 0:
+                continue
+            st = {"step": torch.tensor(float(k)), "square_avg": sq[i]}
+            if mom is not None:
+                st["momentum_buffer"] = mom[i]
+            if gavg is not None:
+                st["grad_avg"] = gavg[i]
+            state[i] = st
+        group = {"lr": lr, "momentum": momentum, "alpha": alpha, "eps": eps, "centered": centered,
+                 "weight_decay": weight_decay, "capturable": False, "foreach": None, "maximize": False,
+                 "differentiable": False, "params": list(range(len(steps)))}
+        if initial_lr is not None:
+            group["initial_lr"] = initial_lr
+        return {"state": state, "param_groups": [group]}
+
+    @staticmethod
+    def optimizer_state_kind(sd):
+        """'rmsprop' for a torch.optim.RMSprop state dict (square_avg entries, or an ``alpha`` in its group), else 'sgd'."""
+        if any(isinstance(st, dict) and "square_avg" in st for st in sd.get("state", {}).values()):
+            return "rmsprop"
+        groups = sd.get("param_groups") or [{}]
+        return "rmsprop" if "alpha" in groups[0] else "sgd"
+
+    def load_optimizer_state_dict(self, sd, optimizer=None):
         """Momentum buffers of a reference checkpoint's ``optimizer`` entry -> momentum arena.  Parameters without
         state (never stepped) keep a zero buffer, which is what SGD's lazy initialisation amounts to after step 1
-        only; so a state-less parameter is reported by name."""
+        only; so a state-less parameter is reported by name.  An RMSprop state dict (``square_avg`` entries) fills the
+        RMSprop arenas and step counters instead.  ``optimizer`` ('sgd' / 'nesterov' / 'rmsprop', as ``--opt``): the
+        optimizer the caller will step with; a state dict of the other kind raises."""
+        kind = self.optimizer_state_kind(sd)
+        if optimizer is not None:
+            want = "rmsprop" if optimizer.lower() == "rmsprop" else "sgd"
+            if kind != want:
+                raise ValueError("optimizer state mismatch: the checkpoint holds %s state but the optimizer is %s (--opt %s)"
+                                 % ("RMSprop" if kind == "rmsprop" else "SGD", "RMSprop" if want == "rmsprop" else "SGD",
+                                    optimizer))
+        if kind == "rmsprop":
+            return self._load_rmsprop_state(sd)
+        if any(st is not None and st.get("momentum_buffer") is not None for st in sd["state"].values()):
+            self._claim_optimizer("sgd")
         views = self._arena_views(self._mom_arena)
         missing = []
         with torch.no_grad():
@@ -508,6 +601,39 @@ class NativeResNet(nn.Module):
                     v.zero_(); missing.append(i)
                 else:
                     v.copy_(st["momentum_buffer"].to(v.device))
+        return missing
+
+    def _load_rmsprop_state(self, sd):
+        self._join_side_work()
+        self._claim_optimizer("rmsprop")
+        states = [sd["state"].get(i, sd["state"].get(str(i))) for i in range(len(self._param_specs()))]
+        group = (sd.get("param_groups") or [{}])[0]
+        centered = bool(group.get("centered", False)) or any(st is not None and st.get("grad_avg") is not None
+                                                             for st in states)
+        self._alloc_rmsprop_state(centered)
+        arenas = [("square_avg", self._sq_arena), ("momentum_buffer", self._mom_arena), ("grad_avg", self._gavg_arena)]
+        missing, steps = [], []
+        with torch.no_grad():
+            for key, arena in arenas:
+                if arena is None:
+                    continue
+                for i, v in enumerate(self._arena_views(arena)):
+                    st = states[i]
+                    if st is None or st.get(key) is None:
+                        v.zero_()
+                    else:
+                        v.copy_(st[key].to(v.device))
+        for i, st in enumerate(states):
+            if st is None or st.get("square_avg") is None:
+                missing.append(i)
+                steps.append(0)
+            else:
+                steps.append(int(float(st["step"])))
+        head = self.block_offsets()["head"]
+        is_head = [self._offsets[(id(m), attr)][0] >= head for (m, attr, _, _) in self._param_specs()]
+        body = max([k for k, h in zip(steps, is_head) if not h], default=0)
+        tail = max([k for k, h in zip(steps, is_head) if h], default=0)
+        self._rms_steps = [body, max(tail - body, 0)]
         return missing
 
     def _arena_views(self, arena):

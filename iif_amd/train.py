@@ -8,9 +8,9 @@ main :168-285), running on the native MI355X engine.
 Differences, all forced by the environment or by the MI355X-first design:
   * datasets are synthetic long-tailed sets (no torchvision / network);
   * the step is the fused native one — forward, fused IIF loss (+mixup), backward,
-    bucketed RCCL all-reduce overlapped with backward, ONE fused SGD launch — instead of
+    bucketed RCCL all-reduce overlapped with backward, ONE fused SGD or RMSprop launch — instead of
     autograd + torch.optim + DistributedDataParallel; schedules are evaluated on the host
-    and passed to the kernel, momentum buffers live in the model's momentum arena;
+    and passed to the kernel, optimizer state lives in the model's arenas;
   * metrics are read back every ``--print-freq`` iterations (the reference syncs the host
     three times per iteration, train.py:87-92);
   * new flags: ``--compute-dtype {bf16,f32}``, ``--max-iters``.
@@ -27,6 +27,9 @@ import torch   # noqa: E402
 
 from . import custom, initialisers, resnet_cifar, resnet_pytorch, utils
 from .ddp import broadcast_parameters, sync_buffers
+
+OPTIMIZERS = ("sgd", "nesterov", "rmsprop")
+RMSPROP_ALPHA, RMSPROP_EPS = 0.9, 0.0316            # the reference's RMSprop constants (train.py:205-207)
 
 
 def lr_at(args, epoch, it, iters_per_epoch):
@@ -63,6 +66,7 @@ def train_one_epoch(model, criterion, data_loader, device, epoch, args, reducer=
     header = "Epoch: [{}]".format(epoch)
     n_iters = len(data_loader)
     nesterov = args.opt.lower() == "nesterov"
+    rmsprop = args.opt.lower() == "rmsprop"
     scale = reducer.grad_scale if reducer is not None else 1.0
     mix = custom.Mixup(criterion, alpha=args.mixup) if args.mixup is not None else None
     it = 0
@@ -90,7 +94,10 @@ def train_one_epoch(model, criterion, data_loader, device, epoch, args, reducer=
                 print("bf16 gradient buckets REFUSED (probe: %.2e relative L2 > tolerance); staying with fp32" % worst)
             reducer.begin()
             reducer.finish()
-        model.sgd_step(lr, args.momentum, args.weight_decay, nesterov, grad_scale=scale)
+        if rmsprop:
+            model.rmsprop_step(lr, RMSPROP_ALPHA, RMSPROP_EPS, args.weight_decay, args.momentum, grad_scale=scale)
+        else:
+            model.sgd_step(lr, args.momentum, args.weight_decay, nesterov, grad_scale=scale)
         imgs_since += image.shape[0]
         if it % args.print_freq == 0 or it == n_iters - 1:
             acc1, acc5 = utils.accuracy(output, target, topk=(1, min(5, output.shape[1])))
@@ -154,7 +161,7 @@ def main(args):
     criterion = initialisers.get_criterion(args, dataset, model, num_classes)
     if args.sync_bn and args.distributed:
         model.enable_sync_bn()                # train.py:190-191: batch statistics over all ranks
-    if args.opt.lower() not in ("sgd", "nesterov"):
+    if args.opt.lower() not in OPTIMIZERS:
         raise RuntimeError("Invalid optimizer {}. Only SGD and RMSprop are supported.".format(args.opt))
     if args.decoup:
         model.select_training_param()       # train.py:123-145: classifier-only stage
@@ -167,7 +174,7 @@ def main(args):
         ckpt = torch.load(args.resume, map_location="cpu", weights_only=False)
         model.load_state_dict(ckpt["model"])
         if "optimizer" in ckpt:
-            model.load_optimizer_state_dict(ckpt["optimizer"])
+            model.load_optimizer_state_dict(ckpt["optimizer"], optimizer=args.opt)
         args.start_epoch = ckpt["epoch"] + 1
     if args.load_from:
         model.load_state_dict(torch.load(args.load_from, map_location="cpu", weights_only=False)["model"])
@@ -187,9 +194,14 @@ def main(args):
         best_acc = max(best_acc, acc)
         if args.output_dir:
             nxt = lr_at(args, epoch + 1, 10 ** 9, 10 ** 9)
+            if args.opt.lower() == "rmsprop":
+                opt_sd = model.rmsprop_state_dict(nxt, RMSPROP_ALPHA, RMSPROP_EPS, args.weight_decay, args.momentum, False,
+                                                  initial_lr=args.lr)
+            else:
+                opt_sd = model.optimizer_state_dict(nxt, args.momentum, args.weight_decay, args.opt.lower() == "nesterov",
+                                                    initial_lr=args.lr)
             ckpt = {"model": model.state_dict(),
-                    "optimizer": model.optimizer_state_dict(nxt, args.momentum, args.weight_decay,
-                                                            args.opt.lower() == "nesterov", initial_lr=args.lr),
+                    "optimizer": opt_sd,
                     "lr_scheduler": scheduler_state_dict(args, epoch + 1),
                     "epoch": epoch, "args": args}
             utils.save_on_master(ckpt, os.path.join(args.output_dir, "model_{}.pth".format(epoch)))

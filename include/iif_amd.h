@@ -330,6 +330,23 @@ int iif_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t
                  const float* d_lr, float momentum, float weight_decay, int nesterov,
                  float grad_scale, void* stream);
 
+/* One fused RMSprop update over a flat fp32 arena.  torch.optim.RMSprop
+ * semantics as used at classification/train.py:205-207 (eps 0.0316, alpha 0.9;
+ * zero-initialised state reproduces torch's lazy initialisation):
+ * g = grad_scale*grad + wd*p; sq = alpha*sq + (1-alpha)*g*g;
+ * avg = sqrt(sq - ga*ga) + eps with ga = lerp(ga, g, 1-alpha) if centered, else
+ * sqrt(sq) + eps; momentum > 0: buf = m*buf + g/avg, p -= lr*buf; else
+ * p -= lr*g/avg.  momentum_buf is read only when momentum > 0 and grad_avg only
+ * when centered (NULL otherwise).  d_lr (nullable) overrides lr with a device
+ * scalar.  IIF_EINVAL: n < 0, a required pointer NULL, or lr / eps / alpha /
+ * momentum / weight_decay negative or not finite (checked before n == 0, which
+ * is IIF_OK); IIF_EUNSUPPORTED: an arena pointer not 16-byte aligned. */
+int iif_rmsprop_step(float* params, const float* grads, float* square_avg,
+                     float* momentum_buf, float* grad_avg,
+                     int64_t n, float lr, const float* d_lr, float alpha, float eps,
+                     float weight_decay, float momentum, int centered,
+                     float grad_scale, void* stream);
+
 /* Cosine / normed classifier heads (resnet_cifar.py:38-78 CosNorm_Classifier,
  * NormedLinear; mmdet normed_predictor.py).  Row maps and their backward; the
  * products run on iif_conv_igemm / iif_conv_wgrad.
