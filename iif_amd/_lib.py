@@ -31,6 +31,7 @@ SIGNATURES = {
     "iif_scale_logits": [_P, _I, _L, _P, _I, _I, _P, _L, _P],
     "iif_softmax": [_P, _I, _L, _P, _I, _I, _P, _L, _P],
     "iif_topk_hits": [_P, _I, _L, _P, _P, _I, _I, _P, _I, _P, _P],
+    "iif_eval_accumulate": [_P, _I, _L, _P, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P],
     "iif_scale_by_device_scalar": [_P, _I, _L, _P, _P, _P],
     "iif_mix_rows": [_P, _I, _P, _F, _I, _L, _P, _P],
     "iif_conv_igemm": [_P, _P, _P, _P, _P, _P, _P],

@@ -113,7 +113,9 @@ def train_one_epoch(model, criterion, data_loader, device, epoch, args, reducer=
             break
 
 
-def evaluate(model, criterion, data_loader, device, print_freq=100):
+def evaluate(model, criterion, data_loader, device, print_freq=100, stats=None, train_targets=None):
+    """``stats`` (an eval_stats.EvalAccumulator, --shot-acc / --calibration-bins): also fed every batch, then reduced over
+    the ranks and reported after the accuracy line (the shot split when ``train_targets`` is given)."""
     model.eval()
     logger = utils.MetricLogger(delimiter="  ")
     with torch.no_grad():
@@ -124,12 +126,37 @@ def evaluate(model, criterion, data_loader, device, print_freq=100):
             if hasattr(criterion, "iif"):
                 output = criterion(output, infer=True)
             acc1, acc5 = utils.accuracy(output, target, topk=(1, min(5, output.shape[1])))
+            if stats is not None:
+                stats.update(output, target)
             n = image.shape[0]
             logger.meters["acc1"].update(acc1.item(), n=n)
             logger.meters["acc5"].update(acc5.item(), n=n)
     logger.synchronize_between_processes()
     print(" * Acc@1 {top1.global_avg:.3f} Acc@5 {top5.global_avg:.3f}".format(top1=logger.acc1, top5=logger.acc5))
+    if stats is not None:
+        report_eval_stats(stats, train_targets)
     return logger.acc1.global_avg
+
+
+def make_eval_stats(args, num_classes):
+    """The accumulator of --shot-acc / --calibration-bins, or None when neither is set (the evaluation of the reference)."""
+    if not (getattr(args, "shot_acc", False) or getattr(args, "calibration_bins", 0)):
+        return None
+    from .eval_stats import EvalAccumulator
+    return EvalAccumulator(num_classes, topk=(1, min(5, num_classes)), num_bins=args.calibration_bins, device=args.device)
+
+
+def report_eval_stats(stats, train_targets):
+    stats.synchronize_between_processes()
+    r = stats.result(train_targets=train_targets)
+    stats.reset()
+    if r["shot"] is not None:
+        many, median, low = r["shot"]
+        print(f"Many shot Acc is: {many}, median shot Acc is: {median}, low shot Acc is: {low}")
+    if r["calibration"] is not None:
+        cal = r["calibration"]
+        print("ECE is: {}, MCE is: {} ({} bins)".format(cal["expected_calibration_error"], cal["max_calibration_error"],
+                                                        stats.num_bins))
 
 
 def build_model(args, num_classes):
@@ -178,8 +205,10 @@ def main(args):
         args.start_epoch = ckpt["epoch"] + 1
     if args.load_from:
         model.load_state_dict(torch.load(args.load_from, map_location="cpu", weights_only=False)["model"])
+    stats = make_eval_stats(args, num_classes)
+    shot_targets = dataset.targets if getattr(args, "shot_acc", False) else None
     if args.test_only:
-        evaluate(model, criterion, data_loader_test, device=device)
+        evaluate(model, criterion, data_loader_test, device=device, stats=stats, train_targets=shot_targets)
         return
     print("Start training")
     start_time = time.time()
@@ -190,7 +219,7 @@ def main(args):
         train_one_epoch(model, criterion, data_loader, device, epoch, args, reducer)
         if args.distributed:
             sync_buffers(model)               # rank 0's BN statistics everywhere, as DDP's broadcast_buffers
-        acc = evaluate(model, criterion, data_loader_test, device=device)
+        acc = evaluate(model, criterion, data_loader_test, device=device, stats=stats, train_targets=shot_targets)
         best_acc = max(best_acc, acc)
         if args.output_dir:
             nxt = lr_at(args, epoch + 1, 10 ** 9, 10 ** 9)
@@ -268,6 +297,10 @@ def get_args_parser(add_help=True):
                    help="reduce bf16 copies of the gradient buckets (refused unless the first step's probe stays in tolerance)")
     p.add_argument("--max-iters", default=0, type=int, help="stop each epoch after this many iterations (0 = all)")
     p.add_argument("--synthetic-scale", dest="synthetic_scale", default=1.0, type=float)
+    p.add_argument("--shot-acc", dest="shot_acc", action="store_true",
+                   help="after each evaluation also print the many / median / low-shot accuracy (per_shot_acc.shot_acc)")
+    p.add_argument("--calibration-bins", dest="calibration_bins", default=0, type=int,
+                   help="after each evaluation also print ECE / MCE over this many reliability bins (0 = off)")
     return p
 
 

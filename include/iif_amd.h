@@ -142,6 +142,20 @@ int iif_topk_hits(const void* logits, int dtype, int64_t ld_logits, const float*
                   const int64_t* targets, int B, int C, const int32_t* k_host, int nk,
                   int32_t* hits, void* stream);
 
+/* Evaluation statistics of logits*table (table NULL = raw logits), accumulated into acc (int64, device,
+ * zeroed by the caller, layout below).  One read of each row.  Integer atomics only => exact and
+ * independent of launch order, batch split and rank count.  nk <= 4; 1 <= nb <= 256.
+ * bin_edges: device float64[nb+1], ascending (the caller passes np.linspace(0, 1, nb+1)).
+ * pred_out (int64[B]) and conf_out (float[B]) are optional per-row outputs.
+ * acc = [rows | out_of_range | hits_k[nk] | n_test[C] | n_hit[C] | bin_count[nb] | bin_hit[nb] | bin_conf[nb]]:
+ * rank of the target as iif_topk_hits; prediction = first index of the maximum (torch.argmax); confidence = the
+ * softmax maximum; bin b holds edges[b] < conf <= edges[b+1] (np.digitize(..., right=True)); bin_conf sums
+ * llrint(conf * 2^32).  A target outside [0, C) counts in rows, out_of_range and the bins (as a miss) only. */
+int iif_eval_accumulate(const void* logits, int dtype, int64_t ld_logits, const float* table,
+                        const int64_t* targets, int B, int C, const int32_t* k_host, int nk,
+                        const double* bin_edges, int nb, int64_t* acc,
+                        int64_t* pred_out, float* conf_out, void* stream);
+
 /* out[i] = x[i] * *d_scalar (device scalar; out may alias x).  Used by the autograd
  * bridge to apply the upstream gradient of the scalar loss without a host sync. */
 int iif_scale_by_device_scalar(const void* x, int dtype, int64_t n, const float* d_scalar, void* out, void* stream);
