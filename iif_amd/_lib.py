@@ -114,6 +114,7 @@ SIGNATURES = {
     "iif_rowmap_backward": [_P, _I, _P, _P, _I, _I, _I, _L, _L, _I, _F, _F, _P, _I, _L, _P],
     "iif_transpose_f32": [_P, _I, _I, _L, _P, _L, _P],
     "iif_dot_window_f32": [_P, _P, _I, _I, _L, _L, _F, _P, _P, _P],
+    "iif_cifar_augment": [_P, _L, _P, _P, _L, _L, _c.c_uint64, _L, _L, _c.c_uint32, _P, _P, _P, _P, _P],
 }
 
 

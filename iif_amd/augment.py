@@ -122,12 +122,16 @@ def _affine(img, a, b, c, d, e, f, fill=128.0 / 255.0):
     return torch.where(ok.unsqueeze(0), out, torch.full_like(out, fill))
 
 
-def _rotate(img, deg):
-    _, h, w = img.shape
+def _rotate_coefficients(h, w, deg):
     t = -math.radians(deg)
     cx, cy = w / 2.0, h / 2.0
     a, b, d, e = math.cos(t), math.sin(t), -math.sin(t), math.cos(t)
-    return _affine(img, a, b, cx - a * cx - b * cy, d, e, cy - d * cx - e * cy)
+    return a, b, cx - a * cx - b * cy, d, e, cy - d * cx - e * cy
+
+
+def _rotate(img, deg):
+    _, h, w = img.shape
+    return _affine(img, *_rotate_coefficients(h, w, deg))
 
 
 def _u8(img):
@@ -187,21 +191,37 @@ def _ranges():
     }
 
 
+GEOMETRIC = ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate")
+
+
+def affine_coefficients(name, m, sign, h, w):
+    """(a, b, c, d, e, f) of ``_affine`` for a geometric operation at magnitude value ``m`` and sign +-1.0, in double."""
+    if name == "ShearX":
+        return 1.0, m * sign, 0.0, 0.0, 1.0, 0.0
+    if name == "ShearY":
+        return 1.0, 0.0, 0.0, m * sign, 1.0, 0.0
+    if name == "TranslateX":
+        return 1.0, 0.0, m * w * sign, 0.0, 1.0, 0.0
+    if name == "TranslateY":
+        return 1.0, 0.0, 0.0, 0.0, 1.0, m * h * sign
+    if name == "Rotate":
+        return _rotate_coefficients(h, w, m * sign)
+    raise ValueError("%r is not a geometric operation" % (name,))
+
+
 def apply_op(img, name, magnitude_idx, gen=None):
     """One auto-augment operation at magnitude index 0..9 (random sign for the signed ones, as the package draws it)."""
-    m = _ranges()[name][magnitude_idx]
     sign = 1.0 if torch.rand((), generator=gen).item() < 0.5 else -1.0
+    return apply_op_signed(img, name, magnitude_idx, sign)
+
+
+def apply_op_signed(img, name, magnitude_idx, sign):
+    """``apply_op`` with its sign given (+1.0 / -1.0) instead of drawn; the device pipeline (iif_amd/cifar.py) draws the
+    sign itself and its test oracle replays it through here."""
+    m = _ranges()[name][magnitude_idx]
     _, h, w = img.shape
-    if name == "ShearX":
-        return _affine(img, 1.0, m * sign, 0.0, 0.0, 1.0, 0.0)
-    if name == "ShearY":
-        return _affine(img, 1.0, 0.0, 0.0, m * sign, 1.0, 0.0)
-    if name == "TranslateX":
-        return _affine(img, 1.0, 0.0, m * w * sign, 0.0, 1.0, 0.0)
-    if name == "TranslateY":
-        return _affine(img, 1.0, 0.0, 0.0, 0.0, 1.0, m * h * sign)
-    if name == "Rotate":
-        return _rotate(img, m * sign)
+    if name in GEOMETRIC:
+        return _affine(img, *affine_coefficients(name, m, sign, h, w))
     if name == "Color":
         return adjust_saturation(img, 1.0 + m * sign)
     if name == "Contrast":

@@ -57,8 +57,11 @@ def get_data(args):
     """initialisers.py:51-112: returns (dataset, num_classes, train_loader, test_loader, train_sampler).
     With ``--data-path`` the long-tailed sets are read from the reference's list files (``--train-txt`` /
     ``--eval-txt`` default to the paths hard-coded at initialisers.py:83-100) through ``LT_Dataset`` /
-    ``LT_Dataset_Eval``; without it they are synthetic sets of the same shape (no dataset ships with the image)."""
+    ``LT_Dataset_Eval``, and CIFAR-10 / CIFAR-100 from their files through get_cifar_device; without it they are
+    synthetic sets of the same shape (no dataset ships with the image)."""
     name = args.dset_name.lower()
+    if name in ("cifar10", "cifar100") and getattr(args, "data_path", ""):
+        return get_cifar_device(args, name)
     key = {"imagenet": "imagenet_lt", "imagenet_lt": "imagenet_lt", "places_lt": "places_lt", "inat18": "inat18"}.get(name)
     if key is not None and getattr(args, "data_path", ""):
         C, train_txt, eval_txt = imbalanced_dataset.LT_LISTS[key]
@@ -91,3 +94,27 @@ def get_data(args):
     loader_test = torch.utils.data.DataLoader(ds_test, batch_size=args.batch_size, shuffle=False, sampler=test_sampler,
                                               num_workers=args.workers, pin_memory=pin)
     return ds, ds.num_classes, loader, loader_test, sampler
+
+
+def get_cifar_device(args, name):
+    """load_cifar (initialisers.py:116-171) with the whole input pipeline on the device: IMBALANCECIFAR10/100 read from
+    ``--data-path``, the full test file for evaluation, and DeviceCIFARLoader batches built by one kernel launch each -
+    RandomCrop(32, 4) + flip, plus CIFAR10Policy and Cutout(1, 16) under ``--auto-augment cifar``, then Normalize.
+    The loader stands in for the train sampler too (``set_epoch``)."""
+    from . import cifar
+    policy = getattr(args, "auto_augment", None)
+    flags = cifar.CROP_FLIP
+    if policy == "cifar":
+        flags |= cifar.POLICY | cifar.CUTOUT
+    elif policy:
+        import warnings
+        warnings.warn("--auto-augment %r has no CIFAR transform (only 'cifar' does); training with crop and flip, as the "
+                      "reference does" % (policy,))
+    ds = cifar.cifar_lt(args.data_path, name, args.imb_type, args.imb_factor, args.rand_number)
+    ds_test = cifar.cifar_test(args.data_path, name)
+    mode = getattr(args, "sampler", "random")
+    dist = getattr(args, "distributed", False)
+    device = getattr(args, "device", "cuda")
+    loader = cifar.DeviceCIFARLoader(ds, args.batch_size, train=True, flags=flags, mode=mode, distributed=dist, device=device)
+    loader_test = cifar.DeviceCIFARLoader(ds_test, args.batch_size, train=False, flags=0, distributed=dist, device=device)
+    return ds, ds.num_classes, loader, loader_test, loader

@@ -85,7 +85,8 @@ def get_args_parser(add_help=True):
     p = argparse.ArgumentParser(description="Many / median / low-shot accuracy of a checkpoint on MI355X", add_help=add_help)
     p.add_argument("--distributed", default=False)
     p.add_argument("--dset_name", default="imagenet_lt", type=str, help="imagenet_lt|places_lt|inat18|cifar10|cifar100")
-    p.add_argument("--data-path", default="", help="dataset root of the list files; empty = synthetic long-tailed sets")
+    p.add_argument("--data-path", default="", help="dataset root of the list files or of the CIFAR python folders; "
+                   "empty = synthetic long-tailed sets")
     p.add_argument("--auto-augment", default=None)
     p.add_argument("--sampler", default="random", type=str)
     p.add_argument("--iif", default="raw", type=str)

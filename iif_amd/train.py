@@ -6,7 +6,8 @@ main :168-285), running on the native MI355X engine.
     python -m torch.distributed.run --nproc-per-node 8 -m iif_amd.train --model resnet50 --dset_name imagenet_lt ...
 
 Differences, all forced by the environment or by the MI355X-first design:
-  * datasets are synthetic long-tailed sets (no torchvision / network);
+  * without ``--data-path`` the datasets are synthetic long-tailed sets (no torchvision / network); CIFAR-10 / -100
+    with ``--data-path`` are read from their files and augmented on the device (iif_amd/cifar.py);
   * the step is the fused native one — forward, fused IIF loss (+mixup), backward,
     bucketed RCCL all-reduce overlapped with backward, ONE fused SGD or RMSprop launch — instead of
     autograd + torch.optim + DistributedDataParallel; schedules are evaluated on the host
@@ -214,7 +215,7 @@ def main(args):
     start_time = time.time()
     best_acc = 0
     for epoch in range(args.start_epoch, args.epochs):
-        if args.distributed:
+        if args.distributed or hasattr(train_sampler, "set_epoch"):     # the device CIFAR loader re-draws per epoch
             train_sampler.set_epoch(epoch)
         train_one_epoch(model, criterion, data_loader, device, epoch, args, reducer)
         if args.distributed:
@@ -241,7 +242,8 @@ def main(args):
 
 def get_args_parser(add_help=True):
     p = argparse.ArgumentParser(description="IIF classification training on MI355X", add_help=add_help)
-    p.add_argument("--data-path", default="", help="dataset root of the list files; empty = synthetic long-tailed sets")
+    p.add_argument("--data-path", default="", help="dataset root of the list files or of the CIFAR python folders; "
+                   "empty = synthetic long-tailed sets")
     p.add_argument("--train-txt", dest="train_txt", default=None, help="training list (default: the reference's path for --dset_name)")
     p.add_argument("--eval-txt", dest="eval_txt", default=None, help="evaluation list (default: the reference's path)")
     p.add_argument("--image-size", dest="image_size", default=224, type=int)

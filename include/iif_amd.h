@@ -710,6 +710,27 @@ int iif_bn_backward_pool_fused(const void* g_pool, const uint8_t* argmax, const 
                                int h, int w, int c, int ho, int wo, const float* stats, const float* gamma, float* dgamma,
                                float* dbeta, void* dx, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* CIFAR training input (iif_amd/cifar.py DeviceCIFARLoader): ONE launch per batch builds out[b] (fp32 NCHW [batch][3][32][32])
+ * and targets[b] = labels[index[b]] from the device-resident dataset data (uint8 [n][3][32][32], the planar rows of the
+ * CIFAR files) and labels (int64 [n]).  flags select the stages, applied in the reference's order (initialisers.py:116-134):
+ *   IIF_CIFAR_CROP_FLIP  pad 4 with 0, random 32x32 crop, horizontal flip with p 0.5
+ *   IIF_CIFAR_POLICY     on the [0, 1] image, one of the 25 CIFAR10Policy sub-policies of iif_amd/augment.py; policy is the
+ *                        device table of per-(sub-policy, op, sign) constants, uint32 [25][2][2][8] (cifar.policy_table)
+ *   IIF_CIFAR_CUTOUT     Cutout(1, 16): centre uniform in 0..31, the clipped 16x16 box set to 0 before normalisation
+ * then always (x - mean) / std with the reference's CIFAR mean (0.4914, 0.4822, 0.4465) and std (0.2023, 0.1994, 0.2010).
+ * Randomness: a counter-based hash (splitmix64 finaliser) of (seed, epoch, rank, pos0 + b, draw slot): no host RNG, the
+ * same arguments give the same batch.  params (nullable) receives the draws, int32 [batch][10]: crop y, crop x, flip,
+ * sub-policy, op 0 applied, op 0 sign positive, op 1 applied, op 1 sign positive, cutout centre y, x.
+ * An index outside [0, n) reads nothing: out[b] = 0 and targets[b] = -1.
+ * IIF_EINVAL before any launch: a null data / labels / index / out / targets (or policy with IIF_CIFAR_POLICY), n <= 0,
+ * batch < 0, pos0 < 0, unknown flag bits. */
+#define IIF_CIFAR_CROP_FLIP 1u
+#define IIF_CIFAR_POLICY 2u
+#define IIF_CIFAR_CUTOUT 4u
+int iif_cifar_augment(const uint8_t* data, int64_t n, const int64_t* labels, const int64_t* index, int64_t batch,
+                      int64_t pos0, uint64_t seed, int64_t epoch, int64_t rank, uint32_t flags, const uint32_t* policy,
+                      float* out, int64_t* targets, int32_t* params, void* stream);
+
 /* Compute-unit budget of the persistent grids (the weights-in-registers kernels, the stem, the streaming 1x1 kernel size their
  * grids to one or two resident blocks per CU).  Process-wide, default 0 = every CU of the device; a rank whose gradient
  * all-reduce (RCCL kernels, classification/train.py:230-234 DDP) overlaps backward sets e.g. 240 so that the reduction's
