@@ -90,13 +90,19 @@ class ColorJitter(object):
     def __init__(self, brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0):
         self.brightness, self.contrast, self.saturation, self.hue = brightness, contrast, saturation, hue
 
-    def __call__(self, img, gen=None):
-        r = lambda: torch.rand((), generator=gen).item()      # noqa: E731
-        order = torch.randperm(4, generator=gen).tolist()
-        fb = max(0.0, 1.0 - self.brightness) + (1.0 + self.brightness - max(0.0, 1.0 - self.brightness)) * r() if self.brightness else None
-        fc = max(0.0, 1.0 - self.contrast) + (1.0 + self.contrast - max(0.0, 1.0 - self.contrast)) * r() if self.contrast else None
-        fs = max(0.0, 1.0 - self.saturation) + (1.0 + self.saturation - max(0.0, 1.0 - self.saturation)) * r() if self.saturation else None
-        fh = -self.hue + 2.0 * self.hue * r() if self.hue else None
+    def factors(self, rand):
+        """(fb, fc, fs, fh) from the uniform source ``rand`` (called once per property with a non-zero amount, in that
+        order); None for a property whose amount is 0."""
+        def blend(v):
+            return max(0.0, 1.0 - v) + (1.0 + v - max(0.0, 1.0 - v)) * rand() if v else None
+        fb, fc, fs = blend(self.brightness), blend(self.contrast), blend(self.saturation)
+        fh = -self.hue + 2.0 * self.hue * rand() if self.hue else None
+        return fb, fc, fs, fh
+
+    @staticmethod
+    def apply(img, order, fb, fc, fs, fh):
+        """The adjustments in ``order`` (a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue) with the given
+        factors; a None factor skips its adjustment."""
         for k in order:
             if k == 0 and fb is not None:
                 img = adjust_brightness(img, fb)
@@ -107,6 +113,10 @@ class ColorJitter(object):
             elif k == 3 and fh is not None:
                 img = adjust_hue(img, fh)
         return img
+
+    def __call__(self, img, gen=None):
+        order = torch.randperm(4, generator=gen).tolist()
+        return self.apply(img, order, *self.factors(lambda: torch.rand((), generator=gen).item()))
 
 
 # ------------------------------------------------------------------------------------------------ auto-augment operations

@@ -197,14 +197,20 @@ def _mix64(z):
         return z ^ (z >> np.uint64(31))
 
 
+def sample_keys(seed, epoch, rank, positions):
+    """The per-sample hash keys mix(mix(mix(mix(seed) ^ epoch) ^ rank) ^ position), uint64 [len(positions)]; draw slot s of a
+    sample is then mix(key ^ s)."""
+    k = _mix64(np.uint64(seed & _M64))
+    k = _mix64(k ^ np.uint64(epoch & _M64))
+    k = _mix64(k ^ np.uint64(rank & _M64))
+    return _mix64(k ^ np.asarray(positions, dtype=np.int64).reshape(-1).astype(np.uint64))
+
+
 def draw_params(seed, epoch, rank, positions, policy=None):
     """numpy restatement of the kernel's draws: int32 [len(positions), 10] in the order of PARAMS.  ``policy`` (the
     policy_table) supplies the application thresholds; without it the two 'applied' columns are 0, as in a launch without
     POLICY."""
-    k = _mix64(np.uint64(seed & _M64))
-    k = _mix64(k ^ np.uint64(epoch & _M64))
-    k = _mix64(k ^ np.uint64(rank & _M64))
-    key = _mix64(k ^ np.asarray(positions, dtype=np.int64).reshape(-1).astype(np.uint64))
+    key = sample_keys(seed, epoch, rank, positions)
     u = np.stack([_mix64(key ^ np.uint64(s)) >> np.uint64(32) for s in range(len(PARAMS))], axis=1)
     below = lambda v, n: ((v * np.uint64(n)) >> np.uint64(32)).astype(np.int32)     # noqa: E731
     top = lambda v: (v >> np.uint64(31)).astype(np.int32)                             # noqa: E731

@@ -184,10 +184,40 @@ LT_LISTS = {   # initialisers.py:83-100: (classes, train list, eval list) relati
 }
 
 
+# per-dataset Normalize constants and ColorJitter hue (imbalanced_dataset.py:189-233): iNaturalist has its own, the others ImageNet's
+MEAN_STD_HUE = {"inat18": ((0.466, 0.471, 0.380), (0.195, 0.194, 0.192), 0.25)}
+IMAGENET_MEAN_STD_HUE = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225), 0.0)
+
+
+def mean_std_hue(dset_name):
+    return MEAN_STD_HUE.get(dset_name, IMAGENET_MEAN_STD_HUE)
+
+
+def rrc_box(h, w, rand):
+    """RandomResizedCrop's box (scale 0.08-1, ratio 3/4-4/3) on an h x w image: 10 tries, each drawing area and log-ratio
+    from ``rand`` and, when the box fits, its top and left; then the centred min(h, w) square.  Returns (top, left, ch, cw)."""
+    import math
+    for _ in range(10):
+        area = h * w * (0.08 + 0.92 * rand())
+        logr = math.log(3 / 4) + (math.log(4 / 3) - math.log(3 / 4)) * rand()
+        cw, ch = int(round(math.sqrt(area * math.exp(logr)))), int(round(math.sqrt(area / math.exp(logr))))
+        if 0 < cw <= w and 0 < ch <= h:
+            return int(rand() * (h - ch + 1)), int(rand() * (w - cw + 1)), ch, cw
+    ch = cw = min(h, w)
+    return (h - ch) // 2, (w - cw) // 2, ch, cw
+
+
+def eval_geometry(h, w, s):
+    """Resize(256 * s / 224) on the short side + CenterCrop(s): (nh, nw, top, left) of the resized image and the window."""
+    short = int(round(s * 256 / 224))
+    nh, nw = (short, max(int(round(w * short / h)), short)) if h <= w else (max(int(round(h * short / w)), short), short)
+    return nh, nw, (nh - s) // 2, (nw - s) // 2
+
+
 class TensorTransform(object):
     def __init__(self, dset_name, train, size=224, seed=0, auto_augment=None, color_jitter=True):
         from . import augment
-        inat = dset_name == "inat18"
+        mean, std, hue = mean_std_hue(dset_name)
         self.colour = None
         if train:
             if auto_augment == "imagenet":
@@ -204,9 +234,9 @@ class TensorTransform(object):
                     warnings.warn("--auto-augment %r is not a policy of the list datasets (imagenet / randaugment / cifar): "
                                   "ColorJitter stays, as in the reference" % (auto_augment,))
                 if color_jitter:
-                    self.colour = augment.ColorJitter(0.4, 0.4, 0.4, 0.25 if inat else 0.0)
-        self.mean = torch.tensor([0.466, 0.471, 0.380] if inat else [0.485, 0.456, 0.406]).view(3, 1, 1)
-        self.std = torch.tensor([0.195, 0.194, 0.192] if inat else [0.229, 0.224, 0.225]).view(3, 1, 1)
+                    self.colour = augment.ColorJitter(0.4, 0.4, 0.4, hue)
+        self.mean = torch.tensor(mean).view(3, 1, 1)
+        self.std = torch.tensor(std).view(3, 1, 1)
         self.train, self.size = train, size
         # The generator is created lazily, per PROCESS, from torch.initial_seed(): the DataLoader sets that to
         # base_seed + worker_id in every worker and draws a new base_seed every epoch, so workers, epochs and DDP ranks get
@@ -235,32 +265,21 @@ class TensorTransform(object):
         return torch.nn.functional.interpolate(t[None], size=(h, w), mode="bilinear", align_corners=False, antialias=True)[0]
 
     def __call__(self, img):
-        import math
         t = self._to_chw(img)
         _, h, w = t.shape
         s = self.size
         if self.train:                                   # RandomResizedCrop(scale 0.08-1, ratio 3/4-4/3), 10 tries, then flip
             gen = self._generator()
             r = lambda: torch.rand((), generator=gen).item()      # noqa: E731
-            for _ in range(10):
-                area = h * w * (0.08 + 0.92 * r())
-                logr = math.log(3 / 4) + (math.log(4 / 3) - math.log(3 / 4)) * r()
-                cw, ch = int(round(math.sqrt(area * math.exp(logr)))), int(round(math.sqrt(area / math.exp(logr))))
-                if 0 < cw <= w and 0 < ch <= h:
-                    top, left = int(r() * (h - ch + 1)), int(r() * (w - cw + 1))
-                    break
-            else:
-                ch = cw = min(h, w); top, left = (h - ch) // 2, (w - cw) // 2
+            top, left, ch, cw = rrc_box(h, w, r)
             t = self._resize(t[:, top:top + ch, left:left + cw], s, s)
             if r() < 0.5:
                 t = t.flip(-1)
             if self.colour is not None:                  # on the [0, 1] image, before normalisation, as the reference composes it
                 t = self.colour(t.clamp(0.0, 1.0), gen)
         else:                                            # Resize(256 * s / 224) on the short side + CenterCrop(s)
-            short = int(round(s * 256 / 224))
-            nh, nw = (short, max(int(round(w * short / h)), short)) if h <= w else (max(int(round(h * short / w)), short), short)
+            nh, nw, top, left = eval_geometry(h, w, s)
             t = self._resize(t, nh, nw)
-            top, left = (nh - s) // 2, (nw - s) // 2
             t = t[:, top:top + s, left:left + s]
         return (t - self.mean) / self.std
 

@@ -57,12 +57,15 @@ def get_data(args):
     """initialisers.py:51-112: returns (dataset, num_classes, train_loader, test_loader, train_sampler).
     With ``--data-path`` the long-tailed sets are read from the reference's list files (``--train-txt`` /
     ``--eval-txt`` default to the paths hard-coded at initialisers.py:83-100) through ``LT_Dataset`` /
-    ``LT_Dataset_Eval``, and CIFAR-10 / CIFAR-100 from their files through get_cifar_device; without it they are
-    synthetic sets of the same shape (no dataset ships with the image)."""
+    ``LT_Dataset_Eval`` (with ``--device-augment``: batches built on the device, get_lt_device), and CIFAR-10 / CIFAR-100
+    from their files through get_cifar_device; without it they are synthetic sets of the same shape (no dataset ships with
+    the image)."""
     name = args.dset_name.lower()
     if name in ("cifar10", "cifar100") and getattr(args, "data_path", ""):
         return get_cifar_device(args, name)
     key = {"imagenet": "imagenet_lt", "imagenet_lt": "imagenet_lt", "places_lt": "places_lt", "inat18": "inat18"}.get(name)
+    if key is not None and getattr(args, "data_path", "") and getattr(args, "device_augment", False):
+        return get_lt_device(args, key)
     if key is not None and getattr(args, "data_path", ""):
         C, train_txt, eval_txt = imbalanced_dataset.LT_LISTS[key]
         ds, ds_test = imbalanced_dataset.get_dataset_lt(args, C, getattr(args, "train_txt", None) or train_txt,
@@ -117,4 +120,26 @@ def get_cifar_device(args, name):
     device = getattr(args, "device", "cuda")
     loader = cifar.DeviceCIFARLoader(ds, args.batch_size, train=True, flags=flags, mode=mode, distributed=dist, device=device)
     loader_test = cifar.DeviceCIFARLoader(ds_test, args.batch_size, train=False, flags=0, distributed=dist, device=device)
+    return ds, ds.num_classes, loader, loader_test, loader
+
+
+def get_lt_device(args, key):
+    """The list datasets of ``--data-path`` with the input pipeline on the device (``--device-augment``): LT_Dataset /
+    LT_Dataset_Eval only decode, DeviceLTLoader cuts the RandomResizedCrop box on the host and resizes, flips, jitters and
+    normalises each batch in one launch (TensorTransform's pipeline; imbalanced_dataset.py:189-233).  The loader stands in
+    for the train sampler too (``set_epoch``)."""
+    from . import lt_device
+    C, train_txt, eval_txt = imbalanced_dataset.LT_LISTS[key]
+    ds = imbalanced_dataset.LT_Dataset(args.data_path, getattr(args, "train_txt", None) or train_txt, C)
+    ds_test = imbalanced_dataset.LT_Dataset_Eval(args.data_path, getattr(args, "eval_txt", None) or eval_txt, ds.class_map, C)
+    ds.num_classes = len(ds.cls_num_list)
+    size = getattr(args, "image_size", 224)
+    mode = getattr(args, "sampler", "random")
+    dist = getattr(args, "distributed", False)
+    device = getattr(args, "device", "cuda")
+    workers = getattr(args, "workers", 4)
+    loader = lt_device.DeviceLTLoader(ds, args.batch_size, train=True, size=size, dset_name=key, seed=args.rand_number,
+                                      mode=mode, distributed=dist, workers=workers, device=device)
+    loader_test = lt_device.DeviceLTLoader(ds_test, args.batch_size, train=False, size=size, dset_name=key,
+                                           distributed=dist, workers=workers, device=device)
     return ds, ds.num_classes, loader, loader_test, loader

@@ -7,7 +7,8 @@ main :168-285), running on the native MI355X engine.
 
 Differences, all forced by the environment or by the MI355X-first design:
   * without ``--data-path`` the datasets are synthetic long-tailed sets (no torchvision / network); CIFAR-10 / -100
-    with ``--data-path`` are read from their files and augmented on the device (iif_amd/cifar.py);
+    with ``--data-path`` are read from their files and augmented on the device (iif_amd/cifar.py); the list datasets
+    are too with ``--device-augment`` (iif_amd/lt_device.py);
   * the step is the fused native one — forward, fused IIF loss (+mixup), backward,
     bucketed RCCL all-reduce overlapped with backward, ONE fused SGD or RMSprop launch — instead of
     autograd + torch.optim + DistributedDataParallel; schedules are evaluated on the host
@@ -171,7 +172,26 @@ def build_model(args, num_classes):
     raise AttributeError("unknown model %r" % (args.model,))
 
 
+HOST_POLICIES = ("imagenet", "randaugment", "cifar", "cifar10")
+
+
+def check_device_augment(args):
+    """--device-augment builds the list datasets' batches on the device: it needs --data-path and refuses the auto-augment
+    policies, which stay on the host.  CIFAR is built on the device already (the flag changes nothing there)."""
+    if not getattr(args, "device_augment", False):
+        return
+    if not getattr(args, "data_path", ""):
+        raise SystemExit("--device-augment needs --data-path: it builds batches from the dataset's files, and the synthetic "
+                         "sets have none")
+    name = args.dset_name.lower()
+    policy = getattr(args, "auto_augment", None)
+    if not name.startswith("cifar") and policy in HOST_POLICIES:
+        raise SystemExit("--device-augment does not run --auto-augment %s: that policy stays on the host; drop one of the two "
+                         "flags" % (policy,))
+
+
 def main(args):
+    check_device_augment(args)
     if args.output_dir:
         utils.mkdir(args.output_dir)
     utils.init_distributed_mode(args)
@@ -285,6 +305,9 @@ def get_args_parser(add_help=True):
     p.add_argument("--pretrained", dest="pretrained", default=None, type=str)
     p.add_argument("--deffered", action="store_true")
     p.add_argument("--auto-augment", default=None)
+    p.add_argument("--device-augment", dest="device_augment", action="store_true",
+                   help="list datasets with --data-path: resize, flip, ColorJitter and Normalize each batch on the device "
+                   "(iif_amd/lt_device.py) instead of in the DataLoader workers")
     p.add_argument("--random-erase", default=0.0, type=float)
     p.add_argument("--apex", action="store_true")
     p.add_argument("--apex-opt-level", default="O2", type=str)

@@ -731,6 +731,29 @@ int iif_cifar_augment(const uint8_t* data, int64_t n, const int64_t* labels, con
                       int64_t pos0, uint64_t seed, int64_t epoch, int64_t rank, uint32_t flags, const uint32_t* policy,
                       float* out, int64_t* targets, int32_t* params, void* stream);
 
+/* List-dataset input (ImageNet-LT / Places-LT / iNaturalist-18; iif_amd/lt_device.py DeviceLTLoader): ONE launch per batch
+ * builds out[b] (fp32 NCHW [batch][size][size] per channel, 3 channels) from source regions the host decoded and cut out,
+ * in TensorTransform's order (iif_amd/imbalanced_dataset.py):
+ *   antialiased bilinear resize of the region to rh x rw (interpolate(mode="bilinear", antialias=True,
+ *   align_corners=False): triangle filter of support max(scale, 1), window clipped to the region, weights renormalised),
+ *   of which only the size x size window at (oy, ox) is formed; then the horizontal flip of that window;
+ *   IIF_LT_JITTER        on the [0, 1] image (clamped), ColorJitter's brightness / contrast / saturation / hue in the
+ *                        recorded order with the recorded factors (augment.ColorJitter.apply; contrast blends toward the
+ *                        grey mean of the image as it stands when contrast runs; a zero hue shift is skipped)
+ * then always (x - mean) / std.
+ * pool: uint8, every region HWC with 3 channels, packed back to back; pool_bytes its size.
+ * desc: int64 [batch][8] = byte offset in pool, region height, width, rh, rw, oy, ox, flip (non-zero: flipped).
+ * jitter (needed with IIF_LT_JITTER): uint32 [batch][8] = the order (bits 2k..2k+1: the op at position k; 0 brightness,
+ *   1 contrast, 2 saturation, 3 hue), then the fp32 bits of fb, 1 - fb, fc, 1 - fc, fs, 1 - fs, fh.  Factor 1 (and
+ *   1 - f = 0) leaves brightness / contrast / saturation out; fh = 0 leaves hue out.
+ * mean_std: 6 floats in HOST memory, mean then std per channel.
+ * A descriptor that reaches outside the pool, has a non-positive size, or a window outside rh x rw reads nothing: out[b] = 0.
+ * IIF_EINVAL before any launch: a null pool / desc / mean_std / out (or jitter with IIF_LT_JITTER), pool_bytes < 0,
+ * batch < 0, size <= 0 or > 16384, unknown flag bits. */
+#define IIF_LT_JITTER 1u
+int iif_lt_augment(const uint8_t* pool, int64_t pool_bytes, const int64_t* desc, const uint32_t* jitter, int64_t batch,
+                   int size, const float* mean_std, uint32_t flags, float* out, void* stream);
+
 /* Compute-unit budget of the persistent grids (the weights-in-registers kernels, the stem, the streaming 1x1 kernel size their
  * grids to one or two resident blocks per CU).  Process-wide, default 0 = every CU of the device; a rank whose gradient
  * all-reduce (RCCL kernels, classification/train.py:230-234 DDP) overlaps backward sets e.g. 240 so that the reduction's
