@@ -116,6 +116,7 @@ SIGNATURES = {
     "iif_dot_window_f32": [_P, _P, _I, _I, _L, _L, _F, _P, _P, _P],
     "iif_cifar_augment": [_P, _L, _P, _P, _L, _L, _c.c_uint64, _L, _L, _c.c_uint32, _P, _P, _P, _P, _P],
     "iif_lt_augment": [_P, _L, _P, _P, _L, _I, _P, _c.c_uint32, _P, _P],
+    "iif_lt_augment_policy": [_P, _L, _P, _P, _L, _I, _P, _P, _P, _P],
 }
 
 

@@ -153,34 +153,41 @@ def epoch_indices(n, epoch, seed=0, train=True, mode="random", labels=None, rank
 
 
 # --------------------------------------------------------------------------------------------------- the policy table
+def op_constants(name, mag, sign, h=SIDE, w=SIDE):
+    """The six constant words p0 .. p5 of one operation at magnitude index ``mag`` and sign -1.0 / +1.0 on an h x w image,
+    uint32 [6]: the fp32 affine coefficients (a, b, c, d, e, f) of a geometric op, (f, 1 - f) of a blend op, the posterize
+    mask or the solarize threshold (integers); zeros for the rest.  Built in double from augment.py's own tables (_ranges(),
+    affine_coefficients) and rounded to fp32 once."""
+    m = augment._ranges()[name][mag]
+    words = np.zeros(6, dtype=np.uint32)
+    if name in augment.GEOMETRIC:
+        words[:] = np.asarray(augment.affine_coefficients(name, m, sign, h, w), np.float32).view(np.uint32)
+    elif name in BLEND:
+        f = 1.0 + m * sign
+        words[:2] = np.asarray([f, 1.0 - f], np.float32).view(np.uint32)
+    elif name == "Posterize":
+        words[0] = (0xFF << (8 - int(m))) & 0xFF
+    elif name == "Solarize":
+        words[0] = int(math.ceil(m))
+    return words
+
+
 def policy_table(subs=None, h=SIDE, w=SIDE):
     """The kernel's constants for the 25 sub-policies ``subs`` (default: augment._P["cifar10"], CIFAR10Policy), uint32
-    [25][2][2][8]: per (sub-policy, op, sign negative / positive) the words
-    [op code, round(prob * 2^24), p0 .. p5] with p = the fp32 affine coefficients (a, b, c, d, e, f) of a geometric op,
-    (f, 1 - f) of a blend op, the posterize mask or the solarize threshold (integers).  Built in double from
-    augment.py's own tables (_P, _ranges(), affine_coefficients) and rounded to fp32 once."""
+    [25][2][2][8]: per (sub-policy, op, sign negative / positive) the words [op code, round(prob * 2^24), p0 .. p5] with
+    p = op_constants(op, magnitude, sign, h, w)."""
     subs = augment._P["cifar10"] if subs is None else subs
     if len(subs) != 25:
         raise ValueError("the kernel draws one of 25 sub-policies, got %d" % len(subs))
-    ranges = augment._ranges()
     tab = np.zeros((len(subs), 2, 2, 8), dtype=np.uint32)
     for s, sub in enumerate(subs):
         for j in range(2):
             name, prob, mag = sub[3 * j:3 * j + 3]
-            m = ranges[name][mag]
             for k, sign in enumerate((-1.0, 1.0)):
                 words = tab[s, j, k]
                 words[0] = OPS.index(name)
                 words[1] = int(round(prob * 2 ** 24))
-                if name in augment.GEOMETRIC:
-                    words[2:8] = np.asarray(augment.affine_coefficients(name, m, sign, h, w), np.float32).view(np.uint32)
-                elif name in BLEND:
-                    f = 1.0 + m * sign
-                    words[2:4] = np.asarray([f, 1.0 - f], np.float32).view(np.uint32)
-                elif name == "Posterize":
-                    words[2] = (0xFF << (8 - int(m))) & 0xFF
-                elif name == "Solarize":
-                    words[2] = int(math.ceil(m))
+                words[2:8] = op_constants(name, mag, sign, h, w)
     return tab
 
 

@@ -126,8 +126,9 @@ def get_cifar_device(args, name):
 def get_lt_device(args, key):
     """The list datasets of ``--data-path`` with the input pipeline on the device (``--device-augment``): LT_Dataset /
     LT_Dataset_Eval only decode, DeviceLTLoader cuts the RandomResizedCrop box on the host and resizes, flips, jitters and
-    normalises each batch in one launch (TensorTransform's pipeline; imbalanced_dataset.py:189-233).  The loader stands in
-    for the train sampler too (``set_epoch``)."""
+    normalises each batch in one launch (TensorTransform's pipeline; imbalanced_dataset.py:189-233); with ``--device-policy``
+    the training loader runs the ``--auto-augment`` policy there in place of ColorJitter.  The loader stands in for the train
+    sampler too (``set_epoch``)."""
     from . import lt_device
     C, train_txt, eval_txt = imbalanced_dataset.LT_LISTS[key]
     ds = imbalanced_dataset.LT_Dataset(args.data_path, getattr(args, "train_txt", None) or train_txt, C)
@@ -138,8 +139,9 @@ def get_lt_device(args, key):
     dist = getattr(args, "distributed", False)
     device = getattr(args, "device", "cuda")
     workers = getattr(args, "workers", 4)
+    policy = getattr(args, "auto_augment", None) if getattr(args, "device_policy", False) else None
     loader = lt_device.DeviceLTLoader(ds, args.batch_size, train=True, size=size, dset_name=key, seed=args.rand_number,
-                                      mode=mode, distributed=dist, workers=workers, device=device)
+                                      mode=mode, distributed=dist, workers=workers, device=device, policy=policy)
     loader_test = lt_device.DeviceLTLoader(ds_test, args.batch_size, train=False, size=size, dset_name=key,
                                            distributed=dist, workers=workers, device=device)
     return ds, ds.num_classes, loader, loader_test, loader

@@ -15,8 +15,13 @@ Draws: every random number comes from the counter-based hash of iif_amd/cifar.py
 this rank's epoch list) with a fixed slot per draw, so the same (seed, epoch, rank) gives the same batches, whatever the
 worker count, and a resumed epoch sees the same inputs.  Slots 0..39: the RandomResizedCrop tries (imbalanced_dataset.rrc_box
 consumes them in order), 40: the flip, 41..43: the jitter order (Fisher-Yates), 44..47: the jitter factors
-(augment.ColorJitter.factors).  The index lists are cifar.epoch_indices': RandomSampler, BalanceClassSampler, their DDP shards.
+(augment.ColorJitter.factors), 48..55: the auto-augment policy (draw_policy); a policy run therefore crops and flips exactly
+the images a jitter run does.  The index lists are cifar.epoch_indices': RandomSampler, BalanceClassSampler, their DDP shards.
 Evaluation is TensorTransform's geometry (imbalanced_dataset.eval_geometry) without draws.
+
+With ``policy`` ("imagenet", "randaugment", "cifar") the policy replaces ColorJitter, as in the reference
+(imbalanced_dataset.py:210-225): the workers draw each image's ops and turn them into op records (policy_record), packed as a
+section of their own, and ``iif_lt_augment_policy`` runs them on the device between the flip and Normalize.
 """
 import ctypes
 import math
@@ -25,7 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib, augment
-from .cifar import _mix64, epoch_indices, sample_keys
+from .cifar import OPS, _mix64, epoch_indices, op_constants, sample_keys
 from .imbalanced_dataset import eval_geometry, mean_std_hue, rrc_box
 
 JITTER = 1                                                 # IIF_LT_JITTER of include/iif_amd.h
@@ -33,6 +38,14 @@ DESC = ("offset", "h", "w", "rh", "rw", "oy", "ox", "flip")        # int64 words
 JITTER_WORDS = ("order", "fb", "gb", "fc", "gc", "fs", "gs", "fh")  # uint32 words per image (g = 1 - f, fp32 bits)
 RRC_SLOTS, FLIP_SLOT, ORDER_SLOT, FACTOR_SLOT, N_SLOTS = 40, 40, 41, 44, 48
 JITTER_AMOUNTS = (0.4, 0.4, 0.4)                           # imbalanced_dataset.py:197,205 ColorJitter(0.4, 0.4, 0.4, hue)
+POLICY_SLOT, N_POLICY_SLOTS = 48, 8                        # slots 48..55 of the same key: the policy draws
+OP_NONE = 0xFF                                             # IIF_LT_OP_NONE: an op slot that does nothing
+RECORD_WORDS = 8                                           # uint32 per op slot: op code, p0 .. p5 (cifar.op_constants), unused
+# --auto-augment value -> augment._P table (None: RandAugment), as TensorTransform maps them
+POLICIES = {"imagenet": "imagenet", "cifar": "cifar10", "cifar10": "cifar10", "randaugment": None}
+RAND_N, RAND_M = 2, 9                                      # augment.RandAugment(): n = 2 ops at magnitude index 9
+# the ops that cost the kernel a sweep of their own: whole-image reductions and gathers (lt_policy.hip)
+SWEEP_OPS = augment.GEOMETRIC + ("Sharpness", "Contrast", "AutoContrast", "Equalize")
 
 
 def uniforms(seed, epoch, rank, pos):
@@ -40,6 +53,44 @@ def uniforms(seed, epoch, rank, pos):
     key = sample_keys(seed, epoch, rank, [pos])[0]
     u = _mix64(key ^ np.arange(N_SLOTS, dtype=np.uint64)) >> np.uint64(11)
     return u.astype(np.float64) * (1.0 / (1 << 53))
+
+
+def policy_uniforms(seed, epoch, rank, pos):
+    """The N_POLICY_SLOTS uniforms of slots POLICY_SLOT.. of one sample, as ``uniforms`` computes its slots."""
+    key = sample_keys(seed, epoch, rank, [pos])[0]
+    u = _mix64(key ^ np.arange(POLICY_SLOT, POLICY_SLOT + N_POLICY_SLOTS, dtype=np.uint64)) >> np.uint64(11)
+    return u.astype(np.float64) * (1.0 / (1 << 53))
+
+
+def draw_policy(policy, u):
+    """The two op slots of one sample from its policy uniforms ``u``: [(name, magnitude index, sign +-1.0) or None] * 2.
+    AutoAugment (imagenet, cifar): sub-policy floor(u0 * 25), op j applied when u(1 + 2j) < its probability, sign +1 when
+    u(2 + 2j) < 0.5.  RandAugment: op j = RandAugment.OPS[floor(u(2j) * 14)] at magnitude RAND_M, sign +1 when u(1 + 2j) < 0.5."""
+    if policy not in POLICIES:
+        raise ValueError("unknown policy %r (%s)" % (policy, ", ".join(POLICIES)))
+    if POLICIES[policy] is None:
+        ops = augment.RandAugment.OPS
+        return [(ops[int(u[2 * j] * len(ops))], RAND_M, 1.0 if u[2 * j + 1] < 0.5 else -1.0) for j in range(RAND_N)]
+    subs = augment._P[POLICIES[policy]]
+    sub = subs[int(u[0] * len(subs))]
+    out = []
+    for j in range(2):
+        name, prob, mag = sub[3 * j:3 * j + 3]
+        out.append((name, mag, 1.0 if u[2 + 2 * j] < 0.5 else -1.0) if u[1 + 2 * j] < prob else None)
+    return out
+
+
+def policy_record(ops, size):
+    """The uint32 [2][8] op records of iif_lt_augment_policy for the slots ``ops`` (draw_policy) at S = ``size``: the op code
+    (the index in cifar.OPS) and op_constants(name, magnitude, sign, size, size); OP_NONE for a slot not applied."""
+    rec = np.zeros((2, RECORD_WORDS), dtype=np.uint32)
+    rec[:, 0] = OP_NONE
+    for j, op in enumerate(ops):
+        if op is not None:
+            name, mag, sign = op
+            rec[j, 0] = OPS.index(name)
+            rec[j, 1:7] = op_constants(name, mag, sign, size, size)
+    return rec
 
 
 def _stream(u, first, last):
@@ -112,9 +163,14 @@ def _align(n, a=16):
 
 def pack(samples):
     """Collate [(region, desc words, jitter record or None, target)] into one uint8 tensor: desc int64 [B][8], jitter uint32
-    [B][8], targets int64 [B], then the regions at 16-byte aligned offsets (desc[:, 0] counts from the pool's start)."""
+    [B][8], targets int64 [B], then the regions at 16-byte aligned offsets (desc[:, 0] counts from the pool's start).
+    Samples of a policy loader carry a fifth item, their op records (policy_record): they go into a section of their own,
+    uint32 [B][2][8], after the targets."""
     B = len(samples)
-    head = B * (8 * 8 + 4 * 8 + 8)
+    policy = B > 0 and len(samples[0]) > 4
+    if any((len(s) > 4) != policy for s in samples):
+        raise ValueError("either every sample carries op records or none does")
+    head = B * (8 * 8 + 4 * 8 + 8) + (B * 2 * RECORD_WORDS * 4 if policy else 0)
     offs, o = [], 0
     for s in samples:
         offs.append(o)
@@ -124,7 +180,11 @@ def pack(samples):
     jit = buf[B * 64:B * 96].view(np.uint32).reshape(B, 8)
     tgt = buf[B * 96:B * 104].view(np.int64)
     pool = buf[_align(head):]
-    for i, (region, words, rec, target) in enumerate(samples):
+    if policy:
+        ops = buf[B * 104:B * 168].view(np.uint32).reshape(B, 2, RECORD_WORDS)
+        for i, sample in enumerate(samples):
+            ops[i] = sample[4]
+    for i, (region, words, rec, target) in enumerate(s[:4] for s in samples):
         desc[i, 0] = offs[i]
         desc[i, 1:] = words
         if rec is not None:
@@ -138,8 +198,13 @@ def _collate(samples):
     return pack(samples), len(samples)
 
 
-def unpack(buf, B):
-    """(pool, desc, jitter, targets) views of a packed batch (on any device)."""
+def unpack(buf, B, policy=False):
+    """(pool, desc, jitter, targets) views of a packed batch (on any device); with ``policy`` (a batch of a policy loader)
+    (pool, desc, jitter, targets, op records int32 [B, 2, 8])."""
+    if policy:
+        head = _align(B * 168)
+        return (buf[head:], buf[:B * 64].view(torch.int64).view(B, 8), buf[B * 64:B * 96].view(torch.int32).view(B, 8),
+                buf[B * 96:B * 104].view(torch.int64), buf[B * 104:B * 168].view(torch.int32).view(B, 2, RECORD_WORDS))
     head = _align(B * 104)
     return (buf[head:], buf[:B * 64].view(torch.int64).view(B, 8), buf[B * 64:B * 96].view(torch.int32).view(B, 8),
             buf[B * 96:B * 104].view(torch.int64))
@@ -165,12 +230,42 @@ def lt_augment(pool, desc, jitter, size, mean, std, flags, out=None):
     return out
 
 
-class _Samples(torch.utils.data.Dataset):
-    """Position p of one rank's epoch list -> (region, desc words, jitter record, target); runs in the DataLoader workers."""
+def lt_augment_policy(pool, desc, ops, size, mean, std, work=None, out=None):
+    """One ``iif_lt_augment_policy`` launch: pool uint8, desc int64 [B, 8], ops int32 / uint32 words [B, 2, 8]
+    (policy_record), all on the device; mean / std three floats each; ``work`` the kernel's scratch image, fp32
+    [B, 3, size, size] (allocated when None).  Returns fp32 [B, 3, size, size]."""
+    _lib.require_gpu(pool, desc, ops, work, out)
+    if pool.dtype != torch.uint8 or desc.dtype != torch.int64 or ops.dtype != torch.int32:
+        raise TypeError("pool uint8, desc int64 and ops int32 expected")
+    B = desc.shape[0]
+    if not (pool.is_contiguous() and desc.is_contiguous()) or desc.dim() != 2 or desc.shape[1] != len(DESC):
+        raise ValueError("contiguous pool and desc [B, %d] expected" % len(DESC))
+    if not ops.is_contiguous() or tuple(ops.shape) != (B, 2, RECORD_WORDS):
+        raise ValueError("contiguous ops [B, 2, %d] expected" % RECORD_WORDS)
+    shape = (B, 3, int(size), int(size))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=desc.device)
+    if work is None:
+        work = torch.empty(shape, dtype=torch.float32, device=desc.device)
+    for name, t in (("work", work), ("out", out)):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous fp32 %s tensor" % (name, list(shape)))
+    if work.data_ptr() == out.data_ptr():
+        raise ValueError("work and out must be distinct buffers")
+    ms = (ctypes.c_float * 6)(*[float(v) for v in mean], *[float(v) for v in std])
+    rc = _lib.lib().iif_lt_augment_policy(_lib.ptr(pool), pool.numel(), _lib.ptr(desc), _lib.ptr(ops), B, int(size),
+                                          ctypes.addressof(ms), _lib.ptr(work), _lib.ptr(out), _lib.stream_ptr())
+    _lib.check(rc, "iif_lt_augment_policy")
+    return out
 
-    def __init__(self, dataset, index, train, size, seed, epoch, rank, jitter):
+
+class _Samples(torch.utils.data.Dataset):
+    """Position p of one rank's epoch list -> (region, desc words, jitter record, target[, op records]); runs in the
+    DataLoader workers."""
+
+    def __init__(self, dataset, index, train, size, seed, epoch, rank, jitter, policy=None):
         self.dataset, self.index, self.train, self.size = dataset, index, train, size
-        self.seed, self.epoch, self.rank, self.jitter = seed, epoch, rank, jitter
+        self.seed, self.epoch, self.rank, self.jitter, self.policy = seed, epoch, rank, jitter, policy
 
     def __len__(self):
         return len(self.index)
@@ -178,6 +273,10 @@ class _Samples(torch.utils.data.Dataset):
     def __getitem__(self, p):
         i = int(self.index[p])
         img = self.dataset.loader(self.dataset.img_path[i])
+        if self.train and self.policy is not None:
+            region, words, _ = train_sample(img, self.size, uniforms(self.seed, self.epoch, self.rank, p))
+            ops = draw_policy(self.policy, policy_uniforms(self.seed, self.epoch, self.rank, p))
+            return region, words, None, int(self.dataset.targets[i]), policy_record(ops, self.size)
         if self.train:
             u = uniforms(self.seed, self.epoch, self.rank, p)
             region, words, rec = train_sample(img, self.size, u, self.jitter)
@@ -189,17 +288,22 @@ class _Samples(torch.utils.data.Dataset):
 class DeviceLTLoader(object):
     """Yields device (image, target) batches of a list dataset (LT_Dataset / LT_Dataset_Eval): ``drop_last`` for training,
     every sample for evaluation.  ``dset_name`` picks mean / std and the jitter's hue (imbalanced_dataset.mean_std_hue);
-    ``jitter=False`` trains with crop and flip only.  ``mode`` = --sampler.  ``set_epoch`` as DistributedSampler; without it
-    each pass over the loader advances the epoch by one."""
+    ``jitter=False`` trains with crop and flip only.  ``policy`` ("imagenet", "randaugment", "cifar"; training only) runs
+    that auto-augment policy on the device instead of the jitter.  ``mode`` = --sampler.  ``set_epoch`` as
+    DistributedSampler; without it each pass over the loader advances the epoch by one."""
 
     def __init__(self, dataset, batch_size, train=True, size=224, dset_name="imagenet_lt", jitter=True, seed=0, mode="random",
-                 distributed=False, rank=None, world=None, workers=4, device="cuda"):
+                 distributed=False, rank=None, world=None, workers=4, device="cuda", policy=None):
         if mode not in ("random", "upsampling", "downsampling"):
             raise ValueError("unknown sampler %r (random, upsampling, downsampling)" % (mode,))
+        if policy is not None and policy not in POLICIES:
+            raise ValueError("unknown policy %r (%s)" % (policy, ", ".join(POLICIES)))
         self.dataset = dataset
         self.batch_size, self.train, self.size, self.seed, self.mode = int(batch_size), train, int(size), int(seed), mode
         self.mean, self.std, hue = mean_std_hue(dset_name)
-        self.jitter = augment.ColorJitter(*JITTER_AMOUNTS, hue) if (train and jitter) else None
+        self.policy = policy if train else None
+        self.jitter = augment.ColorJitter(*JITTER_AMOUNTS, hue) if (train and jitter and self.policy is None) else None
+        self._work = None                                  # iif_lt_augment_policy's scratch image, reused while (B, S) stays
         self.flags = JITTER if self.jitter is not None else 0
         if distributed:
             import torch.distributed as dist
@@ -228,7 +332,8 @@ class DeviceLTLoader(object):
 
     def batches(self, epoch):
         """The packed host batches of one epoch: (uint8 tensor, pinned when a GPU is present; sample count)."""
-        samples = _Samples(self.dataset, self.indices(epoch), self.train, self.size, self.seed, epoch, self.rank, self.jitter)
+        samples = _Samples(self.dataset, self.indices(epoch), self.train, self.size, self.seed, epoch, self.rank, self.jitter,
+                           self.policy)
         return torch.utils.data.DataLoader(samples, batch_size=self.batch_size, shuffle=False, drop_last=self.train,
                                            num_workers=self.workers, collate_fn=_collate, pin_memory=torch.cuda.is_available())
 
@@ -240,6 +345,12 @@ class DeviceLTLoader(object):
 
     def build(self, dev, B):
         """(image, target) of one packed batch of B samples already on the device."""
+        if self.policy is not None:
+            pool, desc, _, tgt, ops = unpack(dev, B, policy=True)
+            shape = (B, 3, self.size, self.size)
+            if self._work is None or tuple(self._work.shape) != shape or self._work.device != dev.device:
+                self._work = torch.empty(shape, dtype=torch.float32, device=dev.device)
+            return lt_augment_policy(pool, desc, ops, self.size, self.mean, self.std, work=self._work), tgt
         pool, desc, jit, tgt = unpack(dev, B)
         img = lt_augment(pool, desc, jit if self.flags & JITTER else None, self.size, self.mean, self.std, self.flags)
         return img, tgt

@@ -8,7 +8,7 @@ main :168-285), running on the native MI355X engine.
 Differences, all forced by the environment or by the MI355X-first design:
   * without ``--data-path`` the datasets are synthetic long-tailed sets (no torchvision / network); CIFAR-10 / -100
     with ``--data-path`` are read from their files and augmented on the device (iif_amd/cifar.py); the list datasets
-    are too with ``--device-augment`` (iif_amd/lt_device.py);
+    are too with ``--device-augment`` (iif_amd/lt_device.py), their auto-augment policies with ``--device-policy``;
   * the step is the fused native one — forward, fused IIF loss (+mixup), backward,
     bucketed RCCL all-reduce overlapped with backward, ONE fused SGD or RMSprop launch — instead of
     autograd + torch.optim + DistributedDataParallel; schedules are evaluated on the host
@@ -173,21 +173,33 @@ def build_model(args, num_classes):
 
 
 HOST_POLICIES = ("imagenet", "randaugment", "cifar", "cifar10")
+DEVICE_POLICIES = HOST_POLICIES                        # lt_device.POLICIES: what --device-policy runs
 
 
 def check_device_augment(args):
     """--device-augment builds the list datasets' batches on the device: it needs --data-path and refuses the auto-augment
-    policies, which stay on the host.  CIFAR is built on the device already (the flag changes nothing there)."""
-    if not getattr(args, "device_augment", False):
+    policies unless --device-policy runs them on the device too.  CIFAR is built on the device already (the flag changes
+    nothing there)."""
+    device_policy = getattr(args, "device_policy", False)
+    augment_on_device = getattr(args, "device_augment", False)
+    if device_policy and not augment_on_device:
+        raise SystemExit("--device-policy needs --device-augment: the policy runs in the device pipeline that flag builds")
+    if not augment_on_device:
         return
     if not getattr(args, "data_path", ""):
         raise SystemExit("--device-augment needs --data-path: it builds batches from the dataset's files, and the synthetic "
                          "sets have none")
     name = args.dset_name.lower()
     policy = getattr(args, "auto_augment", None)
+    if device_policy:
+        if policy in (None, "", "None"):
+            raise SystemExit("--device-policy needs --auto-augment %s" % " | ".join(DEVICE_POLICIES))
+        if policy not in DEVICE_POLICIES:
+            raise SystemExit("--device-policy does not know --auto-augment %r (%s)" % (policy, ", ".join(DEVICE_POLICIES)))
+        return
     if not name.startswith("cifar") and policy in HOST_POLICIES:
         raise SystemExit("--device-augment does not run --auto-augment %s: that policy stays on the host; drop one of the two "
-                         "flags" % (policy,))
+                         "flags; add --device-policy to run it on the device" % (policy,))
 
 
 def main(args):
@@ -308,6 +320,9 @@ def get_args_parser(add_help=True):
     p.add_argument("--device-augment", dest="device_augment", action="store_true",
                    help="list datasets with --data-path: resize, flip, ColorJitter and Normalize each batch on the device "
                    "(iif_amd/lt_device.py) instead of in the DataLoader workers")
+    p.add_argument("--device-policy", dest="device_policy", action="store_true",
+                   help="with --device-augment: run the --auto-augment policy (imagenet, randaugment, cifar) on the device "
+                   "too, in place of ColorJitter (iif_lt_augment_policy)")
     p.add_argument("--random-erase", default=0.0, type=float)
     p.add_argument("--apex", action="store_true")
     p.add_argument("--apex-opt-level", default="O2", type=str)

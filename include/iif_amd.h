@@ -754,6 +754,26 @@ int iif_cifar_augment(const uint8_t* data, int64_t n, const int64_t* labels, con
 int iif_lt_augment(const uint8_t* pool, int64_t pool_bytes, const int64_t* desc, const uint32_t* jitter, int64_t batch,
                    int size, const float* mean_std, uint32_t flags, float* out, void* stream);
 
+/* List-dataset training input with an auto-augment policy (iif_amd/lt_device.py DeviceLTLoader(policy=...)): ONE launch per
+ * batch builds out[b] as iif_lt_augment does without IIF_LT_JITTER, with up to two auto-augment operations between the flip
+ * and Normalize, in TensorTransform's order:
+ *   resize / window / flip (the same values as iif_lt_augment) -> clamp(0, 1) -> the op of record slot 0, then of slot 1
+ *   (augment.apply_op_signed: the affine ops as PIL's nearest-neighbour mapping at pixel centres with grey 128 / 255 fill;
+ *   Posterize / Solarize / Equalize through uint8 levels, Equalize by PIL's LUT rule; AutoContrast by channel min / max;
+ *   Contrast toward the grey mean; Sharpness with the (1 1 1; 1 5 1; 1 1 1) / 13 blur, borders kept) -> (x - mean) / std.
+ * pool, desc, mean_std: as iif_lt_augment.
+ * ops: uint32 [batch][2][8], one record per op slot: word 0 the op code (the index in iif_amd/cifar.py OPS: ShearX, ShearY,
+ *   TranslateX, TranslateY, Rotate, Color, Posterize, Solarize, Contrast, Sharpness, Brightness, AutoContrast, Equalize,
+ *   Invert) or IIF_LT_OP_NONE; words 1..6 its constants as cifar.policy_table encodes them at h = w = size (the fp32 bits of
+ *   the affine a .. f or of the blend's (f, 1 - f); the posterize mask or solarize threshold as an integer); word 7 unused.
+ * work, out: fp32 [batch][3][size][size] each, distinct; work is scratch (the block keeps its image there between sweeps).
+ * A malformed descriptor (as iif_lt_augment) or an unknown op code reads nothing: out[b] = 0.
+ * IIF_EINVAL before any launch: a null pool / desc / ops / mean_std / work / out, pool_bytes < 0, batch < 0,
+ * size <= 0 or > 16384.  batch == 0: IIF_OK, no launch. */
+#define IIF_LT_OP_NONE 0xFFu
+int iif_lt_augment_policy(const uint8_t* pool, int64_t pool_bytes, const int64_t* desc, const uint32_t* ops, int64_t batch,
+                          int size, const float* mean_std, float* work, float* out, void* stream);
+
 /* Compute-unit budget of the persistent grids (the weights-in-registers kernels, the stem, the streaming 1x1 kernel size their
  * grids to one or two resident blocks per CU).  Process-wide, default 0 = every CU of the device; a rank whose gradient
  * all-reduce (RCCL kernels, classification/train.py:230-234 DDP) overlaps backward sets e.g. 240 so that the reduction's

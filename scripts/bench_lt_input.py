@@ -1,15 +1,19 @@
 """List-dataset (ImageNet-LT / Places-LT / iNat18) input pipeline on one MI355X.
 
     python scripts/bench_lt_input.py kernel [--iters 100]    # iif_lt_augment at B = 256, S = 224: train without hue, train
-                                                             # with hue, eval, and a 1200 x 900 large-image train case
+                                                             # with hue, eval, and a 1200 x 900 large-image train case; then
+                                                             # iif_lt_augment_policy with the imagenet and randaugment draws
     rocprofv3 --kernel-trace --stats -d out -o lt -- python scripts/bench_lt_input.py kernel
     python scripts/bench_lt_input.py stats out/lt_results.db # per-case kernel times from that trace
     python scripts/bench_lt_input.py loader [--batches 64] [--workers 16]
                                                              # steady-state loader img/s over pre-decoded .npy files, no
                                                              # model: TensorTransform in the DataLoader against DeviceLTLoader
+                                                             # (--policy imagenet|randaugment: with that auto-augment policy,
+                                                             # on the device through --device-policy)
     python scripts/bench_lt_input.py train [--steps 60] [--paths host|device] [--workers 16]
                                                              # ResNet50 training img/s on a Places-LT-shaped .npy tree, timed
-                                                             # after the epoch's first 40 steps (one path per process)
+                                                             # after the epoch's first 40 steps (one path per process;
+                                                             # --policy as for loader)
     python scripts/bench_lt_input.py jpeg                    # PIL JPEG decode rate, when PIL imports
 
 Sources are seeded synthetic uint8 images of ImageNet-like sizes (short side 256-500); training regions are the
@@ -29,7 +33,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 B, S = 256, 224
-CASES = ("train, no hue", "train, hue (iNat18)", "eval", "train, 1200x900 sources")
+CASES = ("train, no hue", "train, hue (iNat18)", "eval", "train, 1200x900 sources", "train, imagenet policy",
+         "train, randaugment")
 
 
 def _image_shapes(n, seed):
@@ -40,19 +45,23 @@ def _image_shapes(n, seed):
     return [(int(l), int(s)) if p else (int(s), int(l)) for s, l, p in zip(short, long_, port)]
 
 
-def _batch(shapes, train, dset, seed):
+def _batch(shapes, train, dset, seed, policy=None):
     from iif_amd import augment, lt_device
     from iif_amd.imbalanced_dataset import mean_std_hue
-    cj = augment.ColorJitter(0.4, 0.4, 0.4, mean_std_hue(dset)[2]) if train else None
+    cj = augment.ColorJitter(0.4, 0.4, 0.4, mean_std_hue(dset)[2]) if (train and policy is None) else None
     base = np.random.RandomState(seed).randint(0, 256, size=(1300, 1300, 3), dtype=np.uint8)
     samples = []
     for pos, (h, w) in enumerate(shapes):
         img = base[pos % 50:pos % 50 + h, pos % 97:pos % 97 + w]
-        if train:
+        if policy is not None:
+            s = lt_device.train_sample(img, S, lt_device.uniforms(seed, 0, 0, pos))
+            ops = lt_device.draw_policy(policy, lt_device.policy_uniforms(seed, 0, 0, pos))
+            s = s + (0, lt_device.policy_record(ops, S))
+        elif train:
             s = lt_device.train_sample(img, S, lt_device.uniforms(seed, 0, 0, pos), cj)
         else:
             s = lt_device.eval_sample(img, S)
-        samples.append(s + (0,))
+        samples.append(s if policy is not None else s + (0,))
     return lt_device.pack(samples), sum(s[0].nbytes for s in samples)
 
 
@@ -81,6 +90,26 @@ def bench_kernel(iters):
         moved = region_bytes + B * 3 * S * S * 4
         print(json.dumps({"case": label, "B": B, "S": S, "us_per_call_events": round(us, 1), "region_bytes": region_bytes,
                           "bytes": moved, "GB_per_s_at_event_time": round(moved / us / 1e3, 1)}), flush=True)
+    for label, policy in zip(CASES[4:], ("imagenet", "randaugment")):
+        buf, region_bytes = _batch(_image_shapes(B, 1), True, "imagenet_lt", 7, policy)
+        pool, desc, _, _, ops = lt_device.unpack(buf.cuda(), B, policy=True)
+        mean, std, _ = mean_std_hue("imagenet_lt")
+        out, work = torch.empty(B, 3, S, S, device="cuda"), torch.empty(B, 3, S, S, device="cuda")
+        for _ in range(10):
+            lt_device.lt_augment_policy(pool, desc, ops, S, mean, std, work, out)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            lt_device.lt_augment_policy(pool, desc, ops, S, mean, std, work, out)
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) * 1e3 / iters
+        codes = ops[:, :, 0].cpu().numpy()
+        swept = [lt_device.OPS.index(n) for n in lt_device.SWEEP_OPS]           # each one adds a sweep over its image
+        print(json.dumps({"case": label, "B": B, "S": S, "us_per_call_events": round(us, 1), "region_bytes": region_bytes,
+                          "applied_ops": int((codes != lt_device.OP_NONE).sum()),
+                          "extra_sweeps": int(np.isin(codes, swept).sum())}), flush=True)
 
 
 def kernel_stats(db_path, iters=100, warm=10):
@@ -88,7 +117,7 @@ def kernel_stats(db_path, iters=100, warm=10):
     import sqlite3
     import statistics
     rows = sqlite3.connect(db_path).execute("select end - start from kernels where name like '%lt_augment%' "
-                                            "order by start").fetchall()
+                                            "or name like '%lt_policy%' order by start").fetchall()
     for i, label in enumerate(CASES):
         us = [d / 1e3 for (d,) in rows[i * (warm + iters) + warm:(i + 1) * (warm + iters)]]
         print("%-26s %d calls  median %.1f us  min %.1f  max %.1f" % (label, len(us), statistics.median(us), min(us), max(us)))
@@ -110,7 +139,15 @@ def _tree(root, n, classes, files=512, seed=0):
             f.write("\n".join(lines) + "\n")
 
 
-def bench_loader(batches, workers):
+def _paths(policy):
+    """(name, extra CLI flags) of the host and the device input path, with --auto-augment ``policy`` when given."""
+    if policy is None:
+        return (("host TensorTransform", []), ("device DeviceLTLoader", ["--device-augment"]))
+    aa = ["--auto-augment", policy]
+    return (("host TensorTransform", aa), ("device DeviceLTLoader", ["--device-augment", "--device-policy"] + aa))
+
+
+def bench_loader(batches, workers, policy=None):
     """Steady-state loader rate: the first workers * prefetch_factor (+ 4) batches, which the DataLoader dispatches at once
     and builds in parallel before the clock could start, are drained untimed; then ``batches`` batches are timed, each
     moved to the device."""
@@ -118,7 +155,7 @@ def bench_loader(batches, workers):
     warm = workers * 2 + 4                                        # DataLoader's default prefetch_factor is 2
     with tempfile.TemporaryDirectory() as root:
         _tree(root, B * (warm + batches + 2), 365)
-        for name, extra in (("host TensorTransform", []), ("device DeviceLTLoader", ["--device-augment"])):
+        for name, extra in _paths(policy):
             args = train.get_args_parser().parse_args(["--dset_name", "places_lt", "--data-path", root, "--train-txt",
                                                        os.path.join(root, "train.txt"), "--eval-txt",
                                                        os.path.join(root, "eval.txt"), "-b", str(B), "-j", str(workers)]
@@ -136,7 +173,7 @@ def bench_loader(batches, workers):
                 x = x.cuda(non_blocking=True)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            print(json.dumps({"case": "loader", "input": name, "workers": workers, "batch": B, "untimed_batches": warm,
+            print(json.dumps({"case": "loader", "input": name, "policy": policy, "workers": workers, "batch": B, "untimed_batches": warm,
                               "timed_batches": batches, "img_per_s": round(batches * B / dt, 1)}), flush=True)
             del it
 
@@ -159,13 +196,12 @@ class _Timed(object):
             yield batch
 
 
-def bench_train(steps, paths, workers, skip=40):
+def bench_train(steps, paths, workers, skip=40, policy=None):
     from iif_amd import initialisers, train
     bs = 128
     with tempfile.TemporaryDirectory() as root:
         _tree(root, bs * (skip + steps + 8), 365)
-        for name, extra in [c for c in (("host TensorTransform", []), ("device DeviceLTLoader", ["--device-augment"]))
-                            if c[0].split()[0] in paths]:
+        for name, extra in [c for c in _paths(policy) if c[0].split()[0] in paths]:
             args = train.get_args_parser().parse_args(["--model", "resnet50", "--dset_name", "places_lt", "--data-path", root,
                                                        "--train-txt", os.path.join(root, "train.txt"), "--eval-txt",
                                                        os.path.join(root, "eval.txt"), "-b", str(bs), "-j", str(workers),
@@ -182,7 +218,7 @@ def bench_train(steps, paths, workers, skip=40):
             train.train_one_epoch(model, crit, timed, torch.device("cuda"), 1, args)
             torch.cuda.synchronize()
             dt = time.perf_counter() - timed.t
-            print(json.dumps({"case": "train", "model": "resnet50", "input": name, "workers": workers, "untimed_steps": skip,
+            print(json.dumps({"case": "train", "model": "resnet50", "input": name, "policy": policy, "workers": workers, "untimed_steps": skip,
                               "timed_steps": steps, "batch": bs, "img_per_s": round(steps * bs / dt, 1),
                               "ms_per_step": round(dt * 1e3 / steps, 2)}), flush=True)
 
@@ -215,11 +251,12 @@ if __name__ == "__main__":
     p.add_argument("--steps", type=int, default=60)
     p.add_argument("--paths", default="host,device", help="train: which input paths, in this order, in one process")
     p.add_argument("--workers", type=int, default=16)
+    p.add_argument("--policy", default=None, choices=["imagenet", "randaugment"], help="loader / train: --auto-augment policy")
     a = p.parse_args()
     if a.mode == "jpeg":
         bench_jpeg()
         raise SystemExit(0)
     if not torch.cuda.is_available():
         raise SystemExit("bench_lt_input.py needs the MI355X")
-    {"kernel": lambda: bench_kernel(a.iters), "loader": lambda: bench_loader(a.batches, a.workers),
-     "train": lambda: bench_train(a.steps, a.paths.split(","), a.workers)}[a.mode]()
+    {"kernel": lambda: bench_kernel(a.iters), "loader": lambda: bench_loader(a.batches, a.workers, a.policy),
+     "train": lambda: bench_train(a.steps, a.paths.split(","), a.workers, policy=a.policy)}[a.mode]()
