@@ -117,6 +117,7 @@ SIGNATURES = {
     "iif_cifar_augment": [_P, _L, _P, _P, _L, _L, _c.c_uint64, _L, _L, _c.c_uint32, _P, _P, _P, _P, _P],
     "iif_lt_augment": [_P, _L, _P, _P, _L, _I, _P, _c.c_uint32, _P, _P],
     "iif_lt_augment_policy": [_P, _L, _P, _P, _L, _I, _P, _P, _P, _P],
+    "iif_jpeg_decode": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _P, _P],
 }
 
 

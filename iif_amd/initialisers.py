@@ -123,16 +123,21 @@ def get_cifar_device(args, name):
     return ds, ds.num_classes, loader, loader_test, loader
 
 
-def get_lt_device(args, key):
+def get_lt_device(args, key, loader=None):
     """The list datasets of ``--data-path`` with the input pipeline on the device (``--device-augment``): LT_Dataset /
     LT_Dataset_Eval only decode, DeviceLTLoader cuts the RandomResizedCrop box on the host and resizes, flips, jitters and
     normalises each batch in one launch (TensorTransform's pipeline; imbalanced_dataset.py:189-233); with ``--device-policy``
-    the training loader runs the ``--auto-augment`` policy there in place of ColorJitter.  The loader stands in for the train
-    sampler too (``set_epoch``)."""
+    the training loader runs the ``--auto-augment`` policy there in place of ColorJitter; with ``--device-decode`` the
+    baseline JPEG files are decoded on the device too (iif_amd/jpeg.py), which replaces the default loader only: a custom
+    ``loader`` is refused before any device is touched.  The loader stands in for the train sampler too (``set_epoch``)."""
     from . import lt_device
+    decode = "device" if getattr(args, "device_decode", False) else "host"
+    if decode == "device" and loader is not None:
+        raise SystemExit("--device-decode replaces the default image loader; this dataset has a custom loader")
     C, train_txt, eval_txt = imbalanced_dataset.LT_LISTS[key]
-    ds = imbalanced_dataset.LT_Dataset(args.data_path, getattr(args, "train_txt", None) or train_txt, C)
-    ds_test = imbalanced_dataset.LT_Dataset_Eval(args.data_path, getattr(args, "eval_txt", None) or eval_txt, ds.class_map, C)
+    ds = imbalanced_dataset.LT_Dataset(args.data_path, getattr(args, "train_txt", None) or train_txt, C, loader=loader)
+    ds_test = imbalanced_dataset.LT_Dataset_Eval(args.data_path, getattr(args, "eval_txt", None) or eval_txt, ds.class_map, C,
+                                                 loader=loader)
     ds.num_classes = len(ds.cls_num_list)
     size = getattr(args, "image_size", 224)
     mode = getattr(args, "sampler", "random")
@@ -141,7 +146,8 @@ def get_lt_device(args, key):
     workers = getattr(args, "workers", 4)
     policy = getattr(args, "auto_augment", None) if getattr(args, "device_policy", False) else None
     loader = lt_device.DeviceLTLoader(ds, args.batch_size, train=True, size=size, dset_name=key, seed=args.rand_number,
-                                      mode=mode, distributed=dist, workers=workers, device=device, policy=policy)
+                                      mode=mode, distributed=dist, workers=workers, device=device, policy=policy,
+                                      decode=decode)
     loader_test = lt_device.DeviceLTLoader(ds_test, args.batch_size, train=False, size=size, dset_name=key,
-                                           distributed=dist, workers=workers, device=device)
+                                           distributed=dist, workers=workers, device=device, decode=decode)
     return ds, ds.num_classes, loader, loader_test, loader

@@ -22,6 +22,10 @@ Evaluation is TensorTransform's geometry (imbalanced_dataset.eval_geometry) with
 With ``policy`` ("imagenet", "randaugment", "cifar") the policy replaces ColorJitter, as in the reference
 (imbalanced_dataset.py:210-225): the workers draw each image's ops and turn them into op records (policy_record), packed as a
 section of their own, and ``iif_lt_augment_policy`` runs them on the device between the flip and Normalize.
+
+With ``decode="device"`` (--device-decode) the workers only read baseline JPEG files and parse their headers (iif_amd/jpeg.py);
+``iif_jpeg_decode`` decodes each box on the device before the augment launch, and every other file (progressive, CMYK, PNG,
+.npy, ...) is decoded by the dataset's loader in the worker, in the same batch (pack_decode).
 """
 import ctypes
 import math
@@ -29,9 +33,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, augment
+from . import _lib, augment, jpeg
 from .cifar import OPS, _mix64, epoch_indices, op_constants, sample_keys
-from .imbalanced_dataset import eval_geometry, mean_std_hue, rrc_box
+from .imbalanced_dataset import _default_loader, eval_geometry, mean_std_hue, rrc_box
 
 JITTER = 1                                                 # IIF_LT_JITTER of include/iif_amd.h
 DESC = ("offset", "h", "w", "rh", "rw", "oy", "ox", "flip")        # int64 words per image
@@ -157,6 +161,20 @@ def eval_sample(img, size):
     return a, (h, w, nh, nw, top, left, 0), None
 
 
+def train_job(data, hd, size, u, jitter=None):
+    """train_sample of a stream the device decodes (data: its bytes, hd: jpeg.parse's Header): the same draws on the frame's
+    size, which is the decoded image's size; the region is a jpeg.Job for iif_jpeg_decode."""
+    (top, left, ch, cw), flip, order, factors = draw(hd.h, hd.w, u, jitter)
+    rec = None if jitter is None else jitter_record(order, *factors)
+    return jpeg.Job(data, hd, (top, left, ch, cw)), (ch, cw, size, size, 0, 0, int(flip)), rec
+
+
+def eval_job(data, hd, size):
+    """eval_sample of a stream the device decodes: the whole image."""
+    nh, nw, top, left = eval_geometry(hd.h, hd.w, size)
+    return jpeg.Job(data, hd, (0, 0, hd.h, hd.w)), (hd.h, hd.w, nh, nw, top, left, 0), None
+
+
 def _align(n, a=16):
     return (n + a - 1) // a * a
 
@@ -196,6 +214,70 @@ def pack(samples):
 
 def _collate(samples):
     return pack(samples), len(samples)
+
+
+TRAILER = ("jobs", "section", "upload", "out_bytes", "scratch_bytes", "subseq_bits", "unused", "unused")   # int64 words
+
+
+def pack_decode(samples, subseq_bits=jpeg.SUBSEQ_BITS):
+    """``pack`` for a loader that decodes on the device: a sample's region may be a jpeg.Job instead of an array.  The head
+    and the host regions are laid out exactly as ``pack`` lays them out (``unpack`` reads them); the JPEG section follows
+    the regions (jpeg.layout: records, tables, scans), then a trailer of 8 int64 words (TRAILER).  On the device the upload
+    is followed by the regions iif_jpeg_decode writes (out_bytes): the descriptors of the Job samples point there, past the
+    upload, so that iif_lt_augment reads both kinds from the one pool."""
+    B = len(samples)
+    policy = B > 0 and len(samples[0]) > 4
+    if any((len(s) > 4) != policy for s in samples):
+        raise ValueError("either every sample carries op records or none does")
+    head = B * (8 * 8 + 4 * 8 + 8) + (B * 2 * RECORD_WORDS * 4 if policy else 0)
+    pool0 = _align(head)
+    offs, o = [], 0
+    for s in samples:
+        if isinstance(s[0], jpeg.Job):
+            offs.append(None)
+        else:
+            offs.append(o)
+            o = _align(o + s[0].nbytes)
+    jobs = [s[0] for s in samples if isinstance(s[0], jpeg.Job)]
+    sec, _, outs, out_bytes, scr_bytes = jpeg.layout(jobs, pool0 + o, subseq_bits)
+    up = pool0 + o + len(sec) + 8 * len(TRAILER)
+    buf = np.zeros(up, dtype=np.uint8)
+    desc = buf[:B * 64].view(np.int64).reshape(B, 8)
+    jit = buf[B * 64:B * 96].view(np.uint32).reshape(B, 8)
+    tgt = buf[B * 96:B * 104].view(np.int64)
+    pool = buf[pool0:]
+    if policy:
+        ops = buf[B * 104:B * 168].view(np.uint32).reshape(B, 2, RECORD_WORDS)
+        for i, sample in enumerate(samples):
+            ops[i] = sample[4]
+    k = 0
+    for i, (region, words, rec, target) in enumerate(s[:4] for s in samples):
+        if offs[i] is None:
+            desc[i, 0] = up - pool0 + outs[k]
+            k += 1
+        else:
+            desc[i, 0] = offs[i]
+            pool[offs[i]:offs[i] + region.nbytes] = region.reshape(-1)
+        desc[i, 1:] = words
+        if rec is not None:
+            jit[i] = rec
+        tgt[i] = target
+    buf[pool0 + o:pool0 + o + len(sec)] = sec
+    buf[up - 8 * len(TRAILER):].view(np.int64)[:] = (len(jobs), pool0 + o, up, out_bytes, scr_bytes, subseq_bits, 0, 0)
+    return torch.from_numpy(buf)
+
+
+def trailer(buf):
+    """{TRAILER name: value} of a pack_decode batch (a host tensor)."""
+    return dict(zip(TRAILER, buf[-8 * len(TRAILER):].view(torch.int64).tolist()))
+
+
+class _DecodeCollate(object):
+    def __init__(self, subseq_bits):
+        self.subseq_bits = subseq_bits
+
+    def __call__(self, samples):
+        return pack_decode(samples, self.subseq_bits), len(samples)
 
 
 def unpack(buf, B, policy=False):
@@ -263,25 +345,45 @@ class _Samples(torch.utils.data.Dataset):
     """Position p of one rank's epoch list -> (region, desc words, jitter record, target[, op records]); runs in the
     DataLoader workers."""
 
-    def __init__(self, dataset, index, train, size, seed, epoch, rank, jitter, policy=None):
+    def __init__(self, dataset, index, train, size, seed, epoch, rank, jitter, policy=None, decode=False):
         self.dataset, self.index, self.train, self.size = dataset, index, train, size
         self.seed, self.epoch, self.rank, self.jitter, self.policy = seed, epoch, rank, jitter, policy
+        self.decode = decode
 
     def __len__(self):
         return len(self.index)
 
+    def _image(self, i):
+        """(decoded image, None) or, for a stream the device decodes, (None, (bytes, Header)).  A routed file is decoded
+        from the bytes already read, as the default loader decodes it."""
+        path = self.dataset.img_path[i]
+        if self.decode and not path.endswith(".npy"):
+            with open(path, "rb") as f:
+                data = f.read()
+            hd = jpeg.parse(data)
+            if not isinstance(hd, str):
+                return None, (data, hd)
+            import io
+            from PIL import Image
+            return Image.open(io.BytesIO(data)).convert("RGB"), None
+        return self.dataset.loader(path), None
+
     def __getitem__(self, p):
         i = int(self.index[p])
-        img = self.dataset.loader(self.dataset.img_path[i])
+        img, job = self._image(i)
         if self.train and self.policy is not None:
-            region, words, _ = train_sample(img, self.size, uniforms(self.seed, self.epoch, self.rank, p))
+            u = uniforms(self.seed, self.epoch, self.rank, p)
+            region, words, _ = train_sample(img, self.size, u) if job is None else train_job(*job, self.size, u)
             ops = draw_policy(self.policy, policy_uniforms(self.seed, self.epoch, self.rank, p))
             return region, words, None, int(self.dataset.targets[i]), policy_record(ops, self.size)
         if self.train:
             u = uniforms(self.seed, self.epoch, self.rank, p)
-            region, words, rec = train_sample(img, self.size, u, self.jitter)
+            if job is None:
+                region, words, rec = train_sample(img, self.size, u, self.jitter)
+            else:
+                region, words, rec = train_job(*job, self.size, u, self.jitter)
         else:
-            region, words, rec = eval_sample(img, self.size)
+            region, words, rec = eval_sample(img, self.size) if job is None else eval_job(*job, self.size)
         return region, words, rec, int(self.dataset.targets[i])
 
 
@@ -290,14 +392,26 @@ class DeviceLTLoader(object):
     every sample for evaluation.  ``dset_name`` picks mean / std and the jitter's hue (imbalanced_dataset.mean_std_hue);
     ``jitter=False`` trains with crop and flip only.  ``policy`` ("imagenet", "randaugment", "cifar"; training only) runs
     that auto-augment policy on the device instead of the jitter.  ``mode`` = --sampler.  ``set_epoch`` as
-    DistributedSampler; without it each pass over the loader advances the epoch by one."""
+    DistributedSampler; without it each pass over the loader advances the epoch by one.  ``decode="device"``
+    (--device-decode) decodes the baseline JPEG files on the device (iif_jpeg_decode, ``subseq_bits`` its subsequence
+    length) instead of in the workers; it replaces the default loader only.  ``decode_failures()`` counts the images whose
+    scan the device found malformed (their regions are jpeg.FILL)."""
 
     def __init__(self, dataset, batch_size, train=True, size=224, dset_name="imagenet_lt", jitter=True, seed=0, mode="random",
-                 distributed=False, rank=None, world=None, workers=4, device="cuda", policy=None):
+                 distributed=False, rank=None, world=None, workers=4, device="cuda", policy=None, decode="host",
+                 subseq_bits=jpeg.SUBSEQ_BITS):
         if mode not in ("random", "upsampling", "downsampling"):
             raise ValueError("unknown sampler %r (random, upsampling, downsampling)" % (mode,))
         if policy is not None and policy not in POLICIES:
             raise ValueError("unknown policy %r (%s)" % (policy, ", ".join(POLICIES)))
+        if decode not in ("host", "device"):
+            raise ValueError("unknown decode %r (host, device)" % (decode,))
+        if decode == "device" and getattr(dataset, "loader", None) is not _default_loader:
+            raise ValueError("decode='device' replaces the default loader only; this dataset has a custom loader=")
+        if not jpeg.MIN_SUBSEQ_BITS <= int(subseq_bits) <= 1 << 24:
+            raise ValueError("subseq_bits must be in [%d, 2^24]" % jpeg.MIN_SUBSEQ_BITS)
+        self.decode, self.subseq_bits = decode, int(subseq_bits)
+        self._scratch, self._failures = None, None
         self.dataset = dataset
         self.batch_size, self.train, self.size, self.seed, self.mode = int(batch_size), train, int(size), int(seed), mode
         self.mean, self.std, hue = mean_std_hue(dset_name)
@@ -332,16 +446,46 @@ class DeviceLTLoader(object):
 
     def batches(self, epoch):
         """The packed host batches of one epoch: (uint8 tensor, pinned when a GPU is present; sample count)."""
+        device = self.decode == "device"
         samples = _Samples(self.dataset, self.indices(epoch), self.train, self.size, self.seed, epoch, self.rank, self.jitter,
-                           self.policy)
+                           self.policy, decode=device)
         return torch.utils.data.DataLoader(samples, batch_size=self.batch_size, shuffle=False, drop_last=self.train,
-                                           num_workers=self.workers, collate_fn=_collate, pin_memory=torch.cuda.is_available())
+                                           num_workers=self.workers, collate_fn=_DecodeCollate(self.subseq_bits) if device
+                                           else _collate, pin_memory=torch.cuda.is_available())
 
     def __iter__(self):
         epoch = self.epoch
         self.epoch += 1
         for buf, B in self.batches(epoch):
-            yield self.build(buf.to(self.device, non_blocking=True), B)
+            dev = self.upload(buf) if self.decode == "device" else buf.to(self.device, non_blocking=True)
+            yield self.build(dev, B)
+
+    def upload(self, buf):
+        """The device buffer of a pack_decode batch: the upload (one copy), then the regions iif_jpeg_decode writes there
+        (launched here, on the current stream)."""
+        t = trailer(buf)
+        up, n = t["upload"], t["jobs"]
+        dev = torch.empty(up + t["out_bytes"], dtype=torch.uint8, device=self.device)
+        dev[:up].copy_(buf, non_blocking=True)
+        if n:
+            if self._scratch is None or self._scratch.numel() < t["scratch_bytes"] or self._scratch.device != dev.device:
+                self._scratch = torch.empty(t["scratch_bytes"] * 5 // 4 + 16, dtype=torch.uint8, device=dev.device)
+            sec = t["section"]
+            rec = dev[sec:sec + n * jpeg.REC_WORDS * 8].view(torch.int64).view(n, jpeg.REC_WORDS)
+            status = torch.empty(n, dtype=torch.int32, device=dev.device)
+            jpeg.launch(dev[:up], rec, n, self._scratch, dev[up:], status, t["subseq_bits"])
+            fails = (status != 0).sum()
+            self._failures = fails if self._failures is None else self._failures + fails
+        return dev
+
+    def decode_failures(self, reset=False):
+        """Images of this loader's batches since the last reset whose scan the device could not decode (``reset``: start
+        counting again).  Synchronises with the device: ask where the caller waits anyway (train.py: at the end of an
+        epoch)."""
+        n = 0 if self._failures is None else int(self._failures)
+        if reset:
+            self._failures = None
+        return n
 
     def build(self, dev, B):
         """(image, target) of one packed batch of B samples already on the device."""

@@ -184,12 +184,16 @@ def check_device_augment(args):
     augment_on_device = getattr(args, "device_augment", False)
     if device_policy and not augment_on_device:
         raise SystemExit("--device-policy needs --device-augment: the policy runs in the device pipeline that flag builds")
+    if getattr(args, "device_decode", False) and not augment_on_device:
+        raise SystemExit("--device-decode needs --device-augment: the decoded regions feed the device pipeline that flag builds")
     if not augment_on_device:
         return
     if not getattr(args, "data_path", ""):
         raise SystemExit("--device-augment needs --data-path: it builds batches from the dataset's files, and the synthetic "
                          "sets have none")
     name = args.dset_name.lower()
+    if getattr(args, "device_decode", False) and name.startswith("cifar"):
+        raise SystemExit("--device-decode decodes the list datasets' JPEG files; CIFAR reads pickled arrays")
     policy = getattr(args, "auto_augment", None)
     if device_policy:
         if policy in (None, "", "None"):
@@ -200,6 +204,14 @@ def check_device_augment(args):
     if not name.startswith("cifar") and policy in HOST_POLICIES:
         raise SystemExit("--device-augment does not run --auto-augment %s: that policy stays on the host; drop one of the two "
                          "flags; add --device-policy to run it on the device" % (policy,))
+
+
+def report_decode_failures(epoch, train_loader, eval_loader):
+    """--device-decode: the images of this epoch (training and evaluation loaders, this rank) whose scan the device could
+    not decode; both counts restart.  Printed by the main process."""
+    n_train, n_eval = train_loader.decode_failures(reset=True), eval_loader.decode_failures(reset=True)
+    if utils.is_main_process():
+        print("epoch %d: device JPEG decode failures: train %d, eval %d" % (epoch, n_train, n_eval))
 
 
 def main(args):
@@ -253,6 +265,8 @@ def main(args):
         if args.distributed:
             sync_buffers(model)               # rank 0's BN statistics everywhere, as DDP's broadcast_buffers
         acc = evaluate(model, criterion, data_loader_test, device=device, stats=stats, train_targets=shot_targets)
+        if getattr(data_loader, "decode", "host") == "device":
+            report_decode_failures(epoch, data_loader, data_loader_test)
         best_acc = max(best_acc, acc)
         if args.output_dir:
             nxt = lr_at(args, epoch + 1, 10 ** 9, 10 ** 9)
@@ -323,6 +337,9 @@ def get_args_parser(add_help=True):
     p.add_argument("--device-policy", dest="device_policy", action="store_true",
                    help="with --device-augment: run the --auto-augment policy (imagenet, randaugment, cifar) on the device "
                    "too, in place of ColorJitter (iif_lt_augment_policy)")
+    p.add_argument("--device-decode", dest="device_decode", action="store_true",
+                   help="with --device-augment: decode the baseline JPEG files on the device (iif_amd/jpeg.py); the workers "
+                   "only read and parse them, and decode every other file as before")
     p.add_argument("--random-erase", default=0.0, type=float)
     p.add_argument("--apex", action="store_true")
     p.add_argument("--apex-opt-level", default="O2", type=str)

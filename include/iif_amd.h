@@ -774,6 +774,39 @@ int iif_lt_augment(const uint8_t* pool, int64_t pool_bytes, const int64_t* desc,
 int iif_lt_augment_policy(const uint8_t* pool, int64_t pool_bytes, const int64_t* desc, const uint32_t* ops, int64_t batch,
                           int size, const float* mean_std, float* work, float* out, void* stream);
 
+/* Baseline JPEG decoding (iif_amd/jpeg.py; DeviceLTLoader(decode="device"), --device-decode): TWO launches turn the
+ * entropy-coded scans of n images into uint8 HWC regions with 3 channels, equal byte for byte to libjpeg's default decode
+ * (ISLOW IDCT, fancy upsampling, jdcolor's YCbCr -> RGB; grey repeated), each cropped to its record's box:
+ *   one workgroup per image destuffs its scan, decodes it in parallel (one thread per restart interval, or self-synchronising
+ *   bit subsequences of subseq_bits bits), dequantises and inverse-transforms the blocks the box needs; then the pixel
+ *   launch upsamples the chroma, converts and stores.
+ * data: uint8, data_bytes long, 16-byte aligned: what the records point into.
+ * rec: int64 [n][IIF_JPEG_REC_WORDS] (device memory): byte offset in data of the scan (16-aligned; the bytes after the SOS
+ *   header, markers and stuffing included) and its length, offset of the table block (16-aligned: int16 [3][64]
+ *   quantisation tables in natural order, then 6 Huffman lookup tables of 1424 bytes: uint16 [512] 9-bit table (code
+ *   length << 8 | symbol, 0: a longer code), int32 [18] maxcode, int32 [18] symbol offset, uint8 [256] symbols), height,
+ *   width, components (1, or 3 in one interleaved YCbCr scan), the luma sampling factors h, v (1x1, 2x1, 2x2), restart
+ *   interval in MCUs (0: none), box top, left, height, width, byte offset of the region in out, byte offset of the image's
+ *   scratch (16-aligned) and its size (iif_amd/jpeg.py scratch_bytes), then one word per component: DC slot | AC slot << 4;
+ *   the other words are unused.
+ * scratch: uint8, 16-byte aligned, scratch_bytes long.  out: uint8, out_bytes long.  status: int32 [n], written for every
+ *   image: IIF_JPEG_OK or why it was not decoded.
+ * A record that reaches outside data, out or scratch, or whose geometry is invalid, reads nothing and gets the status
+ * IIF_JPEG_BAD_RECORD; its region is filled with IIF_JPEG_FILL when the region's offset and size lie inside out.  A malformed scan (an invalid code, a coefficient index past 63, a scan that ends before the
+ * box's last MCU, a missing restart marker) fills that image's region with IIF_JPEG_FILL; the other images are exact.
+ * IIF_EINVAL before any launch: a null pointer, data or scratch not 16-byte aligned, a negative size, n < 0 or > 65535,
+ * subseq_bits < 32 or > 2^24.  n == 0: IIF_OK, no launch. */
+#define IIF_JPEG_REC_WORDS 32
+#define IIF_JPEG_FILL 128
+#define IIF_JPEG_OK 0
+#define IIF_JPEG_BAD_RECORD 1
+#define IIF_JPEG_BAD_CODE 2
+#define IIF_JPEG_OVERFLOW 3
+#define IIF_JPEG_TRUNCATED 4
+#define IIF_JPEG_NO_RESTART 5
+int iif_jpeg_decode(const uint8_t* data, int64_t data_bytes, const int64_t* rec, int64_t n, uint8_t* scratch,
+                    int64_t scratch_bytes, uint8_t* out, int64_t out_bytes, int subseq_bits, int32_t* status, void* stream);
+
 /* Compute-unit budget of the persistent grids (the weights-in-registers kernels, the stem, the streaming 1x1 kernel size their
  * grids to one or two resident blocks per CU).  Process-wide, default 0 = every CU of the device; a rank whose gradient
  * all-reduce (RCCL kernels, classification/train.py:230-234 DDP) overlaps backward sets e.g. 240 so that the reduction's
