@@ -960,6 +960,34 @@ int iif_bn_finalize_stats_sums(const float* partial, int n_partials, int64_t m, 
                               as_stream(stream), partial2, n_partials2, c2, sums2);
 }
 
+// Inference-mode BN of a whole network in one launch: block = layer, threads stride over its channels.  The arithmetic is
+// torch's on [C] vectors, operation for operation (invstd = rsqrt(var + eps), correctly rounded; a = gamma * invstd; b = beta - mean * a with the
+// product rounded on its own: explicit round-to-nearest intrinsics, no contraction whatever the compiler flags say).
+namespace {
+__global__ void __launch_bounds__(256) bn_fold_kernel(const iif_bn_fold_desc* tab, float eps) {
+    const iif_bn_fold_desc d = tab[blockIdx.x];
+    for (int c = threadIdx.x; c < d.c; c += 256) {
+        const float mean = d.running_mean[c];
+        // (torch's rsqrt kernel on this stack is the correctly rounded 1 / sqrt - rsqrtf / v_rsq_f32 is 1 ulp off on 14 % of
+        // 300 000 probed values, float(1.0 / sqrt(double(x))) on none)
+        const float invstd = (float)(1.0 / sqrt((double)__fadd_rn(d.running_var[c], eps)));
+        const float a = __fmul_rn(d.gamma[c], invstd);
+        d.stats[c] = mean;
+        d.stats[d.c + c] = invstd;
+        d.stats[2 * d.c + c] = a;
+        d.stats[3 * d.c + c] = __fsub_rn(d.beta[c], __fmul_rn(mean, a));
+    }
+}
+}  // namespace
+
+int iif_bn_fold(const iif_bn_fold_desc* table, int n_layers, float eps, void* stream) {
+    if (!table || n_layers <= 0 || !(eps >= 0.f)) return IIF_EINVAL;
+    if (reinterpret_cast<uintptr_t>(table) & 7) return IIF_EUNSUPPORTED;
+    hipLaunchKernelGGL(bn_fold_kernel, dim3((unsigned)n_layers), dim3(256), 0, as_stream(stream), table, eps);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
 int iif_bn_apply(const void* x, int dtype, int64_t m, int c, const float* stats, const void* residual,
                  const float* residual_stats, int relu, void* y, uint8_t* relu_bits, void* stream) {
     if (!x || !stats || !y || m <= 0 || c <= 0) return IIF_EINVAL;

@@ -13,6 +13,18 @@
         if (e__ != hipSuccess) return IIF_ELAUNCH;  \
     } while (0)
 
+// Route probe (iif_conv_affine_route): while g_iif_route_probe points at an int, a forward launch site of the convolution
+// files records its kernel family there and returns IIF_OK INSTEAD of launching - the query walks the very routing code a
+// launch walks, so it cannot drift from it.  Host state like the test switches: not for concurrent callers.
+enum { IIF_ROUTE_NONE = 0, IIF_ROUTE_TILE = 1, IIF_ROUTE_TILE_2STAGE = 2, IIF_ROUTE_TILE_GENERAL = 3, IIF_ROUTE_TILE256 = 4,
+       IIF_ROUTE_HALO = 5, IIF_ROUTE_FRAG = 6, IIF_ROUTE_FRAG_G16 = 7, IIF_ROUTE_STREAM1X1 = 8, IIF_ROUTE_REGW1X1 = 9,
+       IIF_ROUTE_REGW3X3 = 10, IIF_ROUTE_REGSTAGE = 11 };
+extern int* g_iif_route_probe;
+#define IIF_ROUTE_PROBE(code)                                             \
+    do {                                                                  \
+        if (g_iif_route_probe) { *g_iif_route_probe = (code); return IIF_OK; } \
+    } while (0)
+
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
@@ -85,11 +97,14 @@ int iif_regw1x1_fwdbn_launch(const void* src, const void* wgt, void* dst, int M,
                              const void* res, const float* aff, const float* aff2, unsigned char* relu_out, hipStream_t st);
 int iif_regw1x1_stats_launch(const void* src, const void* wgt, float* bn_partial, long long bn_cap, int bn_row0, int* rows_out,
                              int M, int K, int N, int spitch, int ldw, int dpitch, hipStream_t st, const iif_regw_prologue* pro = nullptr);
-// 3x3 / stride 1 / pad 1, C -> C channels (64, 128), forward or data gradient (explicit tap list), optional upstream BN-backward sums
+// 3x3 / stride 1 / pad 1, C -> C channels (64, 128), forward or data gradient (explicit tap list), optional upstream BN-backward sums;
+// aff (forward, no sums): dst = relu(fmaf(a, bf16(conv), b) + r), r = nothing | res | fmaf(a2, res, b2), the coefficient rows of
+// iif_bn_apply; relu_out nullable
 bool iif_regw3x3_ok(int N, int H, int W, int C);
 int iif_regw3x3_launch(const void* src, const void* wgt, void* dst, float* bn_partial, long long bn_cap, int bn_row0, int* rows_out,
                        int N, int H, int W, int C, int ldw, const signed char* tap_dy, const signed char* tap_dx, const unsigned char* tap_w,
-                       const void* bw_x, const unsigned char* bw_bits, const float* bw_stats, hipStream_t st);
+                       const void* bw_x, const unsigned char* bw_bits, const float* bw_stats, hipStream_t st, const float* aff = nullptr,
+                       const float* aff2 = nullptr, const void* res = nullptr, unsigned char* relu_out = nullptr);
 
 // Compute units a persistent grid (one or two resident blocks per CU: conv_regw.hip, conv_stem.hip, the streaming 1x1 kernel)
 // sizes itself to: the device's count, or the budget set by iif_set_cu_budget() when that is smaller (a rank that overlaps

@@ -32,6 +32,8 @@
 #define IIF_CONV_AUX_SRC 0
 #endif
 
+int* g_iif_route_probe = nullptr;
+
 namespace {
 
 template <typename T> struct ET;
@@ -384,8 +386,14 @@ __device__ __forceinline__ void staged_drain(const ConvArgs& a, unsigned char* s
         for (int q = 0; q < 8; ++q) { bmean[q] = a.bw_stats[goff + n + q]; bistd[q] = a.bw_stats[a.dpitch + goff + n + q]; }
     }
     if (a.aff && n < a.Cd) {                        // never together with bw_x: the same registers carry (a, b)
+        // (grouped: channel goff + n of the dpitch-wide coefficient rows, as bw_stats above)
 #pragma unroll
-        for (int q = 0; q < 8; ++q) { bmean[q] = a.aff[2 * a.Cd + n + q]; bistd[q] = a.aff[3 * a.Cd + n + q]; }
+        for (int q = 0; q < 8; ++q) { bmean[q] = a.aff[2 * a.dpitch + goff + n + q]; bistd[q] = a.aff[3 * a.dpitch + goff + n + q]; }
+    }
+    const bool has_aff2 = a.aff && a.aff2;
+    if (has_aff2 && n < a.Cd) {                     // never together with the sums (bn_partial / bw_x / mask_store): bs / bq carry (a2, b2)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { bs[q] = a.aff2[2 * a.dpitch + goff + n + q]; bq[q] = a.aff2[3 * a.dpitch + goff + n + q]; }
     }
     if (n < a.Cd) {
         // Everything a batch of RBATCH rows needs from memory (residual, its ReLU bits, the upstream bits, the upstream x) is
@@ -448,7 +456,10 @@ __device__ __forceinline__ void staged_drain(const ConvArgs& a, unsigned char* s
                     for (int q = 0; q < 4; ++q) {
                         float lo = fmaf(bmean[2 * q], bf16_bits_to_f32(v[q] & 0xffffu), bistd[2 * q]);
                         float hi = fmaf(bmean[2 * q + 1], __uint_as_float(v[q] & 0xffff0000u), bistd[2 * q + 1]);
-                        if (has_res) { lo += bf16_bits_to_f32(rr[q] & 0xffffu); hi += __uint_as_float(rr[q] & 0xffff0000u); }
+                        if (has_aff2) {                 // the shortcut convolution's raw output under its own BN (bn_apply_kernel, RES == 2)
+                            lo += fmaf(bs[2 * q], bf16_bits_to_f32(rr[q] & 0xffffu), bq[2 * q]);
+                            hi += fmaf(bs[2 * q + 1], __uint_as_float(rr[q] & 0xffff0000u), bq[2 * q + 1]);
+                        } else if (has_res) { lo += bf16_bits_to_f32(rr[q] & 0xffffu); hi += __uint_as_float(rr[q] & 0xffff0000u); }
                         bits |= (lo > 0.f ? 1u : 0u) << (2 * q);
                         bits |= (hi > 0.f ? 1u : 0u) << (2 * q + 1);
                         v[q] = pack_bf16x2(fmaxf(lo, 0.f), fmaxf(hi, 0.f));
@@ -1816,7 +1827,10 @@ inline bool use_stream1x1(const ConvArgs& a, bool utap, int esz, bool outf32, St
     const bool force_ = g_sw.force_stream;
     if (g_sw.no_stream || !utap || esz != 2 || outf32 || a.groups > 1 || a.scatter || a.in_shift != 0 || a.sshift != 0) return false;
     if (a.R != 1 || a.S != 1 || a.pad != 0 || a.ntaps != 1 || a.bias || a.src2 || a.sbias || a.mask_store) return false;
+    // (aff by default, measured in the fused evaluation forward at batch 256: ResNet50 4.863 -> 4.898 ms, se_resnet50 7.406 -> 7.354 ms,
+    // +0.7 % / -0.7 %: level, so the affine launches stay on the tile kernels)
     if ((a.no_store || a.aff) && !force_) return false;
+    if (a.aff2) return false;                                               // (its store waves take a plain residual only)
     if (a.Hs != a.Hd || a.Ws != a.Wd || (a.Cs % 32) || a.spitch != a.Cs || a.dpitch != a.Cd) return false;
     const int K = a.Cs, N = a.Cd;
     // the shapes whose whole weight matrix is resident (measured alone AND in the step, scripts/bm_stream1x1.py): 64 -> 256,
@@ -1900,10 +1914,11 @@ int launch_one(ConvArgs a, bool utap, int64_t src_bytes, int64_t wgt_bytes, hipS
     if constexpr (sizeof(T) == 2 && !OUTF32) {          // 3x3 with the weights in registers (conv_regw.hip): 64 -> 64 channels
         if (!force_v1_ && !g_sw.no_regw && utap && src_bytes < 0x7f000000LL && a.ntaps == 9 && a.R == 3 && a.S == 3 && a.pad == 1 &&
             a.Hs == a.Hd && a.Ws == a.Wd && a.groups == 1 && a.Cs == a.Cd && a.spitch == a.Cs && a.dpitch == a.Cd && !a.scatter &&
-            a.in_shift == 0 && !a.res && !a.res_bits && !a.bias && !a.mask_store && !a.src2 && !a.sbias && !a.no_store && !a.aff &&
+            a.in_shift == 0 && (!a.res || a.aff) && !a.res_bits && !a.bias && !a.mask_store && !a.src2 && !a.sbias && !a.no_store &&
             a.Cs == 64 && (!(a.bw_x || a.bw_bits) || a.bn_partial) && iif_regw3x3_ok(a.N, a.Hd, a.Wd, a.Cs)) {
             const int rc = iif_regw3x3_launch(a.src, a.wgt, a.dst, a.bn_partial, a.bn_cap, a.bn_row0, a.rows_out, a.N, a.Hd, a.Wd, a.Cs, a.ldw,
-                                              a.tap_dy, a.tap_dx, a.tap_w, a.bw_x, a.bw_bits, a.bw_stats, st);
+                                              a.tap_dy, a.tap_dx, a.tap_w, a.bw_x, a.bw_bits, a.bw_stats, st, a.aff, a.aff2,
+                                              a.aff ? a.res : nullptr, a.relu_out);
             if (rc != IIF_EUNSUPPORTED) return rc;
         }
     }
@@ -1915,10 +1930,12 @@ int launch_one(ConvArgs a, bool utap, int64_t src_bytes, int64_t wgt_bytes, hipS
         if (blocks2 > 0x7fffffff) return IIF_EUNSUPPORTED;
         if (a.wfrag_kind == 1) {
             if (a.Cs != 64 || a.Cd != 64) return IIF_EINVAL;       // (the 16-channel format describes 64-channel chunks)
+            IIF_ROUTE_PROBE(IIF_ROUTE_FRAG_G16);
             hipLaunchKernelGGL(conv3x3_g16_kernel, dim3((unsigned)blocks2, (unsigned)a.groups), dim3(256), 0, st, a, (unsigned)src_bytes);
             IIF_LAUNCH_CHECK();
             return IIF_OK;
         }
+        IIF_ROUTE_PROBE(IIF_ROUTE_FRAG);
         hipLaunchKernelGGL(conv3x3_v2n64_kernel, dim3((unsigned)blocks2, (unsigned)a.groups), dim3(256), 0, st, a, (unsigned)src_bytes);
         IIF_LAUNCH_CHECK();
         return IIF_OK;
@@ -1931,6 +1948,7 @@ int launch_one(ConvArgs a, bool utap, int64_t src_bytes, int64_t wgt_bytes, hipS
         if (const int rc = claim_partial_rows(a)) return rc;
         const int64_t blocksh = (int64_t)((a.mtiles + 7) / 8) * 8 * a.ntiles;
         if (blocksh > 0x7fffffff) return IIF_EUNSUPPORTED;
+        IIF_ROUTE_PROBE(IIF_ROUTE_HALO);
         if (bm == 128) hipLaunchKernelGGL(conv3x3_halo128_kernel, dim3((unsigned)blocksh), dim3(256), 0, st, a, (unsigned)src_bytes,
                                           (unsigned)wgt_bytes);
         else hipLaunchKernelGGL(conv3x3_halo_kernel, dim3((unsigned)blocksh), dim3(512), 0, st, a, (unsigned)src_bytes,
@@ -1956,6 +1974,7 @@ int launch_one(ConvArgs a, bool utap, int64_t src_bytes, int64_t wgt_bytes, hipS
             }
             const unsigned sb = (unsigned)src_bytes, wb = (unsigned)wgt_bytes;
             const dim3 g((unsigned)grid), blk(64 * (4 + STREAM_SW));
+            IIF_ROUTE_PROBE(IIF_ROUTE_STREAM1X1);
             if (sp.bn == 256) hipLaunchKernelGGL((gemm1x1_stream_kernel<256, 64>), g, blk, 0, st, a, sb, wb);
             else if (sp.bn == 128) hipLaunchKernelGGL((gemm1x1_stream_kernel<128, 256>), g, blk, 0, st, a, sb, wb);
             else hipLaunchKernelGGL((gemm1x1_stream_kernel<64, 256>), g, blk, 0, st, a, sb, wb);
@@ -1969,6 +1988,7 @@ int launch_one(ConvArgs a, bool utap, int64_t src_bytes, int64_t wgt_bytes, hipS
         if (const int rc = claim_partial_rows(a)) return rc;
         const int64_t blocks256 = (int64_t)((a.mtiles + 7) / 8) * 8 * a.ntiles;
         if (blocks256 > 0x7fffffff) return IIF_EUNSUPPORTED;
+        IIF_ROUTE_PROBE(IIF_ROUTE_TILE256);
         hipLaunchKernelGGL((conv_igemm_dma_utap256_kernel<T, OUTF32>), dim3((unsigned)blocks256, (unsigned)a.groups), dim3(512), 0,
                            st, a, (unsigned)src_bytes, (unsigned)wgt_bytes);
         IIF_LAUNCH_CHECK();
@@ -1983,13 +2003,14 @@ int launch_one(ConvArgs a, bool utap, int64_t src_bytes, int64_t wgt_bytes, hipS
     const bool force_v1 = g_sw.regstage;
     // LDS-DMA addressing is a 32-bit byte offset with a hardware range check: both operands must be < 2 GiB
     const bool dma = !force_v1 && src_bytes < 0x7f000000LL && wgt_bytes < 0x7f000000LL;
-    if (a.bn_partial && !dma) return IIF_EUNSUPPORTED;     // partial sums come out of the staged epilogue only
+    if ((a.bn_partial || a.aff) && !dma) return IIF_EUNSUPPORTED;     // partial sums / the BN affine come out of the staged epilogue only
     if (const int rc = claim_partial_rows(a)) return rc;
     if (a.groups > 1 && !dma) return IIF_EUNSUPPORTED;     // grouped convolutions exist on the pipelined kernels only
     if (a.scatter && !(dma && utap)) return IIF_EUNSUPPORTED;
     const dim3 grid((unsigned)blocks, (unsigned)a.groups), blk(256);
     if (dma) {
         const unsigned sb = (unsigned)src_bytes, wb = (unsigned)wgt_bytes;
+        if (!utap) IIF_ROUTE_PROBE(IIF_ROUTE_TILE_GENERAL);
         if (utap) {
             // two-stage / 4-blocks-per-CU variant up to K = 2304
             // (round 5, same-call A/B: the long-K launches of small grids - the 7 x 7 stage's 392-block data gradients with 64 K steps -
@@ -1998,12 +2019,14 @@ int launch_one(ConvArgs a, bool utap, int64_t src_bytes, int64_t wgt_bytes, hipS
             const bool shortk = sizeof(T) == 2 && !OUTF32 && a.ntaps * a.Cs <= kTwoStageK && (a.Cd & 7) == 0 && !a.bias;
             if constexpr (sizeof(T) == 2 && !OUTF32) {
                 if (shortk) {
+                    IIF_ROUTE_PROBE(IIF_ROUTE_TILE_2STAGE);
                     if (narrow) hipLaunchKernelGGL((conv_igemm_dma_utap_k64_kernel<64>), grid, blk, 0, st, a, sb, wb);
                     else hipLaunchKernelGGL((conv_igemm_dma_utap_k64_kernel<128>), grid, blk, 0, st, a, sb, wb);
                     IIF_LAUNCH_CHECK();
                     return IIF_OK;
                 }
             }
+            IIF_ROUTE_PROBE(IIF_ROUTE_TILE);
             if (narrow) hipLaunchKernelGGL((conv_igemm_dma_utap_kernel<T, 64, OUTF32>), grid, blk, 0, st, a, sb, wb);
             else hipLaunchKernelGGL((conv_igemm_dma_utap_kernel<T, 128, OUTF32>), grid, blk, 0, st, a, sb, wb);
         } else {
@@ -2011,6 +2034,7 @@ int launch_one(ConvArgs a, bool utap, int64_t src_bytes, int64_t wgt_bytes, hipS
             else hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 128, OUTF32>), grid, blk, 0, st, a, sb, wb);
         }
     } else {
+        IIF_ROUTE_PROBE(IIF_ROUTE_REGSTAGE);
         if (narrow) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, OUTF32>), grid, blk, 0, st, a);
         else hipLaunchKernelGGL((conv_igemm_kernel<T, 128, OUTF32>), grid, blk, 0, st, a);
     }
@@ -2059,7 +2083,7 @@ int launch_conv(const ConvArgs& a0, int64_t src_bytes, int64_t wgt_bytes, hipStr
             const int rc = iif_regw1x1_fwdbn_launch(a.src, a.wgt, a.dst, a.M, a.Cs, a.Cd, a.spitch, a.ldw, a.dpitch, a.res, a.aff, a.aff2, a.relu_out, st);
             if (rc != IIF_EUNSUPPORTED) return rc;
         }
-        if (a.aff2) return IIF_EUNSUPPORTED;                  // (the tile kernels' BN epilogue takes a plain residual only)
+        // (aff2 beyond this point: staged_drain of the tile / 256-row / halo / fragment kernels, iif_conv_igemm_affine)
         if (a.rx_src2 && !(geo1x1x && iif_regw1x1_rx_ok(a.M, a.Cs, a.Cd, a.rx_k2))) return IIF_EUNSUPPORTED;
         // narrow -> wide 1x1 layers: weights in registers (conv_regw.hip)
         const bool epi = a.res || a.res_bits || a.bw_x || a.bw_bits || a.mask_store;
@@ -2076,7 +2100,8 @@ int launch_conv(const ConvArgs& a0, int64_t src_bytes, int64_t wgt_bytes, hipStr
         if (a.rx_src2) return IIF_EUNSUPPORTED;               // (no other kernel recomputes the upstream x)
     }
     if (a.rx_src2 || a.pro_stats) return IIF_EUNSUPPORTED;
-    if (!utap) return (a.src2 || a.sbias || a.mask_store || a.no_store || a.aff) ? IIF_EUNSUPPORTED : launch_one<T, OUTF32>(a, false, src_bytes, wgt_bytes, st);
+    // (not uniform-tap, e.g. 16 source channels: the general-addressing pipelined kernel drains through staged_drain too)
+    if (!utap) return (a.src2 || a.sbias || a.mask_store || a.no_store || (a.aff && !dma_ok)) ? IIF_EUNSUPPORTED : launch_one<T, OUTF32>(a, false, src_bytes, wgt_bytes, st);
     if (!a.transposed || a.sshift == 0) {
         for (int r = 0; r < a.R; ++r)
             for (int s = 0; s < a.S; ++s) {
@@ -2168,7 +2193,8 @@ namespace {
 struct ConvExtra { int mask_store; const void* src2; int cs2; const float* sbias; int no_store; const float* aff; unsigned char* relu_out; const float* aff2;
                    const void* rx_src2; const void* rx_w3; int rx_k2, rx_ldw3;
                    const float* pro_stats; void* pro_out; unsigned char* pro_bits; float* pro_csum;
-                   float* pg_slab; long long pg_cap; int pg_ld; int* pg_count; };
+                   float* pg_slab; long long pg_cap; int pg_ld; int* pg_count;
+                   int aff_any; };           // aff on every geometry the staged epilogue serves (iif_conv_igemm_affine)
 int conv_entry(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
                const unsigned char* res_bits, const float* bias, float* bn_partial, int64_t bn_partial_floats,
                int32_t* n_partials, void* stream, const void* bw_x = nullptr, const unsigned char* bw_bits = nullptr,
@@ -2355,6 +2381,56 @@ extern "C" int iif_conv_igemm_masked_res(const iif_conv_desc* d, const void* src
     return conv_entry(d, src, wgt, dst, res, res_bits, nullptr, nullptr, 0, nullptr, stream);
 }
 
+namespace {
+// Descriptors whose forward launch ends in a kernel that drains through the LDS-staged epilogue (or the register-weight 3x3
+// kernel's affine drain): bf16 in and out, whole 16-byte vectors per destination row and group, both operands within the
+// 32-bit LDS-DMA range.  Every route of launch_one behind these conditions carries the BN affine.
+bool affine_geometry_ok(const iif_conv_desc* d) {
+    if (!d || g_sw.regstage || d->transposed || d->dtype != IIF_BF16 || d->dst_dtype != IIF_BF16) return false;
+    if (d->n <= 0 || d->hs <= 0 || d->ws <= 0 || d->cs <= 0 || d->hd <= 0 || d->wd <= 0 || d->cd <= 0 || d->r <= 0 || d->s <= 0 || d->pad < 0) return false;
+    if (d->stride != 1 && d->stride != 2) return false;
+    const int64_t g = d->groups > 1 ? d->groups : 1;
+    // (the space-to-depth stem has a kernel of its own without this epilogue, and another K order than the tile kernels)
+    if (d->r == 4 && d->s == 4 && d->cs == 16 && d->cd == 64 && d->pad == 2 && d->stride == 1 && g == 1) return false;
+    if (g > 65535 || (d->cd % 8) || (d->cs % 8) || (d->ldw % 8) || d->ldw < d->r * d->s * d->cs) return false;
+    const int64_t M = (int64_t)d->n * d->hd * d->wd;
+    if (M > 0x7fffff00LL || (int64_t)d->n * d->hs * d->ws > 0x7fffff00LL) return false;
+    if ((int64_t)d->n * d->hs * d->ws * d->cs * g * 2 >= 0x7f000000LL || (int64_t)d->cd * d->ldw * 2 >= 0x7f000000LL) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int iif_conv_affine_ok(const iif_conv_desc* d, int has_res, int has_res_affine) {
+    if (has_res_affine && !has_res) return 0;
+    return affine_geometry_ok(d) ? 1 : 0;
+}
+
+extern "C" int iif_conv_affine_route(const iif_conv_desc* d, int has_res, int has_res_affine, int has_relu_bits) {
+    if (!iif_conv_affine_ok(d, has_res, has_res_affine) || g_iif_route_probe) return IIF_ROUTE_NONE;
+    // stand-in operands (never dereferenced: every launch site returns at its probe)
+    void* const p = reinterpret_cast<void*>(uintptr_t(1) << 20);
+    iif_conv_desc dd = *d;
+    if (dd.wgt_frag) dd.wgt_frag = p;
+    ConvExtra ex{};
+    ex.aff = (const float*)p; ex.aff2 = has_res_affine ? (const float*)p : nullptr; ex.relu_out = has_relu_bits ? (unsigned char*)p : nullptr;
+    ex.aff_any = 1;
+    int code = IIF_ROUTE_NONE;
+    g_iif_route_probe = &code;
+    const int rc = conv_entry(&dd, p, p, p, has_res ? p : nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &ex);
+    g_iif_route_probe = nullptr;
+    return rc == IIF_OK ? code : IIF_ROUTE_NONE;
+}
+
+extern "C" int iif_conv_igemm_affine(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
+                                     const float* res_affine, const float* affine, unsigned char* relu_bits, void* stream) {
+    if (!d || !src || !wgt || !dst || !affine || d->transposed || (res_affine && !res)) return IIF_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(affine) | reinterpret_cast<uintptr_t>(res_affine)) & 3) return IIF_EUNSUPPORTED;
+    if (!iif_conv_affine_ok(d, res != nullptr, res_affine != nullptr)) return IIF_EUNSUPPORTED;
+    ConvExtra ex{};
+    ex.aff = affine; ex.aff2 = res_affine; ex.relu_out = relu_bits; ex.aff_any = 1;
+    return conv_entry(d, src, wgt, dst, res, nullptr, nullptr, nullptr, 0, nullptr, stream, nullptr, nullptr, nullptr, &ex);
+}
+
 extern "C" int iif_conv_igemm(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
                               const float* bias, void* stream) {
     return iif_conv_igemm_bnstats(d, src, wgt, dst, res, bias, nullptr, 0, nullptr, stream);
@@ -2374,7 +2450,9 @@ int conv_entry(const iif_conv_desc* d, const void* src, const void* wgt, void* d
     if (d->dst_dtype != d->dtype && d->dst_dtype != IIF_F32) return IIF_EINVAL;
     const int pe = d->dtype == IIF_F32 ? 4 : 8;
     if (d->cs % pe != 0 || d->ldw % pe != 0 || d->ldw < d->r * d->s * d->cs + (ex && ex->src2 ? ex->cs2 : 0)) return IIF_EUNSUPPORTED;
-    if (ex && (ex->src2 || ex->sbias || ex->mask_store || ex->no_store || ex->aff || ex->pro_stats)) {
+    if (ex && ex->aff_any) {
+        if (!affine_geometry_ok(d) || bias || bn_partial || res_bits || bw_x) return IIF_EUNSUPPORTED;
+    } else if (ex && (ex->src2 || ex->sbias || ex->mask_store || ex->no_store || ex->aff || ex->pro_stats)) {
         // round-3 epilogue / operand options: bf16 1x1 stride-1 launches on the LDS-staged epilogue only
         if (d->dtype != IIF_BF16 || d->dst_dtype != IIF_BF16 || d->r != 1 || d->s != 1 || d->stride != 1 || d->pad != 0 || d->groups > 1 ||
             (d->cd % 8) || bias || (d->cs % 32))

@@ -753,6 +753,7 @@ static int regw_launch2(int mode, const void* src, const void* wgt, void* dst, f
     const unsigned sb = (unsigned)((int64_t)M * spitch * 2);
     const dim3 g((unsigned)grid), b(512);
     if (mode == 2) {
+        IIF_ROUTE_PROBE(IIF_ROUTE_REGW1X1);
         if (K == 64) IIF_REGW(64, 32, 64, 2);
         else if (K == 128) IIF_REGW(128, 32, 64, 2);
         else IIF_REGW(256, 32, 64, 2);
@@ -804,6 +805,9 @@ namespace {
 struct Regw3Args {
     const unsigned char* src; const unsigned char* wgt; unsigned char* dst; float* bn_partial;
     const unsigned char* bw_x; const unsigned char* bw_bits; const float* bw_stats;
+    // EPI == 2: dst = relu(fmaf(a, bf16(conv), b) + r), r = nothing | res | fmaf(a2, res, b2) (aff2), coefficients at [2 C + c] / [3 C + c]
+    // of aff / aff2, relu_out (nullable) one byte of ReLU decisions per 16-byte vector: bn_apply_kernel's arithmetic
+    const float* aff; const float* aff2; const unsigned char* res; unsigned char* relu_out;
     int N, H, W, M, ntiles, tiles_x, tiles_per_image, ldw, bn_row0;
     unsigned m_tpi, m_tx;          // magic multipliers of tiles_per_image and tiles_x
     signed char tap_dy[9], tap_dx[9]; unsigned char tap_w[9];
@@ -815,16 +819,17 @@ __device__ __forceinline__ int fdiv22(int x, float rd) { return (int)(((float)x 
 // four VALU instructions per use even for uniform operands, and the tile bookkeeping below was a third of this kernel's VALU time
 __device__ __forceinline__ unsigned udiv_magic(unsigned t, unsigned m) { return m ? __umulhi(t, m) : t; }      // m = 0: divisor 1
 
-template <bool EPI>
+template <int EPI>      // 0: plain store (+ forward sums), 1: upstream BN-backward sums, 2: BN affine (+ residual) + ReLU of an inference forward (no sums)
 __global__ void __launch_bounds__(256, 2) conv3x3_regw64_kernel(Regw3Args a, unsigned src_bytes) {
     constexpr int C = 64, CW = 32, NCH = 2, CB = 2, PB = 2, TS = 8, WS = TS + 2;      // tile side, window side
     constexpr int HR = 128, CHB = HR * 64, SLOT = NCH * CHB, NSLOT = 3;         // window: 100 pixels in 8 pieces of 16 per 32-channel chunk
     constexpr int PITCH = C * 2 + 16, STG = 64 * PITCH;
     constexpr int NDMA = 2 * NCH;                                               // DMA instructions per wave and tile (pieces w and w + 4)
     constexpr int NV = 2;                                                       // staged 16-byte vectors per thread and tile
-    constexpr int NOPS = EPI ? 2 * NV : 0;                                      // epilogue operand loads per thread and tile
+    constexpr int NOPS = EPI == 1 ? 2 * NV : EPI == 2 ? NV : 0;                                      // epilogue operand loads per thread and tile
     constexpr unsigned OOB = 0x80000000u;
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[NSLOT * SLOT + STG + 4 * 2 * C * 4 + 2 * C * 4];
+    // (the ReLU-bit bytes of EPI == 2 are stores beyond that count: the waits below then ask for more than they need, never for less)
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[NSLOT * SLOT + STG + 4 * 2 * C * 4 + (EPI == 2 ? 4 : 2) * C * 4];
     unsigned char* const stage = smem + NSLOT * SLOT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -903,11 +908,16 @@ __global__ void __launch_bounds__(256, 2) conv3x3_regw64_kernel(Regw3Args a, uns
 #pragma unroll
     for (int q = 0; q < 8; ++q) { bs[q] = 0.f; bq[q] = 0.f; }
     const unsigned char* const dummy = a.wgt;
-    const bool has_bx = EPI && a.bw_x != nullptr, has_bb = EPI && a.bw_bits != nullptr;
+    const bool has_bx = EPI == 1 && a.bw_x != nullptr, has_bb = EPI == 1 && a.bw_bits != nullptr;
     const int vchunk = tid & 7, vrow = tid >> 3;                    // this thread's staged vectors: tile pixels vrow and vrow + 32
     // the upstream statistics wait in LDS (behind the partial-sum scratch): 16 registers less in a kernel that has none to spare
     float* const ustat = reinterpret_cast<float*>(stage + STG + 4 * 2 * C * 4);          // [2][C]: mean, invstd
     if (has_bx && tid < 2 * C) ustat[tid] = a.bw_stats[tid];
+    const bool has_res = EPI == 2 && a.res != nullptr, has_aff2 = EPI == 2 && a.aff2 != nullptr;
+    if (EPI == 2 && tid < 2 * C) {                                                       // [4][C]: a, b, a2, b2 (read behind the tile's two barriers)
+        ustat[tid] = a.aff[2 * C + tid];
+        if (has_aff2) ustat[2 * C + tid] = a.aff2[2 * C + tid];
+    }
     int slot = 0;
     bool first = true;
     for (; tile < tend; tile += per_xcd, slot = slot == NSLOT - 1 ? 0 : slot + 1) {
@@ -927,7 +937,8 @@ __global__ void __launch_bounds__(256, 2) conv3x3_regw64_kernel(Regw3Args a, uns
         for (int i = 0; i < NV; ++i) {
             const int p = vrow + 32 * i;
             vo[i] = ((size_t)((n * H + y0 + (p >> 3)) * W + x0 + (p & 7)) * C + vchunk * 8) * 2;
-            if (EPI) {                                             // the tile's epilogue operands, unconditionally
+            if (EPI == 2) ox[i] = *reinterpret_cast<const u32x4*>(has_res ? a.res + vo[i] : dummy);
+            if (EPI == 1) {                                        // the tile's epilogue operands, unconditionally
                 ox[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(has_bx ? a.bw_x + vo[i] : dummy));
                 ob[i] = *(has_bb ? a.bw_bits + (vo[i] >> 4) : dummy);
             }
@@ -968,9 +979,47 @@ __global__ void __launch_bounds__(256, 2) conv3x3_regw64_kernel(Regw3Args a, uns
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
-            const u32x4 v = *reinterpret_cast<const u32x4*>(stage + (vrow + 32 * i) * PITCH + vchunk * 16);
+            u32x4 v = *reinterpret_cast<const u32x4*>(stage + (vrow + 32 * i) * PITCH + vchunk * 16);
+            if constexpr (EPI == 2) {                              // the rounded tile under the BN affine + ReLU, element for element as bn_apply_kernel
+                float ca[8], cb[8];
+#pragma unroll
+                for (int q = 0; q < 8; q += 4) {
+                    const f32x4 a4 = *reinterpret_cast<const f32x4*>(ustat + vchunk * 8 + q), b4 = *reinterpret_cast<const f32x4*>(ustat + C + vchunk * 8 + q);
+                    ca[q] = a4.x; ca[q + 1] = a4.y; ca[q + 2] = a4.z; ca[q + 3] = a4.w;
+                    cb[q] = b4.x; cb[q + 1] = b4.y; cb[q + 2] = b4.z; cb[q + 3] = b4.w;
+                }
+                float ra[8], rb[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) { ra[q] = 1.f; rb[q] = 0.f; }
+                if (has_aff2) {                                    // block-uniform
+#pragma unroll
+                    for (int q = 0; q < 8; q += 4) {
+                        const f32x4 a4 = *reinterpret_cast<const f32x4*>(ustat + 2 * C + vchunk * 8 + q), b4 = *reinterpret_cast<const f32x4*>(ustat + 3 * C + vchunk * 8 + q);
+                        ra[q] = a4.x; ra[q + 1] = a4.y; ra[q + 2] = a4.z; ra[q + 3] = a4.w;
+                        rb[q] = b4.x; rb[q + 1] = b4.y; rb[q + 2] = b4.z; rb[q + 3] = b4.w;
+                    }
+                }
+                const u32x4 rr = ox[i];
+                unsigned bits = 0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float lo = fmaf(ca[2 * q], bf16_bits_to_f32(v[q] & 0xffffu), cb[2 * q]);
+                    float hi = fmaf(ca[2 * q + 1], __uint_as_float(v[q] & 0xffff0000u), cb[2 * q + 1]);
+                    if (has_aff2) {
+                        lo += fmaf(ra[2 * q], bf16_bits_to_f32(rr[q] & 0xffffu), rb[2 * q]);
+                        hi += fmaf(ra[2 * q + 1], __uint_as_float(rr[q] & 0xffff0000u), rb[2 * q + 1]);
+                    } else if (has_res) {
+                        lo += bf16_bits_to_f32(rr[q] & 0xffffu); hi += __uint_as_float(rr[q] & 0xffff0000u);
+                    }
+                    bits |= (lo > 0.f ? 1u : 0u) << (2 * q);
+                    bits |= (hi > 0.f ? 1u : 0u) << (2 * q + 1);
+                    v[q] = pack_bf16x2(fmaxf(lo, 0.f), fmaxf(hi, 0.f));
+                }
+                if (a.relu_out) a.relu_out[vo[i] >> 4] = (unsigned char)bits;
+            }
             __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(a.dst + vo[i]));      // (whole 128-byte lines: streamed)
-            if (EPI && has_bx) {
+            if constexpr (EPI == 2) continue;
+            if (EPI == 1 && has_bx) {
                 const unsigned mb = has_bb ? ob[i] : 0xffu;
                 float bmean[8], bistd[8];
 #pragma unroll
@@ -1032,12 +1081,15 @@ bool iif_regw3x3_ok(int N, int H, int W, int C) {
 
 int iif_regw3x3_launch(const void* src, const void* wgt, void* dst, float* bn_partial, long long bn_cap, int bn_row0, int* rows_out,
                        int N, int H, int W, int C, int ldw, const signed char* tap_dy, const signed char* tap_dx, const unsigned char* tap_w,
-                       const void* bw_x, const unsigned char* bw_bits, const float* bw_stats, hipStream_t st) {
+                       const void* bw_x, const unsigned char* bw_bits, const float* bw_stats, hipStream_t st, const float* aff, const float* aff2,
+                       const void* res, unsigned char* relu_out) {
     if (!src || !wgt || !dst || !iif_regw3x3_ok(N, H, W, C)) return IIF_EUNSUPPORTED;
+    if (aff ? (bn_partial || bw_x || bw_bits || (aff2 && !res)) : (aff2 || res || relu_out)) return IIF_EUNSUPPORTED;
     const int cus = iif_persistent_cus();
     Regw3Args a{};
     a.src = (const unsigned char*)src; a.wgt = (const unsigned char*)wgt; a.dst = (unsigned char*)dst; a.bn_partial = bn_partial;
     a.bw_x = (const unsigned char*)bw_x; a.bw_bits = bw_bits; a.bw_stats = bw_stats;
+    a.aff = aff; a.aff2 = aff2; a.res = (const unsigned char*)res; a.relu_out = relu_out;
     a.N = N; a.H = H; a.W = W; a.M = N * H * W; a.tiles_x = W / 8; a.tiles_per_image = (H / 8) * (W / 8);
     a.ntiles = N * a.tiles_per_image; a.ldw = ldw; a.bn_row0 = bn_row0;
     for (int t = 0; t < 9; ++t) { a.tap_dy[t] = tap_dy[t]; a.tap_dx[t] = tap_dx[t]; a.tap_w[t] = tap_w[t]; }
@@ -1056,8 +1108,10 @@ int iif_regw3x3_launch(const void* src, const void* wgt, void* dst, float* bn_pa
     const unsigned sb = (unsigned)((int64_t)a.M * C * 2);
     const bool epi = bw_x != nullptr || bw_bits != nullptr;
     const dim3 g((unsigned)grid), b(256);
-    if (epi) hipLaunchKernelGGL(conv3x3_regw64_kernel<true>, g, b, 0, st, a, sb);
-    else hipLaunchKernelGGL(conv3x3_regw64_kernel<false>, g, b, 0, st, a, sb);
+    IIF_ROUTE_PROBE(IIF_ROUTE_REGW3X3);
+    if (aff) hipLaunchKernelGGL(conv3x3_regw64_kernel<2>, g, b, 0, st, a, sb);
+    else if (epi) hipLaunchKernelGGL(conv3x3_regw64_kernel<1>, g, b, 0, st, a, sb);
+    else hipLaunchKernelGGL(conv3x3_regw64_kernel<0>, g, b, 0, st, a, sb);
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }

@@ -40,6 +40,57 @@ def conv_forward(x, w, r, s, stride, pad, out=None, out_dtype=None, bias=None, r
     return out
 
 
+def conv_affine_ok(n, hs, ws, cs, hd, wd, cd, r, s, stride, pad, ldw, dtype, groups=1, has_res=False, has_res_affine=False):
+    """Host-only: whether conv_forward_affine has a fused instance for this geometry (cs / cd per group) and residual form."""
+    code = _lib.IIF_BF16 if dtype == torch.bfloat16 else _lib.IIF_F32
+    d = _desc(n, hs, ws, cs, hd, wd, cd, r, s, stride, pad, 0, ldw, code, code, groups)
+    return bool(lib().iif_conv_affine_ok(ctypes.byref(d), 1 if has_res else 0, 1 if has_res_affine else 0))
+
+
+AFFINE_ROUTES = ("none", "tile", "tile_2stage", "tile_general", "tile256", "halo", "frag", "frag_g16", "stream1x1", "regw1x1",
+                 "regw3x3", "regstage")
+
+
+def conv_affine_route(n, hs, ws, cs, hd, wd, cd, r, s, stride, pad, ldw, groups=1, has_res=False, has_res_affine=False,
+                      has_relu_bits=False, w_frag=None):
+    """Name of the kernel family conv_forward_affine launches for this bf16 geometry (iif_conv_affine_route: the launch
+    routing walked without launching).  ``w_frag``: as for conv_forward (only its presence and kind matter)."""
+    d = _desc(n, hs, ws, cs, hd, wd, cd, r, s, stride, pad, 0, ldw, _lib.IIF_BF16, _lib.IIF_BF16, groups, w_frag)
+    return AFFINE_ROUTES[lib().iif_conv_affine_route(ctypes.byref(d), int(has_res), int(has_res_affine), int(has_relu_bits))]
+
+
+def conv_forward_affine(x, w, r, s, stride, pad, out, affine, res=None, res_affine=None, relu_bits=None, groups=1, w_frag=None):
+    """Inference forward of a conv + BN (+ residual) + ReLU unit in one launch (bf16):
+    out = relu(affine[2] * bf16(conv) + affine[3] + r), r = res, or res_affine[2] * res + res_affine[3] (a raw convolutional
+    shortcut); bit-identical to conv_forward followed by bn_apply.  The grid of ``out`` is taken as given."""
+    require_gpu(x, w, out, affine, res, res_affine, relu_bits)
+    n, h, wd_, cin = x.shape
+    cout, ldw = w.shape
+    ho, wo = out.shape[1], out.shape[2]
+    d = _desc(n, h, wd_, cin // groups, ho, wo, cout // groups, r, s, stride, pad, 0, ldw, dtype_code(x), dtype_code(out),
+              groups, w_frag)
+    check(lib().iif_conv_igemm_affine(ctypes.byref(d), ptr(x), ptr(w), ptr(out), ptr(res), ptr(res_affine), ptr(affine),
+                                      ptr(relu_bits), stream_ptr()), "iif_conv_igemm_affine")
+    return out
+
+
+def bn_fold_table(entries, device):
+    """entries: [(gamma, beta, running_mean, running_var, stats)] -> device table of iif_bn_fold_desc (48 bytes each)."""
+    import struct
+    blob = b""
+    for (g, b, rm, rv, st) in entries:
+        require_gpu(g, b, rm, rv, st)
+        c = g.numel()
+        assert b.numel() == c and rm.numel() == c and rv.numel() == c and st.numel() == 4 * c and st.is_contiguous()
+        blob += struct.pack("<QQQQQii", g.data_ptr(), b.data_ptr(), rm.data_ptr(), rv.data_ptr(), st.data_ptr(), c, 0)
+    return torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(device)
+
+
+def bn_fold(table, n_layers, eps=1e-5):
+    """One launch: the inference-mode (mean, invstd, a, b) rows of every BN layer in ``table`` (bn_fold_table)."""
+    check(lib().iif_bn_fold(ptr(table), n_layers, float(eps), stream_ptr()), "iif_bn_fold")
+
+
 def conv_forward_bnstats(x, w, r, s, stride, pad, out, partial, groups=1, w_frag=None):
     """conv_forward (bf16) that also writes per-tile BN partial sums; returns the tile count."""
     n, h, wd_, cin = x.shape

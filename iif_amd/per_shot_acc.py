@@ -50,6 +50,7 @@ def main(args):
     device = torch.device(args.device)
     dataset, num_classes, _, data_loader_test, _ = initialisers.get_data(args)
     model = train.build_model(args, num_classes)
+    train.enable_fused_eval(model, args)
     table = None
     if args.classif == "iif":
         crit = custom.IIFLoss(dataset, variant=args.iif, iif_norm=0, reduction="mean", device=args.device)
@@ -101,6 +102,8 @@ def get_args_parser(add_help=True):
     # MI355X-native additions (same meaning as in iif_amd.train)
     p.add_argument("--calibration-bins", dest="calibration_bins", default=0, type=int,
                    help="also print ECE / MCE over this many reliability bins (0 = off)")
+    p.add_argument("--fused-eval", dest="fused_eval", action="store_true",
+                   help="eval-mode BN folded into the convolution epilogues (bit-identical logits; bf16 compute only)")
     p.add_argument("--train-txt", dest="train_txt", default=None)
     p.add_argument("--eval-txt", dest="eval_txt", default=None)
     p.add_argument("--image-size", dest="image_size", default=224, type=int)

@@ -171,6 +171,7 @@ class NativeResNet(nn.Module):
         self._saved = None
         self._head_only = False
         self._sync_bn = None            # (process group, world size) once enable_sync_bn() was called
+        self.fused_eval = False         # set_fused_eval(): eval-mode BN folded into the convolution epilogues
         if style == "imagenet":
             self.conv1 = ConvParam(3, 64, 7, 2, 3); self.bn1 = BNParam(64)
             exp = 4 if block == "bottleneck" else 1
@@ -428,6 +429,20 @@ class NativeResNet(nn.Module):
                                    "torch.no_grad() as classification/train.py:97 does, or call model.train()")
             return _NetFunction.apply(self, x, *self._param_list)
         return self.run_forward(x, self.training).clone()
+
+    def set_fused_eval(self, flag=True):
+        """Inference route of a bf16 model: a ``training=False`` forward writes the eval-mode BN affine of every layer with
+        ONE launch (iif_bn_fold) and runs each conv + BN (+ residual) + ReLU unit as one convolution launch with the affine
+        in its epilogue (iif_conv_igemm_affine) wherever ``eval_route`` says "fused".  Bit-identical logits to the default
+        route; the training route is untouched.  Default off."""
+        self.fused_eval = bool(flag)
+        return self
+
+    def eval_route(self, n, h, w):
+        """[(unit name, route)] of an eval forward of ``n`` images of ``h`` x ``w`` with ``fused_eval`` on: "fused", "raw"
+        (a convolutional shortcut, stored raw and normalised in its consumer's epilogue) or "unfused: <reason>" (today's
+        conv + bn_apply launches).  Host-only; the plan takes its routing from the same walk."""
+        return [(name, route) for (name, _, route) in _eval_routes(self, n, h, w)]
 
     def run_forward(self, x, training):
         """Native forward.  Returns fp32 logits [N, num_classes] — a VIEW of the plan's buffer, valid until the next
@@ -1381,6 +1396,8 @@ class _Plan(object):
 
     def forward(self, img, training):
         net = self.net
+        if not training and net.fused_eval and "fused" in self._eval_routing().values():
+            return self._forward_eval_fused(img)
         prep_done = None
         if training and self.wg_stream is not None and self.stem_s2d:
             # The stem needs only its own packed matrix: the cast / transposes / fragment packs of every other layer
@@ -1500,6 +1517,10 @@ class _Plan(object):
             else:
                 ops.bn_apply(x2, last.stats, last.y.view(x2.shape), relu=True, residual=b["inp"].view(x2.shape),
                              relu_bits=last.bits)
+        self._head_forward()
+
+    def _head_forward(self):
+        net = self.net
         ops.avgpool_forward(self.final, out=self.pooled)
         head = net._head
         feat, bias = self.pooled, None
@@ -1520,7 +1541,80 @@ class _Plan(object):
         ops.conv_forward(feat.view(self.n, 1, 1, head.in_features), self.head_w, 1, 1, 1, 0,
                          out=self.logits.view(self.n, 1, 1, head.out_padded), bias=bias)
 
-    def _se_forward(self, b, last, training):
+    # ------------------------------------------------ inference forward, BN folded into the convolutions
+    def _fold_bn(self):
+        """(mean, invstd, a, b) of every BN layer of the plan from the running statistics: one launch per forward, so a write
+        to running_mean / running_var needs no invalidation.  The pointer table is rebuilt when a tensor was replaced."""
+        key = tuple(t.data_ptr() for u in self.units for t in (u.bn.weight, u.bn.bias, u.bn.running_mean, u.bn.running_var))
+        cached = self.__dict__.get("_fold")
+        if cached is None or cached[0] != key:
+            ent = [(u.bn.weight.detach(), u.bn.bias.detach(), u.bn.running_mean, u.bn.running_var, u.stats) for u in self.units]
+            cached = self._fold = (key, ops.bn_fold_table(ent, self.dev), len(ent))
+        ops.bn_fold(cached[1], cached[2], BN_EPS)
+
+    def _eval_unit(self, u, route, res=None, res_affine=None):
+        """One conv + BN (+ residual) + ReLU unit of the inference forward; u.stats hold the folded affine."""
+        k, st, pd = u.geom
+        if route == "fused":
+            ops.conv_forward_affine(u.src, u.w, k, k, st, pd, u.y, u.stats, res=res, res_affine=res_affine, groups=u.groups,
+                                    w_frag=u.wf)
+            return
+        x2 = self._conv_raw(u)
+        ops.bn_apply(x2, u.stats, u.y.view(x2.shape), relu=True, residual=None if res is None else res.view(x2.shape),
+                     residual_stats=res_affine, relu_bits=u.bits)
+
+    def _conv_raw(self, u):
+        k, st, pd = u.geom
+        ops.conv_forward(u.src, u.w, k, k, st, pd, out=u.x, groups=u.groups, out_hw=(u.ho, u.wo), w_frag=u.wf)
+        return u.x.view(u.n * u.ho * u.wo, u.conv.cout)
+
+    def _eval_routing(self):
+        routes = self.__dict__.get("_routes")
+        if routes is None:
+            routes = self._routes = {id(cv): r for (_, cv, r) in _eval_routes(self.net, self.n, self.h, self.w)}
+        return routes
+
+    def _forward_eval_fused(self, img):
+        net = self.net
+        routes = self._eval_routing()
+        self.prepare_weights(False)
+        self._fold_bn()
+        c1 = net.conv1
+        if self.stem_s2d:
+            ops.space_to_depth_nchw(img, S2D_CPAD, self.patches)
+        else:
+            ops.im2col_nchw(img, c1.k, c1.k, c1.stride, c1.pad, c1.ldw, self.dt, out=self.patches)
+        u = self.stem
+        if self.pool_fused:                      # (ImageNet stem: bn1 + ReLU + max-pool stay one pass over the raw output)
+            self._conv_raw(u)
+            _lib.check(_lib.lib().iif_maxpool_bn_forward(_lib.ptr(u.x), _lib.dtype_code(u.x), _lib.ptr(u.stats), u.n, u.ho, u.wo,
+                                                         u.conv.cout, 3, 2, 1, _lib.ptr(self.pool_out), _lib.ptr(self.pool_idx),
+                                                         _lib.ptr(None), _lib.stream_ptr()), "iif_maxpool_bn_forward")
+        else:
+            self._eval_unit(u, routes[id(u.conv)])
+            if net.style == "imagenet":
+                self._maxpool_fwd(u.y)
+        for b in self.blocks:
+            units = b["units"]
+            last = units[-1]
+            for uu in units[:-1]:
+                self._eval_unit(uu, routes[id(uu.conv)])
+            if "se" in b:
+                self._conv_raw(last)
+                self._se_forward(b, last, False, folded=True)
+                continue
+            if "ds" in b:
+                du = b["ds"]
+                self._conv_raw(du)
+                self._eval_unit(last, routes[id(last.conv)], res=du.x, res_affine=du.stats)
+            elif "sc" in b:
+                ops.shortcut_a_forward(b["inp"], b["blk"].out_planes, out=b["sc"])
+                self._eval_unit(last, routes[id(last.conv)], res=b["sc"])
+            else:
+                self._eval_unit(last, routes[id(last.conv)], res=b["inp"])
+        self._head_forward()
+
+    def _se_forward(self, b, last, training, folded=False):
         """y = relu(bn(x) * e + identity), e = sigmoid(W2 relu(W1 mean_hw(bn(x)))) — SEBottleneck.forward
         (resnet_pytorch.py:358-381) / Se_Block.forward (resnet_cifar.py:163-169).  The squeeze and the
         rescale are native streaming kernels; the [N, C]-sized excitation is one native fp32 launch (csrc/se.hip)."""
@@ -1534,7 +1628,10 @@ class _Plan(object):
         res, rstats = b["inp"], None
         if "ds" in b:
             du = b["ds"]
-            self._conv_bn(du, training)
+            if folded:                       # (inference with folded BN: du.stats are written already)
+                self._conv_raw(du)
+            else:
+                self._conv_bn(du, training)
             res, rstats = du.x, du.stats
         elif "sc" in b:
             ops.shortcut_a_forward(b["inp"], b["blk"].out_planes, out=b["sc"])
@@ -2101,6 +2198,63 @@ def _dma_ok(t):
     """The pipelined kernels address their operands with 32-bit LDS-DMA offsets (< 2 GiB); beyond that the
     register-staged fallback runs and the fused epilogue options are not available."""
     return t.numel() * t.element_size() < _DMA_LIMIT
+
+
+def _eval_routes(net, n, h, w):
+    """The units of an inference forward in launch order with their route under ``fused_eval``: [(name, conv, route)].
+    Walks the block list with the geometry _Plan uses (no device memory is touched) and asks iif_conv_affine_ok."""
+    dt = net.compute_dtype
+    esz = 2 if dt == torch.bfloat16 else 4
+    out = []
+    blanket = None if dt == torch.bfloat16 else "unfused: fp32 compute keeps the two-launch route"
+
+    def pitch(cv):
+        return net._offsets[(id(cv), "weight")][2]
+
+    def ask(cv, hi, wi, ho, wo, has_res, has_aff2, patch_cin=None):
+        if patch_cin is not None:           # the stem as a GEMM over gathered patches
+            return ops.conv_affine_ok(n, ho, wo, patch_cin, ho, wo, cv.cout, 1, 1, 1, 0, pitch(cv), dt, 1, has_res, has_aff2)
+        if cv.groups > 1:                   # dense inside chunks of cv.chunk channels
+            g = cv.cin // cv.chunk
+            return ops.conv_affine_ok(n, hi, wi, cv.chunk, ho, wo, cv.cout // g, cv.k, cv.k, cv.stride, cv.pad,
+                                      cv.k * cv.k * cv.chunk, dt, g, has_res, has_aff2)
+        return ops.conv_affine_ok(n, hi, wi, cv.cin, ho, wo, cv.cout, cv.k, cv.k, cv.stride, cv.pad, pitch(cv), dt, 1,
+                                  has_res, has_aff2)
+
+    c1 = net.conv1
+    ho, wo = ops.conv_out_hw(h, w, c1.k, c1.k, c1.stride, c1.pad)
+    if net.style == "imagenet":
+        stem = "unfused: bn1 + ReLU + max-pool already run as one pass over the raw stem output"
+        hh, ww = (ho + 2 - 3) // 2 + 1, (wo + 2 - 3) // 2 + 1
+    else:
+        stem = "fused" if ask(c1, ho, wo, ho, wo, False, False, patch_cin=c1.ldw) else "unfused: no staged-epilogue kernel for the patch GEMM"
+        hh, ww = ho, wo
+    units = [("conv1", c1, stem, n * ho * wo * max(c1.ldw, c1.cout))]
+    stage_names = ["layer%d" % (i + 1) for i in range(len(net._stages))]
+    for sname, st in zip(stage_names, net._stages):
+        for bi, blk in enumerate(st):
+            pairs = blk.units()
+            hi, wi = hh, ww
+            for ui, (cv, _) in enumerate(pairs):
+                oh, ow = ops.conv_out_hw(hi, wi, cv.k, cv.k, cv.stride, cv.pad)
+                name = "%s.%d.conv%d" % (sname, bi, ui + 1)
+                closing = ui == len(pairs) - 1
+                if closing and blk.se is not None:
+                    route = "unfused: the SE excitation needs the whole image's mean before any element is scaled"
+                else:
+                    has_res, has_aff2 = closing, closing and blk.downsample is not None
+                    route = "fused" if ask(cv, hi, wi, oh, ow, has_res, has_aff2) else "unfused: no fused instance for this geometry"
+                units.append((name, cv, route, n * max(hi * wi * cv.cin, oh * ow * cv.cout)))
+                hi, wi = oh, ow
+            if blk.downsample is not None:
+                dcv = blk.downsample[0]
+                units.append(("%s.%d.downsample" % (sname, bi), dcv, "raw", n * max(hh * ww * dcv.cin, hi * wi * dcv.cout)))
+            hh, ww = hi, wi
+    if blanket is None and not all(e * esz < _DMA_LIMIT for (_, _, _, e) in units):
+        blanket = "unfused: an operand lies beyond the 32-bit DMA range"
+    for (name, cv, route, _) in units:
+        out.append((name, cv, route if blanket is None or route == "raw" else blanket))
+    return out
 
 
 def _eval_stats(bn, stats):

@@ -172,6 +172,20 @@ def build_model(args, num_classes):
     raise AttributeError("unknown model %r" % (args.model,))
 
 
+def enable_fused_eval(model, args):
+    """--fused-eval: evaluation forwards with eval-mode BN folded into the convolution epilogues (NativeResNet.set_fused_eval);
+    prints the route summary once."""
+    if not getattr(args, "fused_eval", False):
+        return model
+    model.set_fused_eval(True)
+    size = 32 if args.dset_name.lower().startswith("cifar") else getattr(args, "image_size", 224)
+    route = model.eval_route(args.batch_size, size, size)
+    unfused = [name for (name, r) in route if r.startswith("unfused")]
+    print("fused eval: fused %d of %d units (%d shortcut convolutions stored raw; unfused: %s)"
+          % (sum(r == "fused" for (_, r) in route), len(route), sum(r == "raw" for (_, r) in route), ", ".join(unfused) or "none"))
+    return model
+
+
 HOST_POLICIES = ("imagenet", "randaugment", "cifar", "cifar10")
 DEVICE_POLICIES = HOST_POLICIES                        # lt_device.POLICIES: what --device-policy runs
 
@@ -230,6 +244,7 @@ def main(args):
     dataset, num_classes, data_loader, data_loader_test, train_sampler = initialisers.get_data(args)
     print("Creating model")
     model = build_model(args, num_classes)
+    enable_fused_eval(model, args)
     criterion = initialisers.get_criterion(args, dataset, model, num_classes)
     if args.sync_bn and args.distributed:
         model.enable_sync_bn()                # train.py:190-191: batch statistics over all ranks
@@ -354,6 +369,9 @@ def get_args_parser(add_help=True):
                    help="reduce bf16 copies of the gradient buckets (refused unless the first step's probe stays in tolerance)")
     p.add_argument("--max-iters", default=0, type=int, help="stop each epoch after this many iterations (0 = all)")
     p.add_argument("--synthetic-scale", dest="synthetic_scale", default=1.0, type=float)
+    p.add_argument("--fused-eval", dest="fused_eval", action="store_true",
+                   help="evaluate with eval-mode BN folded into the convolution epilogues (one launch per conv + BN + ReLU unit, "
+                        "bit-identical logits; bf16 compute only)")
     p.add_argument("--shot-acc", dest="shot_acc", action="store_true",
                    help="after each evaluation also print the many / median / low-shot accuracy (per_shot_acc.shot_acc)")
     p.add_argument("--calibration-bins", dest="calibration_bins", default=0, type=int,

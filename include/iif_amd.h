@@ -268,6 +268,17 @@ int iif_bn_forward_stats(const void* x, int dtype, int64_t m, int c, const float
 int iif_bn_apply(const void* x, int dtype, int64_t m, int c, const float* stats,
                  const void* residual, const float* residual_stats, int relu, void* y,
                  uint8_t* relu_bits, void* stream);
+/* Inference-mode BN of every layer of a network in ONE launch: for each table entry (a device array of n_layers
+ * descriptors) the `stats` rows iif_bn_apply reads are written from the affine parameters and the running statistics,
+ * (mean, invstd = rsqrt(running_var + eps), a = gamma * invstd, b = beta - mean * a), each operation rounded on its own -
+ * bit for bit the [C]-vector arithmetic torch does for model.eval().  Runs once per evaluation forward: nothing is cached,
+ * so a write to running_mean needs no invalidation. */
+typedef struct iif_bn_fold_desc {
+    const float* gamma; const float* beta; const float* running_mean; const float* running_var;
+    float* stats;          /* [4][c] */
+    int32_t c, reserved;
+} iif_bn_fold_desc;
+int iif_bn_fold(const iif_bn_fold_desc* table, int n_layers, float eps, void* stream);
 /* second half of iif_bn_forward_stats on externally produced partial sums
  * (partial[t][0][k] = sum, [t][1][k] = sum of squares; fixed-order fp64 reduction).
  * scratch (nullable, >= 128*c floats) lets > 512 partial rows be reduced in two
@@ -535,6 +546,24 @@ int iif_conv_igemm_bn_relu(const iif_conv_desc* d, const void* src, const void* 
  *                               block's convolutional shortcut and is normalised on the way in, fma(a2, res, b2) with a2 / b2 at
  *                               res_stats[2 Cd + c] / [3 Cd + c] (iif_bn_apply's residual_stats arithmetic).  relu_bits required. */
 int iif_conv_fwdbn_ok(const iif_conv_desc* d);
+/* Inference forward: the convolution with a FIXED per-channel affine (eval-mode BN), the residual and the ReLU in its epilogue,
+ *   dst = relu(fmaf(a, bf16(conv), b) + r),   r = nothing | res | fmaf(a2, res, b2) with res_affine (the block's convolutional
+ * shortcut, stored raw).  affine / res_affine are laid out like the `stats` rows of iif_bn_apply (a at [2 C + c], b at [3 C + c],
+ * C = cd * groups), so iif_bn_fold's output serves both routes.  The accumulator tile is rounded to bf16 before the affine,
+ * exactly as the stored tensor would have been: the result is bit-identical to iif_conv_igemm followed by
+ * iif_bn_apply(relu = 1, res, res_affine); relu_bits (nullable) receives the same decision bytes.  bf16 in and out; 1x1 and
+ * 3x3, stride 1 and 2, dense and grouped, any m.  iif_conv_affine_ok (host only, launches nothing) says whether a descriptor
+ * has a fused instance with the given residual form; where it says 0, iif_conv_igemm_affine returns IIF_EUNSUPPORTED. */
+int iif_conv_affine_ok(const iif_conv_desc* d, int has_res, int has_res_affine);
+/* Which kernel family iif_conv_igemm_affine would launch for this descriptor and operand set, found by walking the launch
+ * routing itself with the launches replaced by a record (nothing runs): 0 none, 1 tile (three LDS stages), 2 tile (two
+ * stages, 4 blocks per CU), 3 tile with general addressing (source channels not in 32s), 4 256-row tile, 5 3x3 halo,
+ * 6 3x3 fragment weights, 7 3x3 grouped 16-channel fragments, 8 streaming 1x1, 9 register-weight 1x1, 10 register-weight
+ * 3x3.  d->wgt_frag only has to be non-null where fragments would be supplied.  Follows the IIF_CONV_* switches; the
+ * persistent kernels size themselves by the device, so it needs one.  For tests and route listings. */
+int iif_conv_affine_route(const iif_conv_desc* d, int has_res, int has_res_affine, int has_relu_bits);
+int iif_conv_igemm_affine(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
+                          const float* res_affine, const float* affine, unsigned char* relu_bits, void* stream);
 int iif_conv_igemm_stats_acc(const iif_conv_desc* d, const void* src, const void* wgt, float* bn_partial,
                              int64_t bn_partial_floats, int32_t* n_partials, void* stream);
 int iif_conv_igemm_bn_relu2(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
