@@ -32,8 +32,6 @@
 #define IIF_CONV_AUX_SRC 0
 #endif
 
-int* g_iif_route_probe = nullptr;
-
 namespace {
 
 template <typename T> struct ET;
@@ -1794,38 +1792,14 @@ __global__ void __launch_bounds__(64 * (4 + STREAM_SW)) gemm1x1_stream_kernel(Co
     }
 }
 
-// Test switches of this file (the whole list: DESIGN.md, "Switches"), read from the environment ONCE; iif_conv_reload_env()
-// re-reads them (tests flip them between calls).
-//   IIF_CONV_REGSTAGE        every launch on the register-staged kernels (the fallback for operands >= 2 GiB)
-//   IIF_CONV_NO_STREAM1X1    no launch on the persistent streaming 1x1 kernel;  IIF_CONV_STREAM1X1_FORCE: every shape it has a
-//                            plan for, small grids and data gradients included (default: three forward shapes, see use_stream1x1)
-//   IIF_CONV_NO_HALO / IIF_CONV_HALO_FORCE   3x3 halo kernel off / also on small grids
-//   IIF_CONV_NO_V2 / IIF_CONV_V2_FORCE       3x3 fragment kernel (64 channels) off / also on small grids
-struct ConvSwitches {
-    bool no_stream, force_stream, regstage, no_v2, no_halo, force_halo, v2_force, no_regw, no_regw_fwdbn;
-    static ConvSwitches read() {
-        ConvSwitches c;
-        c.no_stream = getenv("IIF_CONV_NO_STREAM1X1") != nullptr;
-        c.force_stream = getenv("IIF_CONV_STREAM1X1_FORCE") != nullptr;
-        c.regstage = getenv("IIF_CONV_REGSTAGE") != nullptr;
-        c.no_v2 = getenv("IIF_CONV_NO_V2") != nullptr;
-        c.no_halo = getenv("IIF_CONV_NO_HALO") != nullptr;
-        c.v2_force = getenv("IIF_CONV_V2_FORCE") != nullptr;
-        c.force_halo = getenv("IIF_CONV_HALO_FORCE") != nullptr;
-        c.no_regw = getenv("IIF_CONV_NO_REGW") != nullptr;
-        c.no_regw_fwdbn = getenv("IIF_CONV_NO_REGW_FWDBN") != nullptr;      // tests: the BN epilogue on the tile kernels
-        return c;
-    }
-};
 constexpr int kTwoStageK = 2304;          // the two-stage / 4-blocks-per-CU tile variant up to this K (everything the halo / 256-row kernels leave)
-ConvSwitches g_sw = ConvSwitches::read();
 
 // Which launches the streaming kernel takes, and its slice width: (K, N) -> BN columns per block with [BN x K] <= 64 KB
 // resident; S = N / BN slices.  A tile sequence needs a few tiles to pipeline across: mtiles * S >= 4 * grid.
 struct StreamPlan { int bn, kmax, slices; };
-inline bool use_stream1x1(const ConvArgs& a, bool utap, int esz, bool outf32, StreamPlan* pl) {
+inline bool use_stream1x1(const ConvSel& a, bool utap, StreamPlan* pl) {
     const bool force_ = g_sw.force_stream;
-    if (g_sw.no_stream || !utap || esz != 2 || outf32 || a.groups > 1 || a.scatter || a.in_shift != 0 || a.sshift != 0) return false;
+    if (g_sw.no_stream || !utap || a.esz != 2 || a.outf32 || a.groups > 1 || a.scatter || a.in_shift != 0 || a.sshift != 0) return false;
     if (a.R != 1 || a.S != 1 || a.pad != 0 || a.ntaps != 1 || a.bias || a.src2 || a.sbias || a.mask_store) return false;
     // (aff by default, measured in the fused evaluation forward at batch 256: ResNet50 4.863 -> 4.898 ms, se_resnet50 7.406 -> 7.354 ms,
     // +0.7 % / -0.7 %: level, so the affine launches stay on the tile kernels)
@@ -1847,32 +1821,27 @@ inline bool use_stream1x1(const ConvArgs& a, bool utap, int esz, bool outf32, St
 
 // 256-pixel tiles: bf16 uniform-tap launches wide enough for the 128-channel tile whose 256-row grid still fills
 // the chip (2 blocks per CU resident).
-inline bool use_bm256(const ConvArgs& a, bool utap, int esz) {
-    if (!utap || esz != 2 || a.Cd <= 64 || a.groups > 1) return false;
+inline bool use_bm256(const ConvSel& a, bool utap) {
+    if (!utap || a.esz != 2 || a.Cd <= 64 || a.groups > 1) return false;
     // IIF_CONV_NO_BM256_2SRC=1: the two-source data gradient of the BN3 algebra route on the 34 KB / 4-blocks-per-CU tile instead
     // (it starts beside the weight-gradient blocks, profiles/r5_contention.txt; level in the step: 18.33 against 18.34 ms)
-    static const bool no2 = getenv("IIF_CONV_NO_BM256_2SRC") != nullptr;
-    if (no2 && a.src2) return false;
+    if (g_sw.no_bm256_2src && a.src2) return false;
     // measured (scripts/bm_ab.sh): +13..39 % on K >= 1024 (3x3 at 128/256 channels, 1x1 from 1024 channels) when the
     // 256-row grid still offers >= 1.5 blocks per CU; short K loops and small grids are better off with 128 rows
     const int64_t tiles = (int64_t)((a.M + 255) / 256) * ((a.Cd + 127) / 128);
     return tiles >= 384 && a.ntaps * a.Cs >= 1024;
 }
 
-// partial-sum rows of this launch: [bn_row0, bn_row0 + mtiles) of the caller's buffer
-inline int claim_partial_rows(const ConvArgs& a) {
-    if (!a.bn_partial) return IIF_OK;
-    if ((long long)(a.bn_row0 + a.mtiles) * 2 * a.dpitch > a.bn_cap) return IIF_EINVAL;
-    if (a.rows_out) *a.rows_out = a.bn_row0 + a.mtiles;
-    return IIF_OK;
+// bf16 3x3 / stride 1 / pad 1 on one grid, uniform taps: what the window kernels (halo, fragment, register-weight 3x3) share
+inline bool dense3x3(const ConvSel& a, bool utap) {
+    return utap && a.esz == 2 && !a.outf32 && !a.scatter && a.in_shift == 0 && a.ntaps == 9 && a.R == 3 && a.S == 3 && a.pad == 1 &&
+           a.Hs == a.Hd && a.Ws == a.Wd && !a.bias;
 }
 
 // halo kernel: bf16 3x3 / stride 1 / pad 1, dense, >= 128 output channels, window of a 256-pixel tile <= 512 halo rows
-inline bool use_halo(const ConvArgs& a, bool utap, int esz, bool outf32) {
-    const bool off = g_sw.no_halo;
-    if (off || !utap || esz != 2 || outf32 || a.groups > 1 || a.scatter || a.in_shift != 0) return false;
-    if (a.ntaps != 9 || a.R != 3 || a.S != 3 || a.pad != 1 || a.Hs != a.Hd || a.Ws != a.Wd) return false;
-    if (a.Cd < 128 || (a.Cd & 7) || a.bias || (a.Cs % 32)) return false;
+inline bool use_halo(const ConvSel& a, bool utap) {
+    if (g_sw.no_halo || !dense3x3(a, utap) || a.groups > 1) return false;
+    if (a.Cd < 128 || (a.Cd & 7) || (a.Cs % 32)) return false;
     const int HW = a.Hd * a.Wd;
     const int span = (256 + a.Wd - 1) / a.Wd + 1 + 2 * (256 / HW + 1);       // virtual rows a tile can touch
     if ((span + 2) * (a.Wd + 2) > 512) return false;
@@ -1897,9 +1866,8 @@ inline bool v2_geometry_ok(int N, int H, int W, int Cs, int Cd, int groups = 1) 
     const int span = (256 + W - 1) / W + 1 + 2 * (256 / HW + 1);            // virtual rows a 256-pixel tile can touch
     return (span + 2) * (W + 2) <= 640;
 }
-inline bool use_v2(const ConvArgs& a, bool utap, int esz, bool outf32) {
-    if (!a.wfrag || g_sw.no_v2 || !utap || esz != 2 || outf32 || a.scatter || a.in_shift != 0) return false;
-    if (a.ntaps != 9 || a.R != 3 || a.S != 3 || a.pad != 1 || a.Hs != a.Hd || a.Ws != a.Wd || a.bias) return false;
+inline bool use_v2(const ConvSel& a, bool utap) {
+    if (!a.wfrag || g_sw.no_v2 || !dense3x3(a, utap)) return false;
     if (a.groups > 1) {                 // grouped: 64-channel chunks on the 64-channel variant, blockIdx.y = chunk
         if (a.Cs != 64 || a.Cd != 64 || a.groups > 65535) return false;
     } else if (a.spitch != a.Cs || a.dpitch != a.Cd) {
@@ -1908,297 +1876,402 @@ inline bool use_v2(const ConvArgs& a, bool utap, int esz, bool outf32) {
     return v2_geometry_ok(a.N, a.Hd, a.Wd, a.Cs, a.Cd, a.groups);
 }
 
-template <typename T, bool OUTF32>
-int launch_one(ConvArgs a, bool utap, int64_t src_bytes, int64_t wgt_bytes, hipStream_t st) {
-    const bool force_v1_ = g_sw.regstage;
-    if constexpr (sizeof(T) == 2 && !OUTF32) {          // 3x3 with the weights in registers (conv_regw.hip): 64 -> 64 channels
-        if (!force_v1_ && !g_sw.no_regw && utap && src_bytes < 0x7f000000LL && a.ntaps == 9 && a.R == 3 && a.S == 3 && a.pad == 1 &&
-            a.Hs == a.Hd && a.Ws == a.Wd && a.groups == 1 && a.Cs == a.Cd && a.spitch == a.Cs && a.dpitch == a.Cd && !a.scatter &&
-            a.in_shift == 0 && (!a.res || a.aff) && !a.res_bits && !a.bias && !a.mask_store && !a.src2 && !a.sbias && !a.no_store &&
-            a.Cs == 64 && (!(a.bw_x || a.bw_bits) || a.bn_partial) && iif_regw3x3_ok(a.N, a.Hd, a.Wd, a.Cs)) {
-            const int rc = iif_regw3x3_launch(a.src, a.wgt, a.dst, a.bn_partial, a.bn_cap, a.bn_row0, a.rows_out, a.N, a.Hd, a.Wd, a.Cs, a.ldw,
-                                              a.tap_dy, a.tap_dx, a.tap_w, a.bw_x, a.bw_bits, a.bw_stats, st, a.aff, a.aff2,
-                                              a.aff ? a.res : nullptr, a.relu_out);
-            if (rc != IIF_EUNSUPPORTED) return rc;
-        }
+// A grid of mtiles x ntiles tiles, blocks in whole groups of 8 pixel tiles, one partial row per pixel tile
+inline int tile_route(const ConvSel& a, ConvRoute* r, int family, int inst, int bm, int ntiles, unsigned grid_y, unsigned block) {
+    *r = ConvRoute{family, inst, -1, (a.M + bm - 1) / bm, ntiles, 0, grid_y, block, 0, 0};
+    if (const int rc = iif_claim_rows(a, r, r->mtiles)) return rc;
+    const int64_t blocks = (int64_t)((r->mtiles + 7) / 8) * 8 * ntiles;
+    if (blocks > 0x7fffffff) return IIF_EUNSUPPORTED;
+    r->grid = (unsigned)blocks;
+    return IIF_OK;
+}
+
+// The route of ONE launch whose tap list is known (a.ntaps / in_shift / scatter set): the families in the order they are tried.
+int select_one(const ConvSel& a, bool utap, ConvRoute* r) {
+    const bool bf16 = a.esz == 2 && !a.outf32;
+    const bool src_dma = !g_sw.regstage && a.src_bytes < kDmaRange, dma = src_dma && a.wgt_bytes < kDmaRange;
+    // 3x3 with the weights in registers (conv_regw.hip): 64 -> 64 channels
+    if (src_dma && !g_sw.no_regw && dense3x3(a, utap) && a.groups == 1 && a.Cs == a.Cd && a.spitch == a.Cs && a.dpitch == a.Cd &&
+        (!a.res || a.aff) && !a.res_bits && !a.mask_store && !a.src2 && !a.sbias && !a.no_store && a.Cs == 64 &&
+        (!(a.bw_x || a.bw_bits) || a.bn_partial)) {
+        const int rc = iif_regw3x3_select(a, r);
+        if (rc != IIF_EUNSUPPORTED) return rc;
     }
-    if (!force_v1_ && src_bytes < 0x7f000000LL && use_v2(a, utap, (int)sizeof(T), OUTF32)) {
-        a.mtiles = (a.M + 255) / 256;
-        a.ntiles = a.Cd / 64;
-        if (const int rc = claim_partial_rows(a)) return rc;
-        const int64_t blocks2 = (int64_t)((a.mtiles + 7) / 8) * 8 * a.ntiles;
-        if (blocks2 > 0x7fffffff) return IIF_EUNSUPPORTED;
-        if (a.wfrag_kind == 1) {
-            if (a.Cs != 64 || a.Cd != 64) return IIF_EINVAL;       // (the 16-channel format describes 64-channel chunks)
-            IIF_ROUTE_PROBE(IIF_ROUTE_FRAG_G16);
-            hipLaunchKernelGGL(conv3x3_g16_kernel, dim3((unsigned)blocks2, (unsigned)a.groups), dim3(256), 0, st, a, (unsigned)src_bytes);
-            IIF_LAUNCH_CHECK();
-            return IIF_OK;
-        }
-        IIF_ROUTE_PROBE(IIF_ROUTE_FRAG);
-        hipLaunchKernelGGL(conv3x3_v2n64_kernel, dim3((unsigned)blocks2, (unsigned)a.groups), dim3(256), 0, st, a, (unsigned)src_bytes);
-        IIF_LAUNCH_CHECK();
-        return IIF_OK;
+    if (src_dma && use_v2(a, utap)) {
+        if (const int rc = tile_route(a, r, a.wfrag_kind == 1 ? IIF_ROUTE_FRAG_G16 : IIF_ROUTE_FRAG, 64, 256, a.Cd / 64, (unsigned)a.groups, 256)) return rc;
+        return a.wfrag_kind == 1 && (a.Cs != 64 || a.Cd != 64) ? IIF_EINVAL : IIF_OK;       // (the 16-channel format describes 64-channel chunks)
     }
-    if (!force_v1_ && src_bytes < 0x7f000000LL && wgt_bytes < 0x7f000000LL && use_halo(a, utap, (int)sizeof(T), OUTF32)) {
+    if (dma && use_halo(a, utap)) {
         // measured (scripts/halo_ab.sh): two 128-row blocks per CU win at 28x28 (+8 %), one 256-row block elsewhere
         const int bm = a.Wd >= 28 ? 128 : 256;
-        a.mtiles = (a.M + bm - 1) / bm;
-        a.ntiles = (a.Cd + 127) / 128;
-        if (const int rc = claim_partial_rows(a)) return rc;
-        const int64_t blocksh = (int64_t)((a.mtiles + 7) / 8) * 8 * a.ntiles;
-        if (blocksh > 0x7fffffff) return IIF_EUNSUPPORTED;
-        IIF_ROUTE_PROBE(IIF_ROUTE_HALO);
-        if (bm == 128) hipLaunchKernelGGL(conv3x3_halo128_kernel, dim3((unsigned)blocksh), dim3(256), 0, st, a, (unsigned)src_bytes,
-                                          (unsigned)wgt_bytes);
-        else hipLaunchKernelGGL(conv3x3_halo_kernel, dim3((unsigned)blocksh), dim3(512), 0, st, a, (unsigned)src_bytes,
-                                (unsigned)wgt_bytes);
-        IIF_LAUNCH_CHECK();
-        return IIF_OK;
+        return tile_route(a, r, IIF_ROUTE_HALO, bm, bm, (a.Cd + 127) / 128, 1, 2 * bm);
     }
     StreamPlan sp{0, 0, 0};
-    if (!force_v1_ && src_bytes < 0x7f000000LL && wgt_bytes < 0x7f000000LL && use_stream1x1(a, utap, (int)sizeof(T), OUTF32, &sp)) {
-        a.mtiles = (a.M + 127) / 128;
-        a.ntiles = sp.slices;
+    if (dma && use_stream1x1(a, utap, &sp)) {
+        const int mtiles = (a.M + 127) / 128;
         // one block per CU, in whole groups of 8 S (the S slices of a tile sequence on one XCD); a short layer takes fewer
         // sequences, never more than it has tiles
         const int unit = 8 * sp.slices;
         int grid = iif_persistent_grid(unit);
-        const int need = (a.mtiles + 7) / 8 * unit;         // sequences in multiples of 8, S blocks each
+        const int need = (mtiles + 7) / 8 * unit;         // sequences in multiples of 8, S blocks each
         if (need < grid) grid = need;
-        if (grid >= unit) {
-            if (a.bn_partial) {                              // one row per tile sequence that has tiles (sequences 0 .. rows - 1)
-                const int seqs = grid / sp.slices, rows = seqs < a.mtiles ? seqs : a.mtiles;
-                if ((long long)(a.bn_row0 + rows) * 2 * a.dpitch > a.bn_cap) return IIF_EINVAL;
-                if (a.rows_out) *a.rows_out = a.bn_row0 + rows;
-            }
-            const unsigned sb = (unsigned)src_bytes, wb = (unsigned)wgt_bytes;
-            const dim3 g((unsigned)grid), blk(64 * (4 + STREAM_SW));
-            IIF_ROUTE_PROBE(IIF_ROUTE_STREAM1X1);
-            if (sp.bn == 256) hipLaunchKernelGGL((gemm1x1_stream_kernel<256, 64>), g, blk, 0, st, a, sb, wb);
-            else if (sp.bn == 128) hipLaunchKernelGGL((gemm1x1_stream_kernel<128, 256>), g, blk, 0, st, a, sb, wb);
-            else hipLaunchKernelGGL((gemm1x1_stream_kernel<64, 256>), g, blk, 0, st, a, sb, wb);
-            IIF_LAUNCH_CHECK();
-            return IIF_OK;
+        if (grid >= unit) {                               // (a smaller budget: the tile kernels)
+            *r = ConvRoute{IIF_ROUTE_STREAM1X1, sp.bn, -1, mtiles, sp.slices, (unsigned)grid, 1, 64 * (4 + STREAM_SW), 0, 0};
+            const int seqs = grid / sp.slices;            // one row per tile sequence that has tiles (sequences 0 .. rows - 1)
+            return iif_claim_rows(a, r, seqs < mtiles ? seqs : mtiles);
         }
     }
-    if (!force_v1_ && src_bytes < 0x7f000000LL && wgt_bytes < 0x7f000000LL && use_bm256(a, utap, (int)sizeof(T))) {
-        a.mtiles = (a.M + 255) / 256;
-        a.ntiles = (a.Cd + 127) / 128;
-        if (const int rc = claim_partial_rows(a)) return rc;
-        const int64_t blocks256 = (int64_t)((a.mtiles + 7) / 8) * 8 * a.ntiles;
-        if (blocks256 > 0x7fffffff) return IIF_EUNSUPPORTED;
-        IIF_ROUTE_PROBE(IIF_ROUTE_TILE256);
-        hipLaunchKernelGGL((conv_igemm_dma_utap256_kernel<T, OUTF32>), dim3((unsigned)blocks256, (unsigned)a.groups), dim3(512), 0,
-                           st, a, (unsigned)src_bytes, (unsigned)wgt_bytes);
-        IIF_LAUNCH_CHECK();
-        return IIF_OK;
-    }
-    a.mtiles = (a.M + 127) / 128;
-    const bool narrow = a.Cd <= 64;
-    const int bn = narrow ? 64 : 128;
-    a.ntiles = (a.Cd + bn - 1) / bn;
-    const int64_t blocks = (int64_t)((a.mtiles + 7) / 8) * 8 * a.ntiles;
-    if (blocks > 0x7fffffff) return IIF_EUNSUPPORTED;
-    const bool force_v1 = g_sw.regstage;
-    // LDS-DMA addressing is a 32-bit byte offset with a hardware range check: both operands must be < 2 GiB
-    const bool dma = !force_v1 && src_bytes < 0x7f000000LL && wgt_bytes < 0x7f000000LL;
+    if (dma && use_bm256(a, utap)) return tile_route(a, r, IIF_ROUTE_TILE256, 128, 256, (a.Cd + 127) / 128, (unsigned)a.groups, 512);
+    const int bn = a.Cd <= 64 ? 64 : 128, ntiles = (a.Cd + bn - 1) / bn;
+    if ((int64_t)(((a.M + 127) / 128 + 7) / 8) * 8 * ntiles > 0x7fffffff) return IIF_EUNSUPPORTED;
     if ((a.bn_partial || a.aff) && !dma) return IIF_EUNSUPPORTED;     // partial sums / the BN affine come out of the staged epilogue only
-    if (const int rc = claim_partial_rows(a)) return rc;
+    // two-stage / 4-blocks-per-CU variant up to K = 2304
+    // (round 5, same-call A/B: the long-K launches of small grids - the 7 x 7 stage's 392-block data gradients with 64 K steps -
+    // on the three-stage kernel instead, one barrier per step and two steps of prefetch: 18.40 / 18.43 / 18.41 ms per step
+    // against 18.39 / 18.42 / 18.40; for every grid of <= 1 600 blocks 18.42 / 18.42 / 18.43.  Level: knob removed.)
+    const bool shortk = bf16 && a.ntaps * a.Cs <= kTwoStageK && (a.Cd & 7) == 0 && !a.bias;
+    const int family = !dma ? IIF_ROUTE_REGSTAGE : !utap ? IIF_ROUTE_TILE_GENERAL : shortk ? IIF_ROUTE_TILE_2STAGE : IIF_ROUTE_TILE;
+    if (const int rc = tile_route(a, r, family, bn, 128, ntiles, (unsigned)a.groups, 256)) return rc;
     if (a.groups > 1 && !dma) return IIF_EUNSUPPORTED;     // grouped convolutions exist on the pipelined kernels only
     if (a.scatter && !(dma && utap)) return IIF_EUNSUPPORTED;
-    const dim3 grid((unsigned)blocks, (unsigned)a.groups), blk(256);
-    if (dma) {
-        const unsigned sb = (unsigned)src_bytes, wb = (unsigned)wgt_bytes;
-        if (!utap) IIF_ROUTE_PROBE(IIF_ROUTE_TILE_GENERAL);
-        if (utap) {
-            // two-stage / 4-blocks-per-CU variant up to K = 2304
-            // (round 5, same-call A/B: the long-K launches of small grids - the 7 x 7 stage's 392-block data gradients with 64 K steps -
-            // on the three-stage kernel instead, one barrier per step and two steps of prefetch: 18.40 / 18.43 / 18.41 ms per step
-            // against 18.39 / 18.42 / 18.40; for every grid of <= 1 600 blocks 18.42 / 18.42 / 18.43.  Level: knob removed.)
-            const bool shortk = sizeof(T) == 2 && !OUTF32 && a.ntaps * a.Cs <= kTwoStageK && (a.Cd & 7) == 0 && !a.bias;
-            if constexpr (sizeof(T) == 2 && !OUTF32) {
-                if (shortk) {
-                    IIF_ROUTE_PROBE(IIF_ROUTE_TILE_2STAGE);
-                    if (narrow) hipLaunchKernelGGL((conv_igemm_dma_utap_k64_kernel<64>), grid, blk, 0, st, a, sb, wb);
-                    else hipLaunchKernelGGL((conv_igemm_dma_utap_k64_kernel<128>), grid, blk, 0, st, a, sb, wb);
-                    IIF_LAUNCH_CHECK();
-                    return IIF_OK;
-                }
-            }
-            IIF_ROUTE_PROBE(IIF_ROUTE_TILE);
-            if (narrow) hipLaunchKernelGGL((conv_igemm_dma_utap_kernel<T, 64, OUTF32>), grid, blk, 0, st, a, sb, wb);
-            else hipLaunchKernelGGL((conv_igemm_dma_utap_kernel<T, 128, OUTF32>), grid, blk, 0, st, a, sb, wb);
-        } else {
-            if (narrow) hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 64, OUTF32>), grid, blk, 0, st, a, sb, wb);
-            else hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 128, OUTF32>), grid, blk, 0, st, a, sb, wb);
+    return IIF_OK;
+}
+
+// Tap list of a uniform-tap launch: source displacement in pixels of the source grid and weight tap index.
+//   forward:              source (y*stride + r - pad, x*stride + s - pad)
+//   data gradient, s=1:   source (y + pad - r, x + pad - s)
+//   data gradient, s=2:   one dense stride-1 sub-convolution per output parity class (py, px) = cls: only the taps
+//                         with (py + pad - r) even reach that class (1, 2, 2 and 4 of the 9 taps of a 3x3),
+//                         source (yy + (py + pad - r)/2, ...), destination scattered to (2*yy + py, 2*xx + px).
+struct Taps { int n; signed char dy[16], dx[16]; unsigned char w[16]; };
+Taps taps_of(const ConvSel& a, int cls) {
+    Taps t{};
+    const int py = cls >> 1, px = cls & 1;
+    for (int r = 0; r < a.R; ++r)
+        for (int s = 0; s < a.S; ++s) {
+            if (cls >= 0 && (((py + a.pad - r) | (px + a.pad - s)) & 1)) continue;
+            t.dy[t.n] = (signed char)(cls >= 0 ? (py + a.pad - r) / 2 : a.transposed ? a.pad - r : r - a.pad);      // (/ 2 exact: even)
+            t.dx[t.n] = (signed char)(cls >= 0 ? (px + a.pad - s) / 2 : a.transposed ? a.pad - s : s - a.pad);
+            t.w[t.n++] = (unsigned char)(r * a.S + s);
         }
-    } else {
-        IIF_ROUTE_PROBE(IIF_ROUTE_REGSTAGE);
-        if (narrow) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, OUTF32>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((conv_igemm_kernel<T, 128, OUTF32>), grid, blk, 0, st, a);
+    if (cls < 0 && a.src2) { t.dy[1] = 0; t.dx[1] = 0; t.w[1] = 1; t.n = 2; }      // K continues over the second source as "tap 1" of a 1x1 launch
+    return t;
+}
+// ... and the geometry of parity class cls (false: the class has no pixels)
+bool class_of(const ConvSel& a, int cls, ConvSel* c) {
+    *c = a;
+    c->Hd = (a.Hd - (cls >> 1) + 1) / 2; c->Wd = (a.Wd - (cls & 1) + 1) / 2;
+    c->M = a.N * c->Hd * c->Wd;
+    c->scatter = 1;
+    return c->Hd > 0 && c->Wd > 0;
+}
+
+// The launches of a call: one, or the parity classes of a stride-2 data gradient one by one (cumulative bn_row0).
+struct ConvPlan { int n; ConvRoute r[4]; };
+
+// SELECT.  `a`: geometry and operands of the call (sel_of); a pure host function.  The order: stem 4x4, the never-stored passes,
+// prologue, BN epilogue and register-weight 1x1 (conv_regw.hip), then select_one per launch.
+int select_conv(ConvSel a, ConvPlan* p) {
+    const bool bf16 = a.esz == 2 && !a.outf32;
+    const bool dma_ok = !g_sw.regstage && a.src_bytes < kDmaRange && a.wgt_bytes < kDmaRange;
+    const bool utap = dma_ok && (a.Cs % (a.esz == 2 ? 32 : 16)) == 0 && a.R * a.S <= 16 && a.R <= 16 && a.S <= 16;
+    ConvRoute* r = &p->r[0];
+    p->n = 1;
+    a.scatter = 0; a.ntaps = 0; a.in_shift = 0;
+    if (bf16) {
+        // the stem in its space-to-depth form has a kernel of its own (conv_stem.hip)
+        if (dma_ok && !a.transposed && iif_stem4x4_geometry(a) && a.ldw == 256 && a.Hs == a.Hd && a.Ws == a.Wd && !a.res && !a.bias &&
+            !a.bw_x && !a.src2 && !a.sbias && !a.mask_store && !a.no_store && !a.aff) {
+            const int rc = iif_stem4x4_select(a, r);
+            if (rc != IIF_EUNSUPPORTED) return rc;
+        }
+        const bool geo1x1x = dma_ok && iif_dense1x1(a) && !a.bias && !a.src2 && !a.sbias, geo1x1 = geo1x1x && !a.transposed;
+        const bool plain = geo1x1 && a.bn_partial && !a.res && !a.bw_x && !a.mask_store && !a.aff;
+        // the two passes of the never-stored forward (statistics from the accumulators / BN epilogue), the prologue
+        if (a.no_store == 2) return plain ? iif_regw1x1_select(a, IIF_REGW_STATS, r) : IIF_EUNSUPPORTED;
+        if (a.pro_stats)                                      // plain forward + statistics with the prologue: no other kernel has it
+            return plain && !a.no_store && iif_regw1x1_pro_ok(a.M, a.Cs, a.Cd) ? iif_regw1x1_select(a, IIF_REGW_PLAIN, r) : IIF_EUNSUPPORTED;
+        if (a.aff && geo1x1 && a.relu_out && !a.bn_partial && !a.res_bits && !a.bw_x && !a.mask_store && !g_sw.no_regw_fwdbn) {
+            const int rc = iif_regw1x1_select(a, IIF_REGW_FWDBN, r);
+            if (rc != IIF_EUNSUPPORTED) return rc;
+        }
+        // (aff2 beyond this point: staged_drain of the tile / 256-row / halo / fragment kernels, iif_conv_igemm_affine)
+        if (a.rx_src2 && !(geo1x1x && iif_regw1x1_rx_ok(a.M, a.Cs, a.Cd, a.rx_k2))) return IIF_EUNSUPPORTED;
+        // narrow -> wide 1x1 layers: weights in registers
+        const bool epi = a.res || a.res_bits || a.bw_x || a.bw_bits || a.mask_store;
+        if (geo1x1x && !a.aff && (!epi || (a.bn_partial && !a.no_store))) {
+            const int rc = iif_regw1x1_select(a, IIF_REGW_PLAIN, r);
+            if (rc != IIF_EUNSUPPORTED) return rc;
+        }
+    }
+    if (a.rx_src2 || a.pro_stats) return IIF_EUNSUPPORTED;    // (no other kernel recomputes the upstream x or has the prologue)
+    // (not uniform-tap, e.g. 16 source channels: the general-addressing pipelined kernel drains through staged_drain too)
+    if (!utap) return (a.src2 || a.sbias || a.mask_store || a.no_store || (a.aff && !dma_ok)) ? IIF_EUNSUPPORTED : select_one(a, false, r);
+    if (!a.transposed || a.sshift == 0) {
+        if (a.src2 && (a.R * a.S != 1 || (a.Cs2 % (a.esz == 2 ? 32 : 16)) || a.sshift != 0 || a.groups > 1)) return IIF_EUNSUPPORTED;
+        a.ntaps = taps_of(a, -1).n;
+        a.in_shift = a.transposed ? 0 : a.sshift;
+        return select_one(a, true, r);
+    }
+    // stride-2 data gradient: 4 parity classes of the destination grid
+    ConvSel cls[4];
+    int id[4], ncls = 0;
+    for (int k = 0; k < 4; ++k) {
+        ConvSel& c = cls[ncls];
+        if (!class_of(a, k, &c)) continue;
+        c.ntaps = taps_of(a, k).n;
+        // a class without taps receives no contribution (dst += 0): skipped, unless the backward sums of the
+        // upstream unit ride on this launch (every pixel of dst has to be visited once)
+        if (c.ntaps == 0 && c.res_is_dst && !c.bw_x) continue;
+        id[ncls++] = k;
+    }
+    // all classes in one launch where each of them would take the 4-blocks-per-CU tile kernel
+    if (bf16 && a.R * a.S * a.Cs <= kTwoStageK && (a.Cd & 7) == 0 && !a.bias && a.groups == 1 && ncls > 1 && !g_sw.regstage) {
+        const int bn = a.Cd <= 64 ? 64 : 128, ntiles = (a.Cd + bn - 1) / bn;
+        int64_t blocks = 0;
+        int rows = 0;
+        for (int i = 0; i < ncls; ++i) {
+            const int mtiles = (cls[i].M + 127) / 128;
+            blocks += (int64_t)((mtiles + 7) / 8) * 8 * ntiles;
+            rows += mtiles;
+        }
+        if (blocks <= 0x7fffffff) {
+            *r = ConvRoute{IIF_ROUTE_TILE_MC, bn, -1, 0, ntiles, (unsigned)blocks, 1, 256, 0, 0};
+            return iif_claim_rows(a, r, rows);
+        }
+    }
+    p->n = ncls;
+    for (int i = 0; i < ncls; ++i) {
+        if (const int rc = select_one(cls[i], true, &p->r[i])) return rc;
+        p->r[i].cls = id[i];
+        if (i + 1 < ncls) cls[i + 1].bn_row0 = cls[i].bn_row0 + p->r[i].rows;
+    }
+    return IIF_OK;
+}
+
+// LAUNCH: exactly the selected kernel.  `s`: the call's ConvSel with bn_row0 of this launch.
+ConvArgs args_of(const ConvCall& c, const ConvSel& s0, const ConvRoute& r) {
+    ConvSel s = s0;
+    if (r.cls >= 0) class_of(s0, r.cls, &s);
+    ConvArgs a{};
+    a.src = (const unsigned char*)c.src; a.wgt = (const unsigned char*)c.wgt; a.dst = (unsigned char*)c.dst;
+    a.res = (const unsigned char*)c.res; a.bias = c.bias; a.res_bits = c.res_bits;
+    a.wfrag = (const unsigned char*)c.d->wgt_frag; a.wfrag_kind = s.wfrag_kind;
+    if (c.bn_partial) {
+        a.bn_partial = c.bn_partial; a.bn_cap = c.bn_cap;
+        a.bw_x = (const unsigned char*)c.bw_x; a.bw_bits = c.bw_bits; a.bw_stats = c.bw_stats;
+    }
+    a.mask_store = c.mask_store; a.src2 = (const unsigned char*)c.src2; a.Cs2 = c.cs2; a.sbias = c.sbias;
+    a.no_store = c.no_store; a.aff = c.aff; a.relu_out = c.relu_out; a.aff2 = c.aff2;
+    a.N = s.N; a.Hs = s.Hs; a.Ws = s.Ws; a.Cs = s.Cs; a.Hd = s.Hd; a.Wd = s.Wd; a.Cd = s.Cd;
+    a.R = s.R; a.S = s.S; a.sshift = s.sshift; a.pad = s.pad; a.transposed = s.transposed;
+    a.ldw = s.ldw; a.M = s.M; a.K = s.R * s.S * s.Cs; a.groups = s.groups; a.spitch = s.spitch; a.dpitch = s.dpitch;
+    a.mtiles = r.mtiles; a.ntiles = r.ntiles; a.bn_row0 = s0.bn_row0;
+    const bool classes = r.cls >= 0 || r.family == IIF_ROUTE_TILE_MC;
+    a.scatter = a.ds_shift = classes; a.doy = r.cls >= 0 ? r.cls >> 1 : 0; a.dox = r.cls >= 0 ? r.cls & 1 : 0;
+    a.Hfull = s0.Hd; a.Wfull = s0.Wd;
+    if (r.family != IIF_ROUTE_TILE_GENERAL && r.family != IIF_ROUTE_REGSTAGE && r.family != IIF_ROUTE_TILE_MC) {
+        const Taps t = taps_of(s0, r.cls);
+        a.ntaps = t.n; a.in_shift = classes || s.transposed ? 0 : s.sshift;
+        for (int i = 0; i < 16; ++i) { a.tap_dy[i] = t.dy[i]; a.tap_dx[i] = t.dx[i]; a.tap_w[i] = t.w[i]; }
+    }
+    return a;
+}
+
+template <typename T, bool OUTF32>
+int launch_route(const ConvCall& c, const ConvSel& s, const ConvRoute& r, hipStream_t st) {
+    if (r.family == IIF_ROUTE_STEM) return iif_stem4x4_launch(r, c, s, st);
+    if (r.family == IIF_ROUTE_REGW1X1) return iif_regw1x1_launch(r, c, s, st);
+    const ConvArgs a = args_of(c, s, r);
+    const unsigned sb = (unsigned)s.src_bytes, wb = (unsigned)s.wgt_bytes;
+    const dim3 g(r.grid, r.grid_y), b(r.block);
+    const bool narrow = r.inst == 64;
+    switch (r.family) {
+    case IIF_ROUTE_REGW3X3:
+        return iif_regw3x3_launch(r, c, s, a.tap_dy, a.tap_dx, a.tap_w, st);
+    case IIF_ROUTE_FRAG_G16:
+        hipLaunchKernelGGL(conv3x3_g16_kernel, g, b, 0, st, a, sb);
+        break;
+    case IIF_ROUTE_FRAG:
+        hipLaunchKernelGGL(conv3x3_v2n64_kernel, g, b, 0, st, a, sb);
+        break;
+    case IIF_ROUTE_HALO:
+        if (r.inst == 128) hipLaunchKernelGGL(conv3x3_halo128_kernel, g, b, 0, st, a, sb, wb);
+        else hipLaunchKernelGGL(conv3x3_halo_kernel, g, b, 0, st, a, sb, wb);
+        break;
+    case IIF_ROUTE_STREAM1X1:
+        if (r.inst == 256) hipLaunchKernelGGL((gemm1x1_stream_kernel<256, 64>), g, b, 0, st, a, sb, wb);
+        else if (r.inst == 128) hipLaunchKernelGGL((gemm1x1_stream_kernel<128, 256>), g, b, 0, st, a, sb, wb);
+        else hipLaunchKernelGGL((gemm1x1_stream_kernel<64, 256>), g, b, 0, st, a, sb, wb);
+        break;
+    case IIF_ROUTE_TILE256:
+        hipLaunchKernelGGL((conv_igemm_dma_utap256_kernel<T, OUTF32>), g, b, 0, st, a, sb, wb);
+        break;
+    case IIF_ROUTE_TILE_2STAGE:
+        if constexpr (sizeof(T) == 2 && !OUTF32) {              // (bf16 in and out only)
+            if (narrow) hipLaunchKernelGGL((conv_igemm_dma_utap_k64_kernel<64>), g, b, 0, st, a, sb, wb);
+            else hipLaunchKernelGGL((conv_igemm_dma_utap_k64_kernel<128>), g, b, 0, st, a, sb, wb);
+        }
+        break;
+    case IIF_ROUTE_TILE:
+        if (narrow) hipLaunchKernelGGL((conv_igemm_dma_utap_kernel<T, 64, OUTF32>), g, b, 0, st, a, sb, wb);
+        else hipLaunchKernelGGL((conv_igemm_dma_utap_kernel<T, 128, OUTF32>), g, b, 0, st, a, sb, wb);
+        break;
+    case IIF_ROUTE_TILE_GENERAL:
+        if (narrow) hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 64, OUTF32>), g, b, 0, st, a, sb, wb);
+        else hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 128, OUTF32>), g, b, 0, st, a, sb, wb);
+        break;
+    case IIF_ROUTE_REGSTAGE:
+        if (narrow) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, OUTF32>), g, b, 0, st, a);
+        else hipLaunchKernelGGL((conv_igemm_kernel<T, 128, OUTF32>), g, b, 0, st, a);
+        break;
+    case IIF_ROUTE_TILE_MC: {                                   // every parity class of a stride-2 data gradient in one grid
+        ConvArgsMC p{};
+        p.a = a;
+        int64_t bstart = 0;
+        int row0 = a.bn_row0;
+        for (int k = 0; k < 4; ++k) {
+            ConvSel cs;
+            const Taps t = taps_of(s, k);
+            if (!class_of(s, k, &cs) || (t.n == 0 && s.res_is_dst && !s.bw_x)) continue;
+            ConvClass& q = p.cls[p.ncls++];
+            q.Hd = cs.Hd; q.Wd = cs.Wd; q.M = cs.M; q.mtiles = (cs.M + 127) / 128;
+            q.doy = k >> 1; q.dox = k & 1; q.ntaps = t.n; q.bn_row0 = row0; q.bstart = (int)bstart;
+            for (int i = 0; i < 16; ++i) { q.tap_dy[i] = t.dy[i]; q.tap_dx[i] = t.dx[i]; q.tap_w[i] = t.w[i]; }
+            bstart += (int64_t)((q.mtiles + 7) / 8) * 8 * r.ntiles;
+            row0 += q.mtiles;
+        }
+        if (narrow) hipLaunchKernelGGL(conv_igemm_dma_utap_k64_mc64_kernel, g, b, 0, st, p, sb, wb);
+        else hipLaunchKernelGGL(conv_igemm_dma_utap_k64_mc128_kernel, g, b, 0, st, p, sb, wb);
+        break;
+    }
+    default:
+        return IIF_EUNSUPPORTED;
     }
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }
 
-// Host-side planning: which addressing path, and the tap lists of the uniform-tap path.
-//   forward:              source (y*stride + r - pad, x*stride + s - pad)
-//   data gradient, s=1:   source (y + pad - r, x + pad - s)
-//   data gradient, s=2:   one dense stride-1 sub-convolution per output parity class (py, px): only the taps
-//                         with (py + pad - r) even reach that class (1, 2, 2 and 4 of the 9 taps of a 3x3),
-//                         source (yy + (py + pad - r)/2, ...), destination scattered to (2*yy + py, 2*xx + px).
-template <typename T, bool OUTF32>
-int launch_conv(const ConvArgs& a0, int64_t src_bytes, int64_t wgt_bytes, hipStream_t st) {
-    ConvArgs a = a0;
-    const bool dma_ok = !g_sw.regstage && src_bytes < 0x7f000000LL && wgt_bytes < 0x7f000000LL;
-    const bool utap = dma_ok && (a.Cs % ET<T>::KE) == 0 && a.R * a.S <= 16 && a.R <= 16 && a.S <= 16;
-    a.scatter = 0; a.ds_shift = 0; a.doy = a.dox = 0; a.Hfull = a.Hd; a.Wfull = a.Wd; a.ntaps = 0; a.in_shift = 0;
-    if constexpr (sizeof(T) == 2 && !OUTF32) {      // the stem in its space-to-depth form has a kernel of its own (conv_stem.hip)
-        if (dma_ok && !a.transposed && a.sshift == 0 && a.R == 4 && a.S == 4 && a.pad == 2 && a.Cs == 16 && a.spitch == 16 &&
-            a.Cd == 64 && a.dpitch == 64 && a.groups == 1 && a.ldw == 256 && a.Hs == a.Hd && a.Ws == a.Wd && !a.res && !a.bias && !a.bw_x &&
-            !a.src2 && !a.sbias && !a.mask_store && !a.no_store && !a.aff && iif_stem4x4_ok(a.N, a.Hd, a.Wd))
-        {
-            const int rc = iif_stem4x4_launch(a.src, a.wgt, a.dst, a.bn_partial, a.bn_cap, a.bn_row0, a.rows_out, a.N, a.Hd, a.Wd, st);
-            if (rc != IIF_EUNSUPPORTED) return rc;
-        }
-        // the two passes of the never-stored forward (conv_regw.hip: statistics from the accumulators / BN epilogue)
-        const bool geo1x1 = dma_ok && !g_sw.no_regw && a.R == 1 && a.S == 1 && a.sshift == 0 && a.pad == 0 && a.groups == 1 && a.spitch == a.Cs &&
-                            a.dpitch == a.Cd && a.Hs == a.Hd && a.Ws == a.Wd && !a.bias && !a.src2 && !a.sbias && !a.transposed;
-        const bool geo1x1x = dma_ok && !g_sw.no_regw && a.R == 1 && a.S == 1 && a.sshift == 0 && a.pad == 0 && a.groups == 1 && a.spitch == a.Cs &&
-                             a.dpitch == a.Cd && a.Hs == a.Hd && a.Ws == a.Wd && !a.bias && !a.src2 && !a.sbias;
-        const iif_regw_prologue pro{a.pro_stats, a.pro_out, a.pro_bits, a.pro_csum};
-        if (a.no_store == 2) {
-            if (!geo1x1 || !a.bn_partial || a.res || a.bw_x || a.mask_store || a.aff) return IIF_EUNSUPPORTED;
-            return iif_regw1x1_stats_launch(a.src, a.wgt, a.bn_partial, a.bn_cap, a.bn_row0, a.rows_out, a.M, a.Cs, a.Cd, a.spitch, a.ldw, a.dpitch, st,
-                                            a.pro_stats ? &pro : nullptr);
-        }
-        if (a.pro_stats) {                                    // plain forward + statistics with the prologue: no other kernel has it
-            if (!geo1x1 || !a.bn_partial || a.res || a.bw_x || a.mask_store || a.aff || a.no_store || !iif_regw1x1_pro_ok(a.M, a.Cs, a.Cd)) return IIF_EUNSUPPORTED;
-            return iif_regw1x1_launch(a.src, a.wgt, a.dst, a.bn_partial, a.bn_cap, a.bn_row0, a.rows_out, a.M, a.Cs, a.Cd, a.spitch, a.ldw, a.dpitch,
-                                      nullptr, 0, st, &pro);
-        }
-        if (a.aff && geo1x1 && a.relu_out && !a.bn_partial && !a.res_bits && !a.bw_x && !a.mask_store && !g_sw.no_regw_fwdbn &&
-            iif_regw1x1_fwdbn_ok(a.M, a.Cs, a.Cd)) {
-            const int rc = iif_regw1x1_fwdbn_launch(a.src, a.wgt, a.dst, a.M, a.Cs, a.Cd, a.spitch, a.ldw, a.dpitch, a.res, a.aff, a.aff2, a.relu_out, st);
-            if (rc != IIF_EUNSUPPORTED) return rc;
-        }
-        // (aff2 beyond this point: staged_drain of the tile / 256-row / halo / fragment kernels, iif_conv_igemm_affine)
-        if (a.rx_src2 && !(geo1x1x && iif_regw1x1_rx_ok(a.M, a.Cs, a.Cd, a.rx_k2))) return IIF_EUNSUPPORTED;
-        // narrow -> wide 1x1 layers: weights in registers (conv_regw.hip)
-        const bool epi = a.res || a.res_bits || a.bw_x || a.bw_bits || a.mask_store;
-        if (dma_ok && !g_sw.no_regw && a.R == 1 && a.S == 1 && a.sshift == 0 && a.pad == 0 && a.groups == 1 && a.spitch == a.Cs && a.dpitch == a.Cd &&
-            a.Hs == a.Hd && a.Ws == a.Wd && !a.bias && !a.src2 && !a.sbias && !a.aff && (!epi || (a.bn_partial && !a.no_store)) &&
-            iif_regw1x1_ok(a.M, a.Cs, a.Cd, epi))
-        {
-            const iif_regw_epilogue e{a.res, a.res_bits, a.bw_x, a.bw_bits, a.bw_stats, a.mask_store, a.rx_src2, a.rx_w3, a.rx_k2, a.rx_ldw3,
-                                      a.pg_slab, a.pg_cap, a.pg_ld, a.pg_count};
-            const int rc = iif_regw1x1_launch(a.src, a.wgt, a.dst, a.bn_partial, a.bn_cap, a.bn_row0, a.rows_out, a.M, a.Cs, a.Cd, a.spitch,
-                                              a.ldw, a.dpitch, epi ? &e : nullptr, a.no_store, st);
-            if (rc != IIF_EUNSUPPORTED) return rc;
-        }
-        if (a.rx_src2) return IIF_EUNSUPPORTED;               // (no other kernel recomputes the upstream x)
+// Geometry of a descriptor as selection reads it (no validation: conv_select has it)
+void sel_geometry(const iif_conv_desc* d, ConvSel* a) {
+    a->N = d->n; a->Hs = d->hs; a->Ws = d->ws; a->Cs = d->cs; a->Hd = d->hd; a->Wd = d->wd; a->Cd = d->cd;
+    a->R = d->r; a->S = d->s; a->sshift = d->stride - 1; a->pad = d->pad; a->transposed = d->transposed ? 1 : 0;
+    a->ldw = d->ldw; a->M = (int)((int64_t)d->n * d->hd * d->wd);
+    a->groups = d->groups > 1 ? d->groups : 1;
+    a->spitch = a->groups * d->cs; a->dpitch = a->groups * d->cd;
+    a->esz = d->dtype == IIF_F32 ? 4 : 2; a->outf32 = d->dst_dtype == IIF_F32;
+    a->src_bytes = (int64_t)d->n * d->hs * d->ws * a->spitch * a->esz;
+    a->wgt_bytes = (int64_t)d->cd * d->ldw * a->esz;
+    a->wfrag = d->wgt_frag != nullptr; a->wfrag_kind = d->wgt_frag ? d->wgt_frag_kind : 0;
+}
+
+// Descriptors whose forward launch ends in a kernel that drains through the LDS-staged epilogue (or the register-weight 3x3
+// kernel's affine drain): bf16 in and out, whole 16-byte vectors per destination row and group, both operands within the
+// 32-bit LDS-DMA range.  Every route of select_one behind these conditions carries the BN affine.
+bool affine_geometry_ok(const iif_conv_desc* d) {
+    if (!d || g_sw.regstage || d->transposed || d->dtype != IIF_BF16 || d->dst_dtype != IIF_BF16) return false;
+    if (d->n <= 0 || d->hs <= 0 || d->ws <= 0 || d->cs <= 0 || d->hd <= 0 || d->wd <= 0 || d->cd <= 0 || d->r <= 0 || d->s <= 0 || d->pad < 0) return false;
+    if (d->stride != 1 && d->stride != 2) return false;
+    ConvSel a{};
+    sel_geometry(d, &a);
+    // (the space-to-depth stem has a kernel of its own without this epilogue, and another K order than the tile kernels)
+    if (iif_stem4x4_geometry(a)) return false;
+    if (a.groups > 65535 || (d->cd % 8) || (d->cs % 8) || (d->ldw % 8) || d->ldw < d->r * d->s * d->cs) return false;
+    if ((int64_t)d->n * d->hd * d->wd > 0x7fffff00LL || (int64_t)d->n * d->hs * d->ws > 0x7fffff00LL) return false;
+    return a.src_bytes < kDmaRange && a.wgt_bytes < kDmaRange;
+}
+
+// Validation and selection of a call: `a` holds its operands and options (sel_of, or a query's), the geometry is filled in here.
+// unaligned: one of src / wgt / dst / res off 16 bytes; src2_unaligned likewise.
+int conv_select(const iif_conv_desc* d, ConvSel* a, bool unaligned, bool src2_unaligned, int aff_any, ConvPlan* p) {
+    if (d->n <= 0 || d->hs <= 0 || d->ws <= 0 || d->cs <= 0 || d->hd <= 0 || d->wd <= 0 || d->cd <= 0 ||
+        d->r <= 0 || d->s <= 0 || d->pad < 0)
+        return IIF_EINVAL;
+    if (d->stride != 1 && d->stride != 2) return IIF_EUNSUPPORTED;
+    if (d->dtype != IIF_F32 && d->dtype != IIF_BF16) return IIF_EINVAL;
+    if (d->dst_dtype != d->dtype && d->dst_dtype != IIF_F32) return IIF_EINVAL;
+    const int pe = d->dtype == IIF_F32 ? 4 : 8;
+    if (d->cs % pe != 0 || d->ldw % pe != 0 || d->ldw < d->r * d->s * d->cs + (a->src2 ? a->Cs2 : 0)) return IIF_EUNSUPPORTED;
+    const bool bf16 = d->dtype == IIF_BF16 && d->dst_dtype == IIF_BF16;
+    if (aff_any) {
+        if (!affine_geometry_ok(d) || a->bias || a->bn_partial || a->res_bits || a->bw_x) return IIF_EUNSUPPORTED;
+    } else if (a->src2 || a->sbias || a->mask_store || a->no_store || a->aff || a->pro_stats) {
+        // round-3 epilogue / operand options: bf16 1x1 stride-1 launches on the LDS-staged epilogue only
+        if (!bf16 || d->r != 1 || d->s != 1 || d->stride != 1 || d->pad != 0 || d->groups > 1 || (d->cd % 8) || a->bias || (d->cs % 32))
+            return IIF_EUNSUPPORTED;
+        if (a->src2 && ((a->Cs2 % 32) || a->Cs2 <= 0 || src2_unaligned)) return IIF_EUNSUPPORTED;
+        if (a->mask_store && (!a->bw_bits || !a->bn_partial)) return IIF_EINVAL;
+        if (a->no_store && (!a->bn_partial || a->res || a->bw_x)) return IIF_EINVAL;
+        if (a->aff && (a->bn_partial || a->res_bits || a->bw_x || a->no_store)) return IIF_EINVAL;
     }
-    if (a.rx_src2 || a.pro_stats) return IIF_EUNSUPPORTED;
-    // (not uniform-tap, e.g. 16 source channels: the general-addressing pipelined kernel drains through staged_drain too)
-    if (!utap) return (a.src2 || a.sbias || a.mask_store || a.no_store || (a.aff && !dma_ok)) ? IIF_EUNSUPPORTED : launch_one<T, OUTF32>(a, false, src_bytes, wgt_bytes, st);
-    if (!a.transposed || a.sshift == 0) {
-        for (int r = 0; r < a.R; ++r)
-            for (int s = 0; s < a.S; ++s) {
-                const int t = a.ntaps++;
-                a.tap_dy[t] = (signed char)(a.transposed ? a.pad - r : r - a.pad);
-                a.tap_dx[t] = (signed char)(a.transposed ? a.pad - s : s - a.pad);
-                a.tap_w[t] = (unsigned char)(r * a.S + s);
-            }
-        a.in_shift = a.transposed ? 0 : a.sshift;
-        if (a.src2) {                                        // K continues over the second source as "tap 1" of a 1x1 launch
-            if (a.ntaps != 1 || (a.Cs2 % ET<T>::KE) || a.sshift != 0 || a.groups > 1) return IIF_EUNSUPPORTED;
-            a.tap_dy[1] = 0; a.tap_dx[1] = 0; a.tap_w[1] = 1; a.ntaps = 2;
-        }
-        return launch_one<T, OUTF32>(a, true, src_bytes, wgt_bytes, st);
-    }
-    // stride-2 data gradient: 4 parity classes of the destination grid
-    const int H = a.Hd, W = a.Wd;
-    ConvArgs cls[4];
-    int ncls = 0;
-    for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px) {
-            ConvArgs c = a;
-            c.Hd = (H - py + 1) / 2; c.Wd = (W - px + 1) / 2;
-            if (c.Hd <= 0 || c.Wd <= 0) continue;
-            c.M = a.N * c.Hd * c.Wd;
-            c.scatter = 1; c.ds_shift = 1; c.doy = py; c.dox = px; c.Hfull = H; c.Wfull = W;
-            c.ntaps = 0;
-            for (int r = 0; r < a.R; ++r) {
-                if ((py + a.pad - r) & 1) continue;
-                for (int s = 0; s < a.S; ++s) {
-                    if ((px + a.pad - s) & 1) continue;
-                    const int t = c.ntaps++;
-                    c.tap_dy[t] = (signed char)((py + a.pad - r) / 2);      // exact: the numerator is even
-                    c.tap_dx[t] = (signed char)((px + a.pad - s) / 2);
-                    c.tap_w[t] = (unsigned char)(r * a.S + s);
-                }
-            }
-            // a class without taps receives no contribution (dst += 0): skipped, unless the backward sums of the
-            // upstream unit ride on this launch (every pixel of dst has to be visited once)
-            if (c.ntaps == 0 && c.res == c.dst && !c.bw_x) continue;
-            cls[ncls++] = c;
-        }
-    // all classes in one launch where each of them would take the 4-blocks-per-CU tile kernel
-    if constexpr (sizeof(T) == 2 && !OUTF32) {
-        const bool shortk = a.R * a.S * a.Cs <= kTwoStageK && (a.Cd & 7) == 0 && !a.bias && a.groups == 1 && ncls > 1 && !g_sw.regstage;
-        if (shortk) {
-            ConvArgsMC p{};
-            p.a = a;
-            p.a.scatter = 1; p.a.ds_shift = 1; p.a.Hfull = H; p.a.Wfull = W; p.a.in_shift = 0;
-            const bool narrow = a.Cd <= 64;
-            const int bn = narrow ? 64 : 128;
-            p.a.ntiles = (a.Cd + bn - 1) / bn;
-            p.ncls = ncls;
-            int64_t bstart = 0;
-            int row0 = a.rows_out ? *a.rows_out : a.bn_row0;
-            for (int i = 0; i < ncls; ++i) {
-                ConvClass& k = p.cls[i];
-                k.Hd = cls[i].Hd; k.Wd = cls[i].Wd; k.M = cls[i].M; k.mtiles = (cls[i].M + 127) / 128;
-                k.doy = cls[i].doy; k.dox = cls[i].dox; k.ntaps = cls[i].ntaps; k.bn_row0 = row0; k.bstart = (int)bstart;
-                for (int t = 0; t < 16; ++t) { k.tap_dy[t] = cls[i].tap_dy[t]; k.tap_dx[t] = cls[i].tap_dx[t]; k.tap_w[t] = cls[i].tap_w[t]; }
-                bstart += (int64_t)((k.mtiles + 7) / 8) * 8 * p.a.ntiles;
-                row0 += k.mtiles;
-            }
-            if (bstart <= 0x7fffffff) {
-                if (a.bn_partial) {
-                    if ((long long)row0 * 2 * a.dpitch > a.bn_cap) return IIF_EINVAL;
-                    if (a.rows_out) *a.rows_out = row0;
-                }
-                const dim3 grid((unsigned)bstart), blk(256);
-                if (narrow) hipLaunchKernelGGL(conv_igemm_dma_utap_k64_mc64_kernel, grid, blk, 0, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes);
-                else hipLaunchKernelGGL(conv_igemm_dma_utap_k64_mc128_kernel, grid, blk, 0, st, p, (unsigned)src_bytes, (unsigned)wgt_bytes);
-                IIF_LAUNCH_CHECK();
-                return IIF_OK;
-            }
-        }
-    }
-    for (int i = 0; i < ncls; ++i) {
-        ConvArgs& c = cls[i];
-        if (c.rows_out) c.bn_row0 = *c.rows_out;
-        const int rc = launch_one<T, OUTF32>(c, true, src_bytes, wgt_bytes, st);
+    if (unaligned) return IIF_EUNSUPPORTED;
+    if ((int64_t)d->n * d->hd * d->wd > 0x7fffff00LL || (int64_t)d->n * d->hs * d->ws > 0x7fffff00LL) return IIF_EUNSUPPORTED;
+    sel_geometry(d, a);
+    // fused statistics (forward) / backward sums of the upstream unit need the LDS-staged bf16 epilogue of the
+    // pipelined kernels; one partial row per pixel tile, counted where the tile height is chosen (select_one)
+    if (a->bn_partial && !(bf16 && (d->cd % 8) == 0 && !a->bias && (a->bw_x || a->mask_store || !a->res) && !g_sw.regstage &&
+                           a->src_bytes < kDmaRange))
+        return IIF_EUNSUPPORTED;
+    if (a->groups > 65535) return IIF_EUNSUPPORTED;
+    return select_conv(*a, p);
+}
+
+// The operands of a call as selection sees them: present or not
+ConvSel sel_of(const ConvCall& c) {
+    ConvSel a{};
+    a.res = c.res; a.res_bits = c.res_bits; a.bias = c.bias; a.bn_partial = c.bn_partial;
+    a.bw_x = c.bn_partial && c.bw_x; a.bw_bits = c.bn_partial && c.bw_bits; a.bw_stats = c.bn_partial && c.bw_stats;
+    a.src2 = c.src2; a.sbias = c.sbias; a.aff = c.aff; a.aff2 = c.aff2; a.relu_out = c.relu_out;
+    a.rx_src2 = c.rx_src2; a.rx_w3 = c.rx_w3; a.pro_stats = c.pro_stats; a.pg_slab = c.pg_slab; a.pg_count = c.pg_count;
+    a.res_is_dst = c.res == c.dst; a.pg_unaligned = reinterpret_cast<uintptr_t>(c.pg_slab) & 15;
+    a.mask_store = c.mask_store; a.no_store = c.no_store; a.Cs2 = c.cs2; a.rx_k2 = c.rx_k2; a.rx_ldw3 = c.rx_ldw3; a.pg_ld = c.pg_ld;
+    a.bn_cap = c.bn_cap; a.pg_cap = c.pg_cap;
+    return a;
+}
+
+int conv_entry(const ConvCall& c) {
+    const iif_conv_desc* d = c.d;
+    if (!d || !c.src || !c.wgt || !c.dst) return IIF_EINVAL;
+    if (c.n_partials) *c.n_partials = 0;
+    if (c.pg_count) *c.pg_count = 0;
+    ConvSel s = sel_of(c);
+    ConvPlan p;
+    const bool unaligned = (reinterpret_cast<uintptr_t>(c.src) | reinterpret_cast<uintptr_t>(c.wgt) | reinterpret_cast<uintptr_t>(c.dst) |
+                            reinterpret_cast<uintptr_t>(c.res)) & 15;
+    if (const int rc = conv_select(d, &s, unaligned, reinterpret_cast<uintptr_t>(c.src2) & 15, c.aff_any, &p)) return rc;
+    hipStream_t st = as_stream(c.stream);
+    for (int i = 0; i < p.n; ++i) {
+        const ConvRoute& r = p.r[i];
+        const int rc = d->dtype == IIF_BF16 ? (s.outf32 ? launch_route<unsigned short, true>(c, s, r, st)
+                                                        : launch_route<unsigned short, false>(c, s, r, st))
+                                            : launch_route<float, true>(c, s, r, st);
         if (rc != IIF_OK) return rc;
+        s.bn_row0 += r.rows;
+        if (c.n_partials) *c.n_partials = s.bn_row0;
+        if (c.pg_count) *c.pg_count = r.slabs;
     }
     return IIF_OK;
 }
 
 }  // namespace
 
-namespace {
-struct ConvExtra { int mask_store; const void* src2; int cs2; const float* sbias; int no_store; const float* aff; unsigned char* relu_out; const float* aff2;
-                   const void* rx_src2; const void* rx_w3; int rx_k2, rx_ldw3;
-                   const float* pro_stats; void* pro_out; unsigned char* pro_bits; float* pro_csum;
-                   float* pg_slab; long long pg_cap; int pg_ld; int* pg_count;
-                   int aff_any; };           // aff on every geometry the staged epilogue serves (iif_conv_igemm_affine)
-int conv_entry(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
-               const unsigned char* res_bits, const float* bias, float* bn_partial, int64_t bn_partial_floats,
-               int32_t* n_partials, void* stream, const void* bw_x = nullptr, const unsigned char* bw_bits = nullptr,
-               const float* bw_stats = nullptr, const ConvExtra* ex = nullptr);
+ConvSwitches g_sw = ConvSwitches::read();
+ConvSwitches ConvSwitches::read() {
+    ConvSwitches c;
+    c.no_stream = getenv("IIF_CONV_NO_STREAM1X1") != nullptr;
+    c.force_stream = getenv("IIF_CONV_STREAM1X1_FORCE") != nullptr;
+    c.regstage = getenv("IIF_CONV_REGSTAGE") != nullptr;
+    c.no_v2 = getenv("IIF_CONV_NO_V2") != nullptr;
+    c.no_halo = getenv("IIF_CONV_NO_HALO") != nullptr;
+    c.v2_force = getenv("IIF_CONV_V2_FORCE") != nullptr;
+    c.force_halo = getenv("IIF_CONV_HALO_FORCE") != nullptr;
+    c.no_regw = getenv("IIF_CONV_NO_REGW") != nullptr;
+    c.no_regw_fwdbn = getenv("IIF_CONV_NO_REGW_FWDBN") != nullptr;      // tests: the BN epilogue on the tile kernels
+    c.no_bm256_2src = getenv("IIF_CONV_NO_BM256_2SRC") != nullptr;
+    c.regw_k512_cw16 = getenv("IIF_REGW_K512_CW16") != nullptr;
+    c.regw_no_x2 = getenv("IIF_REGW_NO_X2") != nullptr;
+    c.regw_k512_no_epi = getenv("IIF_REGW_K512_NO_EPI") != nullptr;
+    return c;
 }
 
 extern "C" int iif_conv_pack_fragments(const void* src_base, const iif_pack_desc* table, int n_desc, int total_blocks,
@@ -2221,21 +2294,67 @@ extern "C" int iif_conv_pack_fragments_g16(const void* src_base, const iif_pack_
     return IIF_OK;
 }
 
+extern "C" int iif_conv_reload_env(void) {
+    g_sw = ConvSwitches::read();
+    return IIF_OK;
+}
+
+// ---- planning queries: the selectors' own predicates over the descriptor's geometry
+namespace {
+// a forward (transposed 0) or data-gradient (1) descriptor of the register-weight 1x1 kernels' geometry
+bool query_dense1x1(const iif_conv_desc* d, int transposed, ConvSel* a) {
+    if (!d || d->dtype != IIF_BF16 || d->dst_dtype != IIF_BF16) return false;
+    *a = ConvSel{};
+    sel_geometry(d, a);
+    return iif_dense1x1(*a) && a->transposed == transposed;
+}
+}  // namespace
+
 extern "C" int iif_conv3x3_frag_ok(const iif_conv_desc* d) {
     if (!d || g_sw.no_v2 || g_sw.regstage) return 0;
     if (d->dtype != IIF_BF16 || d->dst_dtype != IIF_BF16 || d->r != 3 || d->s != 3 || d->stride != 1 || d->pad != 1) return 0;
     if (d->hs != d->hd || d->ws != d->wd) return 0;
     const int g = d->groups > 1 ? d->groups : 1;
     if (g > 1 && (d->cs != 64 || d->cd != 64)) return 0;
-    if ((int64_t)d->n * d->hs * d->ws * d->cs * g * 2 >= 0x7f000000LL) return 0;
+    if ((int64_t)d->n * d->hs * d->ws * d->cs * g * 2 >= kDmaRange) return 0;
     return v2_geometry_ok(d->n, d->hd, d->wd, d->cs, d->cd, g) ? 1 : 0;
 }
 
-extern "C" int iif_conv_reload_env(void) {
-    g_sw = ConvSwitches::read();
-    return IIF_OK;
+extern "C" int iif_conv_dgrad_rx_ok(const iif_conv_desc* d, int c2) {
+    ConvSel a;
+    return query_dense1x1(d, 1, &a) && iif_regw1x1_rx_ok(a.M, a.Cs, a.Cd, c2) ? 1 : 0;
 }
 
+extern "C" int iif_conv_dgrad_rx_pg_ok(const iif_conv_desc* d, int c2) {
+    ConvSel a;
+    return query_dense1x1(d, 1, &a) && iif_regw1x1_pg_ok(a.M, a.Cs, a.Cd, c2) ? 1 : 0;
+}
+
+extern "C" int iif_conv_fwdbn_ok(const iif_conv_desc* d) {
+    ConvSel a;
+    return query_dense1x1(d, 0, &a) && !g_sw.no_regw_fwdbn && iif_regw1x1_fwdbn_ok(a.M, a.Cs, a.Cd) ? 1 : 0;
+}
+
+extern "C" int iif_conv_pro_ok(const iif_conv_desc* d, int stats_only) {
+    ConvSel a;
+    if (!query_dense1x1(d, 0, &a)) return 0;
+    return (stats_only ? (!g_sw.no_regw_fwdbn && iif_regw1x1_fwdbn_ok(a.M, a.Cs, a.Cd)) : iif_regw1x1_pro_ok(a.M, a.Cs, a.Cd)) ? 1 : 0;
+}
+
+extern "C" int iif_conv_affine_ok(const iif_conv_desc* d, int has_res, int has_res_affine) {
+    if (has_res_affine && !has_res) return 0;
+    return affine_geometry_ok(d) ? 1 : 0;
+}
+
+extern "C" int iif_conv_affine_route(const iif_conv_desc* d, int has_res, int has_res_affine, int has_relu_bits) {
+    if (!iif_conv_affine_ok(d, has_res, has_res_affine)) return IIF_ROUTE_NONE;
+    ConvSel a{};
+    a.aff = true; a.res = has_res; a.aff2 = has_res_affine; a.relu_out = has_relu_bits;
+    ConvPlan p;
+    return conv_select(d, &a, false, false, 1, &p) == IIF_OK ? p.r[0].family : IIF_ROUTE_NONE;
+}
+
+// ---- launching entry points
 extern "C" int iif_conv_igemm_dgrad_bnbwd(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
                                           const unsigned char* res_bits, const void* up_x, const unsigned char* up_bits,
                                           const float* up_stats, float* partial, int64_t partial_floats, int32_t* n_partials,
@@ -2243,7 +2362,11 @@ extern "C" int iif_conv_igemm_dgrad_bnbwd(const iif_conv_desc* d, const void* sr
     if (!d || !up_x || !up_stats || !partial || !n_partials || !d->transposed) return IIF_EINVAL;
     if (res_bits && (!res || d->stride != 1)) return IIF_EINVAL;
     if ((reinterpret_cast<uintptr_t>(up_x) & 15)) return IIF_EUNSUPPORTED;
-    return conv_entry(d, src, wgt, dst, res, res_bits, nullptr, partial, partial_floats, n_partials, stream, up_x, up_bits, up_stats);
+    ConvCall c{};
+    c.d = d; c.src = src; c.wgt = wgt; c.dst = dst; c.res = res; c.res_bits = res_bits; c.stream = stream;
+    c.bn_partial = partial; c.bn_cap = partial_floats; c.n_partials = n_partials;
+    c.bw_x = up_x; c.bw_bits = up_bits; c.bw_stats = up_stats;
+    return conv_entry(c);
 }
 
 extern "C" int iif_conv_igemm_dgrad_masksum(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
@@ -2253,32 +2376,43 @@ extern "C" int iif_conv_igemm_dgrad_masksum(const iif_conv_desc* d, const void* 
     if (!d || !up_bits || !partial || !n_partials || !d->transposed) return IIF_EINVAL;
     if (res_bits && !res) return IIF_EINVAL;
     if (up_x && !up_stats) return IIF_EINVAL;
-    const ConvExtra ex{1, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr};
-    return conv_entry(d, src, wgt, dst, res, res_bits, nullptr, partial, partial_floats, n_partials, stream, up_x, up_bits,
-                      up_x ? up_stats : nullptr, &ex);
+    ConvCall c{};
+    c.d = d; c.src = src; c.wgt = wgt; c.dst = dst; c.res = res; c.res_bits = res_bits; c.stream = stream;
+    c.bn_partial = partial; c.bn_cap = partial_floats; c.n_partials = n_partials;
+    c.bw_x = up_x; c.bw_bits = up_bits; c.bw_stats = up_x ? up_stats : nullptr; c.mask_store = 1;
+    return conv_entry(c);
 }
 
-extern "C" int iif_conv_dgrad_rx_ok(const iif_conv_desc* d, int c2) {
-    if (!d || g_sw.no_regw || g_sw.regstage || !d->transposed) return 0;
-    if (d->dtype != IIF_BF16 || d->dst_dtype != IIF_BF16 || d->r != 1 || d->s != 1 || d->stride != 1 || d->pad != 0 || d->groups > 1) return 0;
-    if (d->hs != d->hd || d->ws != d->wd) return 0;
-    return iif_regw1x1_rx_ok(d->n * d->hd * d->wd, d->cs, d->cd, c2) ? 1 : 0;
+namespace {
+// the masked-store data gradient whose upstream x is recomputed; pg: with the P / Gram slabs
+int dgrad_masksum_rx(bool pg, const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res, const unsigned char* res_bits,
+                     const void* up_a2, int up_c2, const void* up_w3, int up_ldw3, const unsigned char* up_bits, const float* up_stats,
+                     float* partial, int64_t partial_floats, int32_t* n_partials, float* pg_slabs, int64_t pg_floats, int pg_ld,
+                     int32_t* n_slabs, void* stream) {
+    if (!d || !up_bits || !partial || !n_partials || !d->transposed || !up_a2 || !up_w3 || !up_stats || (pg && (!pg_slabs || !n_slabs))) return IIF_EINVAL;
+    if (res_bits && !res) return IIF_EINVAL;
+    if (!(pg ? iif_conv_dgrad_rx_pg_ok(d, up_c2) : iif_conv_dgrad_rx_ok(d, up_c2)) ||
+        ((reinterpret_cast<uintptr_t>(up_a2) | reinterpret_cast<uintptr_t>(up_w3)) & 15))
+        return IIF_EUNSUPPORTED;
+    int count = 0;
+    ConvCall c{};
+    c.d = d; c.src = src; c.wgt = wgt; c.dst = dst; c.res = res; c.res_bits = res_bits; c.stream = stream;
+    c.bn_partial = partial; c.bn_cap = partial_floats; c.n_partials = n_partials;
+    c.bw_bits = up_bits; c.bw_stats = up_stats; c.mask_store = 1;
+    c.rx_src2 = up_a2; c.rx_w3 = up_w3; c.rx_k2 = up_c2; c.rx_ldw3 = up_ldw3;
+    if (pg) { c.pg_slab = pg_slabs; c.pg_cap = (long long)pg_floats; c.pg_ld = pg_ld; c.pg_count = &count; }
+    const int rc = conv_entry(c);
+    if (pg) *n_slabs = count;
+    return rc;
 }
+}  // namespace
 
 extern "C" int iif_conv_igemm_dgrad_masksum_rx(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
                                                const unsigned char* res_bits, const void* up_a2, int up_c2, const void* up_w3, int up_ldw3,
                                                const unsigned char* up_bits, const float* up_stats, float* partial, int64_t partial_floats,
                                                int32_t* n_partials, void* stream) {
-    if (!d || !up_bits || !partial || !n_partials || !d->transposed || !up_a2 || !up_w3 || !up_stats) return IIF_EINVAL;
-    if (res_bits && !res) return IIF_EINVAL;
-    if (!iif_conv_dgrad_rx_ok(d, up_c2) || ((reinterpret_cast<uintptr_t>(up_a2) | reinterpret_cast<uintptr_t>(up_w3)) & 15)) return IIF_EUNSUPPORTED;
-    const ConvExtra ex{1, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, up_a2, up_w3, up_c2, up_ldw3, nullptr, nullptr, nullptr, nullptr};
-    return conv_entry(d, src, wgt, dst, res, res_bits, nullptr, partial, partial_floats, n_partials, stream, nullptr, up_bits, up_stats, &ex);
-}
-
-extern "C" int iif_conv_dgrad_rx_pg_ok(const iif_conv_desc* d, int c2) {
-    if (!iif_conv_dgrad_rx_ok(d, c2)) return 0;
-    return iif_regw1x1_pg_ok(d->n * d->hd * d->wd, d->cs, d->cd, c2) ? 1 : 0;
+    return dgrad_masksum_rx(false, d, src, wgt, dst, res, res_bits, up_a2, up_c2, up_w3, up_ldw3, up_bits, up_stats, partial, partial_floats,
+                            n_partials, nullptr, 0, 0, nullptr, stream);
 }
 
 extern "C" int iif_conv_igemm_dgrad_masksum_rx_pg(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
@@ -2286,15 +2420,8 @@ extern "C" int iif_conv_igemm_dgrad_masksum_rx_pg(const iif_conv_desc* d, const 
                                                   const unsigned char* up_bits, const float* up_stats, float* partial, int64_t partial_floats,
                                                   int32_t* n_partials, float* pg_slabs, int64_t pg_floats, int pg_ld, int32_t* n_slabs,
                                                   void* stream) {
-    if (!d || !up_bits || !partial || !n_partials || !d->transposed || !up_a2 || !up_w3 || !up_stats || !pg_slabs || !n_slabs) return IIF_EINVAL;
-    if (res_bits && !res) return IIF_EINVAL;
-    if (!iif_conv_dgrad_rx_pg_ok(d, up_c2) || ((reinterpret_cast<uintptr_t>(up_a2) | reinterpret_cast<uintptr_t>(up_w3)) & 15)) return IIF_EUNSUPPORTED;
-    int count = 0;
-    const ConvExtra ex{1, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, up_a2, up_w3, up_c2, up_ldw3, nullptr, nullptr, nullptr, nullptr,
-                       pg_slabs, (long long)pg_floats, pg_ld, &count};
-    const int rc = conv_entry(d, src, wgt, dst, res, res_bits, nullptr, partial, partial_floats, n_partials, stream, nullptr, up_bits, up_stats, &ex);
-    *n_slabs = count;
-    return rc;
+    return dgrad_masksum_rx(true, d, src, wgt, dst, res, res_bits, up_a2, up_c2, up_w3, up_ldw3, up_bits, up_stats, partial, partial_floats,
+                            n_partials, pg_slabs, pg_floats, pg_ld, n_slabs, stream);
 }
 
 extern "C" int iif_conv_igemm_dgrad2_bnbwd(const iif_conv_desc* d, const void* src, const void* src2, int cs2, const void* wgt,
@@ -2303,57 +2430,36 @@ extern "C" int iif_conv_igemm_dgrad2_bnbwd(const iif_conv_desc* d, const void* s
                                            void* stream) {
     if (!d || !src2 || !d->transposed) return IIF_EINVAL;
     if (up_x && (!up_stats || !partial || !n_partials)) return IIF_EINVAL;
-    const ConvExtra ex{0, src2, cs2, bias, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr};
-    return conv_entry(d, src, wgt, dst, nullptr, nullptr, nullptr, up_x ? partial : nullptr, partial_floats, n_partials, stream, up_x,
-                      up_bits, up_stats, &ex);
+    ConvCall c{};
+    c.d = d; c.src = src; c.wgt = wgt; c.dst = dst; c.stream = stream;
+    c.bn_partial = up_x ? partial : nullptr; c.bn_cap = partial_floats; c.n_partials = n_partials;
+    c.bw_x = up_x; c.bw_bits = up_bits; c.bw_stats = up_stats;
+    c.src2 = src2; c.cs2 = cs2; c.sbias = bias;
+    return conv_entry(c);
 }
+
+namespace {
+// a forward that writes no convolution output: dst is never written, the source pointer stands in for its non-null / alignment checks
+ConvCall stats_call(const iif_conv_desc* d, const void* src, const void* wgt, float* bn_partial, int64_t bn_partial_floats,
+                    int32_t* n_partials, void* stream, int no_store) {
+    ConvCall c{};
+    c.d = d; c.src = src; c.wgt = wgt; c.dst = const_cast<void*>(src); c.stream = stream;
+    c.bn_partial = bn_partial; c.bn_cap = bn_partial_floats; c.n_partials = n_partials; c.no_store = no_store;
+    return c;
+}
+}  // namespace
 
 extern "C" int iif_conv_igemm_stats_only(const iif_conv_desc* d, const void* src, const void* wgt, float* bn_partial,
                                          int64_t bn_partial_floats, int32_t* n_partials, void* stream) {
     if (!d || !bn_partial || !n_partials || d->transposed) return IIF_EINVAL;
-    const ConvExtra ex{0, nullptr, 0, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr};
-    // dst is never written; the source pointer stands in for the non-null / alignment checks
-    return conv_entry(d, src, wgt, const_cast<void*>(src), nullptr, nullptr, nullptr, bn_partial, bn_partial_floats, n_partials, stream,
-                      nullptr, nullptr, nullptr, &ex);
-}
-
-extern "C" int iif_conv_igemm_bn_relu(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
-                                      const float* stats, unsigned char* relu_bits, void* stream) {
-    if (!d || !stats || d->transposed) return IIF_EINVAL;
-    const ConvExtra ex{0, nullptr, 0, nullptr, 0, stats, relu_bits, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr};
-    return conv_entry(d, src, wgt, dst, res, nullptr, nullptr, nullptr, 0, nullptr, stream, nullptr, nullptr, nullptr, &ex);
-}
-
-extern "C" int iif_conv_fwdbn_ok(const iif_conv_desc* d) {
-    if (!d || g_sw.no_regw || g_sw.regstage || g_sw.no_regw_fwdbn) return 0;
-    if (d->dtype != IIF_BF16 || d->dst_dtype != IIF_BF16 || d->r != 1 || d->s != 1 || d->stride != 1 || d->pad != 0 || d->groups > 1 || d->transposed) return 0;
-    if (d->hs != d->hd || d->ws != d->wd) return 0;
-    return iif_regw1x1_fwdbn_ok(d->n * d->hd * d->wd, d->cs, d->cd) ? 1 : 0;
+    return conv_entry(stats_call(d, src, wgt, bn_partial, bn_partial_floats, n_partials, stream, 1));
 }
 
 extern "C" int iif_conv_igemm_stats_acc(const iif_conv_desc* d, const void* src, const void* wgt, float* bn_partial,
                                         int64_t bn_partial_floats, int32_t* n_partials, void* stream) {
     if (!d || !bn_partial || !n_partials || d->transposed) return IIF_EINVAL;
     if (!iif_conv_fwdbn_ok(d)) return IIF_EUNSUPPORTED;
-    const ConvExtra ex{0, nullptr, 0, nullptr, 2, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr};
-    return conv_entry(d, src, wgt, const_cast<void*>(src), nullptr, nullptr, nullptr, bn_partial, bn_partial_floats, n_partials, stream,
-                      nullptr, nullptr, nullptr, &ex);
-}
-
-extern "C" int iif_conv_igemm_bn_relu2(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
-                                       const float* res_stats, const float* stats, unsigned char* relu_bits, void* stream) {
-    if (!d || !stats || !relu_bits || d->transposed || (res_stats && !res)) return IIF_EINVAL;
-    if (res_stats && !iif_conv_fwdbn_ok(d)) return IIF_EUNSUPPORTED;
-    const ConvExtra ex{0, nullptr, 0, nullptr, 0, stats, relu_bits, res_stats, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr};
-    return conv_entry(d, src, wgt, dst, res, nullptr, nullptr, nullptr, 0, nullptr, stream, nullptr, nullptr, nullptr, &ex);
-}
-
-extern "C" int iif_conv_pro_ok(const iif_conv_desc* d, int stats_only) {
-    if (!d || g_sw.no_regw || g_sw.regstage) return 0;
-    if (d->dtype != IIF_BF16 || d->dst_dtype != IIF_BF16 || d->r != 1 || d->s != 1 || d->stride != 1 || d->pad != 0 || d->groups > 1 || d->transposed) return 0;
-    if (d->hs != d->hd || d->ws != d->wd) return 0;
-    const int M = d->n * d->hd * d->wd;
-    return (stats_only ? (!g_sw.no_regw_fwdbn && iif_regw1x1_fwdbn_ok(M, d->cs, d->cd)) : iif_regw1x1_pro_ok(M, d->cs, d->cd)) ? 1 : 0;
+    return conv_entry(stats_call(d, src, wgt, bn_partial, bn_partial_floats, n_partials, stream, 2));
 }
 
 extern "C" int iif_conv_igemm_bnstats_pro(const iif_conv_desc* d, const void* src_raw, const float* src_stats, void* act_out,
@@ -2361,15 +2467,49 @@ extern "C" int iif_conv_igemm_bnstats_pro(const iif_conv_desc* d, const void* sr
                                           float* bn_partial, int64_t bn_partial_floats, int32_t* n_partials, void* stream) {
     if (!d || !src_raw || !src_stats || !act_out || !act_bits || !bn_partial || !n_partials || d->transposed) return IIF_EINVAL;
     if (!iif_conv_pro_ok(d, dst == nullptr) || ((reinterpret_cast<uintptr_t>(act_out)) & 15)) return IIF_EUNSUPPORTED;
-    const ConvExtra ex{0, nullptr, 0, nullptr, dst ? 0 : 2, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, src_stats, act_out, act_bits, act_csum};
-    return conv_entry(d, src_raw, wgt, dst ? dst : const_cast<void*>(src_raw), nullptr, nullptr, nullptr, bn_partial, bn_partial_floats, n_partials,
-                      stream, nullptr, nullptr, nullptr, &ex);
+    ConvCall c = stats_call(d, src_raw, wgt, bn_partial, bn_partial_floats, n_partials, stream, dst ? 0 : 2);
+    if (dst) c.dst = dst;
+    c.pro_stats = src_stats; c.pro_out = act_out; c.pro_bits = act_bits; c.pro_csum = act_csum;
+    return conv_entry(c);
+}
+
+extern "C" int iif_conv_igemm_bn_relu2(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
+                                       const float* res_stats, const float* stats, unsigned char* relu_bits, void* stream) {
+    if (!d || !stats || !relu_bits || d->transposed || (res_stats && !res)) return IIF_EINVAL;
+    if (res_stats && !iif_conv_fwdbn_ok(d)) return IIF_EUNSUPPORTED;
+    ConvCall c{};
+    c.d = d; c.src = src; c.wgt = wgt; c.dst = dst; c.res = res; c.stream = stream;
+    c.aff = stats; c.aff2 = res_stats; c.relu_out = relu_bits;
+    return conv_entry(c);
+}
+
+extern "C" int iif_conv_igemm_bn_relu(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
+                                      const float* stats, unsigned char* relu_bits, void* stream) {
+    if (!d || !stats || d->transposed) return IIF_EINVAL;
+    ConvCall c{};
+    c.d = d; c.src = src; c.wgt = wgt; c.dst = dst; c.res = res; c.stream = stream;
+    c.aff = stats; c.relu_out = relu_bits;
+    return conv_entry(c);
+}
+
+extern "C" int iif_conv_igemm_affine(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
+                                     const float* res_affine, const float* affine, unsigned char* relu_bits, void* stream) {
+    if (!d || !src || !wgt || !dst || !affine || d->transposed || (res_affine && !res)) return IIF_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(affine) | reinterpret_cast<uintptr_t>(res_affine)) & 3) return IIF_EUNSUPPORTED;
+    if (!iif_conv_affine_ok(d, res != nullptr, res_affine != nullptr)) return IIF_EUNSUPPORTED;
+    ConvCall c{};
+    c.d = d; c.src = src; c.wgt = wgt; c.dst = dst; c.res = res; c.stream = stream;
+    c.aff = affine; c.aff2 = res_affine; c.relu_out = relu_bits; c.aff_any = 1;
+    return conv_entry(c);
 }
 
 extern "C" int iif_conv_igemm_bnstats(const iif_conv_desc* d, const void* src, const void* wgt, void* dst,
                                       const void* res, const float* bias, float* bn_partial, int64_t bn_partial_floats,
                                       int32_t* n_partials, void* stream) {
-    return conv_entry(d, src, wgt, dst, res, nullptr, bias, bn_partial, bn_partial_floats, n_partials, stream);
+    ConvCall c{};
+    c.d = d; c.src = src; c.wgt = wgt; c.dst = dst; c.res = res; c.bias = bias; c.stream = stream;
+    c.bn_partial = bn_partial; c.bn_cap = bn_partial_floats; c.n_partials = n_partials;
+    return conv_entry(c);
 }
 
 extern "C" int iif_conv_igemm_masked_res(const iif_conv_desc* d, const void* src, const void* wgt, void* dst,
@@ -2378,145 +2518,15 @@ extern "C" int iif_conv_igemm_masked_res(const iif_conv_desc* d, const void* src
     // the bit bytes follow the residual's 16-byte vectors: rows must be whole vectors, stores vectorised
     const int v = d && d->dst_dtype == IIF_F32 ? 4 : 8;
     if (!d || d->transposed == 0 || d->stride != 1 || (d->cd * (d->groups > 1 ? d->groups : 1)) % v) return IIF_EUNSUPPORTED;
-    return conv_entry(d, src, wgt, dst, res, res_bits, nullptr, nullptr, 0, nullptr, stream);
-}
-
-namespace {
-// Descriptors whose forward launch ends in a kernel that drains through the LDS-staged epilogue (or the register-weight 3x3
-// kernel's affine drain): bf16 in and out, whole 16-byte vectors per destination row and group, both operands within the
-// 32-bit LDS-DMA range.  Every route of launch_one behind these conditions carries the BN affine.
-bool affine_geometry_ok(const iif_conv_desc* d) {
-    if (!d || g_sw.regstage || d->transposed || d->dtype != IIF_BF16 || d->dst_dtype != IIF_BF16) return false;
-    if (d->n <= 0 || d->hs <= 0 || d->ws <= 0 || d->cs <= 0 || d->hd <= 0 || d->wd <= 0 || d->cd <= 0 || d->r <= 0 || d->s <= 0 || d->pad < 0) return false;
-    if (d->stride != 1 && d->stride != 2) return false;
-    const int64_t g = d->groups > 1 ? d->groups : 1;
-    // (the space-to-depth stem has a kernel of its own without this epilogue, and another K order than the tile kernels)
-    if (d->r == 4 && d->s == 4 && d->cs == 16 && d->cd == 64 && d->pad == 2 && d->stride == 1 && g == 1) return false;
-    if (g > 65535 || (d->cd % 8) || (d->cs % 8) || (d->ldw % 8) || d->ldw < d->r * d->s * d->cs) return false;
-    const int64_t M = (int64_t)d->n * d->hd * d->wd;
-    if (M > 0x7fffff00LL || (int64_t)d->n * d->hs * d->ws > 0x7fffff00LL) return false;
-    if ((int64_t)d->n * d->hs * d->ws * d->cs * g * 2 >= 0x7f000000LL || (int64_t)d->cd * d->ldw * 2 >= 0x7f000000LL) return false;
-    return true;
-}
-}  // namespace
-
-extern "C" int iif_conv_affine_ok(const iif_conv_desc* d, int has_res, int has_res_affine) {
-    if (has_res_affine && !has_res) return 0;
-    return affine_geometry_ok(d) ? 1 : 0;
-}
-
-extern "C" int iif_conv_affine_route(const iif_conv_desc* d, int has_res, int has_res_affine, int has_relu_bits) {
-    if (!iif_conv_affine_ok(d, has_res, has_res_affine) || g_iif_route_probe) return IIF_ROUTE_NONE;
-    // stand-in operands (never dereferenced: every launch site returns at its probe)
-    void* const p = reinterpret_cast<void*>(uintptr_t(1) << 20);
-    iif_conv_desc dd = *d;
-    if (dd.wgt_frag) dd.wgt_frag = p;
-    ConvExtra ex{};
-    ex.aff = (const float*)p; ex.aff2 = has_res_affine ? (const float*)p : nullptr; ex.relu_out = has_relu_bits ? (unsigned char*)p : nullptr;
-    ex.aff_any = 1;
-    int code = IIF_ROUTE_NONE;
-    g_iif_route_probe = &code;
-    const int rc = conv_entry(&dd, p, p, p, has_res ? p : nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &ex);
-    g_iif_route_probe = nullptr;
-    return rc == IIF_OK ? code : IIF_ROUTE_NONE;
-}
-
-extern "C" int iif_conv_igemm_affine(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
-                                     const float* res_affine, const float* affine, unsigned char* relu_bits, void* stream) {
-    if (!d || !src || !wgt || !dst || !affine || d->transposed || (res_affine && !res)) return IIF_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(affine) | reinterpret_cast<uintptr_t>(res_affine)) & 3) return IIF_EUNSUPPORTED;
-    if (!iif_conv_affine_ok(d, res != nullptr, res_affine != nullptr)) return IIF_EUNSUPPORTED;
-    ConvExtra ex{};
-    ex.aff = affine; ex.aff2 = res_affine; ex.relu_out = relu_bits; ex.aff_any = 1;
-    return conv_entry(d, src, wgt, dst, res, nullptr, nullptr, nullptr, 0, nullptr, stream, nullptr, nullptr, nullptr, &ex);
+    ConvCall c{};
+    c.d = d; c.src = src; c.wgt = wgt; c.dst = dst; c.res = res; c.res_bits = res_bits; c.stream = stream;
+    return conv_entry(c);
 }
 
 extern "C" int iif_conv_igemm(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
                               const float* bias, void* stream) {
     return iif_conv_igemm_bnstats(d, src, wgt, dst, res, bias, nullptr, 0, nullptr, stream);
 }
-
-namespace {
-int conv_entry(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
-               const unsigned char* res_bits, const float* bias, float* bn_partial, int64_t bn_partial_floats,
-               int32_t* n_partials, void* stream, const void* bw_x, const unsigned char* bw_bits, const float* bw_stats,
-               const ConvExtra* ex) {
-    if (!d || !src || !wgt || !dst) return IIF_EINVAL;
-    if (d->n <= 0 || d->hs <= 0 || d->ws <= 0 || d->cs <= 0 || d->hd <= 0 || d->wd <= 0 || d->cd <= 0 ||
-        d->r <= 0 || d->s <= 0 || d->pad < 0)
-        return IIF_EINVAL;
-    if (d->stride != 1 && d->stride != 2) return IIF_EUNSUPPORTED;
-    if (d->dtype != IIF_F32 && d->dtype != IIF_BF16) return IIF_EINVAL;
-    if (d->dst_dtype != d->dtype && d->dst_dtype != IIF_F32) return IIF_EINVAL;
-    const int pe = d->dtype == IIF_F32 ? 4 : 8;
-    if (d->cs % pe != 0 || d->ldw % pe != 0 || d->ldw < d->r * d->s * d->cs + (ex && ex->src2 ? ex->cs2 : 0)) return IIF_EUNSUPPORTED;
-    if (ex && ex->aff_any) {
-        if (!affine_geometry_ok(d) || bias || bn_partial || res_bits || bw_x) return IIF_EUNSUPPORTED;
-    } else if (ex && (ex->src2 || ex->sbias || ex->mask_store || ex->no_store || ex->aff || ex->pro_stats)) {
-        // round-3 epilogue / operand options: bf16 1x1 stride-1 launches on the LDS-staged epilogue only
-        if (d->dtype != IIF_BF16 || d->dst_dtype != IIF_BF16 || d->r != 1 || d->s != 1 || d->stride != 1 || d->pad != 0 || d->groups > 1 ||
-            (d->cd % 8) || bias || (d->cs % 32))
-            return IIF_EUNSUPPORTED;
-        if (ex->src2 && ((ex->cs2 % 32) || ex->cs2 <= 0 || (reinterpret_cast<uintptr_t>(ex->src2) & 15))) return IIF_EUNSUPPORTED;
-        if (ex->mask_store && (!bw_bits || !bn_partial)) return IIF_EINVAL;
-        if (ex->no_store && (!bn_partial || res || bw_x)) return IIF_EINVAL;
-        if (ex->aff && (bn_partial || res_bits || bw_x || ex->no_store)) return IIF_EINVAL;
-    }
-    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(wgt) | reinterpret_cast<uintptr_t>(dst) |
-         reinterpret_cast<uintptr_t>(res)) & 15)
-        return IIF_EUNSUPPORTED;
-    const int64_t M = (int64_t)d->n * d->hd * d->wd;
-    if (M > 0x7fffff00LL || (int64_t)d->n * d->hs * d->ws > 0x7fffff00LL) return IIF_EUNSUPPORTED;
-    ConvArgs a{};
-    a.src = (const unsigned char*)src; a.wgt = (const unsigned char*)wgt; a.dst = (unsigned char*)dst;
-    a.res = (const unsigned char*)res; a.bias = bias;
-    a.wfrag = (const unsigned char*)d->wgt_frag;
-    a.wfrag_kind = d->wgt_frag ? d->wgt_frag_kind : 0;
-    a.res_bits = res_bits;
-    a.bn_partial = nullptr;
-    if (n_partials) *n_partials = 0;
-    int rows = 0;
-    if (bn_partial) {
-        // fused statistics (forward) / backward sums of the upstream unit need the LDS-staged bf16 epilogue of the
-        // pipelined kernels; one partial row per pixel tile, counted where the tile height is chosen (launch_one)
-        const int64_t esz0 = 2;
-        const bool ok = d->dtype == IIF_BF16 && d->dst_dtype == IIF_BF16 && (d->cd % 8) == 0 && !bias && (bw_x || (ex && ex->mask_store) || !res) &&
-                        !g_sw.regstage &&
-                        (int64_t)d->n * d->hs * d->ws * d->cs * (d->groups > 1 ? d->groups : 1) * esz0 < 0x7f000000LL;
-        if (!ok) return IIF_EUNSUPPORTED;
-        a.bn_partial = bn_partial;
-        a.bn_cap = bn_partial_floats;
-        a.rows_out = &rows;
-        a.bw_x = (const unsigned char*)bw_x; a.bw_bits = bw_bits; a.bw_stats = bw_stats;
-    }
-    if (ex) {
-        a.mask_store = ex->mask_store; a.src2 = (const unsigned char*)ex->src2; a.Cs2 = ex->cs2; a.sbias = ex->sbias;
-        a.no_store = ex->no_store; a.aff = ex->aff; a.relu_out = ex->relu_out; a.aff2 = ex->aff2;
-        a.rx_src2 = (const unsigned char*)ex->rx_src2; a.rx_w3 = (const unsigned char*)ex->rx_w3; a.rx_k2 = ex->rx_k2; a.rx_ldw3 = ex->rx_ldw3;
-        a.pro_stats = ex->pro_stats; a.pro_out = (unsigned char*)ex->pro_out; a.pro_bits = ex->pro_bits; a.pro_csum = ex->pro_csum;
-        a.pg_slab = ex->pg_slab; a.pg_cap = ex->pg_cap; a.pg_ld = ex->pg_ld; a.pg_count = ex->pg_count;
-    }
-    a.N = d->n; a.Hs = d->hs; a.Ws = d->ws; a.Cs = d->cs; a.Hd = d->hd; a.Wd = d->wd; a.Cd = d->cd;
-    a.R = d->r; a.S = d->s; a.sshift = d->stride - 1; a.pad = d->pad; a.transposed = d->transposed ? 1 : 0;
-    a.ldw = d->ldw; a.M = (int)M; a.K = d->r * d->s * d->cs;
-    a.groups = d->groups > 1 ? d->groups : 1;
-    a.spitch = a.groups * d->cs; a.dpitch = a.groups * d->cd;
-    if (a.groups > 65535) return IIF_EUNSUPPORTED;
-    hipStream_t st = as_stream(stream);
-    const int64_t esz = d->dtype == IIF_F32 ? 4 : 2;
-    const int64_t src_bytes = (int64_t)d->n * d->hs * d->ws * a.spitch * esz;
-    const int64_t wgt_bytes = (int64_t)d->cd * d->ldw * esz;          // one group's weight matrix
-    int rc;
-    if (d->dtype == IIF_BF16) {
-        if (d->dst_dtype == IIF_F32) rc = launch_conv<unsigned short, true>(a, src_bytes, wgt_bytes, st);
-        else rc = launch_conv<unsigned short, false>(a, src_bytes, wgt_bytes, st);
-    } else {
-        rc = launch_conv<float, true>(a, src_bytes, wgt_bytes, st);
-    }
-    if (n_partials) *n_partials = rows;
-    return rc;
-}
-}  // namespace
 
 #ifdef IIF_CONV_STAMPS
 extern "C" int iif_debug_set_stamps(unsigned long long* buf) {

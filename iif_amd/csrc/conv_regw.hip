@@ -590,24 +590,27 @@ static bool regw_plan(int K, int N, bool epi, int* cw, int* mt) {
     if (K == 256 && N == 1024) { *cw = 32; *mt = 64; return true; }
     // K = 512: 32 columns per wave with 32-row tiles (64-row tiles do not fit the LDS beside the staging buffers): half the
     // LDS-DMA bytes per flop of the 16-column form, which is what bounds these launches (IIF_REGW_K512_CW16: the round-5 form)
-    static const bool k512_cw16 = getenv("IIF_REGW_K512_CW16") != nullptr;
+    const bool k512_cw16 = g_sw.regw_k512_cw16;
     // (with epilogue operands at 7 x 7, M = 12 544: 77 against 69 us with 16 columns, +0.05 ms per step with 32 - the tile kernel keeps it)
     if (K == 512 && N == 2048 && !epi) { *cw = k512_cw16 ? 16 : 32; *mt = k512_cw16 ? 64 : 32; return true; }
     // (the wide -> narrow shapes are level with the tile kernels alone, 59.3 / 60.1 and 43.1 / 42.8 us, and level to +0.05 ms in the step)
     // ResNeXt's conv3 (width -> 2 x width; resnet_pytorch.py:141-143 with groups 32, base width 4): the same kernels, fewer slices
-    static const bool no_x2 = getenv("IIF_REGW_NO_X2") != nullptr;      // read once, like every other switch
-    if (!no_x2) {
+    if (!g_sw.regw_no_x2) {                                             // IIF_REGW_NO_X2
         if (K == 128 && N == 256) { *cw = 32; *mt = 64; return true; }
         if (K == 256 && N == 512) { *cw = 32; *mt = 64; return true; }
         // (the data-gradient epilogue too - ResNeXt-101's 23 producers at 14 x 14: 21.09 -> 20.94 ms; IIF_REGW_K512_NO_EPI: off)
-        static const bool k512_no_epi = getenv("IIF_REGW_K512_NO_EPI") != nullptr;
-        if (K == 512 && N == 1024 && (!epi || !k512_no_epi)) { *cw = k512_cw16 && !epi ? 16 : 32; *mt = k512_cw16 && !epi ? 64 : 32; return true; }
+        if (K == 512 && N == 1024 && (!epi || !g_sw.regw_k512_no_epi)) { *cw = k512_cw16 && !epi ? 16 : 32; *mt = k512_cw16 && !epi ? 64 : 32; return true; }
         if (K == 1024 && N == 2048 && !epi) { *cw = 16; *mt = 32; return true; }
     }
     if (K == 512 && N == 128 && !epi) { *cw = 16; *mt = 64; return true; }
     if (K == 1024 && N == 256 && !epi) { *cw = 16; *mt = 32; return true; }
     // (1024 -> 512, ResNeXt-101's conv1 / conv3 data gradient at 14 x 14: level forward, +0.1 ms with the epilogue; tile kernels keep them)
     return false;
+}
+
+bool iif_dense1x1(const ConvSel& a) {
+    return a.esz == 2 && !a.outf32 && !g_sw.regstage && !g_sw.no_regw && a.R == 1 && a.S == 1 && a.sshift == 0 && a.pad == 0 &&
+           a.groups == 1 && a.Hs == a.Hd && a.Ws == a.Wd;
 }
 
 // the data-gradient epilogue with the upstream x recomputed over k2 channels: the (K, k2) pairs that have an instance
@@ -624,7 +627,7 @@ bool iif_regw1x1_pg_ok(int M, int K, int N, int k2) {
 
 bool iif_regw1x1_ok(int M, int K, int N, int epi) {
     int cw, mt;
-    if (M <= 0 || (int64_t)M * K * 2 >= 0x7f000000LL || !regw_plan(K, N, epi != 0, &cw, &mt)) return false;
+    if (M <= 0 || (int64_t)M * K * 2 >= kDmaRange || !regw_plan(K, N, epi != 0, &cw, &mt)) return false;
     return M % mt == 0;
 }
 
@@ -635,151 +638,109 @@ bool iif_regw1x1_pro_ok(int M, int K, int N) {
     return M >= 1024 && ((K == 256 && cw == 32 && mt == 64) || (K == 512 && ((cw == 16 && mt == 64) || (cw == 32 && mt == 32))));
 }
 
-int iif_regw1x1_launch(const void* src, const void* wgt, void* dst, float* bn_partial, long long bn_cap, int bn_row0, int* rows_out,
-                       int M, int K, int N, int spitch, int ldw, int dpitch, const iif_regw_epilogue* e, int no_store, hipStream_t st,
-                       const iif_regw_prologue* pro) {
-    const bool epi = e != nullptr;
-    if (epi && no_store) return IIF_EUNSUPPORTED;
-    if (pro && (epi || no_store || !bn_partial || spitch != K || !pro->stats || !pro->out || !pro->bits || !iif_regw1x1_pro_ok(M, K, N))) return IIF_EUNSUPPORTED;
-    if (!src || !wgt || !dst || !iif_regw1x1_ok(M, K, N, epi)) return IIF_EUNSUPPORTED;
-    int cw = 0, mt = 0;
-    regw_plan(K, N, epi, &cw, &mt);
-    const int S = N / (8 * cw);
-    RegwArgs a{(const unsigned char*)src, (const unsigned char*)wgt, (unsigned char*)dst, bn_partial, M, M / mt, spitch, ldw, N, dpitch,
-               bn_row0, S, nullptr, nullptr, nullptr, nullptr, nullptr, 0, no_store};
-    int k2 = 0;
-    if (epi) {
-        a.res = (const unsigned char*)e->res; a.res_bits = e->res_bits; a.bw_x = (const unsigned char*)e->bw_x; a.bw_bits = e->bw_bits;
-        a.bw_stats = e->bw_stats; a.mask_store = e->mask_store;
-        if (e->rx_src2) {                                  // the upstream x recomputed from (a2, w3)
-            k2 = e->rx_k2;
-            if (!iif_regw1x1_rx_ok(M, K, N, k2) || !e->rx_w3 || !e->bw_stats || e->bw_x || e->rx_ldw3 < k2 || bn_partial == nullptr) return IIF_EUNSUPPORTED;
-            if ((int64_t)M * k2 * 2 >= 0x7f000000LL) return IIF_EUNSUPPORTED;
-            a.src2 = (const unsigned char*)e->rx_src2; a.w3 = (const unsigned char*)e->rx_w3; a.spitch2 = k2; a.ldw3 = e->rx_ldw3;
-            a.src2_bytes = (unsigned)((int64_t)M * k2 * 2);
-            if (e->pg_slab) {
-                if (!iif_regw1x1_pg_ok(M, K, N, k2) || e->pg_ld < k2 || (e->pg_ld & 3) || !e->pg_count ||
-                    (reinterpret_cast<uintptr_t>(e->pg_slab) & 15)) return IIF_EUNSUPPORTED;
-                a.pg_slab = e->pg_slab; a.pg_ld = e->pg_ld;
+// the two passes of the never-stored conv + BN (+ shortcut) + ReLU forward (round 6): 32 columns per wave, N / 256 slices
+// (at least eight 128-row groups: one partial row per tile sequence, never more rows than ceil(M / 128), sequences in eights)
+bool iif_regw1x1_fwdbn_ok(int M, int K, int N) {
+    return M >= 1024 && (M % 64) == 0 && (int64_t)M * K * 2 < kDmaRange && (K == 64 || K == 128 || K == 256) && N >= 256 && N <= 2048 &&
+           (N % 256) == 0;
+}
+
+// Every instance of gemm1x1_regw_kernel, (K, CW, MT, EPI, K2, PRO, PG); ConvRoute::inst is the position in this list.
+// EPI 0: plain, 1: data-gradient options, 4: ... with the upstream x recomputed, 2: forward BN epilogue, 3: statistics only
+#define IIF_REGW_INSTANCES(X)                                                                                                    \
+    X(64, 32, 64, 4, 64, false, true) X(128, 32, 64, 4, 64, false, true)                                                         \
+    X(64, 32, 64, 4, 64, false, false) X(128, 32, 64, 4, 64, false, false) X(128, 32, 64, 4, 128, false, false)                  \
+    X(256, 32, 64, 4, 128, false, false)                                                                                         \
+    X(64, 32, 64, 1, 0, false, false) X(128, 32, 64, 1, 0, false, false) X(256, 32, 64, 1, 0, false, false)                      \
+    X(512, 32, 32, 1, 0, false, false)                                                                                           \
+    X(256, 32, 64, 0, 0, true, false) X(512, 32, 32, 0, 0, true, false) X(512, 16, 64, 0, 0, true, false)                        \
+    X(128, 64, 64, 0, 0, false, false) X(128, 32, 64, 0, 0, false, false) X(256, 32, 64, 0, 0, false, false)                     \
+    X(512, 32, 32, 0, 0, false, false) X(512, 16, 64, 0, 0, false, false) X(1024, 16, 32, 0, 0, false, false)                    \
+    X(64, 32, 64, 2, 0, false, false) X(128, 32, 64, 2, 0, false, false) X(256, 32, 64, 2, 0, false, false)                      \
+    X(64, 32, 64, 3, 0, true, false) X(128, 32, 64, 3, 0, true, false) X(256, 32, 64, 3, 0, true, false)                         \
+    X(64, 32, 64, 3, 0, false, false) X(128, 32, 64, 3, 0, false, false) X(256, 32, 64, 3, 0, false, false)
+struct RegwInst { int K, CW, MT, EPI, K2; bool PRO, PG; };
+#define IIF_REGW_ROW(K, CW, MT, EPI, K2, PRO, PG) {K, CW, MT, EPI, K2, PRO, PG},
+static const RegwInst kRegwInst[] = {IIF_REGW_INSTANCES(IIF_REGW_ROW)};
+#undef IIF_REGW_ROW
+
+int iif_regw1x1_select(const ConvSel& a, int mode, ConvRoute* r) {
+    const int M = a.M, K = a.Cs, N = a.Cd;
+    RegwInst w{K, 32, 64, mode, 0, a.pro_stats, false};
+    if (mode == IIF_REGW_PLAIN) {
+        const bool epi = a.res || a.res_bits || a.bw_x || a.bw_bits || a.mask_store;
+        if (epi && a.no_store) return IIF_EUNSUPPORTED;
+        if (a.pro_stats && (epi || a.no_store || !a.bn_partial || !iif_regw1x1_pro_ok(M, K, N))) return IIF_EUNSUPPORTED;
+        if (!iif_regw1x1_ok(M, K, N, epi)) return IIF_EUNSUPPORTED;
+        regw_plan(K, N, epi, &w.CW, &w.MT);
+        w.EPI = epi;
+        if (epi && a.rx_src2) {                               // the upstream x recomputed from (a2, w3)
+            w.EPI = 4; w.K2 = a.rx_k2;
+            if (!iif_regw1x1_rx_ok(M, K, N, w.K2) || !a.rx_w3 || !a.bw_stats || a.bw_x || a.rx_ldw3 < w.K2 || !a.bn_partial) return IIF_EUNSUPPORTED;
+            if ((int64_t)M * w.K2 * 2 >= kDmaRange) return IIF_EUNSUPPORTED;
+            if (a.pg_slab) {
+                if (!iif_regw1x1_pg_ok(M, K, N, w.K2) || a.pg_ld < w.K2 || (a.pg_ld & 3) || !a.pg_count || a.pg_unaligned) return IIF_EUNSUPPORTED;
+                w.PG = true;
             }
-        } else if (e->pg_slab) {
+        } else if (epi && a.pg_slab) {
             return IIF_EUNSUPPORTED;
         }
+    } else {
+        if (!iif_regw1x1_fwdbn_ok(M, K, N) || a.spitch != K || a.dpitch != N) return IIF_EUNSUPPORTED;
+        if (mode == IIF_REGW_FWDBN ? (a.pro_stats || !a.aff || !a.relu_out || (a.aff2 && !a.res)) : !a.bn_partial) return IIF_EINVAL;
     }
-    if (pro) { a.pro_stats = pro->stats; a.pro_out = (unsigned char*)pro->out; a.pro_bits = pro->bits; a.pro_csum = pro->csum; }
-    const int unit = 8 * S;
+    int inst = 0;
+    constexpr int n_inst = (int)(sizeof(kRegwInst) / sizeof(kRegwInst[0]));
+    for (; inst < n_inst; ++inst) {
+        const RegwInst& i = kRegwInst[inst];
+        if (i.K == w.K && i.CW == w.CW && i.MT == w.MT && i.EPI == w.EPI && i.K2 == w.K2 && i.PRO == w.PRO && i.PG == w.PG) break;
+    }
+    if (inst == n_inst) return IIF_EUNSUPPORTED;
+    const int S = N / (8 * w.CW), unit = 8 * S, mtiles = M / w.MT;
     int grid = iif_persistent_grid(unit);
-    const int need = (a.mtiles + 7) / 8 * unit;
+    const int need = (mtiles + 7) / 8 * unit;
     if (need < grid) grid = need;
     // one partial row per tile sequence, never more rows than the tile kernels write (ceil(M / 128): what callers size for)
     const int rows128 = (M + 127) / 128;
-    if (bn_partial && grid / S > rows128) grid = rows128 / 8 * unit;
+    if (a.bn_partial && grid / S > rows128) grid = rows128 / 8 * unit;
     if (grid < unit) return IIF_EUNSUPPORTED;
     const int G = grid / S;
-    if (bn_partial) {
-        if ((long long)(bn_row0 + G) * 2 * dpitch > bn_cap) return IIF_EINVAL;
-        if (rows_out) *rows_out = bn_row0 + G;
+    *r = ConvRoute{IIF_ROUTE_REGW1X1, inst, -1, mtiles, S, (unsigned)grid, 1, 512, 0, 0};
+    if (const int rc = iif_claim_rows(a, r, G)) return rc;
+    if (w.PG) {
+        if ((long long)G * (N + w.K2) * a.pg_ld > a.pg_cap) return IIF_EINVAL;
+        r->slabs = G;
     }
-    if (a.pg_slab) {
-        if ((long long)G * (N + k2) * a.pg_ld > e->pg_cap) return IIF_EINVAL;
-        *e->pg_count = G;
-    }
-    const unsigned sb = (unsigned)((int64_t)M * spitch * 2);
-    const dim3 g((unsigned)grid), b(512);
-#define IIF_REGW(KK, CW, MT, EP) hipLaunchKernelGGL((gemm1x1_regw_kernel<KK, CW, MT, EP>), g, b, 0, st, a, sb)
-#define IIF_REGWX(KK, K2) hipLaunchKernelGGL((gemm1x1_regw_kernel<KK, 32, 64, 4, K2>), g, b, 0, st, a, sb)
-    if (k2 && a.pg_slab) {
-        if (K == 64) hipLaunchKernelGGL((gemm1x1_regw_kernel<64, 32, 64, 4, 64, false, true>), g, b, 0, st, a, sb);
-        else hipLaunchKernelGGL((gemm1x1_regw_kernel<128, 32, 64, 4, 64, false, true>), g, b, 0, st, a, sb);
-    } else if (k2) {
-        if (K == 64 && k2 == 64) IIF_REGWX(64, 64);
-        else if (K == 128 && k2 == 64) IIF_REGWX(128, 64);
-        else if (K == 128 && k2 == 128) IIF_REGWX(128, 128);
-        else if (K == 256 && k2 == 128) IIF_REGWX(256, 128);
-        else return IIF_EUNSUPPORTED;
-    } else if (epi) {
-        if (K == 64) IIF_REGW(64, 32, 64, 1);
-        else if (K == 128) IIF_REGW(128, 32, 64, 1);
-        else if (K == 256) IIF_REGW(256, 32, 64, 1);
-        else IIF_REGW(512, 32, 32, 1);
-    } else if (pro) {
-        if (K == 256) hipLaunchKernelGGL((gemm1x1_regw_kernel<256, 32, 64, 0, 0, true>), g, b, 0, st, a, sb);
-        else if (cw == 32) hipLaunchKernelGGL((gemm1x1_regw_kernel<512, 32, 32, 0, 0, true>), g, b, 0, st, a, sb);
-        else hipLaunchKernelGGL((gemm1x1_regw_kernel<512, 16, 64, 0, 0, true>), g, b, 0, st, a, sb);
-    } else {
-        if (K == 128 && cw == 64) IIF_REGW(128, 64, 64, 0);
-        else if (K == 128) IIF_REGW(128, 32, 64, 0);
-        else if (K == 256) IIF_REGW(256, 32, 64, 0);
-        else if (K == 512 && cw == 32) IIF_REGW(512, 32, 32, 0);
-        else if (K == 512) IIF_REGW(512, 16, 64, 0);
-        else IIF_REGW(1024, 16, 32, 0);
-    }
-    IIF_LAUNCH_CHECK();
     return IIF_OK;
 }
 
-// ---- the two passes of the never-stored conv + BN (+ shortcut) + ReLU forward (round 6): 32 columns per wave, N / 256 slices
-static bool regw_plan2(int K, int N) { return (K == 64 || K == 128 || K == 256) && N >= 256 && N <= 2048 && (N % 256) == 0; }
-
-bool iif_regw1x1_fwdbn_ok(int M, int K, int N) {
-    // (at least eight 128-row groups: one partial row per tile sequence, never more rows than ceil(M / 128), sequences in eights)
-    return M >= 1024 && (M % 64) == 0 && (int64_t)M * K * 2 < 0x7f000000LL && regw_plan2(K, N);
-}
-
-// mode 2: forward BN epilogue; mode 3: statistics from the accumulators (dst / res / aff unused)
-static int regw_launch2(int mode, const void* src, const void* wgt, void* dst, float* bn_partial, long long bn_cap, int bn_row0, int* rows_out,
-                        int M, int K, int N, int spitch, int ldw, int dpitch, const void* res, const float* aff, const float* aff2,
-                        unsigned char* relu_out, hipStream_t st, const iif_regw_prologue* pro = nullptr) {
-    if (!src || !wgt || !iif_regw1x1_fwdbn_ok(M, K, N) || spitch != K || dpitch != N) return IIF_EUNSUPPORTED;
-    if (pro && (mode != 3 || !pro->stats || !pro->out || !pro->bits)) return IIF_EINVAL;
-    if (mode == 2 && (!dst || !aff || !relu_out || (aff2 && !res))) return IIF_EINVAL;
-    if (mode == 3 && !bn_partial) return IIF_EINVAL;
-    const int S = N / 256;
-    RegwArgs a{(const unsigned char*)src, (const unsigned char*)wgt, (unsigned char*)dst, bn_partial, M, M / 64, spitch, ldw, N, dpitch,
-               bn_row0, S, (const unsigned char*)res, nullptr, nullptr, nullptr, nullptr, 0, 0, aff, aff2, relu_out};
-    if (pro) { a.pro_stats = pro->stats; a.pro_out = (unsigned char*)pro->out; a.pro_bits = pro->bits; a.pro_csum = pro->csum; }
-    const int unit = 8 * S;
-    int grid = iif_persistent_grid(unit);
-    const int need = (a.mtiles + 7) / 8 * unit;
-    if (need < grid) grid = need;
-    const int rows128 = (M + 127) / 128;
-    if (bn_partial && grid / S > rows128) grid = rows128 / 8 * unit;
-    if (grid < unit) return IIF_EUNSUPPORTED;
-    const int G = grid / S;
-    if (bn_partial) {
-        if ((long long)(bn_row0 + G) * 2 * dpitch > bn_cap) return IIF_EINVAL;
-        if (rows_out) *rows_out = bn_row0 + G;
+int iif_regw1x1_launch(const ConvRoute& r, const ConvCall& c, const ConvSel& s, hipStream_t st) {
+    const RegwInst& w = kRegwInst[r.inst];
+    RegwArgs a{};
+    a.src = (const unsigned char*)c.src; a.wgt = (const unsigned char*)c.wgt; a.bn_partial = c.bn_partial;
+    a.M = s.M; a.mtiles = r.mtiles; a.spitch = s.spitch; a.ldw = s.ldw; a.Cd = s.Cd; a.dpitch = s.dpitch; a.bn_row0 = s.bn_row0; a.S = r.ntiles;
+    if (w.EPI != 3) a.dst = (unsigned char*)c.dst;
+    if (w.EPI == 0) a.no_store = c.no_store;
+    if (w.EPI == 1 || w.EPI == 4) {
+        a.res = (const unsigned char*)c.res; a.res_bits = c.res_bits; a.bw_x = (const unsigned char*)c.bw_x; a.bw_bits = c.bw_bits;
+        a.bw_stats = c.bw_stats; a.mask_store = c.mask_store;
     }
-    const unsigned sb = (unsigned)((int64_t)M * spitch * 2);
-    const dim3 g((unsigned)grid), b(512);
-    if (mode == 2) {
-        IIF_ROUTE_PROBE(IIF_ROUTE_REGW1X1);
-        if (K == 64) IIF_REGW(64, 32, 64, 2);
-        else if (K == 128) IIF_REGW(128, 32, 64, 2);
-        else IIF_REGW(256, 32, 64, 2);
-    } else if (pro) {
-        if (K == 64) hipLaunchKernelGGL((gemm1x1_regw_kernel<64, 32, 64, 3, 0, true>), g, b, 0, st, a, sb);
-        else if (K == 128) hipLaunchKernelGGL((gemm1x1_regw_kernel<128, 32, 64, 3, 0, true>), g, b, 0, st, a, sb);
-        else hipLaunchKernelGGL((gemm1x1_regw_kernel<256, 32, 64, 3, 0, true>), g, b, 0, st, a, sb);
-    } else {
-        if (K == 64) IIF_REGW(64, 32, 64, 3);
-        else if (K == 128) IIF_REGW(128, 32, 64, 3);
-        else IIF_REGW(256, 32, 64, 3);
+    if (w.EPI == 2) { a.res = (const unsigned char*)c.res; a.aff = c.aff; a.aff2 = c.aff2; a.relu_out = c.relu_out; }
+    if (w.EPI == 4) {
+        a.src2 = (const unsigned char*)c.rx_src2; a.w3 = (const unsigned char*)c.rx_w3; a.spitch2 = w.K2; a.ldw3 = c.rx_ldw3;
+        a.src2_bytes = (unsigned)((int64_t)s.M * w.K2 * 2);
     }
+    if (w.PG) { a.pg_slab = c.pg_slab; a.pg_ld = c.pg_ld; }
+    if (w.PRO) { a.pro_stats = c.pro_stats; a.pro_out = (unsigned char*)c.pro_out; a.pro_bits = c.pro_bits; a.pro_csum = c.pro_csum; }
+    const unsigned sb = (unsigned)((int64_t)s.M * s.spitch * 2);
+    const dim3 g(r.grid), b(r.block);
+    int i = 0;
+#define IIF_REGW_CASE(K, CW, MT, EPI, K2, PRO, PG) \
+    if (r.inst == i++) hipLaunchKernelGGL((gemm1x1_regw_kernel<K, CW, MT, EPI, K2, PRO, PG>), g, b, 0, st, a, sb); else
+    IIF_REGW_INSTANCES(IIF_REGW_CASE) {}
+#undef IIF_REGW_CASE
     IIF_LAUNCH_CHECK();
     return IIF_OK;
-}
-#undef IIF_REGW
-
-int iif_regw1x1_fwdbn_launch(const void* src, const void* wgt, void* dst, int M, int K, int N, int spitch, int ldw, int dpitch,
-                             const void* res, const float* aff, const float* aff2, unsigned char* relu_out, hipStream_t st) {
-    return regw_launch2(2, src, wgt, dst, nullptr, 0, 0, nullptr, M, K, N, spitch, ldw, dpitch, res, aff, aff2, relu_out, st);
-}
-
-int iif_regw1x1_stats_launch(const void* src, const void* wgt, float* bn_partial, long long bn_cap, int bn_row0, int* rows_out,
-                             int M, int K, int N, int spitch, int ldw, int dpitch, hipStream_t st, const iif_regw_prologue* pro) {
-    return regw_launch2(3, src, wgt, nullptr, bn_partial, bn_cap, bn_row0, rows_out, M, K, N, spitch, ldw, dpitch, nullptr, nullptr, nullptr,
-                        nullptr, st, pro);
 }
 
 // =====================================================================================================================
@@ -1074,43 +1035,38 @@ __global__ void __launch_bounds__(256, 2) conv3x3_regw64_kernel(Regw3Args a, uns
 }
 }  // namespace
 
-bool iif_regw3x3_ok(int N, int H, int W, int C) {
-    if (C != 64 || N <= 0 || H <= 0 || W <= 0 || (H % 8) || (W % 8)) return false;
-    return (int64_t)N * H * W < (1 << 22) && (int64_t)N * H * W * C * 2 < 0x7f000000LL;
+int iif_regw3x3_select(const ConvSel& s, ConvRoute* r) {
+    const int N = s.N, H = s.Hd, W = s.Wd, C = s.Cs;
+    if (C != 64 || N <= 0 || H <= 0 || W <= 0 || (H % 8) || (W % 8)) return IIF_EUNSUPPORTED;
+    if ((int64_t)N * H * W >= (1 << 22) || (int64_t)N * H * W * C * 2 >= kDmaRange) return IIF_EUNSUPPORTED;
+    if (s.aff ? (s.bn_partial || s.bw_x || s.bw_bits || (s.aff2 && !s.res)) : (s.aff2 || s.relu_out)) return IIF_EUNSUPPORTED;
+    const int ntiles = N * (H / 8) * (W / 8);
+    int grid = 2 * iif_persistent_cus() / 8 * 8;                         // two four-wave blocks per CU
+    const int need = (ntiles + 7) / 8 * 8;
+    if (need < grid) grid = need;
+    const int rows128 = (s.M + 127) / 128;
+    if (s.bn_partial && grid > rows128) grid = rows128 / 8 * 8;          // never more partial rows than the tile kernels' ceil(M / 128)
+    if (grid < 8) return IIF_EUNSUPPORTED;
+    // EPI 0: plain store (+ forward sums), 1: upstream BN-backward sums, 2: BN affine (+ residual) + ReLU of an inference forward
+    *r = ConvRoute{IIF_ROUTE_REGW3X3, s.aff ? 2 : (s.bw_x || s.bw_bits) ? 1 : 0, -1, ntiles, 1, (unsigned)grid, 1, 256, 0, 0};
+    return iif_claim_rows(s, r, grid);
 }
 
-int iif_regw3x3_launch(const void* src, const void* wgt, void* dst, float* bn_partial, long long bn_cap, int bn_row0, int* rows_out,
-                       int N, int H, int W, int C, int ldw, const signed char* tap_dy, const signed char* tap_dx, const unsigned char* tap_w,
-                       const void* bw_x, const unsigned char* bw_bits, const float* bw_stats, hipStream_t st, const float* aff, const float* aff2,
-                       const void* res, unsigned char* relu_out) {
-    if (!src || !wgt || !dst || !iif_regw3x3_ok(N, H, W, C)) return IIF_EUNSUPPORTED;
-    if (aff ? (bn_partial || bw_x || bw_bits || (aff2 && !res)) : (aff2 || res || relu_out)) return IIF_EUNSUPPORTED;
-    const int cus = iif_persistent_cus();
+int iif_regw3x3_launch(const ConvRoute& r, const ConvCall& c, const ConvSel& s, const signed char* tap_dy, const signed char* tap_dx,
+                       const unsigned char* tap_w, hipStream_t st) {
     Regw3Args a{};
-    a.src = (const unsigned char*)src; a.wgt = (const unsigned char*)wgt; a.dst = (unsigned char*)dst; a.bn_partial = bn_partial;
-    a.bw_x = (const unsigned char*)bw_x; a.bw_bits = bw_bits; a.bw_stats = bw_stats;
-    a.aff = aff; a.aff2 = aff2; a.res = (const unsigned char*)res; a.relu_out = relu_out;
-    a.N = N; a.H = H; a.W = W; a.M = N * H * W; a.tiles_x = W / 8; a.tiles_per_image = (H / 8) * (W / 8);
-    a.ntiles = N * a.tiles_per_image; a.ldw = ldw; a.bn_row0 = bn_row0;
+    a.src = (const unsigned char*)c.src; a.wgt = (const unsigned char*)c.wgt; a.dst = (unsigned char*)c.dst; a.bn_partial = c.bn_partial;
+    if (c.bn_partial) { a.bw_x = (const unsigned char*)c.bw_x; a.bw_bits = c.bw_bits; a.bw_stats = c.bw_stats; }
+    a.aff = c.aff; a.aff2 = c.aff2; a.res = c.aff ? (const unsigned char*)c.res : nullptr; a.relu_out = c.relu_out;
+    a.N = s.N; a.H = s.Hd; a.W = s.Wd; a.M = s.N * s.Hd * s.Wd; a.tiles_x = s.Wd / 8; a.tiles_per_image = (s.Hd / 8) * (s.Wd / 8);
+    a.ntiles = r.mtiles; a.ldw = s.ldw; a.bn_row0 = s.bn_row0;
     for (int t = 0; t < 9; ++t) { a.tap_dy[t] = tap_dy[t]; a.tap_dx[t] = tap_dx[t]; a.tap_w[t] = tap_w[t]; }
     a.m_tpi = a.tiles_per_image == 1 ? 0u : (unsigned)(((1ull << 32) + a.tiles_per_image - 1) / a.tiles_per_image);
     a.m_tx = a.tiles_x == 1 ? 0u : (unsigned)(((1ull << 32) + a.tiles_x - 1) / a.tiles_x);
-    int grid = 2 * cus / 8 * 8;                                          // two four-wave blocks per CU
-    const int need = (a.ntiles + 7) / 8 * 8;
-    if (need < grid) grid = need;
-    const int rows128 = (a.M + 127) / 128;
-    if (bn_partial && grid > rows128) grid = rows128 / 8 * 8;            // never more partial rows than the tile kernels' ceil(M / 128)
-    if (grid < 8) return IIF_EUNSUPPORTED;
-    if (bn_partial) {
-        if ((long long)(bn_row0 + grid) * 2 * C > bn_cap) return IIF_EINVAL;
-        if (rows_out) *rows_out = bn_row0 + grid;
-    }
-    const unsigned sb = (unsigned)((int64_t)a.M * C * 2);
-    const bool epi = bw_x != nullptr || bw_bits != nullptr;
-    const dim3 g((unsigned)grid), b(256);
-    IIF_ROUTE_PROBE(IIF_ROUTE_REGW3X3);
-    if (aff) hipLaunchKernelGGL(conv3x3_regw64_kernel<2>, g, b, 0, st, a, sb);
-    else if (epi) hipLaunchKernelGGL(conv3x3_regw64_kernel<1>, g, b, 0, st, a, sb);
+    const unsigned sb = (unsigned)((int64_t)a.M * 64 * 2);
+    const dim3 g(r.grid), b(r.block);
+    if (r.inst == 2) hipLaunchKernelGGL(conv3x3_regw64_kernel<2>, g, b, 0, st, a, sb);
+    else if (r.inst == 1) hipLaunchKernelGGL(conv3x3_regw64_kernel<1>, g, b, 0, st, a, sb);
     else hipLaunchKernelGGL(conv3x3_regw64_kernel<0>, g, b, 0, st, a, sb);
     IIF_LAUNCH_CHECK();
     return IIF_OK;

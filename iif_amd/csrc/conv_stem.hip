@@ -166,30 +166,34 @@ __global__ void __launch_bounds__(256, 2) stem4x4_kernel(StemArgs a, unsigned sr
 }
 }  // namespace
 
+bool iif_stem4x4_geometry(const ConvSel& a) {
+    return a.R == 4 && a.S == 4 && a.Cs == 16 && a.Cd == 64 && a.pad == 2 && a.sshift == 0 && a.groups == 1;
+}
+
 // Geometry the kernel covers: tiles of 128 pixels never cross an image and their window fits the halo buffer.
-bool iif_stem4x4_ok(int N, int H, int W) {
+static bool stem4x4_ok(int N, int H, int W) {
     if (N <= 0 || H <= 0 || W <= 0 || (int64_t)N * H * W >= (1 << 26)) return false;
     if (((int64_t)H * W) % SBM) return false;
     const int span = (SBM + W - 2) / W + 1;            // image rows a tile can touch
     return (span + 3) * (W + 3) <= SHR;
 }
 
-int iif_stem4x4_launch(const void* src, const void* wgt, void* dst, float* bn_partial, long long bn_cap, int bn_row0, int* rows_out,
-                       int N, int H, int W, hipStream_t st) {
-    if (!src || !wgt || !dst || !iif_stem4x4_ok(N, H, W)) return IIF_EUNSUPPORTED;
-    const int cus = iif_persistent_cus();
-    StemArgs a{(const unsigned char*)src, (const unsigned char*)wgt, (unsigned char*)dst, bn_partial, N, H, W, N * H * W,
-               N * H * W / SBM, 64, bn_row0};
-    int grid = 2 * cus / 8 * 8;                          // two blocks per CU, whole groups of 8 (one per XCD)
-    const int need = (a.ntiles + 7) / 8 * 8;
+int iif_stem4x4_select(const ConvSel& a, ConvRoute* r) {
+    if (!stem4x4_ok(a.N, a.Hd, a.Wd)) return IIF_EUNSUPPORTED;
+    const int ntiles = a.N * a.Hd * a.Wd / SBM;
+    int grid = 2 * iif_persistent_cus() / 8 * 8;        // two blocks per CU, whole groups of 8 (one per XCD)
+    const int need = (ntiles + 7) / 8 * 8;
     if (need < grid) grid = need;                       // (never more partial rows than the tile kernels' ceil(M / 128) = ntiles)
-    if (bn_partial && grid > a.ntiles) grid = a.ntiles / 8 * 8;
+    if (a.bn_partial && grid > ntiles) grid = ntiles / 8 * 8;
     if (grid < 8) return IIF_EUNSUPPORTED;
-    if (bn_partial) {
-        if ((long long)(bn_row0 + grid) * 2 * a.dpitch > bn_cap) return IIF_EINVAL;
-        if (rows_out) *rows_out = bn_row0 + grid;
-    }
-    hipLaunchKernelGGL(stem4x4_kernel, dim3((unsigned)grid), dim3(256), 0, st, a, (unsigned)((int64_t)N * H * W * 32));
+    *r = ConvRoute{IIF_ROUTE_STEM, 0, -1, ntiles, 1, (unsigned)grid, 1, 256, 0, 0};
+    return iif_claim_rows(a, r, grid);
+}
+
+int iif_stem4x4_launch(const ConvRoute& r, const ConvCall& c, const ConvSel& s, hipStream_t st) {
+    StemArgs a{(const unsigned char*)c.src, (const unsigned char*)c.wgt, (unsigned char*)c.dst, c.bn_partial, s.N, s.Hd, s.Wd,
+               s.N * s.Hd * s.Wd, r.mtiles, 64, s.bn_row0};
+    hipLaunchKernelGGL(stem4x4_kernel, dim3(r.grid), dim3(r.block), 0, st, a, (unsigned)((int64_t)s.N * s.Hd * s.Wd * 32));
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }

@@ -555,12 +555,14 @@ int iif_conv_fwdbn_ok(const iif_conv_desc* d);
  * 3x3, stride 1 and 2, dense and grouped, any m.  iif_conv_affine_ok (host only, launches nothing) says whether a descriptor
  * has a fused instance with the given residual form; where it says 0, iif_conv_igemm_affine returns IIF_EUNSUPPORTED. */
 int iif_conv_affine_ok(const iif_conv_desc* d, int has_res, int has_res_affine);
-/* Which kernel family iif_conv_igemm_affine would launch for this descriptor and operand set, found by walking the launch
- * routing itself with the launches replaced by a record (nothing runs): 0 none, 1 tile (three LDS stages), 2 tile (two
- * stages, 4 blocks per CU), 3 tile with general addressing (source channels not in 32s), 4 256-row tile, 5 3x3 halo,
- * 6 3x3 fragment weights, 7 3x3 grouped 16-channel fragments, 8 streaming 1x1, 9 register-weight 1x1, 10 register-weight
- * 3x3.  d->wgt_frag only has to be non-null where fragments would be supplied.  Follows the IIF_CONV_* switches; the
- * persistent kernels size themselves by the device, so it needs one.  For tests and route listings. */
+/* Which kernel family iif_conv_igemm_affine launches for this descriptor and operand set: the answer of the selection step
+ * the launch itself starts with (a host function of the descriptor and of WHICH operands there are; it touches no operand
+ * and launches nothing): 0 none, 1 tile (three LDS stages), 2 tile (two stages, 4 blocks per CU), 3 tile with general
+ * addressing (source channels not in 32s), 4 256-row tile, 5 3x3 halo, 6 3x3 fragment weights, 7 3x3 grouped 16-channel
+ * fragments, 8 streaming 1x1, 9 register-weight 1x1, 10 register-weight 3x3, 11 register-staged tile.  d->wgt_frag only
+ * has to be non-null where fragments would be supplied.  Follows the IIF_CONV_* switches and the CU budget; the persistent
+ * kernels size themselves by the device's compute units (256 assumed where there is no device).  For tests and route
+ * listings. */
 int iif_conv_affine_route(const iif_conv_desc* d, int has_res, int has_res_affine, int has_relu_bits);
 int iif_conv_igemm_affine(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
                           const float* res_affine, const float* affine, unsigned char* relu_bits, void* stream);
