@@ -122,6 +122,10 @@ SIGNATURES = {
     "iif_lt_augment": [_P, _L, _P, _P, _L, _I, _P, _c.c_uint32, _P, _P],
     "iif_lt_augment_policy": [_P, _L, _P, _P, _L, _I, _P, _P, _P, _P],
     "iif_jpeg_decode": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _P, _P],
+    "iif_seesaw_fwd_bwd": [_P, _I, _L, _P, _P, _P, _I, _F, _F, _F, _F, _I, _F, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P],
+    "iif_seesaw_activation": [_P, _I, _L, _I, _I, _P, _L, _P],
+    "iif_seesaw_accuracy": [_P, _I, _L, _P, _I, _I, _P, _P, _P],
+    "iif_seesaw_scale_grad": [_P, _L, _I, _I, _P, _P, _I, _P, _L, _P],
 }
 
 

@@ -160,6 +160,61 @@ int iif_eval_accumulate(const void* logits, int dtype, int64_t ld_logits, const 
  * bridge to apply the upstream gradient of the scalar loss without a host sync. */
 int iif_scale_by_device_scalar(const void* x, int dtype, int64_t n, const float* d_scalar, void* out, void* stream);
 
+/* ------------------------------------------------------------- Seesaw head (LVIS) */
+
+/* Fused Seesaw loss, forward + gradient.  Replaces mmdet/models/losses/seesaw_loss.py:12-76,199-262
+ * (SeesawLoss.forward: the host loop over labels.unique(), the [C, C] ratio matrix, two softmaxes, pow, log,
+ * cross entropy on the positive rows and the objectness cross entropy) by TWO launches and no host round trip.
+ *
+ * cls_score: [N, C + 2] fp32, leading dimension ld_score >= C + 2 (elements), element-aligned: C class columns z
+ * and two objectness columns o.  labels: int64[N] in [0, C], C = background.  label_weights: float[N] or NULL.
+ *
+ *   launch 1   cum_samples[l] += (float)count(labels == l) when update_counts != 0: an integer histogram, ONE fp32
+ *              addition per class (exact and order independent, also above 2^24); the number of positive rows
+ *   launch 2   with the UPDATED cum_samples[:C], for a positive row (t = label < C), in the log domain:
+ *                a_j = min(0, p * (log max(cum_j, 1) - log max(cum_t, 1)))                          (p > 0)
+ *                b_j = max(0, q * (z_j - lse(z) - max(z_t - lse(z), log eps)))                      (q > 0)
+ *                z'_j = z_j + a_j + b_j (j != t), z'_t = z_t
+ *                class loss_i = w_i * (lse(z') - z_t),  d z = scale_cls' * w_i * (softmax(z') - onehot_t)
+ *              background rows: class loss 0 and a zero class gradient.  Every row: objectness loss_i =
+ *              w_i * (lse(o) - o[label == C]), gradient scale_obj * w_i * (softmax(o) - onehot) in the last two columns.
+ *   loss_out[0] = scale_cls' * sum class loss_i,  loss_out[1] = scale_obj * sum objectness loss_i,
+ *   scale_cls' = scale_cls / (positive rows) when div_by_pos != 0 (reduction 'mean' without avg_factor; no positive
+ *   row: loss 0, gradient 0), else scale_cls.
+ *
+ * cum_samples: float[C + 1], state, updated in place.  loss_rows_cls / loss_rows_obj: float[N], required (the
+ * unscaled loss_i).  loss_out: float[2].  dscore: [N, C + 2] fp32 with ld_dscore, or NULL (losses only); every
+ * element of a row is written.  A label outside [0, C] counts nowhere, zeroes its row (losses and gradient) and sets
+ * d_status (int32[1] or NULL) to 1, as iif_ce_fwd_bwd does.
+ * d_workspace: IIF_SEESAW_WORKSPACE_BYTES of device memory, ZERO on first use; the kernels leave its tickets and
+ * histogram zero again.  One workspace per stream.  Deterministic (integer atomics, fixed-order float sums).
+ * dtype must be IIF_F32 (IIF_EINVAL otherwise); C + 2 > 2048 is IIF_EUNSUPPORTED (the row is register resident).
+ * N == 0 writes two zero losses without a launch and leaves cum_samples alone. */
+int iif_seesaw_fwd_bwd(const void* cls_score, int dtype, int64_t ld_score, const int64_t* labels,
+                       const float* label_weights, float* cum_samples, int update_counts,
+                       float p, float q, float eps, float scale_cls, int div_by_pos, float scale_obj,
+                       int N, int C, float* loss_rows_cls, float* loss_rows_obj, float* loss_out,
+                       void* dscore, int64_t ld_dscore, int32_t* d_status, void* d_workspace, void* stream);
+#define IIF_SEESAW_WORKSPACE_BYTES (4 * (4 + 2048 + 2 * 1024))
+
+/* out[:, :C] = softmax(z) * softmax(o)[0], out[:, C] = softmax(o)[1]; out: [N, C + 1] fp32 with ld_out >= C + 1.
+ * Replaces seesaw_loss.py:157-175 (get_activation).  One launch.  fp32 only, C + 2 <= 2048. */
+int iif_seesaw_activation(const void* cls_score, int dtype, int64_t ld_score, int N, int C,
+                          float* out, int64_t ld_out, void* stream);
+
+/* out[0] = objectness top-1 accuracy over all rows, out[1] = class top-1 accuracy over the positive rows, in percent
+ * (seesaw_loss.py:177-197 + accuracy.py:7-51: float32 hit count times float32(100 / rows); 0 when there is no
+ * positive row, and both 0 for N == 0).  Integer counts and the division on the device, one launch; rank rule of
+ * iif_topk_hits.  d_workspace: int32[4], zero on first use and left zero.  A label outside [0, C] is no positive row. */
+int iif_seesaw_accuracy(const void* cls_score, int dtype, int64_t ld_score, const int64_t* labels, int N, int C,
+                        float* out, int32_t* d_workspace, void* stream);
+
+/* Backward of the two Seesaw losses: out = dscore * g_cls on the C class columns and dscore * g_obj on the two
+ * objectness columns.  g_cls / g_obj: device float[1] (per_row == 0) or float[N] (per_row != 0, reduction 'none').
+ * out may alias dscore. */
+int iif_seesaw_scale_grad(const float* dscore, int64_t ld_dscore, int N, int C, const float* g_cls, const float* g_obj,
+                          int per_row, float* out, int64_t ld_out, void* stream);
+
 /* out[b,:] = lam*x[b,:] + (1-lam)*x[perm[b],:], rows of n elements.
  * Replaces the image blend of classification/custom.py:112 (Mixup.__call__). */
 int iif_mix_rows(const void* x, int dtype, const int64_t* perm, float lam, int B, int64_t n,
