@@ -21,17 +21,21 @@ from .mmdet_iif_loss import IIFLoss
 
 
 class FasaIIFLoss(IIFLoss):
-    """fasa_iif_loss.py:12-208.  ``use_sigmoid`` / ``use_mask`` select stock mmdet criteria in the reference
-    and are not part of the IIF path."""
+    """fasa_iif_loss.py:12-208.  ``use_sigmoid`` / ``use_mask`` replace the IIF cross entropy by mmdet's
+    ``binary_cross_entropy`` / ``mask_cross_entropy`` (fasa_iif_loss.py:35-40), here the native ones of
+    ``mmdet_ce_loss``; the class counters work on either."""
 
     def __init__(self, use_sigmoid=False, use_mask=False, reduction="mean", class_weight=None, loss_weight=1.0,
                  use_cums=False, num_classes=1203, path="./lvis_files/idf_1204.csv", variant="raw", device="cuda"):
         assert (use_sigmoid is False) or (use_mask is False)
-        if use_sigmoid or use_mask:
-            raise NotImplementedError("FasaIIFLoss(use_sigmoid/use_mask) dispatches to stock mmdet criteria")
         super().__init__(use_sigmoid=False, reduction=reduction, class_weight=class_weight, ignore_index=None,
                          loss_weight=loss_weight, num_classes=num_classes, path=path, variant=variant, device=device)
+        self.use_sigmoid = use_sigmoid
         self.use_mask = use_mask
+        if use_sigmoid or use_mask:
+            # imported here: the module registers CrossEntropyLoss into mmdet, which a plain IIF user has not asked for
+            from .mmdet_ce_loss import binary_cross_entropy, mask_cross_entropy
+            self.cls_criterion = binary_cross_entropy if use_sigmoid else mask_cross_entropy
         self._device = device
         self.use_cums = use_cums
         if self.use_cums:
@@ -54,7 +58,10 @@ class FasaIIFLoss(IIFLoss):
         loss_cls = super().forward(cls_score, label, weight=weight, avg_factor=avg_factor,
                                    reduction_override=reduction_override, **kwargs)
         if self.use_cums:
-            rows = loss_cls.detach().float().contiguous()
+            rows = loss_cls.detach().float()
+            if rows.dim() > 1:                      # the sigmoid criterion's [N, C] element losses: a row's sum
+                rows = rows.sum(dim=1)
+            rows = rows.contiguous()
             lb = label.reshape(-1).to(torch.int64).contiguous()
             _lib.check(_lib.lib().iif_class_accumulate(_lib.ptr(rows), _lib.ptr(lb), rows.numel(), self.num_classes + 1,
                                                        _lib.ptr(self.cum_losses), _lib.ptr(self.cum_labels),

@@ -124,6 +124,37 @@ int iif_sigmoid_focal_fwd_bwd(const void* logits, int dtype, int64_t ld_logits,
                               void* dlogits, int64_t ld_dlogits, int32_t* d_status, void* d_workspace,
                               void* stream);
 
+/* Detection-style sigmoid BCE (mmdet's binary_cross_entropy), forward + gradient in ONE launch, no host round trip.
+ * Replaces mmdet/models/losses/cross_entropy_loss.py:53-111 (_expand_onehot_labels, binary_cross_entropy) +
+ * losses/utils.py:29-55 (weight_reduce_loss).
+ *
+ * Label mode (labels != NULL, targets == NULL), element (i, c) of pred [N, C]:
+ *   valid_i = labels_i >= 0 and labels_i != ignore_index
+ *   y_ic    = [labels_i == c]          (a valid label >= C is an all-zero row: background, not an error)
+ *   w_ic    = valid_i * (row_weight_i, 1 if NULL)
+ * Dense mode (targets != NULL, labels == NULL; the reference's pred.dim() == label.dim() branch):
+ *   y_ic = targets[i, c],  w_ic = elem_weight[i, c] (1 if NULL); float [N, C] contiguous; no ignore index.
+ * Either mode, pw_c = class_weight[c] as torch's pos_weight (1 if NULL):
+ *   l_ic     = (1 - y) x + (1 + (pw_c - 1) y) softplus(-x)     (evaluated as (1 - y) softplus(x) + pw_c y softplus(-x):
+ *                                                               exact at every |x|)
+ *   loss     = scale * sum_ic w_ic l_ic      (scale = loss_weight / (N C) for 'mean', loss_weight for 'sum',
+ *                                             loss_weight / avg_factor with an avg_factor)
+ *   dpred_ic = scale * w_ic * ((1 - y) sigmoid(x) - pw_c y (1 - sigmoid(x)))
+ *
+ * pred / dpred: [N, C] row-major with leading dimensions ld_pred / ld_dpred (elements), IIF_F32 or IIF_BF16 (math is
+ * fp32; dpred in the dtype of pred), element-aligned; dpred may be NULL (loss only).  loss_elems: float [N, C]
+ * contiguous or NULL, receives the unscaled w_ic l_ic (reduction 'none').  loss_out: float[1] or NULL; with it
+ * d_workspace is required: IIF_CE_WORKSPACE_BYTES under iif_ce_fwd_bwd's contract (ticket zero on entry and exit, one
+ * workspace per stream), and the scalar leaves the same launch.  Deterministic (fixed-order sums, no float atomics).
+ * The kernel walks the flat element range in 16-byte pieces and carries each piece's (row, column) along: any C >= 1
+ * (C = 1 with N in the hundreds of thousands is the RPN shape), 64-bit indexing.  That form needs ld == C and element
+ * h of every array on a 16-byte boundary, h = the first element of pred that is; any other pitch or phase runs the
+ * same arithmetic one element per lane.  N == 0 writes a zero loss without a launch. */
+int iif_bce_det_fwd_bwd(const void* pred, int dtype, int64_t ld_pred, const int64_t* labels, const float* row_weight,
+                        int64_t ignore_index, const float* targets, const float* elem_weight,
+                        const float* class_weight, float scale, int N, int C, float* loss_elems, float* loss_out,
+                        void* dpred, int64_t ld_dpred, void* d_workspace, void* stream);
+
 /* out = logits * table.  Replaces classification/custom.py:37-39 (infer=True). */
 int iif_scale_logits(const void* logits, int dtype, int64_t ld_logits, const float* table,
                      int B, int C, void* out, int64_t ld_out, void* stream);
