@@ -127,6 +127,8 @@ SIGNATURES = {
     "iif_seesaw_accuracy": [_P, _I, _L, _P, _I, _I, _P, _P, _P],
     "iif_seesaw_scale_grad": [_P, _L, _I, _I, _P, _P, _I, _P, _L, _P],
     "iif_bce_det_fwd_bwd": [_P, _I, _L, _P, _P, _L, _P, _P, _P, _F, _I, _I, _P, _P, _P, _L, _P, _P],
+    "iif_bbox_reg_fwd": [_P, _I, _L, _P, _I, _I, _P, _P, _F, _F, _L, _I, _P, _P, _P, _P, _P],
+    "iif_bbox_reg_scatter_grad": [_P, _P, _I, _I, _I, _P, _P, _I, _L, _P],
 }
 
 

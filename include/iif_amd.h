@@ -155,7 +155,47 @@ int iif_bce_det_fwd_bwd(const void* pred, int dtype, int64_t ld_pred, const int6
                         const float* class_weight, float scale, int N, int C, float* loss_elems, float* loss_out,
                         void* dpred, int64_t ld_dpred, void* d_workspace, void* stream);
 
-/* out = logits * table.  Replaces classification/custom.py:37-39 (infer=True). */
+/* Box-regression loss (mmdet's l1_loss / smooth_l1_loss), forward + COMPACT gradient in ONE launch, no host round trip.
+ * Replaces mmdet/models/losses/smooth_l1_loss.py:10-52 + losses/utils.py:29-55 and, in gather mode, the positive-row
+ * selection of mmdet/models/roi_heads/bbox_heads/bbox_head.py:284-311 (pos_inds.any(), three boolean indexings).
+ *
+ * Plain mode (labels == NULL, C == 1): pred, target and weight are the same flat range of n elements (pred contiguous;
+ *   ld_pred, num_classes and N are not read); n >= 0, not necessarily a multiple of 4.
+ * Gather mode (labels != NULL: int64[N], n == 4N): pred is [N, 4C] with leading dimension ld_pred >= 4C (elements);
+ *   row i is positive iff 0 <= labels_i < num_classes, and its four predictions are pred[i, 4 labels_i .. 4 labels_i + 3]
+ *   (C > 1; num_classes <= C) or pred[i, 0 .. 3] (C == 1: a class-agnostic head, any num_classes >= 1).  target /
+ *   weight / dsel / loss_elems are [N, 4] contiguous; a row that is not positive reads nothing of pred and contributes
+ *   nothing: its dsel and loss_elems are exact zeros.
+ * Per element, d = p - t, a = |d|:
+ *   beta == 0 (L1):        l = a,                  dl = sign(d), sign(0) = 0
+ *   beta  > 0 (smooth L1): a < beta (strict) ?  l = 0.5 a a / beta,  dl = d / beta  :  l = a - 0.5 beta,  dl = sign(d)
+ *   loss = scale * sum w l   (w = weight, 1 if NULL; scale = loss_weight / n for 'mean', loss_weight for 'sum',
+ *                             loss_weight / avg_factor with an avg_factor)
+ *   dsel[e]       = scale * w * dl      (float[n] or NULL: the gradient w.r.t. the SELECTED predictions, fp32)
+ *   loss_elems[e] = w * l               (float[n] or NULL: unscaled, reduction 'none')
+ * pred: IIF_F32 or IIF_BF16 (math is fp32), element-aligned.  loss_out: float[1] or NULL; with it d_workspace is
+ * required: IIF_CE_WORKSPACE_BYTES under iif_ce_fwd_bwd's contract (ticket zero on entry and exit, one workspace per
+ * stream), and the scalar leaves the same launch.  Deterministic (fixed-order sums, no float atomics): bit-identical
+ * from call to call.  A lane takes one box (four elements: 16 bytes of every fp32 array, 16 / 8 bytes of pred) when
+ * pred's boxes sit on a 4-element boundary (base and, in gather mode, ld_pred % 4 == 0) and every fp32 array on a
+ * 16-byte one; any other phase runs one element per lane.  64-bit indexing.  n == 0 writes a zero loss without a
+ * launch.  Backward in plain mode is iif_scale_by_device_scalar on dsel; in gather mode iif_bbox_reg_scatter_grad. */
+int iif_bbox_reg_fwd(const void* pred, int dtype, int64_t ld_pred, const int64_t* labels, int num_classes, int C,
+                     const float* target, const float* weight, float beta, float scale, int64_t n, int N,
+                     float* loss_elems, float* loss_out, float* dsel, void* d_workspace, void* stream);
+
+/* The dense gradient of gather mode in ONE launch, a pure store stream: dpred [N, 4C] (dtype IIF_F32 or IIF_BF16,
+ * leading dimension ld_dpred >= 4C elements, element-aligned) receives *g * dsel[i, 0..3] at row i, columns
+ * 4 labels_i .. 4 labels_i + 3 (C == 1: columns 0 .. 3) for the positive rows (0 <= labels_i < num_classes) and exact
+ * zero in every other column of [0, 4C).  Columns beyond 4C of a wider pitch are not touched.  g: the upstream
+ * gradient of the scalar loss, a DEVICE float (NULL = 1), so nothing synchronises.  Every byte has exactly one writer
+ * within the launch: no memset, no fill-then-overwrite.  dpred on a 16-byte boundary with ld_dpred == 4C is written in
+ * 16-byte pieces (one class of fp32, two classes of bf16 - with odd C a piece straddles two rows); any other base or
+ * pitch goes one element per lane.  N == 0 is a no-op. */
+int iif_bbox_reg_scatter_grad(const float* dsel, const int64_t* labels, int num_classes, int N, int C, const float* g,
+                              void* dpred, int dtype, int64_t ld_dpred, void* stream);
+
+/* out = logits * table. Replaces classification/custom.py:37-39 (infer=True). */
 int iif_scale_logits(const void* logits, int dtype, int64_t ld_logits, const float* table,
                      int B, int C, void* out, int64_t ld_out, void* stream);
 
