@@ -1,0 +1,384 @@
+// Max-IoU box assignment and the 2-D overlap calculator for gfx950 (MI355X): mmdet's MaxIoUAssigner.assign and bbox_overlaps.
+//
+// instance_segmentation/mmdet/core/bbox/assigners/max_iou_assigner.py:61-213 materialises the [G, N] overlap matrix of
+// iou_calculators/iou2d_calculator.py:75-261 (the file's own count: 9 G N floats of temporaries), takes its maxima along both
+// axes, walks the G ground-truth boxes in a Python loop (two launches per box) and asks pos_inds.numel() of the host.  The
+// result is three vectors of length N, and the only quantity that crosses candidates is one maximum per ground-truth box.  Here:
+//
+//   iif_bbox_overlaps    the stand-alone calculator: 'iou' / 'iof' / 'giou', pairwise [M, N] or aligned [N], one lane per output.
+//   iif_max_iou_assign   no [G, N] array anywhere.  One lane per candidate box; the ground-truth (and ignore) boxes pass through
+//                        LDS in chunks of kChunk, so any G works.
+//     pass 1  per candidate: is it ignored (max iof against the ignore boxes > ignore_iof_thr), its maximum overlap and the
+//             LOWEST gt index that attains it.  Per gt: the maximum over the non-ignored candidates and the LOWEST candidate that
+//             attains it, as a 64-bit INTEGER maximum of (bits(overlap) + 1) << 32 | ~candidate: an LDS atomic per overlapping
+//             pair that beats the running LDS value, then one global atomic per gt and block that has one.  Overlaps are >= +0, so
+//             their bits order as unsigned integers; 0 is "no candidate" (the reference's -1) and orders below bits(0.0) + 1.
+//             Pairs that do not intersect (nearly all of them) issue nothing: their overlap is exactly +0, and what they contribute
+//             to a gt's maximum - "0.0, at the lowest non-ignored candidate" - is ONE extra workspace slot for all gts.
+//     pass 2  (match_low_quality only; without it pass 1 finishes the assignment in the same launch) applies the reference's steps
+//             in its order and recomputes the pairs it needs with the same inline function, hence to the same bits: a candidate
+//             can only equal gt i's maximum if that maximum is <= the candidate's own, which leaves few pairs.
+//   Three enqueued operations at most: the workspace clear, pass 1, pass 2.  No float atomics: nothing depends on arrival order.
+//
+// Arithmetic: every step of the reference is one IEEE float32 operation, done here in its order (the build passes
+// -ffp-contract=off; `/` is the correctly rounded division):
+//     area = (x2 - x1) * (y2 - y1);  w, h = max(min(rb) - max(lt), 0);  overlap = w * h
+//     union = max(area1 + area2 - overlap, eps)   ('iof': max(area1, eps));   iou = overlap / union
+//     giou = iou - (max(enclose, eps) - union) / max(enclose, eps)
+// The assigner's eps is the reference's default 1e-6 (> 0), so a pair with overlap == 0 has iou == +0 exactly and the division
+// is skipped.  NaN coordinates are not reproduced (torch's max / clamp propagate NaN, v_max_f32 does not).
+#include "common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kChunk = 256;                   // gt / ignore boxes per LDS chunk: one per thread of the block
+constexpr float kAssignEps = 1e-6f;           // bbox_overlaps' default eps, which MaxIoUAssigner never overrides
+constexpr unsigned kOvMaxBlocks = 1u << 16;   // grid cap of the calculator (grid-stride beyond)
+
+enum { kIoU = 0, kIoF = 1, kGIoU = 2 };
+
+struct alignas(16) Box { float x1, y1, x2, y2; };
+
+// vec: the array's rows are whole 16-byte pieces (base on a 16-byte boundary, pitch a multiple of 4)
+__device__ __forceinline__ Box load_box(const float* p, bool vec) {
+    if (vec) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+        return Box{t.x, t.y, t.z, t.w};
+    }
+    return Box{p[0], p[1], p[2], p[3]};
+}
+
+__device__ __forceinline__ float box_area(const Box& b) { return (b.x2 - b.x1) * (b.y2 - b.y1); }
+
+__device__ __forceinline__ float box_inter(const Box& a, const Box& b) {
+    const float w = fmaxf(fminf(a.x2, b.x2) - fmaxf(a.x1, b.x1), 0.0f);
+    const float h = fmaxf(fminf(a.y2, b.y2) - fmaxf(a.y1, b.y1), 0.0f);
+    return w * h;
+}
+
+// iou of a (ground-truth, candidate) pair as the assigner sees it (eps = kAssignEps > 0); `inter` returns the overlap area.
+// BOTH passes go through this function: pass 2 compares its result with pass 1's for equality.
+__device__ __forceinline__ float pair_iou(const Box& g, float ga, const Box& c, float ca, float& inter) {
+    inter = box_inter(g, c);
+    if (!(inter > 0.0f)) return 0.0f;                       // 0 / max(union, eps) = +0
+    return inter / fmaxf(ga + ca - inter, kAssignEps);
+}
+
+__device__ __forceinline__ unsigned long long pack_max(float v, unsigned idx) {
+    return ((unsigned long long)(__float_as_uint(v) + 1u) << 32) | (unsigned long long)(~idx);
+}
+
+struct AssignArgs {
+    const float* b; int64_t ldb; int N; int vec_b;
+    const float* g; int64_t ldg; int G;
+    const float* ig; int64_t ldi; int I;                    // ig == nullptr: nothing is ignored
+    float pos, neg_lo, neg_hi, min_pos, ign_thr;
+    int assign_all, ign_wrt_cand, low_quality;
+    const int64_t* gt_labels;
+    int64_t* gt_inds; float* max_ov; int64_t* labels;
+    unsigned long long* ws;                                 // [G + 1], zero on entry (low_quality only)
+};
+
+// steps 1 - 3 of assign_wrt_overlaps (max_iou_assigner.py:141-183)
+__device__ __forceinline__ int64_t base_assign(const AssignArgs& a, float mo, int arg) {
+    int64_t gi = -1;
+    if (mo >= a.neg_lo && mo < a.neg_hi) gi = 0;
+    if (mo >= a.pos) gi = (int64_t)arg + 1;
+    return gi;
+}
+
+__device__ __forceinline__ void store_result(const AssignArgs& a, int64_t idx, int64_t gi) {
+    a.gt_inds[idx] = gi;
+    if (a.labels) a.labels[idx] = gi > 0 ? a.gt_labels[gi - 1] : (int64_t)-1;
+}
+
+__global__ void __launch_bounds__(kThreads) assign_pass1_kernel(AssignArgs a) {
+    __shared__ Box s_box[kChunk];
+    __shared__ float s_area[kChunk];
+    __shared__ unsigned long long s_max[kChunk];
+    __shared__ unsigned s_low;                              // ~(lowest non-ignored candidate of the block), 0 = none
+    const int tid = threadIdx.x;
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + tid;
+    const bool live = idx < a.N;
+    if (a.G == 0) {                                         // no ground truth: everything is background (:146-162)
+        if (live) {
+            a.max_ov[idx] = 0.0f;
+            store_result(a, idx, 0);
+        }
+        return;
+    }
+    Box c = {0.0f, 0.0f, 0.0f, 0.0f};
+    float ca = 0.0f;
+    if (live) {
+        c = load_box(a.b + idx * a.ldb, a.vec_b != 0);
+        ca = box_area(c);
+    }
+    if (tid == 0) s_low = 0u;
+
+    // ---- ignored: max over the ignore boxes of iof > ignore_iof_thr (:108-118).  The threshold is > 0 here, so a pair that
+    // does not intersect (iof = +0) never decides.
+    bool ignored = false;
+    if (a.ig) {
+        for (int i0 = 0; i0 < a.I; i0 += kChunk) {
+            const int cn = min(kChunk, a.I - i0);
+            __syncthreads();
+            if (tid < cn) {
+                const Box q = load_box(a.ig + (int64_t)(i0 + tid) * a.ldi, false);
+                s_box[tid] = q;
+                s_area[tid] = box_area(q);
+            }
+            __syncthreads();
+            if (live) {
+                for (int j = 0; j < cn; ++j) {
+                    const float inter = box_inter(c, s_box[j]);
+                    if (inter > 0.0f) {
+                        const float fg = a.ign_wrt_cand ? ca : s_area[j];
+                        if (inter / fmaxf(fg, kAssignEps) > a.ign_thr) ignored = true;
+                    }
+                }
+            }
+        }
+    }
+
+    // ---- the candidate's maximum over the gts; the gts' maxima over the candidates
+    float best = ignored ? -1.0f : 0.0f;                    // an ignored candidate has overlap -1 with every gt
+    int arg = 0;
+    const bool lq = a.low_quality != 0;
+    for (int g0 = 0; g0 < a.G; g0 += kChunk) {
+        const int cn = min(kChunk, a.G - g0);
+        __syncthreads();
+        if (tid < cn) {
+            const Box q = load_box(a.g + (int64_t)(g0 + tid) * a.ldg, false);
+            s_box[tid] = q;
+            s_area[tid] = box_area(q);
+            s_max[tid] = 0ull;
+        }
+        __syncthreads();
+        if (live && !ignored) {
+            for (int j = 0; j < cn; ++j) {
+                float inter;
+                const float v = pair_iou(s_box[j], s_area[j], c, ca, inter);
+                if (inter > 0.0f) {
+                    if (v > best) { best = v; arg = g0 + j; }               // strict: ties stay with the lowest gt
+                    if (lq) {
+                        const unsigned long long p = pack_max(v, (unsigned)idx);
+                        if (p > __hip_atomic_load(&s_max[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+                            __hip_atomic_fetch_max(&s_max[j], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                }
+            }
+        }
+        if (lq) {
+            __syncthreads();
+            if (tid < cn) {
+                const unsigned long long p = s_max[tid];
+                unsigned long long* slot = a.ws + g0 + tid;
+                if (p != 0ull && p > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                    __hip_atomic_fetch_max(slot, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+
+    if (lq) {
+        // the lowest non-ignored candidate: it holds every gt's maximum of 0.0 where no candidate intersects the gt
+        const bool cand = live && !ignored;
+        const unsigned long long m = __ballot(cand);
+        if (cand && (threadIdx.x & 63) == (unsigned)__ffsll((long long)m) - 1u)
+            __hip_atomic_fetch_max(&s_low, ~(unsigned)idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __syncthreads();
+        if (tid == 0 && s_low != 0u) {
+            const unsigned long long p = (1ull << 32) | (unsigned long long)s_low;             // = pack_max(0.0f, lowest)
+            unsigned long long* slot = a.ws + a.G;
+            if (p > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                __hip_atomic_fetch_max(slot, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+
+    if (live) {
+        a.max_ov[idx] = best;
+        if (lq) a.gt_inds[idx] = arg;                       // parked for pass 2
+        else store_result(a, idx, base_assign(a, best, arg));
+    }
+}
+
+// Step 4 (:185-200) on top of steps 1 - 3.  max_ov / gt_inds hold pass 1's per-candidate maximum and argmax.
+__global__ void __launch_bounds__(kThreads) assign_pass2_kernel(AssignArgs a) {
+    __shared__ Box s_box[kChunk];
+    __shared__ float s_area[kChunk];
+    __shared__ float s_gmax[kChunk];                        // the gt's maximum, NaN if it is below min_pos_iou (matches nothing)
+    __shared__ int s_garg[kChunk];                          // the candidate that attains it, -1 likewise
+    const int tid = threadIdx.x;
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + tid;
+    const bool live = idx < a.N;
+    float mo = 0.0f, ca = 0.0f;
+    Box c = {0.0f, 0.0f, 0.0f, 0.0f};
+    int64_t gi = -1;
+    if (live) {
+        mo = a.max_ov[idx];
+        gi = base_assign(a, mo, (int)a.gt_inds[idx]);
+        if (a.assign_all) {
+            c = load_box(a.b + idx * a.ldb, a.vec_b != 0);
+            ca = box_area(c);
+        }
+    }
+    const bool ignored = mo == -1.0f;                       // overlaps are >= 0 otherwise
+    const unsigned long long zero_slot = a.ws[a.G];
+    for (int g0 = 0; g0 < a.G; g0 += kChunk) {
+        const int cn = min(kChunk, a.G - g0);
+        __syncthreads();
+        if (tid < cn) {
+            unsigned long long p = a.ws[g0 + tid];
+            p = p > zero_slot ? p : zero_slot;
+            // no non-ignored candidate at all: the reference's row is all -1, its max -1 at index 0
+            const float gm = p ? __uint_as_float((unsigned)(p >> 32) - 1u) : -1.0f;
+            const int ga = p ? (int)~(unsigned)p : 0;
+            const bool active = gm >= a.min_pos;
+            s_gmax[tid] = active ? gm : __uint_as_float(0x7fc00000u);
+            s_garg[tid] = active ? ga : -1;
+            if (a.assign_all) {
+                const Box q = load_box(a.g + (int64_t)(g0 + tid) * a.ldg, false);
+                s_box[tid] = q;
+                s_area[tid] = box_area(q);
+            }
+        }
+        __syncthreads();
+        if (!live) continue;
+        if (a.assign_all) {
+            for (int j = 0; j < cn; ++j) {
+                const float gm = s_gmax[j];
+                if (!(gm <= mo)) continue;                  // overlap(j, this) <= mo < gm, or gt j takes no part
+                bool hit = true;                            // ignored: mo = -1, so gm = -1 = this candidate's overlap with j
+                if (!ignored) {
+                    float inter;
+                    hit = pair_iou(s_box[j], s_area[j], c, ca, inter) == gm;
+                }
+                if (hit) gi = g0 + j + 1;                   // ascending: the highest gt wins, as in the reference's loop
+            }
+        } else {
+            for (int j = 0; j < cn; ++j)
+                if (s_garg[j] == (int)idx) gi = g0 + j + 1;
+        }
+    }
+    if (live) store_result(a, idx, gi);
+}
+
+struct OvArgs {
+    const float* b1; int64_t ld1; int64_t m; int vec1;
+    const float* b2; int64_t ld2; int64_t n; int vec2;
+    float eps;
+    float* out;
+};
+
+template <int MODE, bool ALIGNED>
+__global__ void __launch_bounds__(kThreads) bbox_overlaps_kernel(OvArgs a) {
+    const int64_t total = ALIGNED ? a.n : a.m * a.n;
+    const int64_t step = (int64_t)gridDim.x * kThreads;
+    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += step) {
+        const int64_t i = ALIGNED ? e : e / a.n;
+        const int64_t j = ALIGNED ? e : e - i * a.n;
+        const Box p = load_box(a.b1 + i * a.ld1, a.vec1 != 0);
+        const Box q = load_box(a.b2 + j * a.ld2, a.vec2 != 0);
+        const float a1 = box_area(p);
+        const float overlap = box_inter(p, q);
+        float uni = MODE == kIoF ? a1 : a1 + box_area(q) - overlap;
+        uni = fmaxf(uni, a.eps);
+        float v = overlap / uni;
+        if (MODE == kGIoU) {
+            const float ew = fmaxf(fmaxf(p.x2, q.x2) - fminf(p.x1, q.x1), 0.0f);
+            const float eh = fmaxf(fmaxf(p.y2, q.y2) - fminf(p.y1, q.y1), 0.0f);
+            const float enc = fmaxf(ew * eh, a.eps);
+            v = v - (enc - uni) / enc;
+        }
+        a.out[e] = v;
+    }
+}
+
+template <int MODE, bool ALIGNED>
+int launch_overlaps(const OvArgs& a, hipStream_t st) {
+    const int64_t total = ALIGNED ? a.n : a.m * a.n;
+    int64_t blocks = cdiv64(total, kThreads);
+    blocks = blocks > kOvMaxBlocks ? kOvMaxBlocks : blocks;
+    hipLaunchKernelGGL((bbox_overlaps_kernel<MODE, ALIGNED>), dim3((unsigned)blocks), dim3(kThreads), 0, st, a);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+bool f32_aligned(const void* p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
+bool rows_are_16_bytes(const void* p, int64_t ld) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % 4 == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int iif_bbox_overlaps(const float* bboxes1, int64_t ld1, int64_t m, const float* bboxes2, int64_t ld2, int64_t n, int mode,
+                      int aligned, float eps, float* out, void* stream) {
+    if (m < 0 || n < 0 || m > INT32_MAX || n > INT32_MAX || ld1 < 4 || ld2 < 4) return IIF_EINVAL;
+    if (mode != kIoU && mode != kIoF && mode != kGIoU) return IIF_EINVAL;
+    if (aligned && m != n) return IIF_EINVAL;
+    if (m == 0 || n == 0) return IIF_OK;
+    if (!bboxes1 || !bboxes2 || !out) return IIF_EINVAL;
+    if (!f32_aligned(bboxes1) || !f32_aligned(bboxes2) || !f32_aligned(out)) return IIF_EINVAL;
+    OvArgs a{};
+    a.b1 = bboxes1; a.ld1 = ld1; a.m = m; a.vec1 = rows_are_16_bytes(bboxes1, ld1);
+    a.b2 = bboxes2; a.ld2 = ld2; a.n = n; a.vec2 = rows_are_16_bytes(bboxes2, ld2);
+    a.eps = eps;
+    a.out = out;
+    hipStream_t st = as_stream(stream);
+    if (aligned) {
+        if (mode == kIoU) return launch_overlaps<kIoU, true>(a, st);
+        if (mode == kIoF) return launch_overlaps<kIoF, true>(a, st);
+        return launch_overlaps<kGIoU, true>(a, st);
+    }
+    if (mode == kIoU) return launch_overlaps<kIoU, false>(a, st);
+    if (mode == kIoF) return launch_overlaps<kIoF, false>(a, st);
+    return launch_overlaps<kGIoU, false>(a, st);
+}
+
+int iif_max_iou_assign(const float* bboxes, int64_t ld_bboxes, int64_t N, const float* gt_bboxes, int64_t ld_gt, int64_t G,
+                       const float* ignore_bboxes, int64_t ld_ignore, int64_t I, float pos_iou_thr, float neg_lo, float neg_hi,
+                       float min_pos_iou, float ignore_iof_thr, int gt_max_assign_all, int ignore_wrt_candidates,
+                       int match_low_quality, const int64_t* gt_labels, int64_t* gt_inds, float* max_overlaps, int64_t* labels,
+                       void* d_workspace, int64_t workspace_bytes, void* stream) {
+    if (N < 0 || G < 0 || I < 0 || N > INT32_MAX || G >= INT32_MAX || I > INT32_MAX) return IIF_EINVAL;
+    if (ld_bboxes < 4 || ld_gt < 4 || (ignore_bboxes && ld_ignore < 4)) return IIF_EINVAL;
+    if (!(neg_lo <= neg_hi) || pos_iou_thr != pos_iou_thr || min_pos_iou != min_pos_iou) return IIF_EINVAL;
+    if (!gt_inds || !max_overlaps) return IIF_EINVAL;
+    if (labels && !gt_labels && G > 0) return IIF_EINVAL;
+    if (N == 0) return IIF_OK;
+    if (!bboxes || (G > 0 && !gt_bboxes)) return IIF_EINVAL;
+    if (!f32_aligned(bboxes) || !f32_aligned(gt_bboxes) || !f32_aligned(ignore_bboxes) || !f32_aligned(max_overlaps)) return IIF_EINVAL;
+    if (reinterpret_cast<uintptr_t>(gt_inds) % 8 != 0 || reinterpret_cast<uintptr_t>(labels) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(gt_labels) % 8 != 0)
+        return IIF_EINVAL;
+    const bool two_pass = match_low_quality && G > 0;
+    if (two_pass) {
+        if (!d_workspace || reinterpret_cast<uintptr_t>(d_workspace) % 8 != 0) return IIF_EINVAL;
+        if (workspace_bytes < IIF_ASSIGN_WORKSPACE_BYTES(G)) return IIF_EINVAL;
+    }
+    AssignArgs a{};
+    a.b = bboxes; a.ldb = ld_bboxes; a.N = (int)N; a.vec_b = rows_are_16_bytes(bboxes, ld_bboxes);
+    a.g = gt_bboxes; a.ldg = ld_gt; a.G = (int)G;
+    // the reference looks at the ignore boxes only for a threshold > 0 and a non-empty set (:108-109)
+    const bool use_ignore = ignore_bboxes && I > 0 && ignore_iof_thr > 0.0f;
+    a.ig = use_ignore ? ignore_bboxes : nullptr; a.ldi = ld_ignore; a.I = use_ignore ? (int)I : 0;
+    a.pos = pos_iou_thr; a.neg_lo = neg_lo; a.neg_hi = neg_hi; a.min_pos = min_pos_iou; a.ign_thr = ignore_iof_thr;
+    a.assign_all = gt_max_assign_all != 0; a.ign_wrt_cand = ignore_wrt_candidates != 0; a.low_quality = two_pass;
+    a.gt_labels = gt_labels;
+    a.gt_inds = gt_inds; a.max_ov = max_overlaps; a.labels = labels;
+    a.ws = static_cast<unsigned long long*>(d_workspace);
+    hipStream_t st = as_stream(stream);
+    const unsigned blocks = (unsigned)cdiv64(N, kThreads);
+    if (two_pass) {
+        if (hipMemsetAsync(d_workspace, 0, (size_t)IIF_ASSIGN_WORKSPACE_BYTES(G), st) != hipSuccess) return IIF_ELAUNCH;
+    }
+    hipLaunchKernelGGL(assign_pass1_kernel, dim3(blocks), dim3(kThreads), 0, st, a);
+    IIF_LAUNCH_CHECK();
+    if (two_pass) {
+        hipLaunchKernelGGL(assign_pass2_kernel, dim3(blocks), dim3(kThreads), 0, st, a);
+        IIF_LAUNCH_CHECK();
+    }
+    return IIF_OK;
+}
+
+}  // extern "C"

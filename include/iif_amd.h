@@ -195,6 +195,44 @@ int iif_bbox_reg_fwd(const void* pred, int dtype, int64_t ld_pred, const int64_t
 int iif_bbox_reg_scatter_grad(const float* dsel, const int64_t* labels, int num_classes, int N, int C, const float* g,
                               void* dpred, int dtype, int64_t ld_dpred, void* stream);
 
+/* ---- Box overlaps and max-IoU assignment (csrc/assign.hip): mmdet/core/bbox/iou_calculators/iou2d_calculator.py:75-261 and
+ * mmdet/core/bbox/assigners/max_iou_assigner.py:61-213 without the [G, N] overlap matrix.
+ *
+ * Boxes are float32 rows <x1, y1, x2, y2> with a row pitch in ELEMENTS (>= 4: an [n, 5] array with a score column is read in
+ * place), element-aligned.  Each step is one IEEE float32 operation in the reference's order, the division correctly rounded:
+ *   area = (x2 - x1) * (y2 - y1);  w, h = max(min(rb) - max(lt), 0);  overlap = w * h
+ *   mode 0 'iou':  overlap / max(area1 + area2 - overlap, eps)      mode 1 'iof':  overlap / max(area1, eps)
+ *   mode 2 'giou': iou - (max(enclose, eps) - union) / max(enclose, eps)
+ * so the results are the reference's float32 numbers bit for bit (NaN coordinates excepted).
+ *
+ * iif_bbox_overlaps: out is float[m, n] contiguous (aligned == 0) or float[n] for the pairs (i, i) (aligned != 0: m == n).
+ * One launch; m == 0 or n == 0 is a no-op. */
+int iif_bbox_overlaps(const float* bboxes1, int64_t ld1, int64_t m, const float* bboxes2, int64_t ld2, int64_t n, int mode,
+                      int aligned, float eps, float* out, void* stream);
+
+/* MaxIoUAssigner.assign for N candidate boxes and G ground-truth boxes (eps = 1e-6, the calculator's default):
+ *   overlap(i, j) = iou(gt i, candidate j), or -1 for every i if candidate j is IGNORED: ignore_bboxes != NULL, I > 0,
+ *     ignore_iof_thr > 0 and max over the ignore boxes k of iof > ignore_iof_thr, where iof = iof(candidate j, ignore k) if
+ *     ignore_wrt_candidates else iof(ignore k, candidate j);
+ *   max_overlaps[j] = max_i overlap(i, j), argmax the LOWEST such i;  gt_max[i] = max_j overlap(i, j), gt_argmax[i] the
+ *     LOWEST such j;
+ *   gt_inds[j] = -1;  = 0 where neg_lo <= max_overlaps[j] < neg_hi (a single threshold t is (0, t));  = argmax + 1 where
+ *     max_overlaps[j] >= pos_iou_thr;  then, if match_low_quality, for i ascending with gt_max[i] >= min_pos_iou:
+ *     gt_inds[j] = i + 1 for every j with overlap(i, j) == gt_max[i] (gt_max_assign_all) or for j = gt_argmax[i] only;
+ *   labels[j] = gt_labels[gt_inds[j] - 1] where gt_inds[j] > 0, else -1  (labels NULL: not wanted; else gt_labels is required).
+ * All comparisons are float32.  G == 0: gt_inds 0, max_overlaps 0, labels -1.  N == 0: a no-op.
+ * d_workspace: IIF_ASSIGN_WORKSPACE_BYTES(G) of device memory on an 8-byte boundary, required when match_low_quality and G > 0;
+ * it belongs to this call until the stream has run it (contents on entry do not matter: the call clears it) - calls on
+ * different streams need different workspaces.  At most three operations are enqueued (the clear and two launches; one launch
+ * without match_low_quality), nothing is allocated, nothing synchronises; the [G, N] matrix is never stored.  Integer atomics
+ * only: the result does not depend on arrival order.  N, G, I < 2^31. */
+#define IIF_ASSIGN_WORKSPACE_BYTES(G) (8 * ((int64_t)(G) + 1))
+int iif_max_iou_assign(const float* bboxes, int64_t ld_bboxes, int64_t N, const float* gt_bboxes, int64_t ld_gt, int64_t G,
+                       const float* ignore_bboxes, int64_t ld_ignore, int64_t I, float pos_iou_thr, float neg_lo, float neg_hi,
+                       float min_pos_iou, float ignore_iof_thr, int gt_max_assign_all, int ignore_wrt_candidates,
+                       int match_low_quality, const int64_t* gt_labels, int64_t* gt_inds, float* max_overlaps, int64_t* labels,
+                       void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* out = logits * table. Replaces classification/custom.py:37-39 (infer=True). */
 int iif_scale_logits(const void* logits, int dtype, int64_t ld_logits, const float* table,
                      int B, int C, void* out, int64_t ld_out, void* stream);
