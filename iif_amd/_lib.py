@@ -131,6 +131,11 @@ SIGNATURES = {
     "iif_bbox_reg_scatter_grad": [_P, _P, _I, _I, _I, _P, _P, _I, _L, _P],
     "iif_bbox_overlaps": [_P, _L, _L, _P, _L, _L, _I, _I, _F, _P, _P],
     "iif_max_iou_assign": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _F, _F, _F, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
+    "iif_bbox2delta": [_P, _L, _P, _L, _L, _P, _P, _P, _P],
+    "iif_delta2bbox": [_P, _L, _P, _L, _L, _I, _P, _P, _F, _I, _F, _I, _F, _F, _P, _P],
+    "iif_random_sample": [_P, _P, _L, _L, _L, _c.c_double, _P, _P, _P, _P, _P, _L, _P],
+    "iif_anchor_targets": [_P, _L, _L, _P, _P, _L, _P, _L, _L, _P, _P, _L, _F, _I, _P, _P, _P, _P, _P, _P, _P],
+    "iif_roi_targets": [_P, _L, _L, _P, _P, _P, _L, _L, _P, _P, _P, _L, _L, _I, _L, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 
 

@@ -1,0 +1,621 @@
+// Box sampling, the delta coder and the two target builders for gfx950 (MI355X): what lies between mmdet's assigner and its
+// losses.
+//
+//   iif_bbox2delta / iif_delta2bbox   instance_segmentation/mmdet/core/bbox/coder/delta_xywh_bbox_coder.py:98-272, one launch
+//                        each (the reference: about twenty elementwise launches each).
+//   iif_random_sample    core/bbox/samplers/base_sampler.py:35-102 + random_sampler.py:32-82 + the index lists of
+//                        sampling_result.py, without nonzero / randperm / unique and without a host read.  The caller gives one
+//                        random int32 key >= 0 per candidate; a class (positive: gt_inds > 0, negative: == 0) that has more
+//                        members than its budget k keeps the k SMALLEST (key, index) pairs - equal keys go to the lower index.
+//     clear   the 2 x 4096 counters and the ticket.
+//     pass 1  (grid) histogram of the top 12 key bits per class: LDS atomics, flushed with integer global atomics.
+//     pass 2  (grid) every block scans the counters: class totals, hence both budgets (the negative budget follows from the
+//             positive total), each class's threshold bin T and the number r it must still take from that bin.  A candidate
+//             below T is selected outright, one in T is a BOUNDARY candidate; pass 2 leaves one word per candidate in the
+//             workspace (0 nothing, 1 / 2 selected, 3 + class << 19 | low 19 key bits: boundary) and the flags of all but the
+//             boundary candidates.  The last block to finish (a ticket) then works alone on those words: two more digit
+//             histograms (10 and 9 bits) give each class's threshold KEY and the number to take among the candidates that
+//             have exactly that key; one ordered sweep (block scans, tile by tile) takes them in index order and writes the
+//             index lists - ascending because the sweep is - and the boundary candidates' flags.  The boundary may be all N
+//             candidates (equal keys): nothing here depends on its length.
+//     Each of gt_inds and keys is read twice (pass 1, pass 2).  Integer atomics only: the result does not depend on arrival order.
+//   iif_anchor_targets   dense_heads/anchor_head.py:224-265 with unmap_outputs: defaults, scatter, encode, unmap; one lane per
+//                        anchor of the full set.
+//   iif_roi_targets      roi_heads/bbox_heads/bbox_head.py:122-186 on the padded lists of iif_random_sample, with the gathers of
+//                        sampling_result.py and bbox2roi: one lane per output row.
+//
+// Arithmetic of the coder: every step is the reference's single IEEE float32 operation in its order (the build passes
+// -ffp-contract=off; `/` is the correctly rounded division); logf / expf are the device library's.
+#include "common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kSelThreads = 1024;             // both sampler kernels; the last block's sweep is written for exactly this
+constexpr int kBins = 4096;                   // top 12 of the 31 key bits
+constexpr int kLowBits = 19;
+constexpr unsigned kLowMask = (1u << kLowBits) - 1u;
+constexpr int kSampleMaxBlocks = 64;
+constexpr int kTicketWord = 2 * kBins;        // workspace, in 32-bit words: [0, 8192) counters, [8192] ticket
+constexpr int kWordsOffset = 65536 / 4;       // the per-candidate words start 64 KiB in
+constexpr unsigned kMaxBlocks = 1u << 16;
+
+typedef unsigned long long u64;
+
+struct alignas(16) Box { float x1, y1, x2, y2; };
+struct Norm { float m[4], s[4]; };
+
+__device__ __forceinline__ Box load_box(const float* p, bool vec) {
+    if (vec) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+        return Box{t.x, t.y, t.z, t.w};
+    }
+    return Box{p[0], p[1], p[2], p[3]};
+}
+
+// bbox2delta (:119-139).  Shared by iif_bbox2delta and both target builders.
+__device__ __forceinline__ f32x4 encode_delta(const Box& p, const Box& g, const Norm& nm) {
+    const float px = (p.x1 + p.x2) * 0.5f, py = (p.y1 + p.y2) * 0.5f;
+    const float pw = p.x2 - p.x1, ph = p.y2 - p.y1;
+    const float gx = (g.x1 + g.x2) * 0.5f, gy = (g.y1 + g.y2) * 0.5f;
+    const float gw = g.x2 - g.x1, gh = g.y2 - g.y1;
+    const float dx = (gx - px) / pw;
+    const float dy = (gy - py) / ph;
+    const float dw = logf(gw / pw);
+    const float dh = logf(gh / ph);
+    f32x4 o;
+    o.x = (dx - nm.m[0]) / nm.s[0];
+    o.y = (dy - nm.m[1]) / nm.s[1];
+    o.z = (dw - nm.m[2]) / nm.s[2];
+    o.w = (dh - nm.m[3]) / nm.s[3];
+    return o;
+}
+
+struct EncArgs { const float* p; int64_t ldp; int vecp; const float* g; int64_t ldg; int vecg; int64_t n; Norm nm; float* out; };
+
+__global__ void __launch_bounds__(kThreads) bbox2delta_kernel(EncArgs a) {
+    const int64_t step = (int64_t)gridDim.x * kThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < a.n; i += step) {
+        const Box p = load_box(a.p + i * a.ldp, a.vecp != 0);
+        const Box g = load_box(a.g + i * a.ldg, a.vecg != 0);
+        *reinterpret_cast<f32x4*>(a.out + 4 * i) = encode_delta(p, g, a.nm);
+    }
+}
+
+struct DecArgs {
+    const float* r; int64_t ldr; int vecr; const float* d; int64_t ldd; int vecd; int64_t n; int K; Norm nm;
+    float max_ratio, ctr_clamp, max_h, max_w; int add_ctr_clamp, clip;
+    float* out;
+};
+
+// torch.where(x < 0, 0, x) then torch.where(x > hi, hi, x): a NaN fails both comparisons and passes through
+__device__ __forceinline__ float clip_coord(float x, float hi) {
+    x = x < 0.0f ? 0.0f : x;
+    return x > hi ? hi : x;
+}
+// torch.clamp: a NaN stays a NaN
+__device__ __forceinline__ float clamp_lo(float x, float lo) { return x < lo ? lo : x; }
+__device__ __forceinline__ float clamp_hi(float x, float hi) { return x > hi ? hi : x; }
+
+// delta2bbox (:206-270), one lane per (row, class)
+__global__ void __launch_bounds__(kThreads) delta2bbox_kernel(DecArgs a) {
+    const int64_t total = a.n * a.K;
+    const int64_t step = (int64_t)gridDim.x * kThreads;
+    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += step) {
+        const int64_t i = e / a.K;
+        const int k = (int)(e - i * a.K);
+        const Box p = load_box(a.r + i * a.ldr, a.vecr != 0);
+        const Box t = load_box(a.d + i * a.ldd + 4 * k, a.vecd != 0);
+        const float dx = t.x1 * a.nm.s[0] + a.nm.m[0];
+        const float dy = t.y1 * a.nm.s[1] + a.nm.m[1];
+        float dw = t.x2 * a.nm.s[2] + a.nm.m[2];
+        float dh = t.y2 * a.nm.s[3] + a.nm.m[3];
+        const float px = (p.x1 + p.x2) * 0.5f, py = (p.y1 + p.y2) * 0.5f;
+        const float pw = p.x2 - p.x1, ph = p.y2 - p.y1;
+        float dxw = pw * dx, dyh = ph * dy;
+        if (a.add_ctr_clamp) {
+            dxw = clamp_hi(clamp_lo(dxw, -a.ctr_clamp), a.ctr_clamp);
+            dyh = clamp_hi(clamp_lo(dyh, -a.ctr_clamp), a.ctr_clamp);
+            dw = clamp_hi(dw, a.max_ratio);
+            dh = clamp_hi(dh, a.max_ratio);
+        } else {
+            dw = clamp_hi(clamp_lo(dw, -a.max_ratio), a.max_ratio);
+            dh = clamp_hi(clamp_lo(dh, -a.max_ratio), a.max_ratio);
+        }
+        const float gw = pw * expf(dw), gh = ph * expf(dh);
+        const float gx = px + dxw, gy = py + dyh;
+        const float hw = gw * 0.5f, hh = gh * 0.5f;
+        f32x4 o;
+        o.x = gx - hw; o.y = gy - hh; o.z = gx + hw; o.w = gy + hh;
+        if (a.clip) {
+            o.x = clip_coord(o.x, a.max_w); o.y = clip_coord(o.y, a.max_h);
+            o.z = clip_coord(o.z, a.max_w); o.w = clip_coord(o.w, a.max_h);
+        }
+        *reinterpret_cast<f32x4*>(a.out + 4 * e) = o;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ sampler
+struct SampleArgs {
+    const int64_t* gt_inds; const int32_t* keys; int N;
+    int nep, num; double ub;
+    int64_t* pos_inds; int64_t* neg_inds; int64_t* counts; int8_t* flags;
+    unsigned* hist; unsigned* ticket; unsigned* w;
+};
+
+__global__ void __launch_bounds__(kSelThreads) sample_hist_kernel(SampleArgs a) {
+    __shared__ unsigned h[2 * kBins];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 2 * kBins; i += kSelThreads) h[i] = 0u;
+    __syncthreads();
+    const int64_t step = (int64_t)gridDim.x * kSelThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kSelThreads + tid; i < a.N; i += step) {
+        const int64_t gi = a.gt_inds[i];
+        if (gi >= 0) {
+            const unsigned key = (unsigned)a.keys[i] & 0x7fffffffu;
+            atomicAdd(&h[(gi > 0 ? 0 : kBins) + (int)(key >> kLowBits)], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < 2 * kBins; i += kSelThreads)
+        if (h[i] != 0u) atomicAdd(a.hist + i, h[i]);
+}
+
+// Exclusive prefix sums over the block's 1024 threads of two 32-bit counts packed in one word (neither half reaches 2^31);
+// `total` is the block's sum.  s_w: 17 words of LDS; reusable after the call returns.
+__device__ __forceinline__ u64 block_scan_excl(u64 v, u64* s_w, u64& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    u64 inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    if (wv == 0) {
+        const u64 x = lane < kSelThreads / 64 ? s_w[lane] : 0ull;
+        u64 xi = x;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const u64 t = __shfl_up(xi, o, 64);
+            if (lane >= o) xi += t;
+        }
+        if (lane < kSelThreads / 64) s_w[lane] = xi - x;
+        if (lane == 63) s_w[kSelThreads / 64] = xi;
+    }
+    __syncthreads();
+    const u64 res = s_w[wv] + inc - v;
+    total = s_w[kSelThreads / 64];
+    __syncthreads();
+    return res;
+}
+
+__device__ __forceinline__ unsigned half_of(u64 v, int c) { return c ? (unsigned)(v >> 32) : (unsigned)v; }
+
+// four consecutive words of the per-candidate array from 4 g on (0 past the end)
+__device__ __forceinline__ u32x4 load_words(const unsigned* w, int64_t g, int N) {
+    const int64_t i = 4 * g;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (i + 3 < N) return *reinterpret_cast<const u32x4*>(w + i);
+    if (i < N) v.x = w[i];
+    if (i + 1 < N) v.y = w[i + 1];
+    if (i + 2 < N) v.z = w[i + 2];
+    return v;
+}
+
+// the bin of `h` (this thread's count of bin threadIdx.x, per class) in which the r-th smallest of a class falls, r >= 1
+__device__ __forceinline__ void find_bin(u64 mine, u64 ex, const unsigned* r, int* s_bin, unsigned* s_rem) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const unsigned e = half_of(ex, c), h = half_of(mine, c);
+        if (r[c] > 0u && e < r[c] && r[c] <= e + h) {
+            s_bin[c] = threadIdx.x;
+            s_rem[c] = r[c] - e;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kSelThreads) sample_select_kernel(SampleArgs a) {
+    __shared__ u64 s_scan[kSelThreads / 64 + 1];
+    __shared__ unsigned s_h[2 * 1024];
+    __shared__ int s_T[2], s_T2[2], s_T3[2];
+    __shared__ unsigned s_r[2], s_r2[2], s_r3[2];
+    __shared__ bool s_last;
+    const int tid = threadIdx.x;
+
+    // ---- class totals, budgets, threshold bins: every block for itself (thread t owns bins 4 t .. 4 t + 3 of both classes)
+    const u32x4 h0 = reinterpret_cast<const u32x4*>(a.hist)[tid];
+    const u32x4 h1 = reinterpret_cast<const u32x4*>(a.hist + kBins)[tid];
+    const unsigned c0 = h0.x + h0.y + h0.z + h0.w, c1 = h1.x + h1.y + h1.z + h1.w;
+    u64 total;
+    const u64 ex = block_scan_excl((u64)c0 | ((u64)c1 << 32), s_scan, total);
+    const long long P = (unsigned)total, Q = (unsigned)(total >> 32);
+    const long long kp = P < a.nep ? P : a.nep;                       // base_sampler.py:83-89
+    long long budget = a.num - kp;                                    // :90-95
+    if (a.ub >= 0.0) {
+        const double capd = a.ub * (double)(kp > 1 ? kp : 1);
+        if (capd < (double)budget) budget = (long long)capd;          // int(): truncation
+    }
+    const long long kn = Q < budget ? Q : budget;
+    const long long k[2] = {kp, kn}, M[2] = {P, Q};
+    if (tid < 2) {
+        s_T[tid] = k[tid] <= 0 ? -1 : kBins;                           // nothing / everything of the class, unless found below
+        s_r[tid] = 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        if (k[c] > 0 && k[c] < M[c]) {
+            const u32x4 hh = c ? h1 : h0;
+            const unsigned hv[4] = {hh.x, hh.y, hh.z, hh.w};
+            long long cum = half_of(ex, c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (cum < k[c] && k[c] <= cum + hv[j]) {
+                    s_T[c] = 4 * tid + j;
+                    s_r[c] = (unsigned)(k[c] - cum);
+                }
+                cum += hv[j];
+            }
+        }
+    }
+    __syncthreads();
+    const int T[2] = {s_T[0], s_T[1]};
+    const unsigned r[2] = {s_r[0], s_r[1]};
+
+    // ---- the grid-wide pass: one word per candidate, the flags of all but the boundary candidates
+    const int64_t step = (int64_t)gridDim.x * kSelThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kSelThreads + tid; i < a.N; i += step) {
+        const int64_t gi = a.gt_inds[i];
+        unsigned ww = 0u;
+        bool boundary = false;
+        if (gi >= 0) {
+            const int cls = gi > 0 ? 0 : 1;
+            const unsigned key = (unsigned)a.keys[i] & 0x7fffffffu;
+            const int bin = (int)(key >> kLowBits);
+            if (bin < T[cls]) ww = 1u + cls;
+            else if (bin == T[cls]) { ww = 3u + (((unsigned)cls << kLowBits) | (key & kLowMask)); boundary = true; }
+        }
+        a.w[i] = ww;
+        if (!boundary) a.flags[i] = (int8_t)ww;
+    }
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = t == gridDim.x - 1u;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+
+    // ---- the last block, alone: the threshold key of each class among its boundary candidates, low 19 bits in two digits
+    const int64_t groups = ((int64_t)a.N + 3) / 4;
+    if (tid < 2) { s_T2[tid] = 0; s_T3[tid] = 0; s_r2[tid] = 0u; s_r3[tid] = 0u; }
+    s_h[tid] = 0u;
+    s_h[1024 + tid] = 0u;
+    __syncthreads();
+    if (r[0] > 0u || r[1] > 0u) {
+        for (int64_t g = tid; g < groups; g += kSelThreads) {
+            const u32x4 v = load_words(a.w, g, a.N);
+            const unsigned e4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (e4[j] >= 3u) {
+                    const unsigned e = e4[j] - 3u;
+                    atomicAdd(&s_h[(e >> kLowBits) * 1024u + ((e & kLowMask) >> 9)], 1u);
+                }
+        }
+        __syncthreads();
+        const u64 mine = (u64)s_h[tid] | ((u64)s_h[1024 + tid] << 32);
+        u64 tot;
+        const u64 ex2 = block_scan_excl(mine, s_scan, tot);
+        find_bin(mine, ex2, r, s_T2, s_r2);
+        __syncthreads();
+        const int T2[2] = {s_T2[0], s_T2[1]};
+        const unsigned r2[2] = {s_r2[0], s_r2[1]};
+        s_h[tid] = 0u;
+        __syncthreads();
+        for (int64_t g = tid; g < groups; g += kSelThreads) {
+            const u32x4 v = load_words(a.w, g, a.N);
+            const unsigned e4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (e4[j] >= 3u) {
+                    const unsigned e = e4[j] - 3u;
+                    const unsigned cls = e >> kLowBits, low = e & kLowMask;
+                    if ((int)(low >> 9) == T2[cls]) atomicAdd(&s_h[cls * 512u + (low & 511u)], 1u);
+                }
+        }
+        __syncthreads();
+        const u64 mine3 = tid < 512 ? ((u64)s_h[tid] | ((u64)s_h[512 + tid] << 32)) : 0ull;
+        const u64 ex3 = block_scan_excl(mine3, s_scan, tot);
+        find_bin(mine3, ex3, r2, s_T3, s_r3);
+        __syncthreads();
+    }
+    unsigned K[2], r3[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        K[c] = ((unsigned)s_T2[c] << 9) | (unsigned)s_T3[c];
+        r3[c] = s_r3[c];
+    }
+
+    // ---- the ordered sweep: tile by tile in index order; among the candidates with exactly the threshold key the first r3
+    u64 run_eq = 0ull, run_sel = 0ull;
+    const int64_t tiles = (groups + kSelThreads - 1) / kSelThreads;
+    for (int64_t t = 0; t < tiles; ++t) {
+        const int64_t g = t * kSelThreads + tid;
+        const u32x4 v = load_words(a.w, g, a.N);
+        const unsigned e4[4] = {v.x, v.y, v.z, v.w};
+        int cls4[4], kind4[4];                                         // kind: 0 not selected, 1 selected, 2 has the threshold key
+        u64 eq = 0ull;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            cls4[j] = 0; kind4[j] = 0;
+            if (e4[j] == 1u || e4[j] == 2u) { cls4[j] = (int)e4[j] - 1; kind4[j] = 1; }
+            else if (e4[j] >= 3u) {
+                const unsigned e = e4[j] - 3u;
+                const unsigned low = e & kLowMask;
+                cls4[j] = (int)(e >> kLowBits);
+                if (low < K[cls4[j]]) kind4[j] = 1;
+                else if (low == K[cls4[j]]) { kind4[j] = 2; eq += cls4[j] ? (1ull << 32) : 1ull; }
+            }
+        }
+        u64 tot;
+        u64 rank = block_scan_excl(eq, s_scan, tot) + run_eq;
+        run_eq += tot;
+        u64 sel = 0ull;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (kind4[j] == 2) {
+                kind4[j] = half_of(rank, cls4[j]) < r3[cls4[j]] ? 1 : 0;
+                rank += cls4[j] ? (1ull << 32) : 1ull;
+            }
+            if (kind4[j] == 1) sel += cls4[j] ? (1ull << 32) : 1ull;
+        }
+        u64 at = block_scan_excl(sel, s_scan, tot) + run_sel;
+        run_sel += tot;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t idx = 4 * g + j;
+            if (e4[j] >= 3u) a.flags[idx] = (int8_t)(kind4[j] == 1 ? 1 + cls4[j] : 0);
+            if (kind4[j] == 1) {
+                const unsigned slot = half_of(at, cls4[j]);
+                if (cls4[j] == 0) { if ((long long)slot < a.nep) a.pos_inds[slot] = idx; }
+                else if ((long long)slot < a.num) a.neg_inds[slot] = idx;
+                at += cls4[j] ? (1ull << 32) : 1ull;
+            }
+        }
+    }
+    for (long long j = kp + tid; j < a.nep; j += kSelThreads) a.pos_inds[j] = -1;
+    for (long long j = kn + tid; j < a.num; j += kSelThreads) a.neg_inds[j] = -1;
+    if (tid == 0) {
+        a.counts[0] = kp;
+        a.counts[1] = kn;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ target builders
+struct AnchorArgs {
+    const float* anchors; int64_t lda; int veca; int64_t A;
+    const int8_t* flags; const int64_t* gt_inds; int64_t M;
+    const float* gt; int64_t ldg; int64_t G; const int64_t* gt_labels; const int64_t* compact;
+    int64_t background; float pos_weight; int decoded; Norm nm;
+    int64_t* labels; float* label_weights; float* bbox_targets; float* bbox_weights;
+};
+
+__global__ void __launch_bounds__(kThreads) anchor_targets_kernel(AnchorArgs a) {
+    const int64_t step = (int64_t)gridDim.x * kThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < a.A; i += step) {
+        int64_t label = a.background;
+        float lw = 0.0f;
+        f32x4 bt = {0.0f, 0.0f, 0.0f, 0.0f}, bw = {0.0f, 0.0f, 0.0f, 0.0f};
+        const int64_t row = a.compact ? a.compact[i] : i;
+        if (row >= 0 && row < a.M) {
+            const int f = a.flags[row];
+            if (f == 1) {
+                const int64_t gi = a.gt_inds[row] - 1;
+                if (gi >= 0 && gi < a.G) {
+                    const Box g = load_box(a.gt + gi * a.ldg, false);
+                    if (a.decoded) { bt.x = g.x1; bt.y = g.y1; bt.z = g.x2; bt.w = g.y2; }
+                    else bt = encode_delta(load_box(a.anchors + i * a.lda, a.veca != 0), g, a.nm);
+                    bw.x = bw.y = bw.z = bw.w = 1.0f;
+                    label = a.gt_labels ? a.gt_labels[gi] : 0;
+                    lw = a.pos_weight <= 0.0f ? 1.0f : a.pos_weight;
+                }
+            } else if (f == 2) {
+                lw = 1.0f;
+            }
+        }
+        a.labels[i] = label;
+        a.label_weights[i] = lw;
+        *reinterpret_cast<f32x4*>(a.bbox_targets + 4 * i) = bt;
+        *reinterpret_cast<f32x4*>(a.bbox_weights + 4 * i) = bw;
+    }
+}
+
+struct RoiArgs {
+    const float* b; int64_t ldb; int vecb; int64_t N;
+    const int64_t* gt_inds; const int64_t* labels_in; const float* gt; int64_t ldg; int64_t G;
+    const int64_t* pos_inds; const int64_t* neg_inds; const int64_t* counts; int64_t cap, cap_pos;
+    float img; int64_t num_classes; float pos_weight; int decoded; Norm nm;
+    float* rois; int64_t* labels; float* label_weights; float* bbox_targets; float* bbox_weights; int64_t* pos_gt;
+};
+
+__global__ void __launch_bounds__(kThreads) roi_targets_kernel(RoiArgs a) {
+    const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= a.cap) return;
+    int64_t np = a.counts[0], nn = a.counts[1];
+    np = np < 0 ? 0 : (np > a.cap_pos ? a.cap_pos : np);
+    nn = nn < 0 ? 0 : (nn > a.cap ? a.cap : nn);
+    int64_t label = a.num_classes, pg = -1;
+    float lw = 0.0f;
+    Box box = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 bt = {0.0f, 0.0f, 0.0f, 0.0f}, bw = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (r < np + nn) {
+        const bool pos = r < np;
+        const int64_t idx = pos ? a.pos_inds[r] : a.neg_inds[r - np];
+        if (idx >= 0 && idx < a.N) {
+            box = load_box(a.b + idx * a.ldb, a.vecb != 0);
+            lw = 1.0f;
+            if (pos) {
+                const int64_t gi = a.gt_inds[idx] - 1;
+                if (gi >= 0 && gi < a.G) {
+                    const Box g = load_box(a.gt + gi * a.ldg, false);
+                    if (a.decoded) { bt.x = g.x1; bt.y = g.y1; bt.z = g.x2; bt.w = g.y2; }
+                    else bt = encode_delta(box, g, a.nm);
+                    bw.x = bw.y = bw.z = bw.w = 1.0f;
+                    label = a.labels_in ? a.labels_in[idx] : 0;
+                    lw = a.pos_weight <= 0.0f ? 1.0f : a.pos_weight;
+                    pg = gi;
+                }
+            }
+        }
+    }
+    float* ro = a.rois + 5 * r;
+    ro[0] = a.img; ro[1] = box.x1; ro[2] = box.y1; ro[3] = box.x2; ro[4] = box.y2;
+    a.labels[r] = label;
+    a.label_weights[r] = lw;
+    *reinterpret_cast<f32x4*>(a.bbox_targets + 4 * r) = bt;
+    *reinterpret_cast<f32x4*>(a.bbox_weights + 4 * r) = bw;
+    a.pos_gt[r] = pg;
+}
+
+bool aligned_to(const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
+bool rows_are_16_bytes(const void* p, int64_t ld) { return aligned_to(p, 16) && ld % 4 == 0; }
+
+bool set_norm(Norm* nm, const float* means, const float* stds) {
+    if (!means || !stds) return false;
+    for (int i = 0; i < 4; ++i) { nm->m[i] = means[i]; nm->s[i] = stds[i]; }
+    return true;
+}
+
+unsigned grid_for(int64_t n) {
+    const int64_t b = cdiv64(n, kThreads);
+    return (unsigned)(b > kMaxBlocks ? kMaxBlocks : b);
+}
+
+}  // namespace
+
+extern "C" {
+
+int iif_bbox2delta(const float* proposals, int64_t ld_proposals, const float* gt, int64_t ld_gt, int64_t n, const float* means,
+                   const float* stds, float* out, void* stream) {
+    EncArgs a{};
+    if (n < 0 || n > INT32_MAX || ld_proposals < 4 || ld_gt < 4 || !set_norm(&a.nm, means, stds)) return IIF_EINVAL;
+    if (n == 0) return IIF_OK;
+    if (!proposals || !gt || !out || !aligned_to(proposals, 4) || !aligned_to(gt, 4) || !aligned_to(out, 16)) return IIF_EINVAL;
+    a.p = proposals; a.ldp = ld_proposals; a.vecp = rows_are_16_bytes(proposals, ld_proposals);
+    a.g = gt; a.ldg = ld_gt; a.vecg = rows_are_16_bytes(gt, ld_gt);
+    a.n = n; a.out = out;
+    hipLaunchKernelGGL(bbox2delta_kernel, dim3(grid_for(n)), dim3(kThreads), 0, as_stream(stream), a);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+int iif_delta2bbox(const float* rois, int64_t ld_rois, const float* deltas, int64_t ld_deltas, int64_t n, int num_classes,
+                   const float* means, const float* stds, float max_ratio, int add_ctr_clamp, float ctr_clamp, int clip,
+                   float max_h, float max_w, float* out, void* stream) {
+    DecArgs a{};
+    if (n < 0 || n > INT32_MAX || num_classes < 1 || ld_rois < 4 || ld_deltas < 4 * (int64_t)num_classes) return IIF_EINVAL;
+    if (!set_norm(&a.nm, means, stds)) return IIF_EINVAL;
+    if (n == 0) return IIF_OK;
+    if (!rois || !deltas || !out || !aligned_to(rois, 4) || !aligned_to(deltas, 4) || !aligned_to(out, 16)) return IIF_EINVAL;
+    a.r = rois; a.ldr = ld_rois; a.vecr = rows_are_16_bytes(rois, ld_rois);
+    a.d = deltas; a.ldd = ld_deltas; a.vecd = rows_are_16_bytes(deltas, ld_deltas);
+    a.n = n; a.K = num_classes;
+    a.max_ratio = max_ratio; a.ctr_clamp = ctr_clamp; a.max_h = max_h; a.max_w = max_w;
+    a.add_ctr_clamp = add_ctr_clamp != 0; a.clip = clip != 0;
+    a.out = out;
+    hipLaunchKernelGGL(delta2bbox_kernel, dim3(grid_for(n * num_classes)), dim3(kThreads), 0, as_stream(stream), a);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+int iif_random_sample(const int64_t* gt_inds, const int32_t* keys, int64_t N, int64_t num_expected_pos, int64_t num,
+                      double neg_pos_ub, int64_t* pos_inds, int64_t* neg_inds, int64_t* counts, int8_t* flags, void* d_workspace,
+                      int64_t workspace_bytes, void* stream) {
+    if (N < 0 || N >= INT32_MAX - 4 || num < 0 || num > INT32_MAX || num_expected_pos < 0 || num_expected_pos > num) return IIF_EINVAL;
+    if (neg_pos_ub != neg_pos_ub || !counts || (num_expected_pos > 0 && !pos_inds) || (num > 0 && !neg_inds)) return IIF_EINVAL;
+    if (N > 0 && (!gt_inds || !keys || !flags)) return IIF_EINVAL;
+    if (!aligned_to(gt_inds, 8) || !aligned_to(keys, 4) || !aligned_to(pos_inds, 8) || !aligned_to(neg_inds, 8) || !aligned_to(counts, 8))
+        return IIF_EINVAL;
+    if (!d_workspace || !aligned_to(d_workspace, 16) || workspace_bytes < IIF_SAMPLE_WORKSPACE_BYTES(N)) return IIF_EINVAL;
+    SampleArgs a{};
+    a.gt_inds = gt_inds; a.keys = keys; a.N = (int)N;
+    a.nep = (int)num_expected_pos; a.num = (int)num; a.ub = neg_pos_ub;
+    a.pos_inds = pos_inds; a.neg_inds = neg_inds; a.counts = counts; a.flags = flags;
+    a.hist = static_cast<unsigned*>(d_workspace);
+    a.ticket = a.hist + kTicketWord;
+    a.w = a.hist + kWordsOffset;
+    hipStream_t st = as_stream(stream);
+    if (hipMemsetAsync(d_workspace, 0, (size_t)(kTicketWord + 4) * 4, st) != hipSuccess) return IIF_ELAUNCH;
+    int64_t blocks = cdiv64(N, kSelThreads);
+    blocks = blocks < 1 ? 1 : (blocks > kSampleMaxBlocks ? kSampleMaxBlocks : blocks);
+    if (N > 0) {
+        hipLaunchKernelGGL(sample_hist_kernel, dim3((unsigned)blocks), dim3(kSelThreads), 0, st, a);
+        IIF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(sample_select_kernel, dim3((unsigned)blocks), dim3(kSelThreads), 0, st, a);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+int iif_anchor_targets(const float* anchors, int64_t ld_anchors, int64_t A, const int8_t* flags, const int64_t* gt_inds,
+                       int64_t rows, const float* gt_bboxes, int64_t ld_gt, int64_t G, const int64_t* gt_labels,
+                       const int64_t* compact_index, int64_t background_label, float pos_weight, int reg_decoded_bbox,
+                       const float* means, const float* stds, int64_t* labels, float* label_weights, float* bbox_targets,
+                       float* bbox_weights, void* stream) {
+    AnchorArgs a{};
+    if (A < 0 || A > INT32_MAX || rows < 0 || G < 0 || ld_anchors < 4 || ld_gt < 4 || !set_norm(&a.nm, means, stds)) return IIF_EINVAL;
+    if (!compact_index && rows != A) return IIF_EINVAL;
+    if (A == 0) return IIF_OK;
+    if (!anchors || !labels || !label_weights || !bbox_targets || !bbox_weights) return IIF_EINVAL;
+    if (rows > 0 && (!flags || !gt_inds)) return IIF_EINVAL;
+    if (G > 0 && !gt_bboxes) return IIF_EINVAL;
+    if (!aligned_to(anchors, 4) || !aligned_to(gt_bboxes, 4) || !aligned_to(gt_inds, 8) || !aligned_to(gt_labels, 8) ||
+        !aligned_to(compact_index, 8) || !aligned_to(labels, 8) || !aligned_to(label_weights, 4) || !aligned_to(bbox_targets, 16) ||
+        !aligned_to(bbox_weights, 16))
+        return IIF_EINVAL;
+    a.anchors = anchors; a.lda = ld_anchors; a.veca = rows_are_16_bytes(anchors, ld_anchors); a.A = A;
+    a.flags = flags; a.gt_inds = gt_inds; a.M = rows;
+    a.gt = gt_bboxes; a.ldg = ld_gt; a.G = G; a.gt_labels = gt_labels; a.compact = compact_index;
+    a.background = background_label; a.pos_weight = pos_weight; a.decoded = reg_decoded_bbox != 0;
+    a.labels = labels; a.label_weights = label_weights; a.bbox_targets = bbox_targets; a.bbox_weights = bbox_weights;
+    hipLaunchKernelGGL(anchor_targets_kernel, dim3(grid_for(A)), dim3(kThreads), 0, as_stream(stream), a);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+int iif_roi_targets(const float* bboxes, int64_t ld_bboxes, int64_t N, const int64_t* gt_inds, const int64_t* labels_in,
+                    const float* gt_bboxes, int64_t ld_gt, int64_t G, const int64_t* pos_inds, const int64_t* neg_inds,
+                    const int64_t* counts, int64_t cap, int64_t cap_pos, int img_index, int64_t num_classes, float pos_weight,
+                    int reg_decoded_bbox, const float* means, const float* stds, float* rois, int64_t* labels,
+                    float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* pos_assigned_gt_inds, void* stream) {
+    RoiArgs a{};
+    if (N < 0 || G < 0 || cap < 0 || cap > INT32_MAX || cap_pos < 0 || cap_pos > cap || ld_bboxes < 4 || ld_gt < 4) return IIF_EINVAL;
+    if (!set_norm(&a.nm, means, stds)) return IIF_EINVAL;
+    if (cap == 0) return IIF_OK;
+    if (!counts || !neg_inds || (cap_pos > 0 && !pos_inds) || !rois || !labels || !label_weights || !bbox_targets || !bbox_weights ||
+        !pos_assigned_gt_inds)
+        return IIF_EINVAL;
+    if (N > 0 && (!bboxes || !gt_inds)) return IIF_EINVAL;
+    if (G > 0 && !gt_bboxes) return IIF_EINVAL;
+    if (!aligned_to(bboxes, 4) || !aligned_to(gt_bboxes, 4) || !aligned_to(gt_inds, 8) || !aligned_to(labels_in, 8) ||
+        !aligned_to(pos_inds, 8) || !aligned_to(neg_inds, 8) || !aligned_to(counts, 8) || !aligned_to(rois, 4) || !aligned_to(labels, 8) ||
+        !aligned_to(label_weights, 4) || !aligned_to(bbox_targets, 16) || !aligned_to(bbox_weights, 16) ||
+        !aligned_to(pos_assigned_gt_inds, 8))
+        return IIF_EINVAL;
+    a.b = bboxes; a.ldb = ld_bboxes; a.vecb = rows_are_16_bytes(bboxes, ld_bboxes); a.N = N;
+    a.gt_inds = gt_inds; a.labels_in = labels_in; a.gt = gt_bboxes; a.ldg = ld_gt; a.G = G;
+    a.pos_inds = pos_inds; a.neg_inds = neg_inds; a.counts = counts; a.cap = cap; a.cap_pos = cap_pos;
+    a.img = (float)img_index; a.num_classes = num_classes; a.pos_weight = pos_weight; a.decoded = reg_decoded_bbox != 0;
+    a.rois = rois; a.labels = labels; a.label_weights = label_weights; a.bbox_targets = bbox_targets; a.bbox_weights = bbox_weights;
+    a.pos_gt = pos_assigned_gt_inds;
+    hipLaunchKernelGGL(roi_targets_kernel, dim3((unsigned)cdiv64(cap, kThreads)), dim3(kThreads), 0, as_stream(stream), a);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+}  // extern "C"

@@ -233,6 +233,74 @@ int iif_max_iou_assign(const float* bboxes, int64_t ld_bboxes, int64_t N, const 
                        int match_low_quality, const int64_t* gt_labels, int64_t* gt_inds, float* max_overlaps, int64_t* labels,
                        void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Box sampling, the delta coder and the target builders (csrc/targets.hip): what lies between the assigner above and the
+ * losses - mmdet/core/bbox/coder/delta_xywh_bbox_coder.py:98-272, core/bbox/samplers/base_sampler.py:35-102 with
+ * random_sampler.py:32-82 and sampling_result.py, dense_heads/anchor_head.py:224-265, roi_heads/bbox_heads/bbox_head.py:122-186.
+ * Every entry enqueues on `stream`, allocates nothing, reads nothing back to the host.  Boxes are float32 rows with a pitch in
+ * ELEMENTS (>= 4), element-aligned, as in iif_bbox_overlaps.  means / stds: HOST pointers to four floats each, read during the
+ * call.  Dense float outputs ([.., 4] targets, weights, decoded boxes) are contiguous and 16-byte aligned.
+ *
+ * iif_bbox2delta: out [n, 4] = ((dx, dy, dw, dh) - means) / stds with px = (x1 + x2) * 0.5, pw = x2 - x1 (likewise g),
+ *   dx = (gx - px) / pw, dw = logf(gw / pw): each step one IEEE float32 operation in the reference's order, so dx, dy are
+ *   the reference's bit for bit and dw, dh up to the logarithm's rounding; zero-width boxes give the reference's infinities and
+ *   NaNs.  One launch, one lane per row; n == 0 is a no-op. */
+int iif_bbox2delta(const float* proposals, int64_t ld_proposals, const float* gt, int64_t ld_gt, int64_t n, const float* means,
+                   const float* stds, float* out, void* stream);
+
+/* iif_delta2bbox: rois [n, >= 4], deltas [n, 4 num_classes] (pitch ld_deltas), out [n, 4 num_classes]; one lane per (row, class):
+ *   d = delta * std + mean (two operations);  dxw = pw * dx;  add_ctr_clamp: dxw, dyh clamped to [-ctr_clamp, ctr_clamp] and
+ *   dw, dh to (.., max_ratio], otherwise dw, dh to [-max_ratio, max_ratio];  gw = pw * expf(dw);  gx = px + dxw;
+ *   x1 = gx - gw * 0.5, x2 = gx + gw * 0.5;  clip != 0: x < 0 ? 0 : x, then x > max ? max : x against max_w (x) and max_h (y).
+ *   A NaN passes through the clamps and the clip as in torch.  max_ratio: float(abs(log(wh_ratio_clip))), computed in double
+ *   by the caller.  clip == 0 is the reference's clip_border=False or max_shape=None.  No batch dimensions. */
+int iif_delta2bbox(const float* rois, int64_t ld_rois, const float* deltas, int64_t ld_deltas, int64_t n, int num_classes,
+                   const float* means, const float* stds, float max_ratio, int add_ctr_clamp, float ctr_clamp, int clip,
+                   float max_h, float max_w, float* out, void* stream);
+
+/* RandomSampler.sample on the assigner's gt_inds [N] (> 0 positive, 0 negative, < 0 ignored) with one random key per
+ * candidate, keys [N] int32 >= 0 (the sign bit is not read):
+ *   positives: all if at most num_expected_pos, else the num_expected_pos SMALLEST (key, index) pairs - equal keys go to the
+ *     lower index;  negatives: budget num - (positives kept), capped at int(neg_pos_ub * max(1, kept)) when neg_pos_ub >= 0
+ *     (a double, multiplied and truncated as Python does); the same rule.
+ *   pos_inds [num_expected_pos], neg_inds [num]: the kept indices ascending (the reference's unique() sorts), unused tails -1;
+ *   counts [2]: positives, negatives kept;  flags [N] int8: 0 not sampled, 1 positive, 2 negative.
+ * With keys[gallery[j]] = inverse_permutation[j] per class this selects exactly the reference's gallery[randperm[:k]].
+ * Three enqueued operations (a clear of 32 KiB + 16 bytes and two launches), no host read; gt_inds and keys are each read twice;
+ * integer atomics only, so the result does not depend on arrival order and is correct for any keys, all equal included.
+ * d_workspace: IIF_SAMPLE_WORKSPACE_BYTES(N) on a 16-byte boundary; it belongs to the call until the stream has run it
+ * (contents on entry do not matter).  N < 2^31 - 4, 0 <= num_expected_pos <= num.  N == 0: the tails and zero counts are written. */
+#define IIF_SAMPLE_WORKSPACE_BYTES(N) (4 * (int64_t)(N) + 65536)
+int iif_random_sample(const int64_t* gt_inds, const int32_t* keys, int64_t N, int64_t num_expected_pos, int64_t num,
+                      double neg_pos_ub, int64_t* pos_inds, int64_t* neg_inds, int64_t* counts, int8_t* flags, void* d_workspace,
+                      int64_t workspace_bytes, void* stream);
+
+/* AnchorHead._get_targets_single after assign and sample, with unmap_outputs=True, in one launch over the FULL anchor set [A]:
+ *   row = compact_index ? compact_index[a] : a  (compact_index: -1 for an anchor that took no part - outside the image - else its
+ *   row in flags / gt_inds [rows]; NULL: identity, rows == A);
+ *   flags[row] == 1: labels = gt_labels ? gt_labels[gt_inds[row] - 1] : 0, label_weights = pos_weight <= 0 ? 1 : pos_weight,
+ *     bbox_targets = reg_decoded_bbox ? gt box : bbox2delta(anchor, gt box) (iif_bbox2delta's arithmetic), bbox_weights = 1;
+ *   flags[row] == 2: label_weights = 1;  otherwise and elsewhere: labels = background_label, zeros.
+ * Rows and gt indices out of range are treated as "took no part". */
+int iif_anchor_targets(const float* anchors, int64_t ld_anchors, int64_t A, const int8_t* flags, const int64_t* gt_inds,
+                       int64_t rows, const float* gt_bboxes, int64_t ld_gt, int64_t G, const int64_t* gt_labels,
+                       const int64_t* compact_index, int64_t background_label, float pos_weight, int reg_decoded_bbox,
+                       const float* means, const float* stds, int64_t* labels, float* label_weights, float* bbox_targets,
+                       float* bbox_weights, void* stream);
+
+/* BBoxHead._get_target_single on the padded lists of iif_random_sample (pos_inds [cap_pos], neg_inds [cap], counts [2]), with
+ * SamplingResult's gathers and bbox2roi; one lane per output row r < cap:
+ *   r < counts[0]: candidate pos_inds[r], a positive: labels = labels_in[candidate] (the assigner's per-candidate labels; NULL: 0),
+ *     label_weights = pos_weight <= 0 ? 1 : pos_weight, bbox_targets as in iif_anchor_targets, bbox_weights = 1,
+ *     pos_assigned_gt_inds = gt_inds[candidate] - 1;
+ *   r < counts[0] + counts[1]: candidate neg_inds[r - counts[0]]: labels = num_classes, label_weights = 1, zeros, -1;
+ *   beyond: padding - a zero box, labels = num_classes, all weights 0, -1: it adds nothing to a loss.
+ *   rois [cap, 5] = (img_index, the candidate's box). */
+int iif_roi_targets(const float* bboxes, int64_t ld_bboxes, int64_t N, const int64_t* gt_inds, const int64_t* labels_in,
+                    const float* gt_bboxes, int64_t ld_gt, int64_t G, const int64_t* pos_inds, const int64_t* neg_inds,
+                    const int64_t* counts, int64_t cap, int64_t cap_pos, int img_index, int64_t num_classes, float pos_weight,
+                    int reg_decoded_bbox, const float* means, const float* stds, float* rois, int64_t* labels,
+                    float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* pos_assigned_gt_inds, void* stream);
+
 /* out = logits * table. Replaces classification/custom.py:37-39 (infer=True). */
 int iif_scale_logits(const void* logits, int dtype, int64_t ld_logits, const float* table,
                      int B, int C, void* out, int64_t ld_out, void* stream);
