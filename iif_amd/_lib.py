@@ -136,6 +136,8 @@ SIGNATURES = {
     "iif_random_sample": [_P, _P, _L, _L, _L, _c.c_double, _P, _P, _P, _P, _P, _L, _P],
     "iif_anchor_targets": [_P, _L, _L, _P, _P, _L, _P, _L, _L, _P, _P, _L, _F, _I, _P, _P, _P, _P, _P, _P, _P],
     "iif_roi_targets": [_P, _L, _L, _P, _P, _P, _L, _L, _P, _P, _P, _L, _L, _I, _L, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "iif_roi_extract_forward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _P],
+    "iif_roi_extract_backward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _L, _P],
 }
 
 
@@ -145,6 +147,11 @@ class ConvDesc(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("n", "hs", "ws", "cs", "hd", "wd", "cd", "r", "s", "stride", "pad",
                                                "transposed", "ldw", "dtype", "dst_dtype", "groups")] + [("wgt_frag", ctypes.c_void_p),
                                                                                                           ("wgt_frag_kind", ctypes.c_int32)]
+
+
+class RoiLevel(ctypes.Structure):
+    """Mirror of ``iif_roi_level`` (include/iif_amd.h)."""
+    _fields_ = [("ptr", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("spatial_scale", ctypes.c_float)]
 
 
 class PackDesc(ctypes.Structure):

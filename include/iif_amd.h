@@ -973,6 +973,45 @@ int iif_bn_backward_pool_fused(const void* g_pool, const uint8_t* argmax, const 
                                int h, int w, int c, int ho, int wo, const float* stats, const float* gamma, float* dgamma,
                                float* dbeta, void* dx, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* SingleRoIExtractor (mmdet roi_heads/roi_extractors/single_level_roi_extractor.py with mmcv's RoIAlign, pool_mode 'avg') in ONE
+ * launch over all FPN levels; iif_amd/mmdet_roi_extractor.py.  levels: a HOST array of num_levels (1 .. 8) descriptors, copied
+ * into the launch: ptr = the level's features, fp32 NHWC [N][H][W][C] (torch's channels_last), the same N and C on every level.
+ * rois [K] rows of (batch index, x1, y1, x2, y2) fp32, ld_rois floats apart (>= 5), read in place.  Per roi, in float32 with
+ * the reference's operations in its order:
+ *   level   num_levels > 1: clamp(floorf(log2f(sqrtf((x2 - x1) * (y2 - y1)) / finest_scale + 1e-6f)), 0, num_levels - 1), from
+ *           the roi as given; a NaN scale is a zero row without gradient (lvl_out -1).  One level: no mapping.
+ *   rescale roi_scale_factor > 0: base_roi_extractor.py roi_rescale, after the level is chosen (<= 0: none).
+ *   RoIAlign  off = aligned ? .5f : 0; start = coord * spatial_scale - off; roi = end - start (not aligned: at least 1);
+ *           bin = roi / pooled; grid = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi / pooled) per axis;
+ *           sample y = start_h + ph * bin_h + (iy + .5f) * bin_h / grid_h; y < -1 || y > H || x < -1 || x > W adds nothing; else
+ *           y = max(y, 0), y_low = (int)y, y_low >= H - 1 ? y_low = y_high = H - 1, y = y_low; four-corner bilinear weights;
+ *           out = sum / max(grid_h * grid_w, 1); grid <= 0 on an axis: a zero bin.  The bin is summed in separable form (per-axis
+ *           pixel weights from those samples), so only the summation order differs from mmcv's loop.
+ *   A batch index < 0 or >= N (or NaN), a non-finite coordinate or a grid count above 65536: a zero row without gradient.
+ * out: fp32 [K][C][pooled_h][pooled_w] (out_channels_last: [K][pooled_h][pooled_w][C]).  lvl_out (nullable): int32 [K].
+ * Allocates nothing, reads nothing back.  IIF_EINVAL before any launch: a null or misaligned (4 bytes) pointer, num_levels
+ * outside 1 .. 8, N / C / H / W / pooled_h / pooled_w <= 0 (pooled > 1024), spatial_scale or (num_levels > 1) finest_scale not
+ * positive, ld_rois < 5, K < 0.  K == 0: IIF_OK, nothing is enqueued. */
+typedef struct iif_roi_level {
+    void* ptr;
+    int32_t H, W;
+    float spatial_scale;
+} iif_roi_level;
+int iif_roi_extract_forward(const iif_roi_level* levels, int num_levels, int N, int C, const float* rois, int64_t ld_rois,
+                            int64_t K, int pooled_h, int pooled_w, int sampling_ratio, int aligned, float finest_scale,
+                            float roi_scale_factor /* <= 0: none */, float* out, int out_channels_last,
+                            int32_t* lvl_out /* int32 [K] or NULL */, void* stream);
+/* The gradient of iif_roi_extract_forward with respect to the features: one clear of `arena` (arena_bytes; every
+ * grad_levels[i].ptr, fp32 NHWC like the features, must lie inside it with its N * H * W * C floats) and one launch that adds
+ * grad_out[k, c, ph, pw] * weight / count into the roi's level with float atomics, 256 contiguous bytes per wave-instruction
+ * - so sums depend on arrival order in their last bits, and a level no roi maps to comes back all zero.  grad_out: the layout
+ * of `out` (grad_channels_last).  The same geometry arguments and checks as the forward entry; K == 0: nothing is enqueued
+ * (the arena is not cleared). */
+int iif_roi_extract_backward(const iif_roi_level* grad_levels, int num_levels, int N, int C, const float* rois, int64_t ld_rois,
+                             int64_t K, int pooled_h, int pooled_w, int sampling_ratio, int aligned, float finest_scale,
+                             float roi_scale_factor, const float* grad_out, int grad_channels_last, void* arena,
+                             int64_t arena_bytes, void* stream);
+
 /* CIFAR training input (iif_amd/cifar.py DeviceCIFARLoader): ONE launch per batch builds out[b] (fp32 NCHW [batch][3][32][32])
  * and targets[b] = labels[index[b]] from the device-resident dataset data (uint8 [n][3][32][32], the planar rows of the
  * CIFAR files) and labels (int64 [n]).  flags select the stages, applied in the reference's order (initialisers.py:116-134):
