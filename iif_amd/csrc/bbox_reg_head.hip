@@ -27,15 +27,17 @@
 // Per element: d = p - t, a = |d|;  L1 (beta = 0): l = a, dl = sign(d) with sign(0) = 0 (torch's abs backward);
 // smooth L1: a < beta ? (0.5 a a / beta, d / beta) : (a - 0.5 beta, sign(d)), the comparison strict as in the reference (so
 // beta = 0 IS L1: no branch on the mode).  loss = scale * sum w l, dsel = scale * w * dl, loss_elems = w * l.
-// The scalar leaves the forward launch by the fence-free ticket of iif_head.hip: no float atomics, a fixed summation order,
+// The scalar leaves the forward launch by the ticketed reduction of loss_reduce.h: no float atomics, a fixed summation order,
 // bit-identical from call to call.  Indexing is 64-bit.
 #include "common.h"
+#include "loss_reduce.h"
 
 namespace {
 
-constexpr unsigned kMaxBlocks = 2048;          // = partial slots of IIF_CE_WORKSPACE_BYTES
+constexpr unsigned kScatterBlocks = 2048;      // scatter grid cap (the scatter launches use no workspace)
 constexpr int kThreads = 256;
 constexpr unsigned kFwdBlocks = 1024;          // forward grid cap: 16 waves per CU, each with a box's three 16-byte loads in flight
+static_assert(kFwdBlocks <= kCePartialSlots, "one partial slot per forward block");
 constexpr int kSmallGrid = 256;                // scatter: one step of work is spread over at most this many blocks (one per CU)
 constexpr int kU = 4;                          // scatter: 16-byte stores in flight per lane and step
 
@@ -116,43 +118,6 @@ __device__ __forceinline__ void store_f32(float* p, const float (&v)[V]) {
     }
 }
 
-// Same protocol as iif_head.hip's finish_with_ticket: workspace = int32 ticket (zero on entry and exit) followed by one
-// float per block.  No release fence: the partial goes out as an agent-scope atomic exchange whose return is waited
-// for before the ticket is taken, and the last block reads the partials with agent-scope atomic loads.
-__device__ __forceinline__ void finish_with_ticket(const FwdArgs& a, float wave_loss) {
-    if (a.ticket == nullptr) return;                // block-uniform
-    __shared__ float sh[kThreads];
-    __shared__ int last;
-    float* partial = reinterpret_cast<float*>(a.ticket + 1);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    if (lane == 0) sh[w] = wave_loss;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float acc = 0.f;
-        for (int i = 0; i < wpb; ++i) acc += sh[i];
-        const float prev = __hip_atomic_exchange(partial + blockIdx.x, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" : : "v"(prev) : "memory");
-        const int t = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!last) return;
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += blockDim.x)
-        acc += __hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *a.loss_out = sh[0] * a.scale;
-        __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
 // The V elements from flat index e on (V = 4: e is a multiple of 4, one box).  Returns the sum of their weighted losses.
 template <typename T, int V>
 __device__ __forceinline__ float unit(const FwdArgs& a, int64_t e) {
@@ -194,7 +159,7 @@ __global__ void __launch_bounds__(kThreads) bbox_reg_fwd_kernel(FwdArgs a) {
         const int64_t e = nu * V + threadIdx.x;
         if (blockIdx.x == gridDim.x - 1 && e < a.n) acc += unit<T, 1>(a, e);
     }
-    finish_with_ticket(a, wave_sum(acc));
+    if (a.ticket != nullptr) ticketed_finish<1>(a.ticket, {wave_sum(acc)}, {a.scale}, {a.loss_out});       // loss_reduce.h
 }
 
 template <typename T, int V>
@@ -301,7 +266,7 @@ int launch_scatter_vec(ScatterArgs a, hipStream_t st) {
         grid = (unsigned)cdiv64(blocks1, k);
     } else {
         const int64_t units = cdiv64(blocks1, kU);
-        const int64_t iters = cdiv64(units, kMaxBlocks);
+        const int64_t iters = cdiv64(units, kScatterBlocks);
         grid = (unsigned)cdiv64(units, iters);
     }
     const uint64_t stride = (uint64_t)grid * kThreads * S;                  // class slots from one of a thread's pieces to the next
@@ -315,7 +280,7 @@ int launch_scatter_vec(ScatterArgs a, hipStream_t st) {
 template <typename T>
 int launch_scatter_elem(const ScatterArgs& a, hipStream_t st) {
     int64_t blocks = cdiv64((int64_t)a.N * 4 * a.C, kThreads);
-    blocks = blocks > kMaxBlocks ? kMaxBlocks : blocks;
+    blocks = blocks > kScatterBlocks ? kScatterBlocks : blocks;
     hipLaunchKernelGGL((bbox_reg_scatter_elem_kernel<T>), dim3((unsigned)blocks), dim3(kThreads), 0, st, a);
     IIF_LAUNCH_CHECK();
     return IIF_OK;

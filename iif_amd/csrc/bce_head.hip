@@ -24,16 +24,15 @@
 //   labels:  y = 0: l = sp(x),  dl/dx = s          y = 1: l = pw_c sp(-x),  dl/dx = -pw_c q
 //   dense :  l = (1 - y) sp(x) + pw_c y sp(-x),   dl/dx = (1 - y) s - pw_c y q
 // which is torch's (1 - y) x + (1 + (pw - 1) y) sp(-x) with x + sp(-x) written as sp(x): exact at every |x|.
-// The scalar loss leaves the same launch by the fence-free ticket of iif_head.hip (block partials published with
-// agent-scope exchanges, a ticket, the last block sums them in a fixed order and re-zeroes the ticket): no float
-// atomics, bit-identical from call to call.
+// The scalar loss leaves the same launch by the ticketed reduction of loss_reduce.h: no float atomics, bit-identical from
+// call to call.
 #include "common.h"
+#include "loss_reduce.h"
 
 namespace {
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
-constexpr unsigned kMaxBlocks = 2048;          // = partial slots of IIF_CE_WORKSPACE_BYTES
 constexpr int kThreads = 256;
 
 struct Args {
@@ -156,43 +155,6 @@ __device__ __forceinline__ void store_f32(float* p, const float (&v)[V]) {
     }
 }
 
-// Same protocol as iif_head.hip's finish_with_ticket: workspace = int32 ticket (zero on entry and exit) followed by one
-// float per block.  No release fence: the partial goes out as an agent-scope atomic exchange whose return is waited
-// for before the ticket is taken, and the last block reads the partials with agent-scope atomic loads.
-__device__ __forceinline__ void finish_with_ticket(const Args& a, float wave_loss) {
-    if (a.ticket == nullptr) return;                // block-uniform
-    __shared__ float sh[kThreads];
-    __shared__ int last;
-    float* partial = reinterpret_cast<float*>(a.ticket + 1);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    if (lane == 0) sh[w] = wave_loss;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float acc = 0.f;
-        for (int i = 0; i < wpb; ++i) acc += sh[i];
-        const float prev = __hip_atomic_exchange(partial + blockIdx.x, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" : : "v"(prev) : "memory");
-        const int t = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!last) return;
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += blockDim.x)
-        acc += __hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *a.loss_out = sh[0] * a.scale;
-        __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
 template <int V> constexpr int unroll_of() { return V == 8 ? 2 : 4; }       // vectors in flight per lane and step (fp32: 64 bytes)
 constexpr int kSmallGrid = 256;                // one step of work is spread over at most this many blocks (one per CU)
 
@@ -206,7 +168,7 @@ __global__ void __launch_bounds__(kThreads) bce_det_kernel(Args a) {
     const int64_t T_ = (int64_t)gridDim.x * kThreads;                      // vectors per grid step
     const int64_t gtid = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const unsigned C = (unsigned)a.C;
-    // (row, column) of this thread's first vector; its flat index is below 2^32 (at most 2048 * 256 * 8 + 7)
+    // (row, column) of this thread's first vector; its flat index is below 2^32 (at most kCePartialSlots * 256 * 8 + 7)
     const unsigned e_first = (unsigned)a.h + (unsigned)gtid * V;
     int64_t i = e_first / C;
     unsigned c = e_first % C;
@@ -277,7 +239,7 @@ __global__ void __launch_bounds__(kThreads) bce_det_kernel(Args a) {
             if (a.elems) a.elems[e] = l;
         }
     }
-    finish_with_ticket(a, wave_sum(acc));
+    if (a.ticket != nullptr) ticketed_finish<1>(a.ticket, {wave_sum(acc)}, {a.scale}, {a.loss_out});       // loss_reduce.h
 }
 
 template <typename T, bool DENSE, int V>
@@ -293,7 +255,7 @@ int launch(Args a, hipStream_t st) {
         grid = (unsigned)cdiv64(blocks1, k);
     } else {
         const int64_t units = cdiv64(blocks1, U);
-        const int64_t iters = cdiv64(units, kMaxBlocks);
+        const int64_t iters = cdiv64(units, kCePartialSlots);
         grid = (unsigned)cdiv64(units, iters);
     }
     const uint64_t stride = (uint64_t)grid * kThreads * V;                  // elements from one of a thread's vectors to the next

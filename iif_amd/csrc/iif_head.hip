@@ -13,10 +13,11 @@
 // expf() here made the kernel VALU-bound (1.9-3.0 TB/s at [65536, 1000]).  The one-hot term of the gradient is
 // patched by the one lane that owns the target column instead of being compared in every lane.
 // The scalar loss comes out of the SAME launch when the caller passes a ticket word: the last block to finish
-// (atomic ticket, agent-scope fence) sums the per-row losses in a fixed order — deterministic, no second launch.
+// (loss_reduce.h: atomic ticket, no fence) sums the block partials in a fixed order — deterministic, no second launch.
 #include <stdlib.h>
 
 #include "common.h"
+#include "loss_reduce.h"
 
 namespace {
 
@@ -105,49 +106,6 @@ struct CeArgs {
     float* loss_out;       // scalar loss = scale * sum(loss_row), written by the last block when ticket != nullptr
     int32_t* ticket;       // zero on entry, zero again on exit
 };
-
-// Single-launch loss reduce.  workspace = int32 ticket (zero on entry / exit) followed by one float per block.
-// Every wave adds up the losses of the rows it walked (fixed order), the block combines its waves (fixed order) into
-// partial[blockIdx]; the last block to take a ticket sums the <= 2048 partials in a fixed tree.  Deterministic for a
-// given (B, C, dtype): the grid depends on nothing else.
-__device__ __forceinline__ void finish_with_ticket(const CeArgs& a, float wave_loss) {
-    if (a.ticket == nullptr) return;                // block-uniform
-    __shared__ float sh[256];
-    __shared__ int last;
-    float* partial = reinterpret_cast<float*>(a.ticket + 1);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    if (lane == 0) sh[w] = wave_loss;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float acc = 0.f;
-        for (int i = 0; i < wpb; ++i) acc += sh[i];
-        // No release fence here: an agent-scope fence writes back the whole XCD L2, which at this point is full of
-        // the gradient rows just stored (it cost 40 % of the kernel).  The partial goes out as an agent-scope atomic
-        // exchange (performed at the coherence point; a returning atomic has completed when its value is back), the
-        // ticket is taken only after that value has returned, and the last block reads the partials with
-        // agent-scope atomic loads: the same ordering without touching the ordinary stores.
-        const float prev = __hip_atomic_exchange(partial + blockIdx.x, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" : : "v"(prev) : "memory");
-        const int t = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!last) return;
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += blockDim.x)
-        acc += __hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *a.loss_out = sh[0] * a.scale;
-        __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
 
 // Per-row scalars shared by the register and the streaming variants.
 struct RowCoef {
@@ -352,7 +310,7 @@ __global__ void __launch_bounds__(256, (NCH * RowIo<T>::V <= 16 ? 6 : 1)) row_re
             }
         }
     }
-    if (MODE != 1) finish_with_ticket(a, wave_loss);
+    if (MODE != 1 && a.ticket != nullptr) ticketed_finish<1>(a.ticket, {wave_loss}, {a.scale}, {a.loss_out});       // loss_reduce.h
 }
 
 // -------------------------------------------- streaming row (any C / alignment)
@@ -395,21 +353,7 @@ __global__ void __launch_bounds__(256) row_stream_kernel(CeArgs a, float* sm_out
             }
         }
     }
-    if (MODE != 1) finish_with_ticket(a, wave_loss);
-}
-
-// fixed-order sum of the per-row losses: one 256-thread block, deterministic
-__global__ void __launch_bounds__(256) loss_reduce_kernel(const float* rows, int B, float scale, float* out) {
-    __shared__ float sh[256];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < B; i += 256) acc += rows[i];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = sh[0] * scale;
+    if (MODE != 1 && a.ticket != nullptr) ticketed_finish<1>(a.ticket, {wave_loss}, {a.scale}, {a.loss_out});       // loss_reduce.h
 }
 
 template <typename T>
@@ -456,14 +400,12 @@ __global__ void __launch_bounds__(256) scale_by_scalar_kernel(const T* x, int64_
 
 inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
-constexpr unsigned kMaxRowBlocks = 2048;      // = partial slots of the single-launch loss workspace
-
 // *inline_reduce (in/out): the caller wants the scalar loss reduced by this launch; cleared when the launch
 // configuration cannot do it (streaming kernel with more blocks than workspace slots).
 template <typename T, int MODE>
 int launch_rows(CeArgs a, float* sm_out, int64_t ld_sm, hipStream_t st, bool* inline_reduce = nullptr) {
     // waves per block: every block stages the table once and takes one ticket, so small batches use fewer, fatter blocks.
-    // finish_with_ticket's tree needs a power of two <= 4 (sh[256], __launch_bounds__(256)): anything else falls back to 4
+    // ticketed_finish's tree needs a power of two <= 4 (sh[256], __launch_bounds__(256)): anything else falls back to 4
     int wpb = 4;                // measured 1 / 2 / 4: [1024, 1204] 23.2 / 13.3 / 9.5 us, [256, 1000] 9.1 / 7.6 / 6.6 us
     const dim3 grid((a.B + wpb - 1) / wpb), block(64 * wpb);
     // register-row kernel: at most 256 CUs x 8 blocks; beyond that a wave walks several rows.  Never more blocks than the
@@ -472,7 +414,7 @@ int launch_rows(CeArgs a, float* sm_out, int64_t ld_sm, hipStream_t st, bool* in
     //   bf16 3.55 / 4.32 / 4.60 / 4.84 / 4.67 TB/s, fp32 5.22 / 5.01 / 4.98 / 4.93 / 4.82 TB/s ([8192, 1204] fp32: 512 best as well)
     unsigned maxb = sizeof(T) == 2 ? 1536u : 512u;
     if (maxb < 1u) maxb = 1u;
-    if (maxb > kMaxRowBlocks) maxb = kMaxRowBlocks;
+    if (maxb > kCePartialSlots) maxb = kCePartialSlots;
     const dim3 pgrid(grid.x < maxb ? grid.x : maxb);
     // rows in 16-byte lane vectors: 4 fp32 / 8 bf16 columns; a bf16 row may end on a half vector (C % 8 == 4: 1204)
     constexpr int V = RowIo<T>::V;
@@ -501,7 +443,7 @@ int launch_rows(CeArgs a, float* sm_out, int64_t ld_sm, hipStream_t st, bool* in
             }
         }
     } else {
-        if (grid.x > kMaxRowBlocks) {
+        if (grid.x > kCePartialSlots) {
             a.ticket = nullptr;
             if (inline_reduce) *inline_reduce = false;
         }
@@ -539,7 +481,7 @@ int iif_ce_fwd_bwd(const void* logits, int dtype, int64_t ld_logits, const float
                               : launch_rows<unsigned short, 0>(a, nullptr, 0, st, &one_launch);
     if (rc != IIF_OK) return rc;
     if (loss_out && !one_launch) {
-        hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, loss_per_row, B, scale, loss_out);
+        hipLaunchKernelGGL(rows_reduce_kernel<float>, dim3(1), dim3(256), 0, st, loss_per_row, B, scale, loss_out);
         IIF_LAUNCH_CHECK();
     }
     return IIF_OK;

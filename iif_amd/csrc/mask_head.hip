@@ -8,6 +8,7 @@
 // (HBM-bound, 4 B read + 4 B target read + 4 B gradient write per element), per-RoI loss partials are reduced
 // by one block in a fixed order (deterministic).
 #include "common.h"
+#include "loss_reduce.h"
 
 namespace {
 
@@ -63,19 +64,6 @@ __global__ void __launch_bounds__(256) mask_bce_kernel(const T* pred, const floa
     if (threadIdx.x == 0) row_loss[n] = tot;
 }
 
-__global__ void __launch_bounds__(256) mask_loss_reduce_kernel(const float* row_loss, int n, double inv_count, float* loss) {
-    __shared__ double sh[256];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) acc += (double)row_loss[i];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (float)(sh[0] * inv_count);
-}
-
 }  // namespace
 
 extern "C" {
@@ -102,7 +90,7 @@ int iif_mask_bce_fwd_bwd(const void* pred, int dtype, const float* target, const
     if (dtype == IIF_F32) hipLaunchKernelGGL(mask_bce_kernel<float>, dim3(n), dim3(256), 0, st, (const float*)pred, target, labels, c, hw, gs, row_loss, dpred, status);
     else hipLaunchKernelGGL(mask_bce_kernel<unsigned short>, dim3(n), dim3(256), 0, st, (const unsigned short*)pred, target, labels, c, hw, gs, row_loss, dpred, status);
     IIF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mask_loss_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, n, inv, loss);
+    hipLaunchKernelGGL(rows_reduce_kernel<double>, dim3(1), dim3(256), 0, st, row_loss, n, inv, loss);
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }

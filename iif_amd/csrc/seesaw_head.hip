@@ -5,7 +5,7 @@
 //   1. seesaw_count_kernel   integer histogram of the labels (LDS atomics, then integer global atomics and a ticketed last
 //                            block), added to cum_samples as ONE fp32 addition per class, plus the number of positive rows;
 //   2. seesaw_loss_kernel    one 64-lane wave per row, the row in registers: both softmaxes, the seesaw terms in the log domain,
-//                            the whole [N, C + 2] gradient, the per-row losses and both scalar losses (fence-free ticket).
+//                            the whole [N, C + 2] gradient, the per-row losses and both scalar losses (loss_reduce.h).
 // Layout: the LVIS row is 1205 floats, so consecutive rows start on every 16-byte phase and no 16-byte vector path applies.
 // Lane l of chunk j owns column j * 64 + l: each wave instruction is a dword access over 256 contiguous bytes, whatever the
 // row's phase; only the last chunk is ragged (lanes beyond C hold -inf).  The kernels are latency / HBM bound: no GEMM, no MFMA.
@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "loss_reduce.h"
 
 namespace {
 
@@ -114,46 +115,6 @@ struct SeesawArgs {
     float* dx; int64_t lddx;
     int32_t* status; int32_t* ws;
 };
-
-// Both scalar losses out of the same launch: the protocol of iif_head.hip's finish_with_ticket (partials published with
-// returning agent-scope exchanges, s_waitcnt vmcnt(0), relaxed ticket, agent-scope loads in the last block; no fence, which
-// would write back an L2 full of gradient rows).  Fixed-order sums: deterministic for a given (N, C).
-__device__ __forceinline__ void seesaw_finish(const SeesawArgs& a, float wave_cls, float wave_obj, float scale_cls) {
-    __shared__ float sh[2][256];
-    __shared__ int last;
-    float* partial = reinterpret_cast<float*>(a.ws + kWsPartial);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    if (lane == 0) { sh[0][w] = wave_cls; sh[1][w] = wave_obj; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float ac = 0.f, ao = 0.f;
-        for (int i = 0; i < wpb; ++i) { ac += sh[0][i]; ao += sh[1][i]; }
-        const float p0 = __hip_atomic_exchange(partial + 2 * blockIdx.x, ac, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const float p1 = __hip_atomic_exchange(partial + 2 * blockIdx.x + 1, ao, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" : : "v"(p0), "v"(p1) : "memory");
-        const int t = __hip_atomic_fetch_add(a.ws, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!last) return;
-    float ac = 0.f, ao = 0.f;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += blockDim.x) {
-        ac += __hip_atomic_load(partial + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ao += __hip_atomic_load(partial + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    sh[0][threadIdx.x] = ac; sh[1][threadIdx.x] = ao;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { sh[0][threadIdx.x] += sh[0][threadIdx.x + o]; sh[1][threadIdx.x] += sh[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        a.loss_out[0] = sh[0][0] * scale_cls;
-        a.loss_out[1] = sh[1][0] * a.scale_obj;
-        __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
 
 // One row's class columns in NCH registers per lane (column j * 64 + lane) and one extra dword: lanes 0 / 1 the two objectness
 // columns, lane 2 the target's logit (column 0 when the row has no class target).  Every address is inside the row.
@@ -291,7 +252,8 @@ __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
             }
         }
     }
-    seesaw_finish(a, wave_cls, wave_obj, sc);
+    // both scalar losses out of the same launch (loss_reduce.h): ticket at ws[0], interleaved cls / obj partials
+    ticketed_finish<2>(a.ws, {wave_cls, wave_obj}, {sc, a.scale_obj}, {a.loss_out, a.loss_out + 1}, kWsPartial);
 }
 
 // ------------------------------------------------------------------------------------------------ activation

@@ -26,15 +26,14 @@
 // exact function at every |x|: see DESIGN.md, "Sigmoid BCE / focal head".
 // Every column is first evaluated as a y = 0 column; the lane(s) owning a target column patch it (mixup: two targets,
 // lam * L(y_a) + (1 - lam) * L(y_b) per element).
-// The scalar loss comes out of the same launch with the ticket protocol of iif_head.hip (exchange of block partials
-// at agent scope, then a ticket; the last block sums the partials in a fixed order and re-zeroes the ticket).
+// The scalar loss comes out of the same launch by the ticketed reduction of loss_reduce.h.
 #include "common.h"
+#include "loss_reduce.h"
 
 namespace {
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
-constexpr unsigned kMaxBlocks = 2048;          // = partial slots of IIF_CE_WORKSPACE_BYTES
 constexpr int kLdsWeights = 8192;              // class weights staged in LDS up to this many classes (32 KB)
 
 __device__ __forceinline__ float exp_neg(float v) { return __builtin_amdgcn_exp2f(-v * kLog2e); }   // e^-v
@@ -153,43 +152,6 @@ template <> struct Vec<unsigned short> {                 // bf16 bits
     static __device__ __forceinline__ void store1(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
 };
 
-// Same protocol as iif_head.hip's finish_with_ticket: workspace = int32 ticket (zero on entry and exit) followed by one
-// float per block.  No release fence: the partial goes out as an agent-scope atomic exchange whose return is waited
-// for before the ticket is taken, and the last block reads the partials with agent-scope atomic loads.
-__device__ __forceinline__ void finish_with_ticket(const Args& a, float wave_loss) {
-    if (a.ticket == nullptr) return;                // block-uniform
-    __shared__ float sh[256];
-    __shared__ int last;
-    float* partial = reinterpret_cast<float*>(a.ticket + 1);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    if (lane == 0) sh[w] = wave_loss;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float acc = 0.f;
-        for (int i = 0; i < wpb; ++i) acc += sh[i];
-        const float prev = __hip_atomic_exchange(partial + blockIdx.x, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" : : "v"(prev) : "memory");
-        const int t = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!last) return;
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += blockDim.x)
-        acc += __hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *a.loss_out = sh[0] * a.scale;
-        __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
 // U lane vectors in flight per wave and body step: 4 KB of logits per wave (4 fp32 / 2 bf16 vectors per lane).
 template <typename T, int GM>
 __global__ void __launch_bounds__(256) sigmoid_focal_kernel(Args a) {
@@ -253,28 +215,14 @@ __global__ void __launch_bounds__(256) sigmoid_focal_kernel(Args a) {
         if (lane == 0) a.loss_row[r] = acc;
         wave_loss += acc;
     }
-    finish_with_ticket(a, wave_loss);
-}
-
-// fixed-order sum of the per-row losses (the launch without a workspace): one 256-thread block, deterministic
-__global__ void __launch_bounds__(256) focal_loss_reduce_kernel(const float* rows, int B, float scale, float* out) {
-    __shared__ float sh[256];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < B; i += 256) acc += rows[i];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = sh[0] * scale;
+    if (a.ticket != nullptr) ticketed_finish<1>(a.ticket, {wave_loss}, {a.scale}, {a.loss_out});       // loss_reduce.h
 }
 
 template <typename T>
 int launch(const Args& a, int gm, hipStream_t st) {
     const int wpb = 4;
     const unsigned want = (unsigned)((a.B + wpb - 1) / wpb);
-    const dim3 grid(want < kMaxBlocks ? want : kMaxBlocks), block(64 * wpb);
+    const dim3 grid(want < kCePartialSlots ? want : kCePartialSlots), block(64 * wpb);
     const size_t lds = (a.w != nullptr && a.C <= kLdsWeights) ? (size_t)a.C * sizeof(float) : 0;
     switch (gm) {
         case 0: hipLaunchKernelGGL((sigmoid_focal_kernel<T, 0>), grid, block, lds, st, a); break;
@@ -335,7 +283,7 @@ int iif_sigmoid_focal_fwd_bwd(const void* logits, int dtype, int64_t ld_logits, 
     const int rc = dtype == IIF_F32 ? launch<float>(a, gm, st) : launch<unsigned short>(a, gm, st);
     if (rc != IIF_OK) return rc;
     if (loss_out && !one_launch) {
-        hipLaunchKernelGGL(focal_loss_reduce_kernel, dim3(1), dim3(256), 0, st, loss_per_row, B, scale, loss_out);
+        hipLaunchKernelGGL(rows_reduce_kernel<float>, dim3(1), dim3(256), 0, st, loss_per_row, B, scale, loss_out);
         IIF_LAUNCH_CHECK();
     }
     return IIF_OK;

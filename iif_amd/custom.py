@@ -14,6 +14,7 @@ import torch.nn as nn
 from scipy.special import ndtri
 
 from . import _lib
+from . import loss_reduction
 
 VARIANTS = ("raw", "smooth", "rel", "normit", "gombit", "base2", "base10")
 
@@ -82,7 +83,7 @@ def _workspace(device, B, own_rows):
     ws = _WS.get(key)
     if ws is None:
         ws = _WS[key] = {"rows": torch.empty(0, dtype=torch.float32, device=device),
-                         "ticket": torch.zeros(1 + 2048, dtype=torch.int32, device=device),      # IIF_CE_WORKSPACE_BYTES
+                         "ticket": torch.zeros(loss_reduction.CE_WORKSPACE_WORDS, dtype=torch.int32, device=device),
                          "status": torch.zeros(1, dtype=torch.int32, device=device)}
     if own_rows:
         rows = torch.empty(B, dtype=torch.float32, device=device)
@@ -120,12 +121,7 @@ class _FusedIIFCrossEntropy(torch.autograd.Function):
         (dlogits,) = ctx.saved_tensors
         if dlogits is None:
             return (None,) * 9
-        g = g_loss.to(torch.float32).contiguous()
-        out = torch.empty_like(dlogits)           # the saved gradient stays intact: backward may run twice
-        rc = _lib.lib().iif_scale_by_device_scalar(_lib.ptr(dlogits), _lib.dtype_code(dlogits), dlogits.numel(),
-                                                   _lib.ptr(g), _lib.ptr(out), _lib.stream_ptr())
-        _lib.check(rc, "iif_scale_by_device_scalar")
-        return (out,) + (None,) * 8
+        return (loss_reduction.scale_by_device_scalar(dlogits, g_loss),) + (None,) * 8
 
 
 def fused_iif_cross_entropy(pred, table, targets, targets_b=None, lam=1.0, row_weight=None, class_weight=None,
@@ -136,16 +132,10 @@ def fused_iif_cross_entropy(pred, table, targets, targets_b=None, lam=1.0, row_w
     per-row vector (its gradient path scales rows by the upstream vector).
     """
     B = pred.shape[0]
-    if reduction == "mean":
-        scale = loss_weight / (float(avg_factor) if avg_factor is not None else float(max(B, 1)))
-    elif reduction == "sum":
-        if avg_factor is not None:
-            raise ValueError('avg_factor can not be used with reduction="sum"')
-        scale = loss_weight
-    elif reduction == "none":
+    loss_reduction.check_reduction(reduction, avg_factor)
+    if reduction == "none":
         return _rows_loss(pred, table, targets, targets_b, lam, row_weight, class_weight, ignore_index) * loss_weight
-    else:
-        raise ValueError("unknown reduction %r" % (reduction,))
+    scale = loss_reduction.reduction_scale(reduction, avg_factor, B, loss_weight)
     loss = _FusedIIFCrossEntropy.apply(pred, table, targets, targets_b, lam, row_weight, class_weight,
                                        ignore_index, scale)
     if B == 0 and reduction == "mean" and avg_factor is None:
@@ -293,12 +283,7 @@ class _FusedSigmoidFocal(torch.autograd.Function):
         (dlogits,) = ctx.saved_tensors
         if dlogits is None:
             return (None,) * 8
-        g = g_loss.to(torch.float32).contiguous()
-        out = torch.empty_like(dlogits)           # the saved gradient stays intact: backward may run twice
-        rc = _lib.lib().iif_scale_by_device_scalar(_lib.ptr(dlogits), _lib.dtype_code(dlogits), dlogits.numel(),
-                                                   _lib.ptr(g), _lib.ptr(out), _lib.stream_ptr())
-        _lib.check(rc, "iif_scale_by_device_scalar")
-        return (out,) + (None,) * 7
+        return (loss_reduction.scale_by_device_scalar(dlogits, g_loss),) + (None,) * 7
 
 
 class FocalLoss(nn.Module):

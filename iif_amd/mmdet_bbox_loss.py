@@ -20,13 +20,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import custom
-
-
-def _check_reduction(reduction, avg_factor):
-    if reduction not in ("none", "mean", "sum"):
-        raise ValueError("unknown reduction %r" % (reduction,))
-    if avg_factor is not None and reduction == "sum":
-        raise ValueError('avg_factor can not be used with reduction="sum"')
+from .loss_reduction import check_reduction, reduction_scale, register_losses, scale_by_device_scalar
 
 
 def _launch_fwd(pred, labels, num_classes, C, target, weight, beta, scale, want_grad, want_elems):
@@ -49,16 +43,6 @@ def _launch_fwd(pred, labels, num_classes, C, target, weight, beta, scale, want_
     return loss, elems, dsel
 
 
-def _scale_by(dsel, g, dtype):
-    """``dsel * g`` for a device scalar ``g`` (a fresh tensor: the saved gradient stays intact, backward may run twice)."""
-    g = g.to(torch.float32).contiguous()
-    out = torch.empty_like(dsel)
-    rc = _lib.lib().iif_scale_by_device_scalar(_lib.ptr(dsel), _lib.dtype_code(dsel), dsel.numel(), _lib.ptr(g), _lib.ptr(out),
-                                               _lib.stream_ptr())
-    _lib.check(rc, "iif_scale_by_device_scalar")
-    return out if dtype == torch.float32 else out.to(dtype)
-
-
 class _FusedReg(torch.autograd.Function):
     """Scalar loss from ONE launch in plain mode; the gradient comes out of the same launch and backward only multiplies
     it by the upstream scalar on the device."""
@@ -75,7 +59,7 @@ class _FusedReg(torch.autograd.Function):
         (dsel,) = ctx.saved_tensors
         if dsel is None:
             return (None,) * 5
-        return (_scale_by(dsel, g_loss, ctx.pred_dtype),) + (None,) * 4
+        return (scale_by_device_scalar(dsel, g_loss, ctx.pred_dtype),) + (None,) * 4
 
 
 class _FusedRegElems(torch.autograd.Function):
@@ -129,7 +113,7 @@ def _native_dtype(pred):
 def _reg_loss(pred, target, weight, beta, reduction, avg_factor, loss_weight=1.0):
     """``loss_weight *`` the weighted, reduced element loss of smooth_l1_loss.py:10-52 (``beta`` 0: L1) under
     weight_reduce_loss (losses/utils.py:29-55), ``loss_weight`` folded into the kernel's scale."""
-    _check_reduction(reduction, avg_factor)
+    check_reduction(reduction, avg_factor)
     _lib.require_gpu(pred, target, weight)
     if target.numel() == 0:
         # the reference returns pred.sum() * 0 here, a 0-d zero, and THEN applies the weight and the reduction to it:
@@ -151,13 +135,7 @@ def _reg_loss(pred, target, weight, beta, reduction, avg_factor, loss_weight=1.0
     if reduction == "none":                         # 'none' ignores avg_factor (utils.py:50-52)
         elems = _FusedRegElems.apply(x, t, w, beta)
         return elems if loss_weight == 1.0 else loss_weight * elems
-    if reduction == "sum":
-        scale = loss_weight
-    elif avg_factor is not None:
-        scale = loss_weight / float(avg_factor)
-    else:
-        scale = loss_weight / float(x.numel())
-    return _FusedReg.apply(x, t, w, beta, scale)
+    return _FusedReg.apply(x, t, w, beta, reduction_scale(reduction, avg_factor, x.numel(), loss_weight))     # (numel >= 1 here)
 
 
 def smooth_l1_loss(pred, target, weight=None, reduction="mean", avg_factor=None, beta=1.0):
@@ -216,7 +194,7 @@ def bbox_head_reg_loss(loss_bbox, bbox_pred, labels, bbox_targets, bbox_weights,
     if native:
         assert reduction_override in (None, "none", "mean", "sum")
         reduction = reduction_override if reduction_override else loss_bbox.reduction
-        _check_reduction(reduction, bbox_targets.size(0))
+        check_reduction(reduction, bbox_targets.size(0))
     if not native or reduction == "none":
         pos_inds = (labels >= 0) & (labels < num_classes)
         if not pos_inds.any():
@@ -256,13 +234,7 @@ def bbox_head_reg_loss(loss_bbox, bbox_pred, labels, bbox_targets, bbox_weights,
 
 def register_into_mmdet():
     """Register the native classes as mmdet's ``L1Loss`` / ``SmoothL1Loss`` if mmdet is importable."""
-    try:
-        from mmdet.models.builder import LOSSES
-    except Exception:
-        return False
-    LOSSES.register_module(name="L1Loss", force=True, module=L1Loss)
-    LOSSES.register_module(name="SmoothL1Loss", force=True, module=SmoothL1Loss)
-    return True
+    return register_losses({"L1Loss": L1Loss, "SmoothL1Loss": SmoothL1Loss})
 
 
 register_into_mmdet()

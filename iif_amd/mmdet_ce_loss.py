@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import custom
+from .loss_reduction import check_reduction, reduction_scale, register_losses, scale_by_device_scalar
 from .mmdet_mask_loss import mask_cross_entropy          # noqa: F401  (re-exported)
 
 _ONES = {}
@@ -30,18 +31,11 @@ def _ones_table(device, C):
     return t
 
 
-def _check_reduction(reduction, avg_factor):
-    if reduction not in ("none", "mean", "sum"):
-        raise ValueError("unknown reduction %r" % (reduction,))
-    if avg_factor is not None and reduction == "sum":
-        raise ValueError('avg_factor can not be used with reduction="sum"')
-
-
 def cross_entropy(pred, label, weight=None, reduction="mean", avg_factor=None, class_weight=None, ignore_index=-100):
     """cross_entropy_loss.py:10-50 + losses/utils.py:29-55 in one fused launch: softmax cross entropy with per-class
     weights, ignore index, per-row weights; 'mean' divides by N (ignored rows included) or by ``avg_factor``."""
     ignore_index = -100 if ignore_index is None else ignore_index
-    _check_reduction(reduction, avg_factor)
+    check_reduction(reduction, avg_factor)
     if reduction == "none":
         avg_factor = None            # 'none' ignores avg_factor (utils.py:50-52)
     _lib.require_gpu(pred)
@@ -126,12 +120,7 @@ class _FusedBCE(torch.autograd.Function):
         (dpred,) = ctx.saved_tensors
         if dpred is None:
             return (None,) * 8
-        g = g_loss.to(torch.float32).contiguous()
-        out = torch.empty_like(dpred)             # the saved gradient stays intact: backward may run twice
-        rc = _lib.lib().iif_scale_by_device_scalar(_lib.ptr(dpred), _lib.dtype_code(dpred), dpred.numel(), _lib.ptr(g),
-                                                   _lib.ptr(out), _lib.stream_ptr())
-        _lib.check(rc, "iif_scale_by_device_scalar")
-        return (out,) + (None,) * 7
+        return (scale_by_device_scalar(dpred, g_loss),) + (None,) * 7
 
 
 class _FusedBCEElems(torch.autograd.Function):
@@ -160,7 +149,7 @@ def binary_cross_entropy(pred, label, weight=None, reduction="mean", avg_factor=
     value per row); with as many it is a float target per element (``weight``: per element, no ignore index).  'none'
     returns the float32 element losses in ``pred``'s shape and ignores ``avg_factor``; 'mean' over nothing is NaN."""
     ignore_index = -100 if ignore_index is None else ignore_index
-    _check_reduction(reduction, avg_factor)
+    check_reduction(reduction, avg_factor)
     _lib.require_gpu(pred, label, weight)
     if pred.dtype not in (torch.float32, torch.bfloat16):
         pred = pred.float()
@@ -178,13 +167,7 @@ def binary_cross_entropy(pred, label, weight=None, reduction="mean", avg_factor=
     if reduction == "none":
         return _FusedBCEElems.apply(x, *modes, class_weight).view(shape)
     n = x.numel()
-    if reduction == "sum":
-        scale = 1.0
-    elif avg_factor is not None:
-        scale = 1.0 / float(avg_factor)
-    else:
-        scale = 1.0 / float(max(n, 1))
-    loss = _FusedBCE.apply(x, *modes, class_weight, scale)
+    loss = _FusedBCE.apply(x, *modes, class_weight, reduction_scale(reduction, avg_factor, n))
     if n == 0 and reduction == "mean" and avg_factor is None:
         return loss * float("nan")              # torch: mean of an empty tensor
     return loss
@@ -306,13 +289,7 @@ class CrossEntropyCounterLoss(_CEBase):
 
 def register_into_mmdet():
     """Register the native classes as mmdet's ``CrossEntropyLoss`` / ``CrossEntropyCounterLoss`` if mmdet is importable."""
-    try:
-        from mmdet.models.builder import LOSSES
-    except Exception:
-        return False
-    LOSSES.register_module(name="CrossEntropyLoss", force=True, module=CrossEntropyLoss)
-    LOSSES.register_module(name="CrossEntropyCounterLoss", force=True, module=CrossEntropyCounterLoss)
-    return True
+    return register_losses({"CrossEntropyLoss": CrossEntropyLoss, "CrossEntropyCounterLoss": CrossEntropyCounterLoss})
 
 
 register_into_mmdet()

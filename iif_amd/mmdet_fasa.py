@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .loss_reduction import register_losses
 from .mmdet_iif_loss import IIFLoss
 
 
@@ -165,12 +166,7 @@ class FasaFeatureBank(nn.Module):
 
 
 def register_into_mmdet():
-    try:
-        from mmdet.models.builder import LOSSES
-    except Exception:
-        return False
-    LOSSES.register_module(name="FasaIIFLoss", force=True, module=FasaIIFLoss)
-    return True
+    return register_losses({"FasaIIFLoss": FasaIIFLoss})
 
 
 register_into_mmdet()

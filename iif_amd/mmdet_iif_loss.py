@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from . import _lib
 from .custom import fused_iif_cross_entropy
+from .loss_reduction import check_avg_factor, register_losses
 from .utils import topk_hit_counts
 
 
@@ -88,8 +89,7 @@ class IIFLoss(nn.Module):
                       ignore_index=-100):
         """iif_loss.py:157-202 + losses/utils.py:29-55 in one fused launch."""
         ignore_index = -100 if ignore_index is None else ignore_index
-        if avg_factor is not None and reduction == "sum":
-            raise ValueError('avg_factor can not be used with reduction="sum"')
+        check_avg_factor(reduction, avg_factor)
         if reduction == "none":
             avg_factor = None            # 'none' ignores avg_factor (utils.py:50-52)
         return fused_iif_cross_entropy(pred, self._table(pred), label, row_weight=weight,
@@ -112,12 +112,7 @@ class IIFLoss(nn.Module):
 
 def register_into_mmdet():
     """Register the native class as mmdet's ``IIFLoss`` if mmdet is importable."""
-    try:
-        from mmdet.models.builder import LOSSES
-    except Exception:
-        return False
-    LOSSES.register_module(name="IIFLoss", force=True, module=IIFLoss)
-    return True
+    return register_losses({"IIFLoss": IIFLoss})
 
 
 register_into_mmdet()

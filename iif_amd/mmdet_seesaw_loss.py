@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import custom
+from .loss_reduction import check_avg_factor, reduction_scale, register_losses
 
 MAX_CHANNELS = 2048          # C + 2: the row is register resident (csrc/seesaw_head.hip)
 _WS = {}
@@ -187,8 +188,7 @@ class SeesawLoss(nn.Module):
         reduction = reduction_override if reduction_override else self.reduction
         C = self.num_classes
         assert cls_score.size(-1) == C + 2
-        if avg_factor is not None and reduction == "sum":
-            raise ValueError('avg_factor can not be used with reduction="sum"')
+        check_avg_factor(reduction, avg_factor)
         _lib.require_gpu(cls_score, labels, label_weights)
         if self.cum_samples.device != cls_score.device:
             self.cum_samples = self.cum_samples.to(cls_score.device)
@@ -200,12 +200,9 @@ class SeesawLoss(nn.Module):
             loss_cls_classes = lw * rows_cls[labels < C]          # the output's shape is the positive count: one sync
             loss_cls_objectness = lw * rows_obj
         else:
-            if reduction == "sum":
-                scale_cls, div_pos, scale_obj = lw, False, lw
-            elif avg_factor is not None:
-                scale_cls, div_pos, scale_obj = lw / float(avg_factor), False, lw / float(avg_factor)
-            else:
-                scale_cls, div_pos, scale_obj = lw, True, lw / float(max(N, 1))
+            scale_obj = reduction_scale(reduction, avg_factor, N, lw)
+            div_pos = reduction != "sum" and avg_factor is None      # the class loss is divided by the positive count on the device
+            scale_cls = lw if div_pos else scale_obj
             loss_cls_classes, loss_cls_objectness = _FusedSeesaw.apply(
                 cls_score, labels, label_weights, self.cum_samples, self.p, self.q, self.eps, scale_cls, div_pos,
                 scale_obj, C)
@@ -218,12 +215,7 @@ class SeesawLoss(nn.Module):
 
 def register_into_mmdet():
     """Register the native class as mmdet's ``SeesawLoss`` if mmdet is importable."""
-    try:
-        from mmdet.models.builder import LOSSES
-    except Exception:
-        return False
-    LOSSES.register_module(name="SeesawLoss", force=True, module=SeesawLoss)
-    return True
+    return register_losses({"SeesawLoss": SeesawLoss})
 
 
 register_into_mmdet()

@@ -398,7 +398,7 @@ def test_bn_reduce_and_finalize_in_one_launch_is_bit_identical(nt, c):
 
 
 def test_ticketed_single_launch_reductions_under_memory_load():
-    """The fence-free ticket protocol (bn.hip bn_reduce_finalize_kernel, iif_head.hip finish_with_ticket: partials published
+    """The fence-free ticket protocol (bn.hip bn_reduce_finalize_kernel, loss_reduce.h ticketed_finish: partials published
     with agent-scope atomic exchanges, s_waitcnt, relaxed ticket; the last block reads them with agent-scope atomic loads)
     is only as good as the hardware property it rests on, and the bit-identity tests above run on an idle GPU.  Here the
     single-launch forms run 60 times each while a second stream keeps every XCD's L2 and the HBM busy with large copies
