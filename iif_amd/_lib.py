@@ -138,6 +138,8 @@ SIGNATURES = {
     "iif_roi_targets": [_P, _L, _L, _P, _P, _P, _L, _L, _P, _P, _P, _L, _L, _I, _L, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "iif_roi_extract_forward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _P],
     "iif_roi_extract_backward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _L, _P],
+    "iif_nms": [_P, _L, _P, _P, _L, _I, _F, _I, _F, _L, _P, _P, _P, _P, _L, _P],
+    "iif_rpn_proposals": [_P, _I, _I, _P, _I, _I, _F, _F, _I, _P, _P, _F, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P],
 }
 
 
@@ -152,6 +154,13 @@ class ConvDesc(ctypes.Structure):
 class RoiLevel(ctypes.Structure):
     """Mirror of ``iif_roi_level`` (include/iif_amd.h)."""
     _fields_ = [("ptr", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("spatial_scale", ctypes.c_float)]
+
+
+class RpnLevel(ctypes.Structure):
+    """Mirror of ``iif_rpn_level`` (include/iif_amd.h)."""
+    _fields_ = [("scores", ctypes.c_void_p), ("deltas", ctypes.c_void_p), ("anchors", ctypes.c_void_p),
+                ("score_strides", ctypes.c_int64 * 4), ("delta_strides", ctypes.c_int64 * 4), ("ld_anchors", ctypes.c_int64),
+                ("A", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class PackDesc(ctypes.Structure):

@@ -1,0 +1,553 @@
+// Non-maximum suppression and the RPN proposal step for gfx950 (MI355X): mmcv's nms / batched_nms and mmdet's
+// RPNHead.get_bboxes (instance_segmentation/mmdet/models/dense_heads/rpn_head.py:79-225) without a sort, a host copy of the
+// suppression matrix or a host read.
+//
+//   iif_nms             5 enqueued operations for any N <= IIF_NMS_MAX_BOXES and any data:
+//     clear     the 4 KiB workspace header (coordinate maximum, valid count).
+//     prepare   one sort key per box: valid << 56 | order-preserving bits of the score << 24 | ~index; the ids as int32; the
+//               maximum coordinate as an integer maximum of order-preserving bits.
+//     rank      every box counts the keys greater than its own (keys stream through LDS in tiles of 1024, so N is not bounded
+//               by LDS) and scatters itself to that position: score descending, equal scores to the lower index, boxes that
+//               take no part behind all others.  With ids the ranked copy holds the SHIFTED coordinates box + id * (max + 1),
+//               formed in float32 as batched_nms forms them.
+//     matrix    the upper triangle of the suppression bit matrix in 64 x 64 tiles: one wave per tile, the column boxes in LDS,
+//               one 64-bit word per (row, column block).  id_mode 2 tests pairs of equal id only.
+//     scan      one workgroup: mmcv's greedy walk over the ranked list.  The 64 diagonal bits of a block-row are resolved in
+//               one wave from registers (v_readlane); the words of the kept rows are ORed into a `removed` mask in LDS.  The
+//               block-row r + 1 is loaded (all 64 rows, whatever will be decided) before block-row r is resolved, so the walk
+//               never waits a memory round trip per kept box.  Writes keep, dets, the count and the padding; stops at max_num.
+//   iif_rpn_proposals   10 enqueued operations for any B <= 16, any number of levels <= 8 and any data:
+//     clear     header, histograms.
+//     select    x 5: the nms_pre largest (logit, lower flattened index first) of every (image, level) at once, as a radix select
+//               on the 56-bit number key << 24 | ~index in digits of 12, 12, 12, 12 and 8 bits: each pass histograms its digit
+//               among the elements that match the digits found so far (LDS atomics, flushed with integer global atomics); the
+//               next pass scans the histogram for the threshold digit.  The numbers are distinct, so five digits give the exact
+//               threshold: no boundary pass, no ordered sweep.  Scores and deltas are read in place through element strides.
+//     gather    takes the elements at or above the threshold, decodes them with the coder's shared device function
+//               (box_coder.h), computes the sigmoid, the min-size flag and the per-image coordinate maximum over the valid ones.
+//               A candidate's slot within its level comes from an integer counter; the rank step orders them, so the
+//               result does not depend on arrival order.
+//     rank, matrix, scan   as above, for all images at once, with the level as id (id_mode 1) and the key built from the LOGIT
+//               and the index into the concatenated anchors.
+//
+// Overlap test (mmcv nms_cuda_kernel.cuh), each step one IEEE float32 operation in this order (-ffp-contract=off):
+//     left = max(a.x1, b.x1), right = min(a.x2, b.x2), ...;  w = max(right - left + offset, 0), h likewise;  inter = w * h
+//     Sa = (a.x2 - a.x1 + offset) * (a.y2 - a.y1 + offset);  suppressed: inter / (Sa + Sb - inter) > iou_threshold (NaN: no)
+// Integer atomics only.  Nothing is allocated, nothing is read back.
+#include "common.h"
+#include "box_coder.h"
+
+namespace {
+
+typedef unsigned long long u64;
+typedef unsigned int u32;
+
+constexpr int kThreads = 256;
+constexpr int kSelThreads = 1024;             // the selection passes: thread t owns bins 4 t .. 4 t + 3
+constexpr int kScanThreads = 1024;            // the scan: 256 word columns x 4 groups of 16 rows
+constexpr int kBins = 4096;
+constexpr int kPasses = 5;                    // digits of 12, 12, 12, 12, 8 bits
+constexpr int kSegBlocks = 16;                // blocks per (image, level) in a selection pass
+constexpr int kRankTile = 1024;
+constexpr int kMaxLevels = 8, kMaxImages = 16;
+constexpr int kHeaderBytes = 4096;            // u32 words: [0, 16) coordinate maxima, [16, 144) level counters, [144, 160) valid counts
+constexpr int kHdrCount = 16, kHdrValid = 144;
+constexpr int64_t kHistBytes = (int64_t)kMaxLevels * kPasses * kBins * 4;     // per image
+constexpr int64_t kFrontPerImage = kHistBytes + 4096;                          // ... and its selection states
+constexpr u32 kIndexMask = 0xFFFFFFu;
+
+static_assert(kFrontPerImage == 659456, "IIF_NMS_WORKSPACE_BYTES counts 659456 bytes of histograms and states per image");
+
+struct SelState { u64 prefix; u32 rem; u32 pad; };
+
+// bits that order as unsigned integers the way the floats order; -0 and +0 are one value
+__device__ __forceinline__ u32 fkey(float f) {
+    u32 u = __float_as_uint(f);
+    if (f == 0.0f) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float fkey_inv(u32 k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+__device__ __forceinline__ u32 wave_max_u(u32 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const u32 t = (u32)__shfl_xor((int)v, o, 64);
+        v = t > v ? t : v;
+    }
+    return v;
+}
+
+// The sections of the workspace behind the header, histograms and states; Np = N rounded up to 64.
+struct Ws {
+    u32* hdr; u32* hist; SelState* state;
+    u64* sk; f32x4* sbox; f32x4* cbox; int* sorig; int* sid; float* cscore; int* ccidx; int* clevel; u64* mask;
+};
+
+Ws carve(void* ws, int B, int64_t Np) {
+    Ws w;
+    char* p = static_cast<char*>(ws);
+    w.hdr = reinterpret_cast<u32*>(p);
+    w.hist = reinterpret_cast<u32*>(p + kHeaderBytes);
+    w.state = reinterpret_cast<SelState*>(p + kHeaderBytes + (int64_t)B * kHistBytes);
+    p += kHeaderBytes + (int64_t)B * kFrontPerImage;
+    const int64_t e = (int64_t)B * Np;
+    w.sk = reinterpret_cast<u64*>(p); p += 8 * e;
+    w.sbox = reinterpret_cast<f32x4*>(p); p += 16 * e;
+    w.cbox = reinterpret_cast<f32x4*>(p); p += 16 * e;
+    w.sorig = reinterpret_cast<int*>(p); p += 4 * e;
+    w.sid = reinterpret_cast<int*>(p); p += 4 * e;
+    w.cscore = reinterpret_cast<float*>(p); p += 4 * e;
+    w.ccidx = reinterpret_cast<int*>(p); p += 4 * e;
+    w.clevel = reinterpret_cast<int*>(p); p += 4 * e;
+    w.mask = reinterpret_cast<u64*>(p);
+    return w;
+}
+
+// ------------------------------------------------------------------------------------------------ the NMS stage
+struct NmsArgs {
+    int B, N, Np, nw;
+    const float* boxes; int64_t ldb, box_img;             // box i of image b: boxes + b * box_img + i * ldb
+    const float* scores; int64_t score_img;
+    const int* ids;                                       // [B][Np] int32 in the workspace, or nullptr
+    int id_mode; float thr, offset;
+    int64_t cap;
+    int64_t* keep; float* dets; int64_t* count;
+    Ws w;
+    int64_t* cand_index; float* cand_boxes; float* cand_scores; int32_t* cand_level; int8_t* cand_valid;
+};
+
+struct PrepArgs {
+    const float* boxes; int64_t ldb; const float* scores; const int64_t* ids; int N; float score_thr; int want_max;
+    u64* sk; int* wid; u32* hdr;
+};
+
+__global__ void __launch_bounds__(kThreads) nms_prepare_kernel(PrepArgs a) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    u32 mk = 0u;
+    if (i < a.N) {
+        const float s = a.scores[i];
+        const bool valid = !(a.score_thr > 0.0f) || s > a.score_thr;       // NMSop.forward: filters only for a threshold > 0
+        a.sk[i] = ((u64)(valid ? 1u : 0u) << 56) | ((u64)fkey(s) << 24) | (u64)(kIndexMask - (u32)i);
+        if (a.ids) a.wid[i] = (int)a.ids[i];
+        if (a.want_max) {
+            const float* p = a.boxes + (int64_t)i * a.ldb;
+            mk = fkey(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])));
+        }
+    }
+    if (a.want_max) {
+        mk = wave_max_u(mk);
+        if ((threadIdx.x & 63) == 0 && mk != 0u) atomicMax(a.hdr, mk);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) nms_rank_kernel(NmsArgs a) {
+    __shared__ u64 s_tile[kRankTile];
+    __shared__ int s_nv;
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int i = blockIdx.x * kThreads + tid;
+    const int64_t row0 = (int64_t)b * a.Np;
+    const u64* sk = a.w.sk + row0;
+    const bool live = i < a.N;
+    const u64 my = live ? sk[i] : 0ull;
+    if (tid == 0) s_nv = 0;
+    int rank = 0;
+    for (int j0 = 0; j0 < a.N; j0 += kRankTile) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < kRankTile / kThreads; ++q) {
+            const int j = j0 + q * kThreads + tid;
+            s_tile[q * kThreads + tid] = j < a.N ? sk[j] : 0ull;           // 0 is greater than no key
+        }
+        __syncthreads();
+        const int cn = min(kRankTile, (a.N - j0 + 3) & ~3);
+        for (int j = 0; j < cn; j += 4) {
+            rank += (s_tile[j] > my) + (s_tile[j + 1] > my) + (s_tile[j + 2] > my) + (s_tile[j + 3] > my);
+        }
+    }
+    const bool valid = live && ((my >> 56) & 1ull);
+    const u64 vm = __ballot(valid);
+    if ((tid & 63) == 0 && vm) atomicAdd(&s_nv, __popcll(vm));
+    __syncthreads();
+    if (tid == 0 && s_nv) atomicAdd(a.w.hdr + kHdrValid + b, (u32)s_nv);
+    if (!live) return;
+    const float* p = a.boxes + (int64_t)b * a.box_img + (int64_t)i * a.ldb;
+    const Box box = {p[0], p[1], p[2], p[3]};
+    const int id = a.ids ? a.ids[row0 + i] : 0;
+    f32x4 s = {box.x1, box.y1, box.x2, box.y2};
+    if (a.id_mode) {
+        // batched_nms: offsets = idxs.to(boxes) * (boxes.max() + 1); boxes_for_nms = boxes + offsets[:, None]
+        const float off = (float)id * (fkey_inv(a.w.hdr[b]) + 1.0f);
+        s.x = box.x1 + off; s.y = box.y1 + off; s.z = box.x2 + off; s.w = box.y2 + off;
+    }
+    const int64_t o = row0 + rank;
+    a.w.sbox[o] = s;
+    a.w.sorig[o] = valid ? i : ~i;
+    a.w.sid[o] = id;
+    if (a.cand_index) {
+        const int64_t c = (int64_t)b * a.N + rank;
+        a.cand_index[c] = a.w.ccidx[row0 + i];
+        if (a.cand_boxes) *reinterpret_cast<f32x4*>(a.cand_boxes + 4 * c) = f32x4{box.x1, box.y1, box.x2, box.y2};
+        if (a.cand_scores) a.cand_scores[c] = a.scores[(int64_t)b * a.score_img + i];
+        if (a.cand_level) a.cand_level[c] = id;
+        if (a.cand_valid) a.cand_valid[c] = valid ? 1 : 0;
+    }
+}
+
+// One wave per 64 x 64 tile of the upper triangle: lane = row, the 64 column boxes in LDS.
+__global__ void __launch_bounds__(64) nms_matrix_kernel(NmsArgs a) {
+    __shared__ f32x4 s_box[64];
+    __shared__ float s_area[64];
+    __shared__ int s_id[64];
+    const int cb = blockIdx.x, rb = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
+    if (cb < rb) return;
+    const int nv = (int)a.w.hdr[kHdrValid + b];
+    if (rb * 64 >= nv) return;                               // rows that take no part are never read
+    const int64_t row0 = (int64_t)b * a.Np;
+    const float off = a.offset;
+    const int j = cb * 64 + lane;
+    if (j < nv) {
+        const f32x4 q = a.w.sbox[row0 + j];
+        s_box[lane] = q;
+        s_area[lane] = (q.z - q.x + off) * (q.w - q.y + off);
+        s_id[lane] = a.w.sid[row0 + j];
+    }
+    __syncthreads();
+    const int i = rb * 64 + lane;
+    if (i >= nv) return;
+    const f32x4 p = a.w.sbox[row0 + i];
+    const float sa = (p.z - p.x + off) * (p.w - p.y + off);
+    const int id = a.w.sid[row0 + i];
+    const bool same_id_only = a.id_mode == 2;
+    const int cn = min(64, nv - cb * 64);
+    u64 word = 0ull;
+    for (int c = 0; c < cn; ++c) {
+        const f32x4 q = s_box[c];
+        const float left = fmaxf(p.x, q.x), right = fminf(p.z, q.z);
+        const float top = fmaxf(p.y, q.y), bottom = fminf(p.w, q.w);
+        const float w = fmaxf(right - left + off, 0.0f), h = fmaxf(bottom - top + off, 0.0f);
+        const float inter = w * h;
+        const float iou = inter / (sa + s_area[c] - inter);
+        const bool hit = iou > a.thr && cb * 64 + c > i && (!same_id_only || s_id[c] == id);
+        word |= hit ? (1ull << c) : 0ull;
+    }
+    a.w.mask[(row0 + i) * a.nw + cb] = word;
+}
+
+__global__ void __launch_bounds__(kScanThreads) nms_scan_kernel(NmsArgs a) {
+    __shared__ u64 s_removed[256];
+    __shared__ u64 s_kept;
+    __shared__ int s_total;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int c = tid & 255, g = tid >> 8;                  // word column, group of 16 rows
+    const int64_t row0 = (int64_t)b * a.Np;
+    const int nw = a.nw;
+    const u64* mask = a.w.mask + row0 * nw;
+    int nv = (int)a.w.hdr[kHdrValid + b];
+    nv = nv > a.N ? a.N : nv;
+    const int nrb = (nv + 63) >> 6;
+    const int64_t cap = a.cap;
+    if (tid < 256) s_removed[tid] = 0ull;
+    if (tid == 0) { s_total = 0; s_kept = 0ull; }
+
+    // rows g * 16 .. + 15 of block-row r in column c (columns right of the diagonal), and the diagonal word of row `tid`
+    u64 cur[16], nxt[16];
+    u64 dcur = 0ull, dnxt = 0ull;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { cur[k] = 0ull; nxt[k] = 0ull; }
+    if (nrb > 0) {
+        if (c > 0 && c < nw) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) cur[k] = mask[(int64_t)(g * 16 + k) * nw + c];
+        }
+        if (tid < 64) dcur = mask[(int64_t)tid * nw];
+    }
+    int total = 0;
+    for (int r = 0; r < nrb; ++r) {
+        if (r + 1 < nrb) {
+            const int64_t base = (int64_t)(r + 1) * 64;
+            if (c > r + 1 && c < nw) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) nxt[k] = mask[(base + g * 16 + k) * nw + c];
+            }
+            if (tid < 64) dnxt = mask[(base + tid) * nw + r + 1];
+        }
+        __syncthreads();                                    // s_removed[r] is final
+        if (tid < 64) {
+            const int rows = min(64, nv - r * 64);
+            u64 rem = s_removed[r] | (rows == 64 ? 0ull : ~0ull << rows);
+            const u32 dlo = (u32)dcur, dhi = (u32)(dcur >> 32);
+            u64 kept = 0ull;
+#pragma unroll
+            for (int i = 0; i < 64; ++i) {
+                const u64 di = (u64)(u32)__builtin_amdgcn_readlane((int)dlo, i) |
+                               ((u64)(u32)__builtin_amdgcn_readlane((int)dhi, i) << 32);
+                const bool k = !((rem >> i) & 1ull);
+                kept |= k ? (1ull << i) : 0ull;
+                rem |= k ? di : 0ull;
+            }
+            const int64_t room = cap - total;
+            while ((int64_t)__popcll(kept) > room) kept &= ~(1ull << (63 - __clzll((long long)kept)));
+            if ((kept >> tid) & 1ull) {
+                const int64_t pos = total + __popcll(kept & ((1ull << tid) - 1ull));
+                const int o = a.w.sorig[row0 + r * 64 + tid];
+                if (a.keep) a.keep[(int64_t)b * cap + pos] = o;
+                if (a.dets) {
+                    const float* p = a.boxes + (int64_t)b * a.box_img + (int64_t)o * a.ldb;
+                    float* d = a.dets + ((int64_t)b * cap + pos) * 5;
+                    d[0] = p[0]; d[1] = p[1]; d[2] = p[2]; d[3] = p[3];
+                    d[4] = a.scores[(int64_t)b * a.score_img + o];
+                }
+            }
+            if (tid == 0) { s_kept = kept; s_total = total + __popcll(kept); }
+        }
+        __syncthreads();
+        const u64 kept = s_kept;
+        total = s_total;
+        if (total >= cap) break;                            // max_num: the rest of the walk cannot add a box
+        if (c > r && c < nw) {
+            const u32 kg = (u32)(kept >> (g * 16)) & 0xFFFFu;
+            u64 acc = 0ull;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) acc |= ((kg >> k) & 1u) ? cur[k] : 0ull;
+            if (acc) atomicOr(&s_removed[c], acc);
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) cur[k] = nxt[k];
+        dcur = dnxt;
+    }
+    for (int64_t pos = total + tid; pos < cap; pos += kScanThreads) {
+        if (a.keep) a.keep[(int64_t)b * cap + pos] = -1;
+        if (a.dets) {
+            float* d = a.dets + ((int64_t)b * cap + pos) * 5;
+            d[0] = 0.0f; d[1] = 0.0f; d[2] = 0.0f; d[3] = 0.0f; d[4] = 0.0f;
+        }
+    }
+    if (tid == 0) a.count[b] = total;
+}
+
+int launch_nms_stage(const NmsArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(nms_rank_kernel, dim3((unsigned)cdiv64(a.N, kThreads), (unsigned)a.B), dim3(kThreads), 0, st, a);
+    IIF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nms_matrix_kernel, dim3((unsigned)a.nw, (unsigned)a.nw, (unsigned)a.B), dim3(64), 0, st, a);
+    IIF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nms_scan_kernel, dim3((unsigned)a.B), dim3(kScanThreads), 0, st, a);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the RPN selection
+struct RpnArgs {
+    iif_rpn_level lv[kMaxLevels];
+    int L, B, Np;
+    int n[kMaxLevels], k[kMaxLevels], cand_off[kMaxLevels], anchor_off[kMaxLevels], vec_anchor[kMaxLevels];
+    float max_h[kMaxImages], max_w[kMaxImages];
+    Norm nm; float max_ratio, ctr_clamp, min_size; int add_ctr_clamp, clip;
+    Ws w;
+};
+
+__device__ __forceinline__ int digit_shift(int p) { return p < 4 ? 44 - 12 * p : 0; }
+__device__ __forceinline__ int digit_bits(int p) { return p < 4 ? 12 : 8; }
+
+// exclusive prefix sums over the block's 1024 threads; s_w: 17 words of LDS, reusable after the call returns
+__device__ __forceinline__ u32 block_scan_excl(u32 v, u32* s_w) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    u32 inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u32 t = (u32)__shfl_up((int)inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    if (wv == 0) {
+        const u32 x = lane < kSelThreads / 64 ? s_w[lane] : 0u;
+        u32 xi = x;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const u32 t = (u32)__shfl_up((int)xi, o, 64);
+            if (lane >= o) xi += t;
+        }
+        if (lane < kSelThreads / 64) s_w[lane] = xi - x;
+    }
+    __syncthreads();
+    const u32 res = s_w[wv] + inc - v;
+    __syncthreads();
+    return res;
+}
+
+// Pass p = 0 .. 4 histograms digit p; pass 5 gathers and decodes.  Every pass p >= 1 first turns the histogram of pass p - 1 into
+// the threshold digit (every block for itself; block 0 of the segment leaves the state for the next launch).
+__global__ void __launch_bounds__(kSelThreads) rpn_select_kernel(RpnArgs a, int p) {
+    __shared__ u32 s_h[kBins];
+    __shared__ u32 s_scan[kSelThreads / 64 + 1];
+    __shared__ u32 s_bin, s_rem;
+    const int tid = threadIdx.x;
+    const int seg = blockIdx.y, b = seg / a.L, l = seg - b * a.L;
+    const iif_rpn_level& lv = a.lv[l];
+    const int n = a.n[l], k = a.k[l];
+    SelState st;
+    st.prefix = 0ull; st.rem = (u32)k; st.pad = 0u;
+    if (p >= 1) {
+        if (p >= 2) st = a.w.state[seg * kPasses + p - 2];
+        const u32x4 h = reinterpret_cast<const u32x4*>(a.w.hist + ((int64_t)seg * kPasses + p - 1) * kBins)[tid];
+        const u32 hv[4] = {h.x, h.y, h.z, h.w};
+        if (tid == 0) { s_bin = 0u; s_rem = 1u; }
+        u32 cum = block_scan_excl(h.x + h.y + h.z + h.w, s_scan);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (cum < st.rem && st.rem <= cum + hv[j]) { s_bin = 4u * tid + j; s_rem = st.rem - cum; }
+            cum += hv[j];
+        }
+        __syncthreads();
+        const int bits = digit_bits(p - 1);
+        st.prefix = (st.prefix << bits) | (u64)(((1u << bits) - 1u) - s_bin);      // bins run from the largest digit down
+        st.rem = s_rem;
+        if (blockIdx.x == 0 && tid == 0) a.w.state[seg * kPasses + p - 1] = st;
+    }
+    const bool gather = p == kPasses;
+    if (!gather) {
+        for (int i = tid; i < kBins; i += kSelThreads) s_h[i] = 0u;
+        __syncthreads();
+    }
+    const int shift = gather ? 0 : digit_shift(p);
+    const u32 dmask = gather ? 0u : (1u << digit_bits(p)) - 1u;
+    const int pshift = p >= 1 ? digit_shift(p - 1) : 0;
+    const float* sp = lv.scores + (int64_t)b * lv.score_strides[0];
+    const float* dp = lv.deltas + (int64_t)b * lv.delta_strides[0];
+    const int64_t row0 = (int64_t)b * a.Np;
+    u32 mk = 0u;
+    for (int base = blockIdx.x * kSelThreads; base < n; base += kSegBlocks * kSelThreads) {
+        const int f = base + tid;                           // flattened index (h * W + w) * A + anchor
+        if (f < n) {
+            const int an = f % lv.A, hw = f / lv.A;
+            const int x = hw % lv.W, y = hw / lv.W;
+            const float logit = sp[an * lv.score_strides[1] + y * lv.score_strides[2] + x * lv.score_strides[3]];
+            const u32 key = fkey(logit);
+            const u64 cmp = ((u64)key << 24) | (u64)(kIndexMask - (u32)f);
+            if (!gather) {
+                if (p == 0 || (cmp >> pshift) == st.prefix) atomicAdd(&s_h[dmask - ((u32)(cmp >> shift) & dmask)], 1u);
+            } else if (cmp >= st.prefix) {
+                const u32 slot = atomicAdd(a.w.hdr + kHdrCount + seg, 1u);
+                if ((int)slot < k) {
+                    const Box anc = load_box(lv.anchors + (int64_t)f * lv.ld_anchors, a.vec_anchor[l] != 0);
+                    const float* d = dp + (int64_t)(4 * an) * lv.delta_strides[1] + y * lv.delta_strides[2] + x * lv.delta_strides[3];
+                    const Box t = {d[0], d[lv.delta_strides[1]], d[2 * lv.delta_strides[1]], d[3 * lv.delta_strides[1]]};
+                    const f32x4 o = decode_box(anc, t, a.nm, a.max_ratio, a.add_ctr_clamp, a.ctr_clamp, a.clip, a.max_h[b], a.max_w[b]);
+                    const bool valid = a.min_size < 0.0f || ((o.z - o.x) > a.min_size && (o.w - o.y) > a.min_size);
+                    const int cidx = a.anchor_off[l] + f;
+                    const int64_t at = row0 + a.cand_off[l] + slot;
+                    a.w.cbox[at] = o;
+                    a.w.cscore[at] = 1.0f / (1.0f + expf(-logit));
+                    a.w.ccidx[at] = cidx;
+                    a.w.clevel[at] = l;
+                    a.w.sk[at] = ((u64)(valid ? 1u : 0u) << 56) | ((u64)key << 24) | (u64)(kIndexMask - (u32)cidx);
+                    if (valid) mk = max(mk, fkey(fmaxf(fmaxf(o.x, o.y), fmaxf(o.z, o.w))));
+                }
+            }
+        }
+    }
+    if (gather) {
+        mk = wave_max_u(mk);
+        if ((tid & 63) == 0 && mk != 0u) atomicMax(a.w.hdr + b, mk);
+    } else {
+        __syncthreads();
+        u32* hist = a.w.hist + ((int64_t)seg * kPasses + p) * kBins;
+        for (int i = tid; i < kBins; i += kSelThreads)
+            if (s_h[i] != 0u) atomicAdd(hist + i, s_h[i]);
+    }
+}
+
+bool aligned_to(const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int iif_nms(const float* boxes, int64_t ld_boxes, const float* scores, const int64_t* ids, int64_t N, int id_mode,
+            float iou_threshold, int offset, float score_threshold, int64_t max_num, int64_t* keep, float* dets, int64_t* count,
+            void* d_workspace, int64_t workspace_bytes, void* stream) {
+    if (N < 0 || N > IIF_NMS_MAX_BOXES || ld_boxes < 4 || id_mode < 0 || id_mode > 2 || (offset != 0 && offset != 1)) return IIF_EINVAL;
+    if (iou_threshold != iou_threshold || score_threshold != score_threshold || !count || !aligned_to(count, 8)) return IIF_EINVAL;
+    if (!aligned_to(boxes, 4) || !aligned_to(scores, 4) || !aligned_to(ids, 8) || !aligned_to(keep, 8) || !aligned_to(dets, 4)) return IIF_EINVAL;
+    hipStream_t st = as_stream(stream);
+    if (N == 0) {
+        if (hipMemsetAsync(count, 0, 8, st) != hipSuccess) return IIF_ELAUNCH;
+        return IIF_OK;
+    }
+    if (!boxes || !scores || !keep || (id_mode != 0 && !ids)) return IIF_EINVAL;
+    if (!d_workspace || !aligned_to(d_workspace, 16) || workspace_bytes < IIF_NMS_WORKSPACE_BYTES(1, N)) return IIF_EINVAL;
+    NmsArgs a{};
+    a.B = 1; a.N = (int)N; a.Np = (int)((N + 63) / 64 * 64); a.nw = a.Np / 64;
+    a.w = carve(d_workspace, 1, a.Np);
+    a.boxes = boxes; a.ldb = ld_boxes; a.box_img = 0;
+    a.scores = scores; a.score_img = 0;
+    a.id_mode = id_mode; a.thr = iou_threshold; a.offset = (float)offset;
+    a.cap = max_num > 0 && max_num < N ? max_num : N;
+    a.keep = keep; a.dets = dets; a.count = count;
+    // the unranked ids live in the candidate-level section, which the plain entry does not use otherwise
+    a.ids = id_mode ? a.w.clevel : nullptr;
+    PrepArgs p{};
+    p.boxes = boxes; p.ldb = ld_boxes; p.scores = scores; p.ids = id_mode ? ids : nullptr; p.N = (int)N;
+    p.score_thr = score_threshold; p.want_max = id_mode != 0;
+    p.sk = a.w.sk; p.wid = a.w.clevel; p.hdr = a.w.hdr;
+    if (hipMemsetAsync(d_workspace, 0, kHeaderBytes, st) != hipSuccess) return IIF_ELAUNCH;
+    hipLaunchKernelGGL(nms_prepare_kernel, dim3((unsigned)cdiv64(N, kThreads)), dim3(kThreads), 0, st, p);
+    IIF_LAUNCH_CHECK();
+    return launch_nms_stage(a, st);
+}
+
+int iif_rpn_proposals(const iif_rpn_level* levels, int num_levels, int B, const float* img_hw, int nms_pre, int max_per_img,
+                      float min_bbox_size, float iou_threshold, int offset, const float* means, const float* stds, float max_ratio,
+                      int add_ctr_clamp, float ctr_clamp, int clip, float* dets, int64_t* counts, int64_t* cand_index,
+                      float* cand_boxes, float* cand_scores, int32_t* cand_level, int8_t* cand_valid, void* d_workspace,
+                      int64_t workspace_bytes, void* stream) {
+    if (!levels || num_levels < 1 || num_levels > kMaxLevels || B < 1 || B > kMaxImages || !img_hw || !means || !stds) return IIF_EINVAL;
+    if (max_per_img < 1 || (offset != 0 && offset != 1) || iou_threshold != iou_threshold || min_bbox_size != min_bbox_size) return IIF_EINVAL;
+    if (!dets || !counts || !aligned_to(dets, 4) || !aligned_to(counts, 8) || !aligned_to(cand_index, 8) || !aligned_to(cand_boxes, 16) ||
+        !aligned_to(cand_scores, 4) || !aligned_to(cand_level, 4))
+        return IIF_EINVAL;
+    if ((cand_boxes || cand_scores || cand_level || cand_valid) && !cand_index) return IIF_EINVAL;
+    RpnArgs r{};
+    int64_t ncand = 0, nanchor = 0;
+    for (int l = 0; l < num_levels; ++l) {
+        const iif_rpn_level& lv = levels[l];
+        if (!lv.scores || !lv.deltas || !lv.anchors || !aligned_to(lv.scores, 4) || !aligned_to(lv.deltas, 4) || !aligned_to(lv.anchors, 4))
+            return IIF_EINVAL;
+        if (lv.A < 1 || lv.H < 1 || lv.W < 1 || lv.ld_anchors < 4) return IIF_EINVAL;
+        const int64_t n = (int64_t)lv.A * lv.H * lv.W;
+        if (n > (int64_t)kIndexMask) return IIF_EINVAL;
+        const int64_t k = nms_pre > 0 && n > nms_pre ? nms_pre : n;
+        r.lv[l] = lv;
+        r.n[l] = (int)n; r.k[l] = (int)k; r.cand_off[l] = (int)ncand; r.anchor_off[l] = (int)nanchor;
+        r.vec_anchor[l] = aligned_to(lv.anchors, 16) && lv.ld_anchors % 4 == 0;
+        ncand += k; nanchor += n;
+        if (ncand > IIF_NMS_MAX_BOXES || nanchor > (int64_t)kIndexMask) return IIF_EINVAL;
+    }
+    if (!d_workspace || !aligned_to(d_workspace, 16) || workspace_bytes < IIF_NMS_WORKSPACE_BYTES(B, ncand)) return IIF_EINVAL;
+    const int Np = (int)((ncand + 63) / 64 * 64);
+    r.L = num_levels; r.B = B; r.Np = Np;
+    for (int b = 0; b < B; ++b) { r.max_h[b] = img_hw[2 * b]; r.max_w[b] = img_hw[2 * b + 1]; }
+    for (int i = 0; i < 4; ++i) { r.nm.m[i] = means[i]; r.nm.s[i] = stds[i]; }
+    r.max_ratio = max_ratio; r.ctr_clamp = ctr_clamp; r.min_size = min_bbox_size;
+    r.add_ctr_clamp = add_ctr_clamp != 0; r.clip = clip != 0;
+    r.w = carve(d_workspace, B, Np);
+    NmsArgs a{};
+    a.B = B; a.N = (int)ncand; a.Np = Np; a.nw = Np / 64;
+    a.w = r.w;
+    a.boxes = reinterpret_cast<const float*>(r.w.cbox); a.ldb = 4; a.box_img = 4 * (int64_t)Np;
+    a.scores = r.w.cscore; a.score_img = Np;
+    a.ids = r.w.clevel;
+    a.id_mode = 1; a.thr = iou_threshold; a.offset = (float)offset;
+    a.cap = max_per_img;
+    a.keep = nullptr; a.dets = dets; a.count = counts;
+    a.cand_index = cand_index; a.cand_boxes = cand_boxes; a.cand_scores = cand_scores; a.cand_level = cand_level; a.cand_valid = cand_valid;
+    hipStream_t st = as_stream(stream);
+    if (hipMemsetAsync(d_workspace, 0, (size_t)(kHeaderBytes + (int64_t)B * kHistBytes), st) != hipSuccess) return IIF_ELAUNCH;
+    for (int p = 0; p <= kPasses; ++p) {
+        hipLaunchKernelGGL(rpn_select_kernel, dim3(kSegBlocks, (unsigned)(B * num_levels)), dim3(kSelThreads), 0, st, r, p);
+        IIF_LAUNCH_CHECK();
+    }
+    return launch_nms_stage(a, st);
+}
+
+}  // extern "C"

@@ -27,6 +27,7 @@
 // Arithmetic of the coder: every step is the reference's single IEEE float32 operation in its order (the build passes
 // -ffp-contract=off; `/` is the correctly rounded division); logf / expf are the device library's.
 #include "common.h"
+#include "box_coder.h"
 
 namespace {
 
@@ -41,17 +42,6 @@ constexpr int kWordsOffset = 65536 / 4;       // the per-candidate words start 6
 constexpr unsigned kMaxBlocks = 1u << 16;
 
 typedef unsigned long long u64;
-
-struct alignas(16) Box { float x1, y1, x2, y2; };
-struct Norm { float m[4], s[4]; };
-
-__device__ __forceinline__ Box load_box(const float* p, bool vec) {
-    if (vec) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        return Box{t.x, t.y, t.z, t.w};
-    }
-    return Box{p[0], p[1], p[2], p[3]};
-}
 
 // bbox2delta (:119-139).  Shared by iif_bbox2delta and both target builders.
 __device__ __forceinline__ f32x4 encode_delta(const Box& p, const Box& g, const Norm& nm) {
@@ -88,15 +78,6 @@ struct DecArgs {
     float* out;
 };
 
-// torch.where(x < 0, 0, x) then torch.where(x > hi, hi, x): a NaN fails both comparisons and passes through
-__device__ __forceinline__ float clip_coord(float x, float hi) {
-    x = x < 0.0f ? 0.0f : x;
-    return x > hi ? hi : x;
-}
-// torch.clamp: a NaN stays a NaN
-__device__ __forceinline__ float clamp_lo(float x, float lo) { return x < lo ? lo : x; }
-__device__ __forceinline__ float clamp_hi(float x, float hi) { return x > hi ? hi : x; }
-
 // delta2bbox (:206-270), one lane per (row, class)
 __global__ void __launch_bounds__(kThreads) delta2bbox_kernel(DecArgs a) {
     const int64_t total = a.n * a.K;
@@ -106,31 +87,7 @@ __global__ void __launch_bounds__(kThreads) delta2bbox_kernel(DecArgs a) {
         const int k = (int)(e - i * a.K);
         const Box p = load_box(a.r + i * a.ldr, a.vecr != 0);
         const Box t = load_box(a.d + i * a.ldd + 4 * k, a.vecd != 0);
-        const float dx = t.x1 * a.nm.s[0] + a.nm.m[0];
-        const float dy = t.y1 * a.nm.s[1] + a.nm.m[1];
-        float dw = t.x2 * a.nm.s[2] + a.nm.m[2];
-        float dh = t.y2 * a.nm.s[3] + a.nm.m[3];
-        const float px = (p.x1 + p.x2) * 0.5f, py = (p.y1 + p.y2) * 0.5f;
-        const float pw = p.x2 - p.x1, ph = p.y2 - p.y1;
-        float dxw = pw * dx, dyh = ph * dy;
-        if (a.add_ctr_clamp) {
-            dxw = clamp_hi(clamp_lo(dxw, -a.ctr_clamp), a.ctr_clamp);
-            dyh = clamp_hi(clamp_lo(dyh, -a.ctr_clamp), a.ctr_clamp);
-            dw = clamp_hi(dw, a.max_ratio);
-            dh = clamp_hi(dh, a.max_ratio);
-        } else {
-            dw = clamp_hi(clamp_lo(dw, -a.max_ratio), a.max_ratio);
-            dh = clamp_hi(clamp_lo(dh, -a.max_ratio), a.max_ratio);
-        }
-        const float gw = pw * expf(dw), gh = ph * expf(dh);
-        const float gx = px + dxw, gy = py + dyh;
-        const float hw = gw * 0.5f, hh = gh * 0.5f;
-        f32x4 o;
-        o.x = gx - hw; o.y = gy - hh; o.z = gx + hw; o.w = gy + hh;
-        if (a.clip) {
-            o.x = clip_coord(o.x, a.max_w); o.y = clip_coord(o.y, a.max_h);
-            o.z = clip_coord(o.z, a.max_w); o.w = clip_coord(o.w, a.max_h);
-        }
+        const f32x4 o = decode_box(p, t, a.nm, a.max_ratio, a.add_ctr_clamp, a.ctr_clamp, a.clip, a.max_h, a.max_w);
         *reinterpret_cast<f32x4*>(a.out + 4 * e) = o;
     }
 }

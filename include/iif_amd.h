@@ -1012,6 +1012,74 @@ int iif_roi_extract_backward(const iif_roi_level* grad_levels, int num_levels, i
                              float roi_scale_factor, const float* grad_out, int grad_channels_last, void* arena,
                              int64_t arena_bytes, void* stream);
 
+/* Non-maximum suppression (mmcv 1.3.8 ops/nms.py nms / batched_nms; iif_amd/mmdet_nms.py) in 5 enqueued operations for any N and
+ * any data: a 4 KiB clear, the sort keys, the rank, the suppression bit matrix, the greedy scan (csrc/nms.hip).
+ * boxes [N] rows of (x1, y1, x2, y2, ...) fp32, ld_boxes floats apart (>= 4), read in place; scores [N] fp32.
+ *   rank     score descending, equal scores to the LOWER index (mmcv's sort is unstable: any tie order is one of its outputs).
+ *   test     box b is suppressed by a kept box a of higher rank when inter / (Sa + Sb - inter) > iou_threshold, with
+ *            w = max(min(a.x2, b.x2) - max(a.x1, b.x1) + offset, 0), h likewise, inter = w * h, S = (x2 - x1 + offset) *
+ *            (y2 - y1 + offset): single float32 operations in this order; a NaN quotient does not suppress.  offset: 0 or 1.
+ *   scan     mmcv's: walk the ranked list, keep a box unless a box KEPT earlier suppresses it.
+ *   ids      int64 [N], read for id_mode != 0.  1: every coordinate gets id * (max over all coordinates of `boxes` + 1) added in
+ *            float32 (the maximum is reduced on the device) and every pair is tested on the shifted boxes - batched_nms below
+ *            split_thr, including its quirk that boxes of different ids can meet when coordinates lie below -1.  2: the same
+ *            shifted boxes, pairs of equal id only - batched_nms at or above split_thr (a plain NMS per id, merged by rank).
+ *            Ids must lie in the int32 range: they are narrowed to int32 before the conversion to float (mmcv converts the int64
+ *            directly); the module's callers pass class or level numbers.  The maximum is reduced with fmaxf: a NaN coordinate
+ *            is dropped from it, where torch's max would make every shift NaN.  NaN coordinates are not reproduced.
+ *   score_threshold > 0: boxes with score <= score_threshold take no part (mmcv filters only for a threshold above 0).
+ *   max_num > 0: the scan stops after max_num kept boxes.
+ * keep: int64 [cap], cap = max_num > 0 ? min(max_num, N) : N: the kept input indices in rank order, then -1.  dets (nullable):
+ * fp32 [cap][5] = the kept boxes as given (unshifted) and their scores, then zeros.  count: int64 [1].
+ * d_workspace: IIF_NMS_WORKSPACE_BYTES(1, N) on a 16-byte boundary; it belongs to the call until the stream has run it.  Its
+ * contents on entry do not matter.  Allocates nothing, reads nothing back; integer atomics only.
+ * IIF_EINVAL before anything is enqueued: N < 0 or > IIF_NMS_MAX_BOXES (the matrix is N^2 / 8 bytes: 32 MiB there), ld_boxes < 4,
+ * id_mode outside 0 .. 2, offset outside 0 .. 1, a NaN threshold, a null or misaligned count, and for N > 0 a null boxes / scores /
+ * keep (ids with id_mode != 0) or a null, misaligned or short workspace.  N == 0: count = 0 (one operation). */
+#define IIF_NMS_MAX_BOXES 16384
+#define IIF_NMS_WORKSPACE_BYTES(B, N) (4096 + (int64_t)(B) * (659456 + (((int64_t)(N) + 63) / 64 * 64) * (64 + (((int64_t)(N) + 63) / 64 * 64) / 8)))
+int iif_nms(const float* boxes, int64_t ld_boxes, const float* scores, const int64_t* ids /* int64 [N] or NULL */, int64_t N,
+            int id_mode, float iou_threshold, int offset, float score_threshold, int64_t max_num, int64_t* keep,
+            float* dets /* nullable */, int64_t* count, void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* The RPN proposal step (mmdet models/dense_heads/rpn_head.py:79-225 with the sigmoid classifier) for B images and all levels
+ * in 10 enqueued operations, whatever B, the number of levels and the data: a clear, five radix-select passes, the gather with
+ * decode, then the rank, matrix and scan of the NMS entry for all images at once.
+ * levels: a HOST array of num_levels (1 .. 8) descriptors, copied into the launches.  scores is the head's [B, A, H, W] output and
+ * deltas its [B, 4 A, H, W] output, both fp32 and read IN PLACE through their four element strides (NCHW and channels_last both
+ * work); anchors [A H W] rows of 4 floats, ld_anchors apart, in the order of the flattened index (h * W + w) * A + a.
+ * Per image and level the nms_pre largest logits are taken, equal logits to the lower flattened index; a level with at most nms_pre
+ * anchors, or nms_pre <= 0, gives all of them.  (Sigmoid is monotone, so this is the reference's selection by score wherever the
+ * float32 sigmoid keeps distinct logits distinct.)  The candidates are decoded with the arithmetic of the delta2bbox entry (the
+ * same device function) against max_shape = img_hw[b] (a HOST array of B pairs (max_h, max_w); clip: the coder's clip_border);
+ * score = 1 / (1 + expf(-logit)); with min_bbox_size >= 0 a candidate takes part only if w > min_bbox_size && h > min_bbox_size.
+ * The NMS is batched_nms with the level as id, ALWAYS id_mode 1 above (the reference switches to a per-level NMS when split_thr
+ * or more candidates take part: the caller keeps Ncand below its split_thr, as iif_amd/mmdet_nms.py does; the maximum runs over
+ * the candidates that take part), ranked by
+ * (logit descending, index into the concatenated anchors ascending).
+ * dets: fp32 [B][max_per_img][5], the kept boxes and scores in rank order, then zeros; counts: int64 [B].
+ * cand_* (cand_index NULL: none; the others nullable): the RANKED candidates of every image, Ncand = sum over the levels of
+ * min(nms_pre, A H W) each, those that take no part behind the others: cand_index int64 [B][Ncand] (index into the concatenated
+ * anchors), cand_boxes fp32 [B][Ncand][4] (16-byte aligned), cand_scores fp32, cand_level int32, cand_valid int8.
+ * d_workspace: IIF_NMS_WORKSPACE_BYTES(B, Ncand) on a 16-byte boundary, contents on entry do not matter.
+ * IIF_EINVAL before anything is enqueued: a null levels / img_hw / means / stds / dets / counts, num_levels outside 1 .. 8, B outside
+ * 1 .. 16, max_per_img < 1, offset outside 0 .. 1, a NaN threshold or size, a level with a null or misaligned pointer, A / H / W < 1
+ * or ld_anchors < 4, Ncand > IIF_NMS_MAX_BOXES, 2^24 or more anchors per image, a null, misaligned or short workspace. */
+typedef struct iif_rpn_level {
+    const float* scores;
+    const float* deltas;
+    const float* anchors;
+    int64_t score_strides[4];
+    int64_t delta_strides[4];
+    int64_t ld_anchors;
+    int32_t A, H, W, reserved;
+} iif_rpn_level;
+int iif_rpn_proposals(const iif_rpn_level* levels, int num_levels, int B, const float* img_hw, int nms_pre, int max_per_img,
+                      float min_bbox_size, float iou_threshold, int offset, const float* means, const float* stds, float max_ratio,
+                      int add_ctr_clamp, float ctr_clamp, int clip, float* dets, int64_t* counts, int64_t* cand_index /* nullable */,
+                      float* cand_boxes, float* cand_scores, int32_t* cand_level, int8_t* cand_valid, void* d_workspace,
+                      int64_t workspace_bytes, void* stream);
+
 /* CIFAR training input (iif_amd/cifar.py DeviceCIFARLoader): ONE launch per batch builds out[b] (fp32 NCHW [batch][3][32][32])
  * and targets[b] = labels[index[b]] from the device-resident dataset data (uint8 [n][3][32][32], the planar rows of the
  * CIFAR files) and labels (int64 [n]).  flags select the stages, applied in the reference's order (initialisers.py:116-134):
