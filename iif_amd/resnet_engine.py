@@ -25,6 +25,7 @@ fp32 MFMA, used to match the CPU reference to 1e-4).
 """
 import math
 import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -811,6 +812,33 @@ class _ConvUnit(object):
                  "groups", "dwp", "bits", "geom", "s2d", "wf", "wtf")
 
 
+class _Route(NamedTuple):
+    """How the closing conv + BN of one block runs in a training step.  Decided once per plan by _train_routes, in the order
+    of the fields; the default is the standard route of every unit."""
+    backward: str = "standard"    # standard | pure (sums from P) | producer (its sums from the stored output) | rx (... recomputed)
+    forward: str = "stored"       # stored | twopass | nostore
+    prologue: bool = False        # bn2 + ReLU in conv3's operand path
+    csum_rows: bool = False       # ... and that launch leaves the column sums of a2 for the algebra
+    gram: Optional[str] = None    # where a2^T a2 is formed: ahead | stacked (behind P) | producer; None without the algebra
+    ds_algebra: bool = False      # the block's stride-1 shortcut takes the same algebra (_ds_algebra)
+
+
+_STANDARD = _Route()
+
+
+class _Conv3State(object):
+    """Buffers of one closing unit's route and what the last launches left in them.  prologue: ``u2``, the conv2 unit; csum_rows:
+    ``rows`` / ``sums``, partial rows of a2's column sums and the [2, cin] sums, ``rows_count`` rows from the last forward (0: no
+    prologue ran); gram "producer": ``slabs`` of P / Gram and the ``slab_count`` of the last launch; ``g_rows``: where the
+    producer leaves its per-tile sums of g~ (ds_algebra: rows of their own, else the plan's bw_partial)."""
+    __slots__ = ("u2", "rows", "sums", "rows_count", "slabs", "slab_count", "g_rows")
+
+    def __init__(self, g_rows):
+        self.u2 = self.rows = self.sums = self.slabs = None
+        self.rows_count = self.slab_count = 0
+        self.g_rows = g_rows
+
+
 class _Plan(object):
     def __init__(self, net, n, h, w):
         self.net = net
@@ -938,117 +966,7 @@ class _Plan(object):
                                       dtype=torch.float32, device=dev)
         self.fuse_bwd = dt == torch.bfloat16 and not os.environ.get("IIF_NO_BWD_FUSE")
         self._bw_ready = None
-        # BN backward through the expanding 1x1 layer of a bottleneck by algebra (csrc/bn3_algebra.hip): the block-output
-        # gradient arrives already gated by the block's ReLU (the producing data gradient stores it so), and conv3's output is
-        # never re-read by a BN-backward pass.  Units: the last conv+BN of every bottleneck with <= 256 input channels.
-        # Two variants (measured): "pure" takes sum g~ y from P = g~^T a2 (conv3's output is not read at all in
-        # backward, 4 passes over that tensor saved, but P sits on the compute stream before the data gradient) - it wins
-        # where the tensor is large (>= 1.5e8 elements: the 56 x 56 stage at batch 256); otherwise the producing data gradient
-        # still reads conv3's output once for sum g~ xhat (3 passes saved) and P moves to the weight-gradient stream.
         self.wg_lag = int(os.environ.get("IIF_WG_LAG", "2"))      # blocks the weight-gradient stream may lag (explained where the side streams are created; 3 / 4 / 6 measured level)
-        self.alg3_units = set()
-        # (round 6: 9e7 = the 56 x 56 and 28 x 28 stages at batch 256 - "sums from P" is what lets the forward pass never store
-        # conv3's output, see nostore_units below; 1.5e8 = the 56 x 56 stage only, as in rounds 3-5)
-        self.a3_pure_min = float(os.environ.get("IIF_BN3_ALGEBRA_PURE_MIN_ELEMS", "9e7"))
-        if self.fuse_bwd and net._sync_bn is None and not os.environ.get("IIF_NO_BN3_ALGEBRA"):
-            for bi, b in enumerate(self.blocks[:-1]):
-                if "se" in b or "sc" in b or len(b["units"]) != 3:
-                    continue
-                u3 = b["units"][-1]
-                cv3 = u3.conv
-                # the route is taken only if the producer of this block's output gradient - the next block's conv1 data
-                # gradient - can store it gated and emit the sums (decided here, so that the Gram matrix of a unit is only
-                # ever computed for a unit that will use it)
-                nxt = self.blocks[bi + 1]
-                f = nxt["units"][0]
-                producer = ("se" not in nxt and f.conv.k == 1 and f.conv.stride == 1 and f.conv.groups == 1 and _dma_ok(f.x)
-                            and _dma_ok(nxt["inp"]))
-                if (producer and cv3.k == 1 and cv3.stride == 1 and cv3.groups == 1 and cv3.cin in (64, 128, 256) and cv3.cout % 64 == 0
-                        and cv3.cout <= 4096 and _dma_ok(u3.x) and u3.n * u3.ho * u3.wo < (1 << 30)):
-                    self.alg3_units.add(u3)
-        # Two-pass forward (conv3's raw output is never stored): pass 1 = statistics only, pass 2 = the same convolution with
-        # BN + identity + ReLU in its epilogue (bit-identical to conv + bn_apply).  Only where backward never needs that
-        # output: "sums from P" algebra units of identity blocks whose gradient producer (the next block's conv1 data gradient)
-        # takes the gated-store route.  Measured level with conv + bn_apply (339 against 341 us per 56 x 56 block: the statistics
-        # pass costs a whole convolution launch although it stores nothing), so it is opt-in: IIF_TWOPASS=1.
-        self.twopass_units = set()
-        if self.alg3_units and os.environ.get("IIF_TWOPASS"):
-            for bi, b in enumerate(self.blocks[:-1]):
-                u3 = b["units"][-1]
-                nxt = self.blocks[bi + 1]
-                f = nxt["units"][0]
-                if (u3 in self.alg3_units and self._a3_is_pure(u3) and "ds" not in b and "se" not in nxt and f.conv.k == 1
-                        and f.conv.stride == 1 and f.groups == 1 and _dma_ok(f.y) and _dma_ok(u3.src)):
-                    self.twopass_units.add(u3)
-        # Never-stored forward on the register-weight kernel (round 6): pass 1 = the convolution's statistics straight from the
-        # accumulators (iif_conv_igemm_stats_acc: nothing staged, nothing stored, ~the time of reading a2 once), finalisation,
-        # pass 2 = the convolution again with bn3 + identity (or the NORMALISED output of the block's convolutional shortcut) +
-        # ReLU + ReLU bits in its epilogue (iif_conv_igemm_bn_relu2).  conv3's raw output - the widest tensor of the block - is
-        # neither written nor read: -2 passes over [M, C] per block for one more pass over [M, c].  Units: every "sums from P"
-        # algebra unit whose shape the kernel takes, downsample blocks included.  IIF_NO_NOSTORE=1 switches it off.
-        # "sums from the producer" WITHOUT the stored output (round 6, iif_conv_igemm_dgrad_masksum_rx): the data gradient that
-        # produces g~ recomputes conv3's tile from a2 and W3 on the matrix pipe for its sum g~ xhat.  P leaves the compute stream again
-        # (7 launches, 1.4 ms at batch 256: profiles/r6 timeline) and nothing reads conv3's output.  Preferred over "sums from P"
-        # wherever the register-weight kernel has the (K, c) instance.  IIF_NO_RX=1 switches it off.
-        self.rx_units = set()
-        if self.alg3_units and not os.environ.get("IIF_NO_RX"):
-            for bi, b in enumerate(self.blocks[:-1]):
-                u3 = b["units"][-1]
-                f = self.blocks[bi + 1]["units"][0]
-                if u3 in self.alg3_units and ops.conv_dgrad_rx_ok(f.n, f.hi, f.wi, f.conv.cout, f.conv.cin, u3.conv.cin, dt):
-                    self.rx_units.add(u3)
-        self.nostore_units = set()
-        if self.alg3_units and not os.environ.get("IIF_NO_NOSTORE"):
-            for b in self.blocks[:-1]:
-                u3 = b["units"][-1]
-                if (u3 in self.alg3_units and (self._a3_is_pure(u3) or u3 in self.rx_units) and u3 not in self.twopass_units
-                        and ops.conv_fwdbn_ok(u3.n, u3.ho, u3.wo, u3.conv.cin, u3.conv.cout, dt) and _dma_ok(u3.src)):
-                    self.nostore_units.add(u3)
-        # bn2 + ReLU in conv3's operand path (round 6, iif_conv_igemm_bnstats_pro): conv3 (or its statistics pass) reads conv2's RAW
-        # output, normalises each tile in LDS and writes a2 / its ReLU bits / its column sums as by-products: one launch and one pass
-        # over a2 less per bottleneck.  pro_units: conv3 unit -> (conv2 unit, rows of column sums or None).  IIF_NO_PROLOGUE=1: off.
-        self.pro_units = {}
-        # (K = 512 - the 7 x 7 stage, ResNeXt-101's 14 x 14 one - stays with the separate bn_apply launch: every N slice of the
-        # register-weight kernel normalises the whole [rows x K] tile again, 22 us on top of a 39 us launch against a 10 us bn_apply;
-        # ResNeXt-101 21.28 -> 21.14 ms, ResNet-50 level, profiles/r6_ab.txt ab11)
-        pro_max_k = int(os.environ.get("IIF_PRO_MAX_K", "256"))
-        if dt == torch.bfloat16 and net._sync_bn is None and not os.environ.get("IIF_NO_PROLOGUE"):
-            for b in self.blocks:
-                if "se" in b or len(b["units"]) != 3:
-                    continue
-                u2, u3 = b["units"][1], b["units"][2]
-                cv3 = u3.conv
-                if not (cv3.k == 1 and cv3.stride == 1 and cv3.groups == 1 and _dma_ok(u2.x)) or u3 in self.twopass_units:
-                    continue
-                if cv3.cin > pro_max_k:
-                    continue
-                if ops.conv_pro_ok(u3.n, u3.ho, u3.wo, cv3.cin, cv3.cout, dt, u3 in self.nostore_units):
-                    rows = None
-                    if u3 in self.alg3_units:
-                        rows = torch.zeros(((u3.n * u3.ho * u3.wo + 127) // 128 + 8) * 2 * cv3.cin, dtype=torch.float32, device=dev)
-                    fin = torch.zeros((2, cv3.cin), dtype=torch.float32, device=dev) if rows is not None else None
-                    # [conv2 unit, partial rows of a2's column sums, their count in the last forward, instance kind, the sums themselves]
-                    self.pro_units[u3] = [u2, rows, 0, u3 in self.nostore_units, fin]
-        self.a3 = None
-        if self.alg3_units:
-            cm = max(u.conv.cin for u in self.alg3_units)
-            Cm = max(u.conv.cout for u in self.alg3_units)
-            ldm = max(u.conv.ldw for u in self.alg3_units)
-            F = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)   # noqa: E731
-            # per-block scratch rotates over wg_lag slots (the weight-gradient stream finishes block b before block b - wg_lag
-            # starts: _wgrad_fence); Gram / colsum are issued one block AHEAD on another stream, so they rotate over wg_lag + 1
-            # "P" holds P = g~^T a2 [C, ldw] and, behind it, the Gram matrix a2^T a2 [c, ldw] where one stacked launch writes both
-            self.a3 = [{"P": F(Cm + cm, ldm), "coef": F(3, Cm), "bias": F(cm),
-                        "wt": torch.zeros(cm * (Cm + cm), dtype=dt, device=dev),
-                        "scr": torch.empty(max(ops.lib().iif_bn3_algebra_prep_scratch_floats(u.conv.cout, u.conv.cin)
-                                               for u in self.alg3_units), dtype=torch.float32, device=dev),
-                        "tickets": torch.zeros(64, dtype=torch.int32, device=dev)}
-                       for _ in range(self.wg_lag)]
-            self.a3g = [{"gram": F(cm, ldm), "csum": F(2, cm), "ws_gram": torch.empty(64 << 20, dtype=torch.uint8, device=dev),
-                         "ws_sum": ops.bn_workspace(max(u.n * u.ho * u.wo for u in self.alg3_units), cm, dev), "ev": None, "ev_csum": None,
-                         "csum_fwd": None}
-                        for _ in range(self.wg_lag + 1)]
-            self.a3_ws = torch.empty(64 << 20, dtype=torch.uint8, device=dev)          # split-K slabs of P on the compute stream
         wmax = max(max(u.conv.cout * (u.dwp.shape[1] if u.dwp is not None else u.conv.ldw) for u in self.units),
                    head.out_padded * head.in_features)
         self.wg_ws = torch.empty(min(16 * wmax * 4, 512 << 20), dtype=torch.uint8, device=dev)
@@ -1093,49 +1011,80 @@ class _Plan(object):
         if self.wg_stream is not None and ds_units and dt == torch.bfloat16 and not os.environ.get("IIF_NO_BWD_SIDE"):
             self.ds_stream = torch.cuda.Stream(device=dev)
             self.bn_ws_ds = ops.bn_workspace(max(u.n * u.ho * u.wo for u in ds_units), max(u.conv.cout for u in ds_units), dev)
-        # BN backward of a stride-1 convolutional shortcut by the same algebra as bn3 (round 5): the shortcut's BN sees the SAME
-        # gated block-output gradient g~ as bn3, and its input x_in is the narrow block input, so
-        #     d x_in (shortcut part) = [g~ | x_in] [A o Wd ; Wd^T diag(B) Wd]^T + D Wd,   sum g~ y_d = rowdot(g~^T x_in, Wd)
-        # replaces the reduction pass, the normalisation pass and the data gradient over the C-wide shortcut output
-        # (3.1 -> 1.3 GB at 56 x 56, all of it on the shortcut stream, which the compute stream used to wait ~120 us for at the
-        # end of layer1.0).  Units: 1 x 1 / stride 1 shortcuts of a block whose last unit takes the bn3 algebra (ResNet-50: layer1.0).
-        self.ds_alg = {}
-        self._alg_rows = {}
-        if self.ds_stream is not None and self.alg3_units and not os.environ.get("IIF_NO_DS_ALGEBRA"):
-            for b in self.blocks:
-                du = b.get("ds")
-                if du is None or "se" in b or b["units"][-1] not in self.alg3_units:
-                    continue
+        # ---- how every block's closing conv + BN runs: decided once (_train_routes), read through _route(); the buffers follow
+        self.standard_routes = False      # True: _route() answers with the standard routes (tests compare the routes on one live plan)
+        table = _train_routes(net, n, h, w, dt, self.wg_stream is not None, self.ds_stream is not None)
+        assert len(table) == len(self.blocks)
+        self._c3_routes = {b["units"][-1]: r for b, (_, r) in zip(self.blocks, table)}
+        F = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)   # noqa: E731
+        self.c3 = {}                      # closing unit -> its route's buffers and per-step counts
+        self.ds_alg = {}                  # id(shortcut unit) -> scratch of its BN backward by algebra (_ds_algebra)
+        for b in self.blocks:
+            u3 = b["units"][-1]
+            r, cv3 = self._c3_routes[u3], u3.conv
+            S = self.c3[u3] = _Conv3State(self.bw_partial)
+            if r.prologue:
+                S.u2 = b["units"][1]
+            if r.csum_rows:
+                S.rows = F(((u3.n * u3.ho * u3.wo + 127) // 128 + 8) * 2 * cv3.cin)
+                S.sums = F(2, cv3.cin)
+            if r.gram == "producer":
+                # up to 256 slabs (one per resident block) + the second reduction stage's ceil(256 / 16)
+                S.slabs = torch.empty((256 + 17) * (cv3.cout + cv3.cin) * cv3.ldw, dtype=torch.float32, device=dev)
+            if r.ds_algebra:
+                du = b["ds"]
                 cv = du.conv
-                if (cv.k == 1 and cv.stride == 1 and cv.groups == 1 and cv.cin in (64, 128, 256) and cv.cout % 64 == 0 and cv.cout <= 4096
-                        and _dma_ok(du.x) and _dma_ok(b["inp"]) and du.n * du.ho * du.wo < (1 << 30)):
-                    F = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)   # noqa: E731
-                    C, c = cv.cout, cv.cin
-                    self.ds_alg[id(du)] = {
-                        "P": F(C, cv.ldw), "coef": F(3, C), "bias": F(c), "wt": torch.zeros((c, C + c), dtype=dt, device=dev),
-                        "scr": torch.empty(ops.lib().iif_bn3_algebra_prep_scratch_floats(C, c), dtype=torch.float32, device=dev),
-                        "tickets": torch.zeros(64, dtype=torch.int32, device=dev), "gram": F(c, cv.ldw), "csum": F(2, c),
-                        "rows": torch.empty(self.bw_partial.numel(), dtype=torch.float32, device=dev),
-                        "ws": torch.empty(64 << 20, dtype=torch.uint8, device=dev),
-                        "ws_sum": ops.bn_workspace(du.n * du.ho * du.wo, c, dev)}
-                    # the data gradient that feeds this block's last unit writes its per-tile sums of g~ straight into "rows":
-                    # both branches read them, and the compute stream's next fused data gradient does not overwrite them
-                    # (round 5: the copy out of bw_partial was a 65 us blit on the compute stream)
-                    self._alg_rows[id(b["units"][-1])] = self.ds_alg[id(du)]["rows"]
-        # P = g~^T a2 and Gram = a2^T a2 of an algebra unit as BY-PRODUCTS of the recomputing producer (round 6,
-        # iif_conv_igemm_dgrad_masksum_rx_pg): the block that forms a tile of g~ holds it in its staging buffers and a2's tile in LDS;
-        # one fp32 slab per tile sequence, summed on the weight-gradient stream (iif_slab_sum).  Replaces the stacked weight-gradient
-        # launch that re-read g~ and a2 (0.5 GB per bottleneck at 56 x 56).  Units: c = 64 (the 56 x 56 stage).  IIF_NO_PG=1: off.
-        self.pg_units = {}
-        if self.rx_units and self.wg_stream is not None and not os.environ.get("IIF_NO_PG"):
-            for bi, b in enumerate(self.blocks[:-1]):
-                u3 = b["units"][-1]
-                f = self.blocks[bi + 1]["units"][0]
-                cv3 = u3.conv
-                if (u3 in self.rx_units and self._a3_gram_stacked(u3) and cv3.ldw % 4 == 0 and cv3.ldw >= cv3.cin
-                        and ops.conv_dgrad_rx_pg_ok(f.n, f.hi, f.wi, f.conv.cout, f.conv.cin, cv3.cin, dt)):
-                    # up to 256 slabs (one per resident block) + the second reduction stage's ceil(256 / 16); [slabs, count of the last launch]
-                    self.pg_units[u3] = [torch.empty((256 + 17) * (cv3.cout + cv3.cin) * cv3.ldw, dtype=torch.float32, device=dev), 0]
+                C, c = cv.cout, cv.cin
+                self.ds_alg[id(du)] = {
+                    "P": F(C, cv.ldw), "coef": F(3, C), "bias": F(c), "wt": torch.zeros((c, C + c), dtype=dt, device=dev),
+                    "scr": torch.empty(ops.lib().iif_bn3_algebra_prep_scratch_floats(C, c), dtype=torch.float32, device=dev),
+                    "tickets": torch.zeros(64, dtype=torch.int32, device=dev), "gram": F(c, cv.ldw), "csum": F(2, c),
+                    "rows": torch.empty(self.bw_partial.numel(), dtype=torch.float32, device=dev),
+                    "ws": torch.empty(64 << 20, dtype=torch.uint8, device=dev),
+                    "ws_sum": ops.bn_workspace(du.n * du.ho * du.wo, c, dev)}
+                # the data gradient that feeds this block's last unit writes its per-tile sums of g~ straight into "rows":
+                # both branches read them, and the compute stream's next fused data gradient does not overwrite them
+                # (round 5: the copy out of bw_partial was a 65 us blit on the compute stream)
+                S.g_rows = self.ds_alg[id(du)]["rows"]
+        self.a3 = None
+        alg = [u for u, r in self._c3_routes.items() if r.backward != "standard"]
+        if alg:
+            cm = max(u.conv.cin for u in alg)
+            Cm = max(u.conv.cout for u in alg)
+            ldm = max(u.conv.ldw for u in alg)
+            # per-block scratch rotates over wg_lag slots (the weight-gradient stream finishes block b before block b - wg_lag
+            # starts: _wgrad_fence); Gram / colsum are issued one block AHEAD on another stream, so they rotate over wg_lag + 1
+            # "P" holds P = g~^T a2 [C, ldw] and, behind it, the Gram matrix a2^T a2 [c, ldw] where one stacked launch writes both
+            self.a3 = [{"P": F(Cm + cm, ldm), "coef": F(3, Cm), "bias": F(cm),
+                        "wt": torch.zeros(cm * (Cm + cm), dtype=dt, device=dev),
+                        "scr": torch.empty(max(ops.lib().iif_bn3_algebra_prep_scratch_floats(u.conv.cout, u.conv.cin)
+                                               for u in alg), dtype=torch.float32, device=dev),
+                        "tickets": torch.zeros(64, dtype=torch.int32, device=dev)}
+                       for _ in range(self.wg_lag)]
+            self.a3g = [{"gram": F(cm, ldm), "csum": F(2, cm), "ws_gram": torch.empty(64 << 20, dtype=torch.uint8, device=dev),
+                         "ws_sum": ops.bn_workspace(max(u.n * u.ho * u.wo for u in alg), cm, dev), "ev": None, "ev_csum": None,
+                         "csum_fwd": None}
+                        for _ in range(self.wg_lag + 1)]
+            self.a3_ws = torch.empty(64 << 20, dtype=torch.uint8, device=dev)          # split-K slabs of P on the compute stream
+
+    def _route(self, u):
+        """The route of the block that unit ``u`` closes (the standard one for any other unit): the step's one lookup."""
+        r = self._c3_routes.get(u, _STANDARD)
+        if self.standard_routes:          # on this plan's buffers: the prologue stays where its kernel instance stores conv3's output
+            keep = r.prologue and r.forward != "nostore"
+            r = _Route(prologue=keep, csum_rows=keep and r.csum_rows)
+        return r
+
+    # read-only views of the route table (bench.py's byte model, tests, scripts); the step does not consult them
+    def _closing(self, pred):
+        return {u for u, r in self._c3_routes.items() if pred(r)}
+
+    alg3_units = property(lambda self: self._closing(lambda r: r.backward != "standard"))
+    rx_units = property(lambda self: self._closing(lambda r: r.backward == "rx"))
+    twopass_units = property(lambda self: self._closing(lambda r: r.forward == "twopass"))
+    nostore_units = property(lambda self: self._closing(lambda r: r.forward == "nostore"))
+    pg_units = property(lambda self: self._closing(lambda r: r.gram == "producer"))
+    pro_units = property(lambda self: {u: (self.c3[u].u2, self.c3[u].rows) for u, r in self._c3_routes.items() if r.prologue})
 
     def _finish_weight_plan(self):
         """One arena for every dense transposed weight copy ([cin][k*k*cout], the data-gradient operand) and
@@ -1357,7 +1306,8 @@ class _Plan(object):
                               u.stats, BN_EPS, BN_MOMENTUM)
 
     # ---------------------------------------------------------------- forward
-    def _conv_bn(self, u, training, side=False, pro=None):
+    def _conv_bn(self, u, training, side=False, pro=None, fwd="stored"):
+        """``pro`` (_Conv3State): the previous unit's BN + ReLU in this launch's operand path; ``fwd``: other than "stored", statistics only."""
         cv = u.conv
         k, st, pd = u.geom
         m = u.n * u.ho * u.wo
@@ -1366,17 +1316,21 @@ class _Plan(object):
         if training and self.dt == torch.bfloat16 and cv.cout % 8 == 0 and _dma_ok(u.src):
             # statistics come out of the convolution's epilogue: no extra pass over x
             partial, scratch = (self.bn_partial_side, self.bn_scratch_side) if side else (self.bn_partial, self.bn_scratch)
-            if pro is not None:              # the previous unit's BN + ReLU in this launch's operand path (pro_units)
-                u2 = pro[0]
-                nt = ops.conv_forward_bnstats_pro(u2.x, u2.stats, u2.y, u2.bits, u.w, u.x, partial, act_csum=pro[1])
-                pro[2] = nt
+            if pro is not None:
+                u2 = pro.u2
+                nt = pro.rows_count = ops.conv_forward_bnstats_pro(u2.x, u2.stats, u2.y, u2.bits, u.w, u.x if fwd == "stored" else None,
+                                                                   partial, act_csum=pro.rows)
+            elif fwd == "nostore":           # straight from the accumulators: nothing staged, nothing stored
+                nt = ops.conv_forward_stats_acc(u.src, u.w, partial)
+            elif fwd == "twopass":
+                nt = ops.conv_forward_stats_only(u.src, u.w, partial)
             else:
                 nt = ops.conv_forward_bnstats(u.src, u.w, k, k, st, pd, u.x, partial, groups=u.groups, w_frag=u.wf)
             if sync is not None:
                 self._sync_finalize(u, ops.bn_partial_sums(partial, nt, cv.cout, self._sync_sums(cv.cout, side)), m, sync)
                 return x2
             # (with the prologue's column-sum rows: reduced by this same launch, ops.bn_finalize_stats)
-            extra = (pro[1], nt, pro[0].conv.cout, pro[4]) if (pro is not None and pro[1] is not None) else None
+            extra = (pro.rows, nt, pro.u2.conv.cout, pro.sums) if (pro is not None and pro.rows is not None) else None
             ops.bn_finalize_stats(partial, nt, m, cv.cout, u.bn.weight, u.bn.bias, u.bn.running_mean,
                                   u.bn.running_var, u.stats, BN_EPS, BN_MOMENTUM, scratch=scratch,
                                   tickets=self.bn_tickets_side if side else self.bn_tickets, extra_sums=extra)
@@ -1455,68 +1409,33 @@ class _Plan(object):
                     ds_done = torch.cuda.Event()
                     ds_done.record()
             last = units[-1]
-            nostore = training and last in self.nostore_units and last in self.alg3_units and self.fuse_bwd
-            pro = self.pro_units.get(last) if (training and self.fuse_bwd) else None
-            if pro is not None and pro[3] != nostore:
-                pro = None                                   # (the instance was chosen for the other route: tests switch routes on a live plan)
-            if last in self.pro_units and pro is None:
-                self.pro_units[last][2] = 0                  # no column-sum rows from this forward
+            route = self._route(last) if (training and self.fuse_bwd) else _STANDARD
+            pro = self.c3[last] if route.prologue else None
+            self.c3[last].rows_count = 0                     # no column-sum rows from this forward, unless its prologue runs
             for uu in units[:-1]:
                 x2 = self._conv_bn(uu, training)
-                if pro is not None and uu is pro[0]:
+                if pro is not None and uu is pro.u2:
                     continue                                 # its normalisation happens in conv3's operand path
                 ops.bn_apply(x2, uu.stats, uu.y.view(x2.shape), relu=True, relu_bits=uu.bits)
-            if nostore:
-                cv = last.conv
-                m = last.n * last.ho * last.wo
-                if pro is not None:
-                    u2 = pro[0]
-                    nt = ops.conv_forward_bnstats_pro(u2.x, u2.stats, u2.y, u2.bits, last.w, None, self.bn_partial, act_csum=pro[1])
-                    pro[2] = nt
-                else:
-                    nt = ops.conv_forward_stats_acc(last.src, last.w, self.bn_partial)
-                extra = (pro[1], nt, cv.cin, pro[4]) if (pro is not None and pro[1] is not None) else None
-                ops.bn_finalize_stats(self.bn_partial, nt, m, cv.cout, last.bn.weight, last.bn.bias, last.bn.running_mean,
-                                      last.bn.running_var, last.stats, BN_EPS, BN_MOMENTUM, scratch=self.bn_scratch,
-                                      tickets=self.bn_tickets, extra_sums=extra)
-                if "ds" in b:
-                    du = b["ds"]
-                    if ds_done is not None:
-                        torch.cuda.current_stream().wait_event(ds_done)
-                    else:
-                        self._conv_bn(du, training)
-                    ops.conv_forward_bn_relu2(last.src, last.w, last.y, last.stats, last.bits, res=du.x, res_stats=du.stats)
-                else:
-                    ops.conv_forward_bn_relu2(last.src, last.w, last.y, last.stats, last.bits, res=b["inp"])
-                continue
-            if training and last in self.twopass_units:
-                cv = last.conv
-                m = last.n * last.ho * last.wo
-                nt = ops.conv_forward_stats_only(last.src, last.w, self.bn_partial)
-                ops.bn_finalize_stats(self.bn_partial, nt, m, cv.cout, last.bn.weight, last.bn.bias, last.bn.running_mean,
-                                      last.bn.running_var, last.stats, BN_EPS, BN_MOMENTUM, scratch=self.bn_scratch,
-                                      tickets=self.bn_tickets)
-                ops.conv_forward_bn_relu(last.src, last.w, last.y, last.stats, res=b["inp"], relu_bits=last.bits)
-                continue
-            x2 = self._conv_bn(last, training, pro=pro)
+            x2 = self._conv_bn(last, training, pro=pro, fwd=route.forward)
             if "se" in b:
                 self._se_forward(b, last, training)
                 continue
-            if "ds" in b:
-                du = b["ds"]
-                if ds_done is not None:
-                    torch.cuda.current_stream().wait_event(ds_done)
-                    xd = du.x.view(x2.shape)
-                else:
-                    xd = self._conv_bn(du, training)
-                ops.bn_apply(x2, last.stats, last.y.view(x2.shape), relu=True, residual=xd, residual_stats=du.stats,
-                             relu_bits=last.bits)
-            elif "sc" in b:
-                ops.shortcut_a_forward(b["inp"], b["blk"].out_planes, out=b["sc"])
-                ops.bn_apply(x2, last.stats, last.y.view(x2.shape), relu=True, residual=b["sc"].view(x2.shape),
-                             relu_bits=last.bits)
+            du = b.get("ds")
+            if ds_done is not None:
+                torch.cuda.current_stream().wait_event(ds_done)
+            elif du is not None:
+                self._conv_bn(du, training)
+            # a never-stored conv3 (its statistics are known now) runs again with BN + residual + ReLU in its epilogue
+            res, res_stats = (b["inp"], None) if du is None else (du.x, du.stats)      # identity, or the normalised shortcut
+            if route.forward == "nostore":
+                ops.conv_forward_bn_relu2(last.src, last.w, last.y, last.stats, last.bits, res=res, res_stats=res_stats)
+            elif route.forward == "twopass":
+                ops.conv_forward_bn_relu(last.src, last.w, last.y, last.stats, res=res, relu_bits=last.bits)
             else:
-                ops.bn_apply(x2, last.stats, last.y.view(x2.shape), relu=True, residual=b["inp"].view(x2.shape),
+                if "sc" in b:
+                    res = ops.shortcut_a_forward(b["inp"], b["blk"].out_planes, out=b["sc"])
+                ops.bn_apply(x2, last.stats, last.y.view(x2.shape), relu=True, residual=res.view(x2.shape), residual_stats=res_stats,
                              relu_bits=last.bits)
         self._head_forward()
 
@@ -1746,6 +1665,8 @@ class _Plan(object):
         ready = None
         if ws is self.bn_ws:                     # (the shortcut branch on its own stream never consumes fused sums)
             ready, self._bw_ready = self._bw_ready, None
+        by_algebra = ready is not None and ready[0] is u and len(ready) == 3
+        assert by_algebra or not self.fuse_bwd or self._route(u).forward == "stored", "standard BN backward of a never-stored output"
         sync = self.net._sync_bn
         if sync is not None:
             # SyncBatchNorm backward: local (sum g, sum g*xhat) -> dgamma / dbeta; all-reduced sums + global count -> dx
@@ -1765,10 +1686,8 @@ class _Plan(object):
             ops.bn_backward_apply_sums(g2, None if (mask is None or bits is not None) else mask.view(m, cv.cout), u.x.view(m, cv.cout),
                                        u.stats, bn.weight, local, total, float(m) * world, bn._dgamma, bn._dbeta, dx, coef,
                                        gmasked=None if gmasked is None else gmasked.view(m, cv.cout), relu_bits=bits)
-        elif ready is not None and ready[0] is u and len(ready) == 3:
+        elif by_algebra:
             return self._bn3_algebra(u, gy, ready[1], par, self._cur_block, dgrad_out, fuse_up, ready[2])
-        elif u in self.twopass_units or (u in self.nostore_units and u in self.alg3_units):
-            raise RuntimeError("two-pass unit reached the standard BN backward: its convolution output was never stored")
         elif ready is not None and ready[0] is u and gmasked is None:
             # the data gradient that wrote gy already reduced (sum g, sum g*xhat) per tile: no reduction pass
             dx = self._gbuf((dxkey, m, cv.cout, par), (m, cv.cout)) if keep_gy else g2
@@ -1802,23 +1721,24 @@ class _Plan(object):
         if (fuse_up is not None and self.fuse_bwd and (u.groups == 1 or cv.stride == 1) and dgrad_out is not None
                 and _dma_ok(dx4)):
             up, up_bits = fuse_up
-            if up in self.alg3_units and cv.k == 1 and cv.stride == 1 and up_bits is not None:
+            route = self._route(up)
+            if route.backward != "standard" and cv.k == 1 and cv.stride == 1 and up_bits is not None:
                 # the upstream unit's BN backward runs by algebra: store the gradient gated by its block's ReLU, emit its
                 # column sums only (conv3's output is not read)
-                rows = self._alg_rows.get(id(up), self.bw_partial)
-                if up in self.rx_units:
-                    pg = self.pg_units.get(up)
-                    if pg is not None:
-                        nt, pg[1] = ops.conv_dgrad_masksum_rx_pg(dx4, u.wt, (u.hi, u.wi), dgrad_out, up_bits, rows, up.src, up.w, up.stats,
-                                                                 pg[0], up.conv.ldw, res=dgrad_res, res_bits=dgrad_res_bits)
+                S = self.c3[up]
+                rows = S.g_rows
+                if route.backward == "rx":
+                    if route.gram == "producer":
+                        nt, S.slab_count = ops.conv_dgrad_masksum_rx_pg(dx4, u.wt, (u.hi, u.wi), dgrad_out, up_bits, rows, up.src, up.w,
+                                                                        up.stats, S.slabs, up.conv.ldw, res=dgrad_res, res_bits=dgrad_res_bits)
                     else:
                         nt = ops.conv_dgrad_masksum_rx(dx4, u.wt, (u.hi, u.wi), dgrad_out, up_bits, rows, up.src, up.w, up.stats,
                                                        res=dgrad_res, res_bits=dgrad_res_bits)
                     self._bw_ready = (up, nt, rows)
                     return dgrad_out
                 nt = ops.conv_dgrad_masksum(dx4, u.wt, (u.hi, u.wi), dgrad_out, up_bits, rows, res=dgrad_res,
-                                            res_bits=dgrad_res_bits, up_x=None if self._a3_is_pure(up) else up.x,
-                                            up_stats=None if self._a3_is_pure(up) else up.stats)
+                                            res_bits=dgrad_res_bits, up_x=None if route.backward == "pure" else up.x,
+                                            up_stats=None if route.backward == "pure" else up.stats)
                 self._bw_ready = (up, nt, rows)
                 return dgrad_out
             nt = ops.conv_dgrad_bnbwd(dx4, u.wt, cv.k, cv.k, cv.stride, cv.pad, (u.hi, u.wi), dgrad_out, up.x, up_bits, up.stats,
@@ -1828,17 +1748,6 @@ class _Plan(object):
         return ops.conv_dgrad(dx4, u.wt, cv.k, cv.k, cv.stride, cv.pad, (u.hi, u.wi), out=dgrad_out, res=dgrad_res,
                               groups=u.groups, res_bits=dgrad_res_bits, w_frag=u.wtf)
 
-    def _a3_is_pure(self, u):
-        """"Sums from P" (P = g~^T a2 on the compute stream before the coefficients); never where the producer recomputes x."""
-        return u not in getattr(self, "rx_units", ()) and u.n * u.ho * u.wo * u.conv.cout >= self.a3_pure_min
-
-    def _a3_gram_stacked(self, u):
-        """The Gram matrix a2^T a2 rides in the launch that forms P on the weight-gradient stream ([g~ | a2]^T a2,
-        iif_wgrad1x1_stacked: the extra channel tile re-reads rows of a2 the launch streams anyway) instead of a launch and a
-        slab reduction of its own a block ahead.  Not where P is formed on the compute stream ("pure" units): there the extra
-        tile would lengthen the critical path."""
-        return (not self._a3_is_pure(u)) and u.conv.cout % 128 == 0 and self.wg_stream is not None and not os.environ.get("IIF_NO_GRAM_STACKED")
-
     def _bn3_gram_async(self, u, bi):
         """Gram = a2^T a2 and colsum(a2) of an algebra unit's input: forward data only, so it is issued a block ahead on the
         shortcut stream (idle outside the four downsample blocks) and never waited for in practice."""
@@ -1846,12 +1755,13 @@ class _Plan(object):
         cv = u.conv
         a2 = u.src
         A["csum_fwd"] = None
-        pro = self.pro_units.get(u) if self.fuse_bwd else None
-        if pro is not None and pro[1] is not None and pro[2] > 0:
+        route, S = self._route(u), self.c3[u]
+        stacked = route.gram in ("stacked", "producer")                  # the Gram matrix comes with P on the weight-gradient stream (_bn3_algebra)
+        if route.csum_rows and S.rows_count > 0:
             # the forward pass already left the column sums of a2 (bn2's prologue in conv3's launch, reduced by that unit's
             # finalisation): nothing to compute, and with the Gram matrix stacked behind P nothing to launch or wait for at all
-            A["csum_fwd"] = pro[4]
-            if self._a3_gram_stacked(u):
+            A["csum_fwd"] = S.sums
+            if stacked:
                 A["ev"] = A["ev_csum"] = None
                 return
 
@@ -1860,7 +1770,7 @@ class _Plan(object):
                 ops.bn_stats_sums(a2.view(-1, cv.cin), A["csum"].view(-1)[:2 * cv.cin].view(2, cv.cin), A["ws_sum"])
 
         def gram():
-            if not self._a3_gram_stacked(u):
+            if not stacked:
                 ops.conv_wgrad(a2, a2, 1, 1, 1, 0, ldw=cv.ldw, out=A["gram"].view(-1)[:cv.cin * cv.ldw].view(cv.cin, cv.ldw),
                                workspace=A["ws_gram"])
         st = self.ds_stream if self.ds_stream is not None else self.wg_stream
@@ -1892,7 +1802,8 @@ class _Plan(object):
         g4 = gt.view(u.n, u.ho, u.wo, C)
         wb = u.w                                                   # the bf16 weights the forward multiplied with, [C, ldw]
         P = A["P"].view(-1)[:C * cv.ldw].view(C, cv.ldw)          # contiguous [C, ldw]: conv_wgrad writes with pitch ldw
-        pure = self._a3_is_pure(u)
+        route, S = self._route(u), self.c3[u]
+        pure = route.backward == "pure"
         if pure:
             ops.conv_wgrad(u.src, g4, 1, 1, 1, 0, ldw=cv.ldw, out=P, workspace=self.a3_ws)
         wt = A["wt"][:c * (C + c)].view(c, C + c)
@@ -1906,16 +1817,15 @@ class _Plan(object):
         ops.bn3_algebra_prep(P if pure else None, wb, c, rows, nt, u.stats, bn.weight, m, coef, bn._dgamma, bn._dbeta, wt,
                              A["bias"][:c], A["scr"], A["tickets"], colsum2=csum_a2)
 
-        stacked = self._a3_gram_stacked(u)
+        stacked = route.gram in ("stacked", "producer")
 
         def finish_dw(ws, sp):
             gram = Ag["gram"].view(-1)[:c * cv.ldw].view(c, cv.ldw)
-            pg = self.pg_units.get(u)
-            if stacked and pg is not None and pg[1] > 0:
+            if route.gram == "producer" and S.slab_count > 0:
                 # the producer of g~ left P and Gram behind, one slab per tile sequence: add them up (no pass over g~ and a2)
                 ext = A["P"].view(-1)[:(C + c) * cv.ldw].view(C + c, cv.ldw)
-                ops.slab_sum(pg[0], pg[1], C + c, cv.ldw, c, ext)
-                pg[1] = 0
+                ops.slab_sum(S.slabs, S.slab_count, C + c, cv.ldw, c, ext)
+                S.slab_count = 0
                 gram = ext[C:]
             elif stacked:
                 ext = A["P"].view(-1)[:(C + c) * cv.ldw].view(C + c, cv.ldw)
@@ -1935,8 +1845,13 @@ class _Plan(object):
 
     def _ds_algebra(self, du, D, gt, x_in, nt, gin_ds):
         """Backward of a stride-1 convolutional shortcut (1x1 conv + BN, no ReLU of its own) from the gated block-output gradient
-        ``gt`` without reading the shortcut's output (see ``ds_alg`` in __init__).  Runs on the shortcut stream; ``gin_ds`` receives
-        the gradient w.r.t. the block input through the shortcut, the first unit's data gradient adds it as its residual."""
+        ``gt`` without reading the shortcut's output (taken where _train_routes says ``ds_algebra``).  The shortcut's BN
+        sees the SAME gated gradient g~ as bn3, and its input x_in is the narrow block input, so
+            d x_in (shortcut part) = [g~ | x_in] [A o Wd ; Wd^T diag(B) Wd]^T + D Wd,   sum g~ y_d = rowdot(g~^T x_in, Wd)
+        replaces the reduction pass, the normalisation pass and the data gradient over the C-wide shortcut output (3.1 -> 1.3 GB
+        at 56 x 56, all of it on the shortcut stream, which the compute stream used to wait ~120 us for at the end of layer1.0).
+        Runs on the shortcut stream; ``gin_ds`` receives the gradient w.r.t. the block input through the shortcut, the first
+        unit's data gradient adds it as its residual."""
         cv, bn = du.conv, du.bn
         C, c = cv.cout, cv.cin
         m = du.n * du.ho * du.wo
@@ -2090,8 +2005,8 @@ class _Plan(object):
             # shortcut stream BEHIND this block's shortcut branch, which the compute stream waits for at the end of the block (round 5:
             # in front of it, it delayed the branch by its ~100-150 us: the compute stream idled 120-230 us at every downsample block,
             # profiles/r5_b_step_timeline.txt)
-            if bi > 0 and self.blocks[bi - 1]["units"][-1] in self.alg3_units:
-                self._bn3_gram_async(self.blocks[bi - 1]["units"][-1], bi - 1)
+            if prev is not None and self._route(prev["units"][-1]).backward != "standard":
+                self._bn3_gram_async(prev["units"][-1], bi - 1)
             if "se" in b:
                 G = self._se_backward(b, last, g, par)
                 d = self._unit_backward(last, G, None, par=par, dgrad_out=self._gbuf(dkey, last.src.shape),
@@ -2199,6 +2114,90 @@ def _dma_ok(t):
     """The pipelined kernels address their operands with 32-bit LDS-DMA offsets (< 2 GiB); beyond that the
     register-staged fallback runs and the fused epilogue options are not available."""
     return t.numel() * t.element_size() < _DMA_LIMIT
+
+
+def _train_routes(net, n, h, w, dt, wg_stream, ds_stream):
+    """[(block name, _Route)] of a training step, in forward order.  Walks the block list with the geometry _Plan uses, reads each
+    switch of this area once and asks the library's planning queries; no device memory is touched.
+    backward - BN backward of a bottleneck's expanding 1x1 layer by algebra (csrc/bn3_algebra.hip) from the block-output gradient
+      stored gated by the block's ReLU: only where its producer, the next block's conv1 data gradient, can store it so and emit
+      the sums.  "rx": the producer recomputes conv3's tile for sum g~ xhat, wherever the register-weight kernel has the instance;
+      "pure": sum g~ y from P = g~^T a2 on the compute stream, for tensors of >= IIF_BN3_ALGEBRA_PURE_MIN_ELEMS elements (9e7: the
+      56 x 56 and 28 x 28 stages at batch 256); "producer": it reads conv3's stored output once, P on the weight-gradient stream.
+    forward - neither "twopass" (opt-in: measured level) nor "nostore" stores conv3's raw output: a statistics pass, then the
+      convolution with BN + residual + ReLU in its epilogue.  "twopass" is decided on the size alone: with the recomputing
+      producer on, such a unit runs a two-pass forward and an "rx" backward.  "nostore": "pure" and "rx" units the kernel takes.
+    prologue - conv3 normalises conv2's RAW output tile by tile in LDS.  K > IIF_PRO_MAX_K stays with the separate bn_apply: every
+      N slice normalises the whole tile again (22 us on a 39 us launch against a 10 us bn_apply, profiles/r6_ab.txt ab11).
+    gram - "stacked": a2^T a2 rides in the launch that forms P on the weight-gradient stream, not a block ahead in a launch of
+      its own (not where P sits on the compute stream); "producer": P and Gram are by-products of the recomputing producer.
+    ds_algebra - the same algebra for a stride-1 convolutional shortcut: it sees the same g~ (ResNet-50: layer1.0)."""
+    env = os.environ.get
+    bf16 = dt == torch.bfloat16
+    esz = 2 if bf16 else 4
+    dma = lambda elems: elems * esz < _DMA_LIMIT                                          # noqa: E731
+    dense1x1 = lambda cv: cv.k == 1 and cv.stride == 1 and cv.groups == 1               # noqa: E731
+    # a layer [m, cin] -> [m, cout] whose BN backward the algebra takes
+    algebra_ok = lambda cv, m: (dense1x1(cv) and cv.cin in (64, 128, 256) and cv.cout % 64 == 0 and cv.cout <= 4096     # noqa: E731
+                                and dma(m * cv.cout) and m < (1 << 30))
+    fuse_bwd = bf16 and not env("IIF_NO_BWD_FUSE")
+    local_bn = net._sync_bn is None
+    algebra_on = fuse_bwd and local_bn and not env("IIF_NO_BN3_ALGEBRA")
+    pure_min = float(env("IIF_BN3_ALGEBRA_PURE_MIN_ELEMS", "9e7"))
+    twopass_on, rx_on, nostore_on = bool(env("IIF_TWOPASS")), not env("IIF_NO_RX"), not env("IIF_NO_NOSTORE")
+    prologue_on = fuse_bwd and local_bn and not env("IIF_NO_PROLOGUE")
+    pro_max_k = int(env("IIF_PRO_MAX_K", "256"))
+    stacked_on = wg_stream and not env("IIF_NO_GRAM_STACKED")
+    pg_on = wg_stream and not env("IIF_NO_PG")
+    ds_on = ds_stream and not env("IIF_NO_DS_ALGEBRA")
+
+    c1 = net.conv1
+    hh, ww = ops.conv_out_hw(h, w, c1.k, c1.k, c1.stride, c1.pad)
+    if net.style == "imagenet":
+        hh, ww = (hh + 2 - 3) // 2 + 1, (ww + 2 - 3) // 2 + 1
+    blocks = [("layer%d.%d" % (si + 1, bi), blk) for si, st in enumerate(net._stages) for bi, blk in enumerate(st)]
+    table = []
+    for i, (name, blk) in enumerate(blocks):
+        convs = [cv for (cv, _) in blk.units()]
+        m_in = n * hh * ww
+        for cv in convs:
+            hh, ww = ops.conv_out_hw(hh, ww, cv.k, cv.k, cv.stride, cv.pad)
+        cv3, m = convs[-1], n * hh * ww                       # the closing unit is [m, cin] -> [m, cout]
+        big = m * cv3.cout >= pure_min
+        bottleneck = len(convs) == 3 and blk.se is None
+        nxt = blocks[i + 1][1] if i + 1 < len(blocks) else None
+        # ---- backward.  The producer of this block's output gradient is the next block's conv1 data gradient: dense 1 x 1 /
+        # stride 1, so its input is this block's output ([m, cv3.cout], inside the DMA range by algebra_ok) and its output has m rows
+        f = nxt.units()[0][0] if nxt is not None else None
+        backward = "standard"
+        if (algebra_on and bottleneck and (blk.downsample is not None or not blk.shortcut_a) and algebra_ok(cv3, m)
+                and f is not None and nxt.se is None and dense1x1(f) and dma(m * f.cout)):
+            if rx_on and ops.conv_dgrad_rx_ok(n, hh, ww, f.cout, f.cin, cv3.cin, dt):
+                backward = "rx"
+            else:
+                backward = "pure" if big else "producer"
+        alg = backward != "standard"
+        # ---- forward
+        forward = "stored"
+        if alg and dma(m * cv3.cin):
+            if twopass_on and big and blk.downsample is None:
+                forward = "twopass"
+            elif nostore_on and backward != "producer" and ops.conv_fwdbn_ok(n, hh, ww, cv3.cin, cv3.cout, dt):
+                forward = "nostore"
+        # ---- prologue (conv2's raw output has conv3's rows)
+        prologue = bool(prologue_on and bottleneck and dense1x1(cv3) and dma(m * cv3.cin) and forward != "twopass"
+                        and cv3.cin <= pro_max_k and ops.conv_pro_ok(n, hh, ww, cv3.cin, cv3.cout, dt, forward == "nostore"))
+        # ---- Gram matrix
+        gram = "ahead" if alg else None
+        if alg and backward != "pure" and cv3.cout % 128 == 0 and stacked_on:
+            gram = "stacked"
+            if (backward == "rx" and pg_on and cv3.ldw % 4 == 0 and cv3.ldw >= cv3.cin
+                    and ops.conv_dgrad_rx_pg_ok(n, hh, ww, f.cout, f.cin, cv3.cin, dt)):
+                gram = "producer"
+        dcv = blk.downsample[0] if blk.downsample is not None else None
+        ds_algebra = bool(ds_on and alg and dcv is not None and algebra_ok(dcv, m) and dma(m_in * dcv.cin))
+        table.append((name, _Route(backward, forward, prologue, prologue and alg, gram, ds_algebra)))
+    return table
 
 
 def _eval_routes(net, n, h, w):

@@ -396,10 +396,10 @@ def test_bn3_backward_by_algebra_inside_the_step(monkeypatch, pure, streams):
     assert len(plan.alg3_units) == 13                       # layer1..layer3 (conv3 input channels <= 256)
     alg = net._grad_arena.clone()
     assert len(plan.twopass_units) == (10 if pure else 0)   # the identity blocks of layer1..layer3 (2 + 3 + 5)
-    keep, plan.alg3_units, keep2, plan.twopass_units = plan.alg3_units, set(), plan.twopass_units, set()
+    plan.standard_routes = True
     loss_std, _ = net.loss_and_backward(xd, yd, crit)
     std = net._grad_arena.clone()
-    plan.alg3_units, plan.twopass_units = keep, keep2
+    plan.standard_routes = False
     loss_alg, _ = net.loss_and_backward(xd, yd, crit)
     assert loss_alg.item() == loss_std.item()               # the two-pass forward is bit-identical to conv + bn_apply
     assert torch.equal(net._grad_arena, alg)                # fixed summation orders, event-ordered hand-overs
@@ -450,10 +450,10 @@ def test_never_stored_conv3_forward_inside_the_step(monkeypatch, streams):
     loss_again, _ = net.loss_and_backward(xd, yd, crit)
     assert loss_again.item() == loss_ns and torch.equal(net._grad_arena, ns)
     assert not torch.isnan(ns).any()
-    keep, plan.alg3_units = plan.alg3_units, set()
+    plan.standard_routes = True
     loss_std, _ = net.loss_and_backward(xd, yd, crit)
     std = net._grad_arena.clone()
-    plan.alg3_units = keep
+    plan.standard_routes = False
     assert abs(loss_ns - loss_std.item()) <= 2e-3 * abs(loss_std.item())
     assert abs(loss_ns - loss32.item()) <= 2e-3 * abs(loss32.item())
     rel = lambda a_, b_: (a_ - b_).norm().item() / max(b_.norm().item(), 1e-12)      # noqa: E731

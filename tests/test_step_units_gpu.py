@@ -169,11 +169,11 @@ def test_negative_controls_flag_exactly_the_affected_unit(monkeypatch):
     assert flagged(m2) == {names[id(v.conv)]}, U.failures(m2, bf16_bound)
     v.stats[1].div_(1.05)
     # (c) one prologue column-sum compensation dropped between forward and backward
-    target = next(w for w in alg if plan.pro_units.get(w) is not None and plan.pro_units[w][1] is not None)
+    target = next(w for w in alg if plan._route(w).csum_rows)
     orig = resnet_engine._Plan.backward
 
     def backward(self, reducer=None):
-        self.pro_units[target][4].zero_()
+        self.c3[target].sums.zero_()
         return orig(self, reducer)
 
     monkeypatch.setattr(resnet_engine._Plan, "backward", backward)

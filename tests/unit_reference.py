@@ -221,10 +221,11 @@ def routes(plan, cap):
     """Route inventory of the step the capture recorded."""
     alg = [u for u in plan.units if cap.records.get(id(u), {}).get("alg")]
     ds_alg = [b["ds"] for b in plan.blocks if "ds" in b and id(b["ds"]) not in cap.records]
-    return {"alg3": len(alg), "alg3_pure": sum(1 for u in alg if plan._a3_is_pure(u)),
-            "rx": sum(1 for u in alg if u in plan.rx_units), "nostore": len(plan.nostore_units),
-            "twopass": len(plan.twopass_units), "pg": len(plan.pg_units),
-            "pro": len(plan.pro_units), "pro_rows": sum(1 for v in plan.pro_units.values() if v[1] is not None),
+    rs = [plan._route(b["units"][-1]) for b in plan.blocks]
+    return {"alg3": len(alg), "alg3_pure": sum(1 for u in alg if plan._route(u).backward == "pure"),
+            "rx": sum(1 for u in alg if plan._route(u).backward == "rx"), "nostore": sum(1 for r in rs if r.forward == "nostore"),
+            "twopass": sum(1 for r in rs if r.forward == "twopass"), "pg": sum(1 for r in rs if r.gram == "producer"),
+            "pro": sum(1 for r in rs if r.prologue), "pro_rows": sum(1 for r in rs if r.csum_rows),
             "ds_alg": len(ds_alg), "pool_fused_bwd": bool(plan.pool_fused and plan.pool_x is not None),
             "wg_stream": plan.wg_stream is not None, "ds_stream": plan.ds_stream is not None}
 
@@ -316,8 +317,8 @@ def check_step(net, img, cap):
         inp = P(b["inp"])
         lrec = rec[id(last)]
         alg = lrec["alg"]
-        nostore = last in plan.nostore_units and alg
-        unrounded_last = nostore or last in plan.twopass_units
+        route = plan._route(last)
+        unrounded_last = (route.forward == "nostore" and alg) or route.forward == "twopass"
         # forward
         xrs, sts = [], []
         for ui, u in enumerate(units[:-1]):
@@ -338,9 +339,9 @@ def check_step(net, img, cap):
         sts.append(st)
         # backward, last unit: x-hat of the route ("sums from P": the unrounded product, the producer that recomputes conv3's
         # tile: that tile rounded, stored units: the stored output)
-        if alg and plan._a3_is_pure(last):
+        if alg and route.backward == "pure":
             xsrc = xr
-        elif alg and last in plan.rx_units:
+        elif alg and route.backward == "rx":
             xsrc = rnd(xr)
         else:
             xsrc = P(last.x)
