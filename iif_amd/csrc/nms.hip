@@ -34,19 +34,13 @@
 //     left = max(a.x1, b.x1), right = min(a.x2, b.x2), ...;  w = max(right - left + offset, 0), h likewise;  inter = w * h
 //     Sa = (a.x2 - a.x1 + offset) * (a.y2 - a.y1 + offset);  suppressed: inter / (Sa + Sb - inter) > iou_threshold (NaN: no)
 // Integer atomics only.  Nothing is allocated, nothing is read back.
-#include "common.h"
+#include "nms_common.h"
 #include "box_coder.h"
 
 namespace {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
 constexpr int kThreads = 256;
-constexpr int kSelThreads = 1024;             // the selection passes: thread t owns bins 4 t .. 4 t + 3
 constexpr int kScanThreads = 1024;            // the scan: 256 word columns x 4 groups of 16 rows
-constexpr int kBins = 4096;
-constexpr int kPasses = 5;                    // digits of 12, 12, 12, 12, 8 bits
 constexpr int kSegBlocks = 16;                // blocks per (image, level) in a selection pass
 constexpr int kRankTile = 1024;
 constexpr int kMaxLevels = 8, kMaxImages = 16;
@@ -54,28 +48,8 @@ constexpr int kHeaderBytes = 4096;            // u32 words: [0, 16) coordinate m
 constexpr int kHdrCount = 16, kHdrValid = 144;
 constexpr int64_t kHistBytes = (int64_t)kMaxLevels * kPasses * kBins * 4;     // per image
 constexpr int64_t kFrontPerImage = kHistBytes + 4096;                          // ... and its selection states
-constexpr u32 kIndexMask = 0xFFFFFFu;
 
 static_assert(kFrontPerImage == 659456, "IIF_NMS_WORKSPACE_BYTES counts 659456 bytes of histograms and states per image");
-
-struct SelState { u64 prefix; u32 rem; u32 pad; };
-
-// bits that order as unsigned integers the way the floats order; -0 and +0 are one value
-__device__ __forceinline__ u32 fkey(float f) {
-    u32 u = __float_as_uint(f);
-    if (f == 0.0f) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(u32 k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-__device__ __forceinline__ u32 wave_max_u(u32 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u32 t = (u32)__shfl_xor((int)v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
 
 // The sections of the workspace behind the header, histograms and states; Np = N rounded up to 64.
 struct Ws {
@@ -221,13 +195,7 @@ __global__ void __launch_bounds__(64) nms_matrix_kernel(NmsArgs a) {
     const int cn = min(64, nv - cb * 64);
     u64 word = 0ull;
     for (int c = 0; c < cn; ++c) {
-        const f32x4 q = s_box[c];
-        const float left = fmaxf(p.x, q.x), right = fminf(p.z, q.z);
-        const float top = fmaxf(p.y, q.y), bottom = fminf(p.w, q.w);
-        const float w = fmaxf(right - left + off, 0.0f), h = fmaxf(bottom - top + off, 0.0f);
-        const float inter = w * h;
-        const float iou = inter / (sa + s_area[c] - inter);
-        const bool hit = iou > a.thr && cb * 64 + c > i && (!same_id_only || s_id[c] == id);
+        const bool hit = nms_suppresses(p, sa, s_box[c], s_area[c], off, a.thr) && cb * 64 + c > i && (!same_id_only || s_id[c] == id);
         word |= hit ? (1ull << c) : 0ull;
     }
     a.w.mask[(row0 + i) * a.nw + cb] = word;
@@ -344,36 +312,6 @@ struct RpnArgs {
     Norm nm; float max_ratio, ctr_clamp, min_size; int add_ctr_clamp, clip;
     Ws w;
 };
-
-__device__ __forceinline__ int digit_shift(int p) { return p < 4 ? 44 - 12 * p : 0; }
-__device__ __forceinline__ int digit_bits(int p) { return p < 4 ? 12 : 8; }
-
-// exclusive prefix sums over the block's 1024 threads; s_w: 17 words of LDS, reusable after the call returns
-__device__ __forceinline__ u32 block_scan_excl(u32 v, u32* s_w) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u32 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 t = (u32)__shfl_up((int)inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    if (wv == 0) {
-        const u32 x = lane < kSelThreads / 64 ? s_w[lane] : 0u;
-        u32 xi = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 t = (u32)__shfl_up((int)xi, o, 64);
-            if (lane >= o) xi += t;
-        }
-        if (lane < kSelThreads / 64) s_w[lane] = xi - x;
-    }
-    __syncthreads();
-    const u32 res = s_w[wv] + inc - v;
-    __syncthreads();
-    return res;
-}
 
 // Pass p = 0 .. 4 histograms digit p; pass 5 gathers and decodes.  Every pass p >= 1 first turns the histogram of pass p - 1 into
 // the threshold digit (every block for itself; block 0 of the segment leaves the state for the next launch).

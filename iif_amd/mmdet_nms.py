@@ -12,8 +12,8 @@ Ranking is by score descending with equal scores to the lower index (the referen
 of its outputs); the overlap test and the id shift are mmcv's float32 operations in mmcv's order, so ``keep`` is exactly what
 the reference keeps.
 
-Deliberately not offered: ``multiclass_nms`` (1 000 x 1 203 candidates on LVIS need a segmented per-class design, not an N^2
-matrix), ``soft_nms``, ``nms_match``, ``fast_nms``; more than 16 384 boxes; the two-class softmax RPN; ``rescale``; the ONNX
+``multiclass_nms`` (1 000 x 1 203 candidates on LVIS) has a segmented per-class design of its own, not this N^2 matrix:
+mmdet_multiclass_nms.py.  Deliberately not offered: ``soft_nms``, ``nms_match``, ``fast_nms``; more than 16 384 boxes; the two-class softmax RPN; ``rescale``; the ONNX
 branches; a tensor ``max_shape``; ``with_nms=False``; on the RPN path ``split_thr`` candidates or more per image (the
 reference's data-dependent switch to a per-level NMS).  The padded proposals cannot yet feed the assigner without the one read:
 it has no valid-count input.  When mmdet is importable a subclass of its ``RPNHead`` registers itself as ``RPNHead``.

@@ -1080,6 +1080,39 @@ int iif_rpn_proposals(const iif_rpn_level* levels, int num_levels, int B, const 
                       float* cand_boxes, float* cand_scores, int32_t* cand_level, int8_t* cand_valid, void* d_workspace,
                       int64_t workspace_bytes, void* stream);
 
+/* mmdet's multiclass_nms (core/post_processing/bbox_nms.py:8-95; iif_amd/mmdet_multiclass_nms.py) for B images of R padded rows
+ * and C foreground classes each, in 12 enqueued operations whatever the sizes and the data (csrc/multiclass_nms.hip): a clear,
+ * the filter, the rank and walk of the all-pairs regime, the per-class walk, six selection passes, the finish.
+ * scores fp32 [B][R] rows of C + 1 values, ld_scores floats apart (>= C + 1); the last column (background) is never read.
+ * boxes fp32 [B][R] rows, ld_boxes floats apart: 4 C values (boxes_per_class != 0, box c at 4 c) or 4 values shared by the classes.
+ * score_factors (nullable) fp32 [B][R]; row_counts (nullable) int64 [B] on the DEVICE: rows at or beyond it take no part.
+ *   candidates  (r, c) with flat index f = r * C + c takes part iff score[r, c] > score_thr (strict, the raw score).  Its ranked
+ *               score is score[r, c] * factor[r] (one float32 multiply; the score itself without factors).  M = how many take part.
+ *   regime      decided on the device.  0 < M < split_thr: mmcv's nms over ALL pairs of the shifted boxes box + float(c) * (max + 1),
+ *               max over all coordinates of the boxes that take part, formed in float32 - including mmcv's quirk that boxes of
+ *               different classes can meet when coordinates lie below -1.  M >= split_thr: one plain NMS per class on the same
+ *               shifted boxes, merged by score.  The rank, the overlap test and the walk are those of iif_nms above: ranked score
+ *               descending, equal scores to the lower f; single float32 operations; a NaN quotient does not suppress.
+ *   cap         the result is the first cap of the ranked kept candidates (the caller folds nms_cfg['max_num'] and max_num into it).
+ * dets fp32 [B][cap][5]: the kept UNSHIFTED boxes and ranked scores in rank order, then zeros.  labels int64 [B][cap]: c, then
+ * -1.  inds int64 [B][cap]: f, then -1.  counts int64 [B].  num_candidates (nullable) int64 [B]: M.
+ * d_workspace: IIF_MULTICLASS_NMS_WORKSPACE_BYTES(B, R, C, cap) on a 16-byte boundary; it belongs to the call until the stream has
+ * run it; its contents on entry do not matter.  Allocates nothing, reads nothing back; integer atomics only; the result does not
+ * depend on their arrival order.
+ * IIF_EINVAL before anything is enqueued: B outside 1 .. 16, R outside 0 .. IIF_MULTICLASS_NMS_MAX_ROWS, C outside
+ * 1 .. IIF_MULTICLASS_NMS_MAX_CLASSES, R C >= 2^24, cap outside 1 .. IIF_MULTICLASS_NMS_MAX_CAP, offset outside 0 .. 1, a NaN
+ * threshold, a row pitch smaller than the row, split_thr > IIF_NMS_MAX_BOXES while R C exceeds it (the all-pairs regime holds
+ * IIF_NMS_MAX_BOXES candidates), a null or misaligned scores / boxes / output, a null, misaligned or short workspace. */
+#define IIF_MULTICLASS_NMS_MAX_ROWS 1024
+#define IIF_MULTICLASS_NMS_MAX_CLASSES 4096
+#define IIF_MULTICLASS_NMS_MAX_CAP 4096
+#define IIF_MULTICLASS_NMS_WORKSPACE_BYTES(B, R, C, cap) (4096 + (int64_t)(B) * (212992 + 4 * (((int64_t)(C) + 3) / 4 * 4) + 16 * (int64_t)(R) * (int64_t)(C) + 8 * (int64_t)(cap)))
+int iif_multiclass_nms(const float* boxes, int64_t ld_boxes, int boxes_per_class, const float* scores, int64_t ld_scores,
+                       const float* score_factors /* nullable */, const int64_t* row_counts /* nullable */, int B, int64_t R, int64_t C,
+                       float score_thr, float iou_threshold, int offset, int64_t split_thr, int64_t cap, float* dets,
+                       int64_t* labels, int64_t* inds, int64_t* counts, int64_t* num_candidates /* nullable */, void* d_workspace,
+                       int64_t workspace_bytes, void* stream);
+
 /* CIFAR training input (iif_amd/cifar.py DeviceCIFARLoader): ONE launch per batch builds out[b] (fp32 NCHW [batch][3][32][32])
  * and targets[b] = labels[index[b]] from the device-resident dataset data (uint8 [n][3][32][32], the planar rows of the
  * CIFAR files) and labels (int64 [n]).  flags select the stages, applied in the reference's order (initialisers.py:116-134):
