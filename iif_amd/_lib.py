@@ -138,6 +138,8 @@ SIGNATURES = {
     "iif_roi_targets": [_P, _L, _L, _P, _P, _P, _L, _L, _P, _P, _P, _L, _L, _I, _L, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "iif_roi_extract_forward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _P],
     "iif_roi_extract_backward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _L, _P],
+    "iif_mask_targets": [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P],
+    "iif_paste_masks": [_P, _I, _I, _P, _P, _L, _L, _I, _I, _I, _I, _I, _F, _P, _P],
     "iif_nms": [_P, _L, _P, _P, _L, _I, _F, _I, _F, _L, _P, _P, _P, _P, _L, _P],
     "iif_rpn_proposals": [_P, _I, _I, _P, _I, _I, _F, _F, _I, _P, _P, _F, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P],
     "iif_multiclass_nms": [_P, _L, _I, _P, _L, _P, _P, _I, _L, _L, _F, _F, _I, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P],
@@ -155,6 +157,12 @@ class ConvDesc(ctypes.Structure):
 class RoiLevel(ctypes.Structure):
     """Mirror of ``iif_roi_level`` (include/iif_amd.h)."""
     _fields_ = [("ptr", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("spatial_scale", ctypes.c_float)]
+
+
+class MaskImage(ctypes.Structure):
+    """Mirror of ``iif_mask_image`` (include/iif_amd.h)."""
+    _fields_ = [("ptr", ctypes.c_void_p), ("G", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("ld_row", ctypes.c_int64), ("ld_mask", ctypes.c_int64)]
 
 
 class RpnLevel(ctypes.Structure):

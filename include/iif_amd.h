@@ -1012,6 +1012,54 @@ int iif_roi_extract_backward(const iif_roi_level* grad_levels, int num_levels, i
                              float roi_scale_factor, const float* grad_out, int grad_channels_last, void* arena,
                              int64_t arena_bytes, void* stream);
 
+/* The two ends of the Mask R-CNN mask branch (csrc/mask_ops.hip; iif_amd/mmdet_mask_target.py, iif_amd/mmdet_mask_loss.py).
+ *
+ * iif_mask_targets: mask_target (mmdet core/mask/mask_target.py:7-127) with BitmapMasks.crop_and_resize
+ * (core/mask/structures.py:333-367) for all images of a batch in ONE launch.  images: a HOST array of num_images (1 .. 16)
+ * descriptors, copied into the launch: ptr = the image's gt masks, uint8 (any non-zero byte is "inside"), G masks of H x W, rows
+ * ld_row bytes apart (>= W), masks ld_mask bytes apart (>= (H - 1) * ld_row + W): masks are read IN PLACE through the gt index,
+ * no float copy of a mask is formed.  G == 0 (ptr may be NULL): every roi of that image is a zero row.
+ * rois [K] rows of (image index, x1, y1, x2, y2) fp32, ld_rois floats apart (>= 5): what iif_roi_targets returns.
+ * gt_inds int64 [K].  Per roi, in float32 with the reference's operations in its order:
+ *   clip      x = fminf(fmaxf(x, 0), W), y likewise with H (np.clip on the float32 proposal)
+ *   RoIAlign  the definition at iif_roi_extract_forward with spatial_scale 1, sampling_ratio 0, aligned, pooled = (mask_h, mask_w)
+ *             on the image  m[y, x] = (byte != 0);  summed in the separable form, so only the summation order differs
+ *   out       binarize != 0: value >= 0.5f ? 1.0f : 0.0f; else the value (soft_mask_target)
+ *   A zero row: an image index outside [0, num_images) (NaN included; the -1 padding rows of the padded samplings), a gt index
+ *   outside [0, G), a non-finite coordinate, a grid count above 65536.
+ * out: fp32 [K][mask_h][mask_w].  The result is a pure function of the arguments' values: no atomics, and the same bits wherever
+ * the masks lie in memory and whatever their pitches.  Allocates nothing, reads nothing back.
+ * IIF_EINVAL before any launch: a null or misaligned pointer (rois / out 4 bytes, gt_inds 8), num_images outside 1 .. 16, G < 0,
+ * H / W / mask_h / mask_w <= 0, ld_row < W, ld_mask too small, ld_rois < 5, K < 0.  IIF_EUNSUPPORTED: W > 4096 or mask_h /
+ * mask_w > 64 (the per-axis weights and the output tile live in LDS).  K == 0: IIF_OK, nothing is enqueued. */
+typedef struct iif_mask_image {
+    const uint8_t* ptr;
+    int32_t G, H, W;
+    int64_t ld_row, ld_mask;
+} iif_mask_image;
+int iif_mask_targets(const iif_mask_image* images, int num_images, const float* rois, int64_t ld_rois, const int64_t* gt_inds,
+                     int64_t K, int mask_h, int mask_w, int binarize, float* out, void* stream);
+/* iif_paste_masks: FCNMaskHead.get_seg_masks between the logits and the boolean image (fcn_mask_head.py:228-306 with
+ * _do_paste_mask, :344-412, skip_empty=False) in ONE launch.  mask_pred [N][C][h][w], dtype IIF_F32 or IIF_BF16 (widened to
+ * float32): logits, or with activated != 0 probabilities.  labels int64 [N], or NULL: channel 0 (class-agnostic heads).
+ * boxes [N] rows of (x0, y0, x1, y1, ...) fp32, ld_boxes floats apart (>= 4): det_bboxes [N, 5] is read in place.
+ * Per detection and pixel (py, px) of the img_h x img_w image, in float32 with the reference's operations in its order:
+ *   value   p = 1 / (1 + expf(-logit)) of the label's channel (activated: the value itself)
+ *   grid    gx = ((px + .5f) - x0) / (x1 - x0) * 2 - 1, +-inf replaced by 0; gy likewise
+ *   sample  grid_sample, bilinear, align_corners=False, zero padding: ix = ((gx + 1) * w - 1) / 2, x_nw = floorf(ix), weights
+ *           (x_nw + 1 - ix) and (ix - x_nw) per axis, the four taps added in the order nw, ne, sw, se, taps outside the tile add
+ *           nothing
+ *   out     value >= threshold ? 1 : 0 (uint8; torch.bool's storage).  A pixel whose four taps lie outside is 0 >= threshold.
+ *   A label outside [0, C): an all-zero mask.  A NaN coordinate (0 / 0: a zero-size box edge exactly at a pixel centre) is not
+ *   offered: such a pixel is treated as one with its four taps outside.
+ * out: uint8 [N][img_h][img_w], any alignment.  Allocates nothing, reads nothing back.
+ * IIF_EINVAL before any launch: a null or misaligned pointer, an unknown dtype, C / h / w / img_h / img_w <= 0, ld_boxes < 4,
+ * N < 0 or > 65535, threshold < 0 (the reference's uint8 visualisation branch) or NaN.  IIF_EUNSUPPORTED: h or w > 64, img_h *
+ * img_w >= 2^31.  N == 0: IIF_OK, nothing is enqueued. */
+int iif_paste_masks(const void* mask_pred, int dtype, int activated, const int64_t* labels /* NULL: channel 0 */,
+                    const float* boxes, int64_t ld_boxes, int64_t N, int C, int h, int w, int img_h, int img_w, float threshold,
+                    uint8_t* out, void* stream);
+
 /* Non-maximum suppression (mmcv 1.3.8 ops/nms.py nms / batched_nms; iif_amd/mmdet_nms.py) in 5 enqueued operations for any N and
  * any data: a 4 KiB clear, the sort keys, the rank, the suppression bit matrix, the greedy scan (csrc/nms.hip).
  * boxes [N] rows of (x1, y1, x2, y2, ...) fp32, ld_boxes floats apart (>= 4), read in place; scores [N] fp32.
