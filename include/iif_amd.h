@@ -1060,6 +1060,41 @@ int iif_paste_masks(const void* mask_pred, int dtype, int activated, const int64
                     const float* boxes, int64_t ld_boxes, int64_t N, int C, int h, int w, int img_h, int img_w, float threshold,
                     uint8_t* out, void* stream);
 
+/* The class-selected mask predictor (csrc/mask_predictor.hip; iif_amd/mmdet_mask_predictor.py): FCNMaskHead's conv_logits
+ * (fcn_mask_head.py:135, a 1x1 convolution to C channels) evaluated at each RoI's label channel only - the one channel that
+ * mask_cross_entropy (cross_entropy_loss.py:158-162) and get_seg_masks (fcn_mask_head.py:289-290) keep.  The [N, C, HW] logits
+ * are never formed.  x [n][cin][hw], IIF_F32 or IIF_BF16, NCHW-contiguous; weight fp32 rows of cin values, ld_w floats apart
+ * (>= cin; the row of class k starts at weight + k * ld_w); bias fp32 [c] or NULL; labels int64 [n].  With l = labels[i]:
+ *
+ * iif_mask_predict_fwd (one launch; two with a target)
+ *   z[i, p] = bias[l] + sum_k weight[l, k] * x[i, k, p]           fp32 [n][hw], nullable when a target is given
+ *   target (fp32 [n][hw], nullable):  *loss = 1 / (n hw) * sum BCEWithLogits(z, target) (row partials in fp32, their sum in
+ *   double), g0[i, p] = (sigmoid(z) - target) / (n hw) (fp32 [n][hw], nullable: the compact gradient the two backward entries
+ *   take).  row_loss: scratch of n * ((hw + 63) / 64) floats.  Without a target row_loss and loss are not touched and g0 must be
+ *   NULL.  A label outside [0, c) sets bit 0 of *status (device int, caller-zeroed); that RoI gets z = 0, g0 = 0 and adds nothing
+ *   to the loss, whose divisor stays n * hw.
+ * iif_mask_predict_bwd_input (one launch, no clearing launch)
+ *   dx[i, k, p] = up * g[i, p] * weight[l, k]                     dx [n][cin][hw] in `dtype`, EVERY element written once
+ *   g fp32 [n][hw]; up: a DEVICE scalar (the upstream gradient of the loss), NULL = 1.  Reads no x.  A label outside [0, c): a
+ *   zero slice.
+ * iif_mask_predict_bwd_weight (two launches)
+ *   scratch[i, k] = up * sum_p g[i, p] * x[i, k, p], scratch[i, cin] = up * sum_p g[i, p]      fp32 [n][cin + 1]
+ *   dweight[j, k] = sum over the RoIs with labels[i] == j, in ascending i, of scratch[i, k];  dbias[j] likewise of scratch[i, cin]
+ *   dweight fp32 [c][cin] and dbias fp32 [c], either nullable: EVERY row is written, zeros for a class no RoI has.  A label
+ *   outside [0, c) contributes nothing.
+ * All sums are fp32 in a fixed order without float atomics: the same bits from call to call.  Nothing is allocated or read back.
+ * IIF_EINVAL before any launch: a required pointer NULL, n < 0 or > 65535, c < 1, cin outside 1 .. 2048, hw outside 1 .. 4096,
+ * ld_w < cin, an unknown dtype.  n == 0: IIF_OK, nothing is enqueued (dweight / dbias are not written). */
+int iif_mask_predict_fwd(const void* x, int dtype, const float* weight, int64_t ld_w, const float* bias /* nullable */,
+                         const int64_t* labels, const float* target /* nullable */, int n, int c, int cin, int hw,
+                         float* z /* nullable */, float* g0 /* nullable */, float* row_loss, float* loss, int* status,
+                         void* stream);
+int iif_mask_predict_bwd_input(const float* g, const float* up /* nullable */, const float* weight, int64_t ld_w,
+                               const int64_t* labels, int n, int c, int cin, int hw, void* dx, int dtype, void* stream);
+int iif_mask_predict_bwd_weight(const void* x, int dtype, const float* g, const float* up /* nullable */, const int64_t* labels,
+                                int n, int c, int cin, int hw, float* scratch, float* dweight /* nullable */,
+                                float* dbias /* nullable */, void* stream);
+
 /* Non-maximum suppression (mmcv 1.3.8 ops/nms.py nms / batched_nms; iif_amd/mmdet_nms.py) in 5 enqueued operations for any N and
  * any data: a 4 KiB clear, the sort keys, the rank, the suppression bit matrix, the greedy scan (csrc/nms.hip).
  * boxes [N] rows of (x1, y1, x2, y2, ...) fp32, ld_boxes floats apart (>= 4), read in place; scores [N] fp32.
