@@ -1095,6 +1095,55 @@ int iif_mask_predict_bwd_weight(const void* x, int dtype, const float* g, const 
                                 int n, int c, int cin, int hw, float* scratch, float* dweight /* nullable */,
                                 float* dbias /* nullable */, void* stream);
 
+/* The mask head's tail fused (csrc/mask_tail.hip; iif_amd/mmdet_mask_tail.py): FCNMaskHead's upsample (a ConvTranspose2d with
+ * kernel = stride = 2, no padding), its ReLU and conv_logits at each RoI's label channel (fcn_mask_head.py:131-136), on the
+ * fp32-input MFMA.  The [n][co][2h][2w] activation between the two layers and its gradient are never stored.
+ * f [n][ci][h][w], IIF_F32 or IIF_BF16, NCHW-contiguous; up_weight fp32 [ci][co][2][2] contiguous; up_bias fp32 [co] or NULL;
+ * weight fp32 rows of co values, ld_w floats apart (>= co); bias fp32 [c] or NULL; labels int64 [n].  With l = labels[i],
+ * P = (2y + a, 2x + b):
+ *   pre[i, k, P] = up_bias[k] + sum_m f[i, m, y, x] * up_weight[m, k, a, b],   z[i, P] = bias[l] + sum_k weight[l, k] * max(pre, 0)
+ *
+ * iif_mask_tail_fwd (one launch; two with a target)
+ *   z fp32 [n][2h][2w], nullable when a target is given.  target (fp32 [n][2h][2w], nullable): *loss = 1 / (4 n h w) * sum
+ *   BCEWithLogits(z, target), g0 = (sigmoid(z) - target) / (4 n h w) (fp32 [n][2h][2w], nullable).  row_loss: scratch of
+ *   n * ((h w + 63) / 64) floats.  Without a target row_loss and loss are not touched and g0 must be NULL.  A label outside
+ *   [0, c) sets bit 0 of *status (device int, caller-zeroed); that RoI gets z = 0, g0 = 0 and adds nothing to the loss, whose
+ *   divisor stays 4 n h w.
+ * iif_mask_tail_bwd_rows (one launch): recomputes pre for the gradient g fp32 [n][2h][2w] (times the DEVICE scalar up, NULL = 1)
+ *   signs[i][t][j]: bit q of the word is pre[i, k, P] > 0 for input pixel 32 t + q and j = 4 k + 2 a + b;
+ *                   n * ((h w + 31) / 32) * 4 co words, which the two entries below read
+ *   rows[i, k] = up * sum_P g[i, P] * max(pre[i, k, P], 0), rows[i, co] = up * sum_P g[i, P]      fp32 [n][co + 1], nullable
+ * iif_mask_tail_bwd_input (one launch, no clearing launch)
+ *   df[i, m, y, x] = sum_{k,a,b} dpre[i, k, P] * up_weight[m, k, a, b],  dpre = up * g[i, P] * weight[l, k] * [pre > 0]
+ *   df [n][ci][h][w] in `dtype`, EVERY element written once.  up_weight must be 16-byte aligned (IIF_EUNSUPPORTED otherwise).
+ * iif_mask_tail_bwd_params (two launches)
+ *   dup_weight[m, k, a, b] = sum_{i,y,x} f * dpre, dup_bias[k] = sum dpre (either nullable): the RoIs are cut into
+ *   iif_mask_tail_splits(n, ci, co) ranges, one partial each, summed in range order.  partial: scratch of
+ *   splits * (ci + 1) * 4 co floats.
+ * iif_mask_tail_bwd_classes (one launch): dweight[j, k] = sum over the RoIs with labels[i] == j, in ascending i, of rows[i, k];
+ *   dbias[j] likewise of rows[i, co].  dweight fp32 [c][co], dbias fp32 [c], either nullable: EVERY row is written.
+ * A label outside [0, c) gives a zero df slice and contributes nothing to any parameter gradient.  All sums are fp32 in a fixed
+ * order without float atomics: the same bits from call to call.  Nothing is allocated or read back.
+ * IIF_EINVAL before any launch: a required pointer NULL, n < 0 or > 65535, c < 1, ci or co outside 1 .. 1024, h or w < 1,
+ * h * w > 1024, ld_w < co, a dtype other than IIF_F32 / IIF_BF16.  n == 0: IIF_OK, nothing enqueued. */
+int iif_mask_tail_fwd(const void* f, int dtype, const float* up_weight, const float* up_bias /* nullable */, const float* weight,
+                      int64_t ld_w, const float* bias /* nullable */, const int64_t* labels, const float* target /* nullable */,
+                      int n, int c, int ci, int co, int h, int w, float* z /* nullable */, float* g0 /* nullable */,
+                      float* row_loss, float* loss, int* status, void* stream);
+int iif_mask_tail_bwd_rows(const void* f, int dtype, const float* up_weight, const float* up_bias /* nullable */, const float* g,
+                           const float* up /* nullable */, const int64_t* labels, int n, int c, int ci, int co, int h, int w,
+                           unsigned int* signs, float* rows /* nullable */, void* stream);
+int iif_mask_tail_bwd_input(const float* g, const float* up /* nullable */, const float* up_weight, const float* weight,
+                            int64_t ld_w, const int64_t* labels, const unsigned int* signs, int n, int c, int ci, int co, int h,
+                            int w, void* df, int dtype, void* stream);
+int iif_mask_tail_splits(int n, int ci, int co);
+int iif_mask_tail_bwd_params(const void* f, int dtype, const float* g, const float* up /* nullable */, const float* weight,
+                             int64_t ld_w, const int64_t* labels, const unsigned int* signs, int n, int c, int ci, int co, int h,
+                             int w, float* partial, float* dup_weight /* nullable */, float* dup_bias /* nullable */,
+                             void* stream);
+int iif_mask_tail_bwd_classes(const float* rows, const int64_t* labels, int n, int c, int co, float* dweight /* nullable */,
+                              float* dbias /* nullable */, void* stream);
+
 /* Non-maximum suppression (mmcv 1.3.8 ops/nms.py nms / batched_nms; iif_amd/mmdet_nms.py) in 5 enqueued operations for any N and
  * any data: a 4 KiB clear, the sort keys, the rank, the suppression bit matrix, the greedy scan (csrc/nms.hip).
  * boxes [N] rows of (x1, y1, x2, y2, ...) fp32, ld_boxes floats apart (>= 4), read in place; scores [N] fp32.
