@@ -136,6 +136,9 @@ SIGNATURES = {
     "iif_random_sample": [_P, _P, _L, _L, _L, _c.c_double, _P, _P, _P, _P, _P, _L, _P],
     "iif_anchor_targets": [_P, _L, _L, _P, _P, _L, _P, _L, _L, _P, _P, _L, _F, _I, _P, _P, _P, _P, _P, _P, _P],
     "iif_roi_targets": [_P, _L, _L, _P, _P, _P, _L, _L, _P, _P, _P, _L, _L, _I, _L, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "iif_roi_stage_targets": [_P, _I, _P, _L, _L, _L, _P, _P, _L, _F, _F, _F, _F, _I, _I, _I, _L, _L, _c.c_double, _L, _F, _I, _P, _P,
+                              _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "iif_refine_bboxes": [_P, _L, _P, _P, _L, _I, _I, _P, _P, _I, _L, _P, _P, _P, _F, _I, _F, _I, _P, _P, _P],
     "iif_roi_extract_forward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _P],
     "iif_roi_extract_backward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _L, _P],
     "iif_mask_targets": [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P],
@@ -172,6 +175,12 @@ class MaskImage(ctypes.Structure):
     """Mirror of ``iif_mask_image`` (include/iif_amd.h)."""
     _fields_ = [("ptr", ctypes.c_void_p), ("G", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
                 ("ld_row", ctypes.c_int64), ("ld_mask", ctypes.c_int64)]
+
+
+class RoiImage(ctypes.Structure):
+    """Mirror of ``iif_roi_image`` (include/iif_amd.h)."""
+    _fields_ = [("gt_bboxes", ctypes.c_void_p), ("ld_gt", ctypes.c_int64), ("gt_labels", ctypes.c_void_p), ("G", ctypes.c_int32),
+                ("img_index", ctypes.c_int32)]
 
 
 class RpnLevel(ctypes.Structure):

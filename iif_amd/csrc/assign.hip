@@ -28,46 +28,15 @@
 // The assigner's eps is the reference's default 1e-6 (> 0), so a pair with overlap == 0 has iou == +0 exactly and the division
 // is skipped.  NaN coordinates are not reproduced (torch's max / clamp propagate NaN, v_max_f32 does not).
 #include "common.h"
+#include "assign_common.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kChunk = 256;                   // gt / ignore boxes per LDS chunk: one per thread of the block
-constexpr float kAssignEps = 1e-6f;           // bbox_overlaps' default eps, which MaxIoUAssigner never overrides
 constexpr unsigned kOvMaxBlocks = 1u << 16;   // grid cap of the calculator (grid-stride beyond)
 
 enum { kIoU = 0, kIoF = 1, kGIoU = 2 };
-
-struct alignas(16) Box { float x1, y1, x2, y2; };
-
-// vec: the array's rows are whole 16-byte pieces (base on a 16-byte boundary, pitch a multiple of 4)
-__device__ __forceinline__ Box load_box(const float* p, bool vec) {
-    if (vec) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        return Box{t.x, t.y, t.z, t.w};
-    }
-    return Box{p[0], p[1], p[2], p[3]};
-}
-
-__device__ __forceinline__ float box_area(const Box& b) { return (b.x2 - b.x1) * (b.y2 - b.y1); }
-
-__device__ __forceinline__ float box_inter(const Box& a, const Box& b) {
-    const float w = fmaxf(fminf(a.x2, b.x2) - fmaxf(a.x1, b.x1), 0.0f);
-    const float h = fmaxf(fminf(a.y2, b.y2) - fmaxf(a.y1, b.y1), 0.0f);
-    return w * h;
-}
-
-// iou of a (ground-truth, candidate) pair as the assigner sees it (eps = kAssignEps > 0); `inter` returns the overlap area.
-// BOTH passes go through this function: pass 2 compares its result with pass 1's for equality.
-__device__ __forceinline__ float pair_iou(const Box& g, float ga, const Box& c, float ca, float& inter) {
-    inter = box_inter(g, c);
-    if (!(inter > 0.0f)) return 0.0f;                       // 0 / max(union, eps) = +0
-    return inter / fmaxf(ga + ca - inter, kAssignEps);
-}
-
-__device__ __forceinline__ unsigned long long pack_max(float v, unsigned idx) {
-    return ((unsigned long long)(__float_as_uint(v) + 1u) << 32) | (unsigned long long)(~idx);
-}
 
 struct AssignArgs {
     const float* b; int64_t ldb; int N; int vec_b;
@@ -79,14 +48,6 @@ struct AssignArgs {
     int64_t* gt_inds; float* max_ov; int64_t* labels;
     unsigned long long* ws;                                 // [G + 1], zero on entry (low_quality only)
 };
-
-// steps 1 - 3 of assign_wrt_overlaps (max_iou_assigner.py:141-183)
-__device__ __forceinline__ int64_t base_assign(const AssignArgs& a, float mo, int arg) {
-    int64_t gi = -1;
-    if (mo >= a.neg_lo && mo < a.neg_hi) gi = 0;
-    if (mo >= a.pos) gi = (int64_t)arg + 1;
-    return gi;
-}
 
 __device__ __forceinline__ void store_result(const AssignArgs& a, int64_t idx, int64_t gi) {
     a.gt_inds[idx] = gi;

@@ -1,6 +1,7 @@
-// The box type and the decode step of the delta coder, shared by targets.hip (iif_delta2bbox) and nms.hip (the RPN proposals):
-// one definition, so both produce the same bits.  Every step is the reference's single IEEE float32 operation in its order
-// (core/bbox/coder/delta_xywh_bbox_coder.py:206-270; the build passes -ffp-contract=off); expf is the device library's.
+// The box type and the two steps of the delta coder, shared by targets.hip (iif_bbox2delta / iif_delta2bbox, the target builders),
+// nms.hip (the RPN proposals), assign.hip and roi_stage.hip: one definition, so all produce the same bits.  Every step is the
+// reference's single IEEE float32 operation in its order (core/bbox/coder/delta_xywh_bbox_coder.py:119-139, :206-270; the build
+// passes -ffp-contract=off); logf / expf are the device library's.
 #pragma once
 #include "common.h"
 
@@ -9,6 +10,7 @@ namespace {
 struct alignas(16) Box { float x1, y1, x2, y2; };
 struct Norm { float m[4], s[4]; };
 
+// vec: the array's rows are whole 16-byte pieces (base on a 16-byte boundary, pitch a multiple of 4)
 __device__ __forceinline__ Box load_box(const float* p, bool vec) {
     if (vec) {
         const f32x4 t = *reinterpret_cast<const f32x4*>(p);
@@ -54,6 +56,24 @@ __device__ __forceinline__ f32x4 decode_box(const Box& p, const Box& t, const No
         o.x = clip_coord(o.x, max_w); o.y = clip_coord(o.y, max_h);
         o.z = clip_coord(o.z, max_w); o.w = clip_coord(o.w, max_h);
     }
+    return o;
+}
+
+// bbox2delta (:119-139).  Shared by iif_bbox2delta, both target builders (targets.hip) and the RoI stage (roi_stage.hip).
+__device__ __forceinline__ f32x4 encode_delta(const Box& p, const Box& g, const Norm& nm) {
+    const float px = (p.x1 + p.x2) * 0.5f, py = (p.y1 + p.y2) * 0.5f;
+    const float pw = p.x2 - p.x1, ph = p.y2 - p.y1;
+    const float gx = (g.x1 + g.x2) * 0.5f, gy = (g.y1 + g.y2) * 0.5f;
+    const float gw = g.x2 - g.x1, gh = g.y2 - g.y1;
+    const float dx = (gx - px) / pw;
+    const float dy = (gy - py) / ph;
+    const float dw = logf(gw / pw);
+    const float dh = logf(gh / ph);
+    f32x4 o;
+    o.x = (dx - nm.m[0]) / nm.s[0];
+    o.y = (dy - nm.m[1]) / nm.s[1];
+    o.z = (dw - nm.m[2]) / nm.s[2];
+    o.w = (dh - nm.m[3]) / nm.s[3];
     return o;
 }
 

@@ -43,24 +43,6 @@ constexpr unsigned kMaxBlocks = 1u << 16;
 
 typedef unsigned long long u64;
 
-// bbox2delta (:119-139).  Shared by iif_bbox2delta and both target builders.
-__device__ __forceinline__ f32x4 encode_delta(const Box& p, const Box& g, const Norm& nm) {
-    const float px = (p.x1 + p.x2) * 0.5f, py = (p.y1 + p.y2) * 0.5f;
-    const float pw = p.x2 - p.x1, ph = p.y2 - p.y1;
-    const float gx = (g.x1 + g.x2) * 0.5f, gy = (g.y1 + g.y2) * 0.5f;
-    const float gw = g.x2 - g.x1, gh = g.y2 - g.y1;
-    const float dx = (gx - px) / pw;
-    const float dy = (gy - py) / ph;
-    const float dw = logf(gw / pw);
-    const float dh = logf(gh / ph);
-    f32x4 o;
-    o.x = (dx - nm.m[0]) / nm.s[0];
-    o.y = (dy - nm.m[1]) / nm.s[1];
-    o.z = (dw - nm.m[2]) / nm.s[2];
-    o.w = (dh - nm.m[3]) / nm.s[3];
-    return o;
-}
-
 struct EncArgs { const float* p; int64_t ldp; int vecp; const float* g; int64_t ldg; int vecg; int64_t n; Norm nm; float* out; };
 
 __global__ void __launch_bounds__(kThreads) bbox2delta_kernel(EncArgs a) {

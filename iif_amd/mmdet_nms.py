@@ -15,8 +15,8 @@ the reference keeps.
 ``multiclass_nms`` (1 000 x 1 203 candidates on LVIS) has a segmented per-class design of its own, not this N^2 matrix:
 mmdet_multiclass_nms.py.  Deliberately not offered: ``soft_nms``, ``nms_match``, ``fast_nms``; more than 16 384 boxes; the two-class softmax RPN; ``rescale``; the ONNX
 branches; a tensor ``max_shape``; ``with_nms=False``; on the RPN path ``split_thr`` candidates or more per image (the
-reference's data-dependent switch to a per-level NMS).  The padded proposals cannot yet feed the assigner without the one read:
-it has no valid-count input.  When mmdet is importable a subclass of its ``RPNHead`` registers itself as ``RPNHead``.
+reference's data-dependent switch to a per-level NMS).  The padded proposals feed the RoI stage without a read:
+``mmdet_roi_stage.roi_stage_targets_padded`` takes ``(dets, counts)`` as they are.  When mmdet is importable a subclass of its ``RPNHead`` registers itself as ``RPNHead``.
 """
 import ctypes
 

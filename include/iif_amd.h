@@ -301,6 +301,59 @@ int iif_roi_targets(const float* bboxes, int64_t ld_bboxes, int64_t N, const int
                     int reg_decoded_bbox, const float* means, const float* stds, float* rois, int64_t* labels,
                     float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* pos_assigned_gt_inds, void* stream);
 
+/* ---- The RoI stage in one launch (csrc/roi_stage.hip): assign, add the ground truth, sample and build the targets for all B
+ * images of a batch, reading each image's number of valid proposals from DEVICE memory - what roi_heads/standard_roi_head.py:85-100
+ * and BBoxHead.get_targets do per image.  One workgroup per image.
+ *
+ * images: HOST array of B descriptors, copied into the launch: the image's ground-truth boxes [G, >= 4] (pitch ld_gt elements)
+ *   and labels [G] on the device, G (known from the shapes: no read) and the image index written into the rois.
+ * proposals: float32 rows <x1, y1, x2, y2, ...>; row i of image b at proposals + b * ld_image + i * ld_row (ld_row >= 4: dets
+ *   [B, P, 5] and refined boxes [B, P, 4] both go in unchanged).  n_b = clamp(proposal_counts[b], 0, P), or P when
+ *   proposal_counts is NULL; rows at or beyond n_b are NEVER READ.
+ * Candidates of image b: the ground-truth boxes, then the n_b proposals, when add_gt_as_proposals and G > 0 (front = G), else the
+ *   proposals alone (front = 0); M_b = front + n_b, candidate c < front is gt c.
+ * Assignment: iif_max_iou_assign's definition above on the PROPOSALS (no ignore boxes; the low-quality match never sees the gt
+ *   boxes as candidates; lowest gt on equal overlaps, lowest proposal for a gt's maximum), then the gt candidates get
+ *   gt_inds c + 1 and their own labels, as AssignResult.add_gt_ does.  Per-gt maxima are 64-bit integer maxima in LDS.
+ * Sampling: iif_random_sample's rule with the key of candidate c of image b at keys[b * ld_keys + c] (ld_keys >= max front + P):
+ *   the num_expected_pos smallest (key, index) pairs of the positives, the negative budget num - kept positives capped by
+ *   neg_pos_ub in the same double arithmetic; index lists ascending; correct for any keys, all equal included.
+ * Rows [b * num, (b + 1) * num) of rois [B num, 5], labels, label_weights, bbox_targets [B num, 4], bbox_weights,
+ *   pos_assigned_gt_inds: positives, negatives, padding - iif_roi_targets' rows for that image, bit for bit.
+ * counts [B, 2]: positives, negatives kept.  pos_is_gt [B num] uint8: 1 where the row is a ground-truth box (0 on negatives and
+ *   padding).  Rows [b * num_expected_pos, ..) of pos_rois [.., 5], pos_gt_inds, pos_labels: the positives alone, for the mask
+ *   branch; unused rows carry image index -1, gt index -1, label num_classes.
+ * Limits: 1 <= B <= 16, P <= 4096, G <= 1024, num <= 1024, 0 <= num_expected_pos <= num; beyond them IIF_EINVAL.
+ * One launch, nothing allocated, nothing synchronises, no workspace; integer atomics only: no result depends on arrival order. */
+typedef struct iif_roi_image {
+    const float* gt_bboxes;
+    int64_t ld_gt;
+    const int64_t* gt_labels;
+    int32_t G;
+    int32_t img_index;
+} iif_roi_image;
+int iif_roi_stage_targets(const iif_roi_image* images, int B, const float* proposals, int64_t ld_row, int64_t ld_image, int64_t P,
+                          const int64_t* proposal_counts, const int32_t* keys, int64_t ld_keys, float pos_iou_thr, float neg_lo,
+                          float neg_hi, float min_pos_iou, int gt_max_assign_all, int match_low_quality, int add_gt_as_proposals,
+                          int64_t num_expected_pos, int64_t num, double neg_pos_ub, int64_t num_classes, float pos_weight,
+                          int reg_decoded_bbox, const float* means, const float* stds, float* rois, int64_t* labels,
+                          float* label_weights, float* bbox_targets, float* bbox_weights, int64_t* pos_assigned_gt_inds,
+                          int64_t* counts, uint8_t* pos_is_gt, float* pos_rois, int64_t* pos_gt_inds, int64_t* pos_labels,
+                          void* stream);
+
+/* BBoxHead.refine_bboxes + regress_by_class (bbox_heads/bbox_head.py:380-496) on the padded rows of one stage, one workgroup
+ * per image.  Of image b the rows r < clamp(counts[2 b] + counts[2 b + 1], 0, num) are valid; rows beyond are NEVER READ.
+ *   A valid row whose pos_is_gt is set is dropped.  Every other valid row is decoded with iif_delta2bbox's arithmetic from
+ *   rois[row, 1:5] and the four deltas at bbox_preds[row, 4 label ..] (at 0 when reg_class_agnostic; a label outside
+ *   [0, num_classes) reads nothing and decodes zero deltas), clipped to img_hw[b] = (h, w) (HOST array [B, 2]) when clip != 0.
+ *   proposals [B, num, 4]: the kept boxes compacted in their original order, zero rows behind them; proposal_counts [B]: their
+ *   number - the (proposals, proposal_counts) input of iif_roi_stage_targets.
+ * Limits: 1 <= B <= 16, num <= 1024.  One launch, nothing allocated, nothing synchronises, no atomics. */
+int iif_refine_bboxes(const float* rois, int64_t ld_rois, const int64_t* labels, const float* bbox_preds, int64_t ld_preds,
+                      int num_classes, int reg_class_agnostic, const uint8_t* pos_is_gt, const int64_t* counts, int B, int64_t num,
+                      const float* img_hw, const float* means, const float* stds, float max_ratio, int add_ctr_clamp,
+                      float ctr_clamp, int clip, float* proposals, int64_t* proposal_counts, void* stream);
+
 /* out = logits * table. Replaces classification/custom.py:37-39 (infer=True). */
 int iif_scale_logits(const void* logits, int dtype, int64_t ld_logits, const float* table,
                      int B, int C, void* out, int64_t ld_out, void* stream);
