@@ -143,6 +143,12 @@ SIGNATURES = {
     "iif_roi_extract_backward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _L, _P],
     "iif_mask_targets": [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P],
     "iif_paste_masks": [_P, _I, _I, _P, _P, _L, _L, _I, _I, _I, _I, _I, _F, _P, _P],
+    "iif_rle_workspace_bytes": [_L, _I, _I],
+    "iif_paste_rle_count": [_P, _I, _I, _P, _P, _L, _L, _I, _I, _I, _I, _I, _F, _P, _L, _P, _P],
+    "iif_paste_rle_fill": [_P, _I, _I, _P, _P, _L, _L, _I, _I, _I, _I, _I, _F, _P, _L, _P, _L, _P, _P, _P],
+    "iif_mask_rle_count": [_P, _L, _L, _L, _I, _I, _P, _L, _P, _P],
+    "iif_mask_rle_fill": [_P, _L, _L, _L, _I, _I, _P, _L, _P, _L, _P, _P, _P],
+    "iif_rle_to_string": [_P, _L, _P, _L, _P],
     "iif_mask_predict_fwd": [_P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "iif_mask_predict_bwd_input": [_P, _P, _P, _L, _P, _I, _I, _I, _I, _P, _I, _P],
     "iif_mask_predict_bwd_weight": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
@@ -217,7 +223,7 @@ def lib():
         for name, argtypes in SIGNATURES.items():
             fn = getattr(l, name)
             fn.argtypes = argtypes
-            fn.restype = _L if name in ("iif_bn_workspace_bytes", "iif_bn3_algebra_prep_scratch_floats") else _I
+            fn.restype = _L if name in ("iif_bn_workspace_bytes", "iif_bn3_algebra_prep_scratch_floats", "iif_rle_workspace_bytes") else _I
         _lib = l
     return _lib
 

@@ -112,3 +112,25 @@ extern "C" int iif_build_table(const int64_t* counts, int C, int variant, int no
     }
     return IIF_OK;
 }
+
+// pycocotools' rleToString (common/maskApi.c) for counts that are already on the host (csrc/mask_rle.hip produces them)
+extern "C" int iif_rle_to_string(const uint32_t* counts, int64_t m, char* out, int64_t cap, int64_t* len) {
+    if (len) *len = 0;
+    if (m < 0 || cap < 0 || (m > 0 && !counts) || (cap > 0 && !out)) return IIF_EINVAL;
+    int64_t p = 0;
+    for (int64_t i = 0; i < m; ++i) {
+        int64_t x = (int64_t)counts[i];
+        if (i > 2) x -= (int64_t)counts[i - 2];
+        bool more;
+        do {
+            int c = (int)(x & 0x1f);
+            x >>= 5;
+            more = (c & 0x10) ? x != -1 : x != 0;
+            if (more) c |= 0x20;
+            if (p < cap) out[p] = (char)(c + 48);
+            ++p;
+        } while (more);
+    }
+    if (len) *len = p;
+    return p <= cap ? IIF_OK : IIF_EINVAL;
+}

@@ -25,9 +25,11 @@
 // boundary of the address, 16 pixels per 16-byte store, a scalar tail (img_w is arbitrary, so rows start anywhere).  A
 // conservative pixel rectangle around the box (two pixels and a tap's reach wider than where any tap can land) lets chunks, rows
 // and whole bands outside it be written as the constant  0 >= threshold  without touching LDS or computing a coordinate; inside
-// it every pixel evaluates the reference's float32 expressions in their order and decides by the taps themselves.
+// it every pixel evaluates the reference's float32 expressions in their order and decides by the taps themselves.  The pixel's
+// definition lives in mask_paste.h, which mask_rle.hip (the same masks as COCO run lengths, without the image) shares.
 #include "common.h"
 #include "roi_geom.h"
+#include "mask_paste.h"
 
 namespace {
 
@@ -221,7 +223,6 @@ __global__ void __launch_bounds__(kThreads) mask_targets_kernel(TargetArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- paste
-constexpr int kMaxPred = 64;                  // h, w of the predicted mask
 constexpr int kBandBytes = 65536;
 
 struct PasteArgs {
@@ -233,80 +234,19 @@ struct PasteArgs {
     uint8_t* out;
 };
 
-// _do_paste_mask's normalised coordinate of pixel p on an axis with box edges (a, b), with its replacement of +-inf by 0
-__device__ __forceinline__ float paste_coord(int p, float a, float b) {
-    float v = ((float)p + 0.5f - a) / (b - a) * 2.0f - 1.0f;
-    if (fabsf(v) > 3.402823466e38f) v = 0.0f;
-    return v;
-}
-
-// grid_sample's source coordinate (align_corners=False)
-__device__ __forceinline__ float paste_unnormalize(float v, int size) { return ((v + 1.0f) * (float)size - 1.0f) / 2.0f; }
-
-// Pixels [lo, hi] outside which no tap of this axis can land inside the tile.  A tap lands inside for
-// p in (a - .5 - d / 2size, b - .5 + d / 2size), d = b - a (mirrored for d < 0); the range returned is wider than that by more
-// than 1.5 pixels, against float32 rounding of a few 2^-22 of the quantities involved.  Edges that are tiny, huge or not finite
-// (where the reference's quotient may overflow to inf and be replaced by 0, i.e. land in the CENTRE of the tile): the whole axis.
-__device__ __forceinline__ void paste_bounds(float a, float b, int size, int img, int* lo, int* hi) {
-    *lo = 0; *hi = img - 1;
-    const float ad = fabsf(b - a);
-    if (finite_f(a) && finite_f(b) && ad >= 0.0009765625f && fabsf(a) <= 1048576.0f && fabsf(b) <= 1048576.0f) {
-        const float m = ad / (float)size + 2.0f;
-        const float flo = floorf(fminf(a, b) - m), fhi = ceilf(fmaxf(a, b) + m);
-        *lo = max(0, (int)flo);
-        *hi = min(img - 1, (int)fhi);
-    }
-}
-
-struct PasteBox {
-    float x0, y0, x1, y1, thr;
-    int xlo, xhi, ylo, yhi, h, w;
-    bool any;                                 // some pixel of this block may have a tap inside the tile (the tile is loaded)
-    uint8_t fill;                             // every other pixel
-};
-
-__device__ __forceinline__ uint8_t paste_pixel(const PasteBox& b, const float* tile, int y, int x) {
-    if (!b.any || y < b.ylo || y > b.yhi || x < b.xlo || x > b.xhi) return b.fill;
-    const float ix = paste_unnormalize(paste_coord(x, b.x0, b.x1), b.w);
-    const float iy = paste_unnormalize(paste_coord(y, b.y0, b.y1), b.h);
-    if (!(ix > -1.0f && ix < (float)b.w && iy > -1.0f && iy < (float)b.h)) return b.fill;      // four taps outside (NaN too)
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int xi = (int)fx, yi = (int)fy;
-    const float wx1 = ix - fx, wx0 = (fx + 1.0f) - ix, wy1 = iy - fy, wy0 = (fy + 1.0f) - iy;
-    const bool xa = xi >= 0, xb = xi + 1 < b.w, ya = yi >= 0, yb = yi + 1 < b.h;
-    float v = 0.0f;
-    if (ya && xa) v += tile[yi * b.w + xi] * (wx0 * wy0);
-    if (ya && xb) v += tile[yi * b.w + xi + 1] * (wx1 * wy0);
-    if (yb && xa) v += tile[(yi + 1) * b.w + xi] * (wx0 * wy1);
-    if (yb && xb) v += tile[(yi + 1) * b.w + xi + 1] * (wx1 * wy1);
-    return v >= b.thr ? 1 : 0;
-}
-
 __global__ void __launch_bounds__(kThreads) paste_masks_kernel(PasteArgs a) {
     __shared__ float tile[kMaxPred * kMaxPred];
     const int tid = threadIdx.x;
     const int64_t n = blockIdx.y;
     const int yb0 = (int)blockIdx.x * a.rows_per_band;
     const int yb1 = min(a.img_h, yb0 + a.rows_per_band);
-    const float* bx = a.boxes + n * a.ldb;
     PasteBox b;
-    b.x0 = bx[0]; b.y0 = bx[1]; b.x1 = bx[2]; b.y1 = bx[3];
-    b.thr = a.thr; b.h = a.h; b.w = a.w;
-    const int64_t c = a.labels ? a.labels[n] : 0;
-    const bool valid = c >= 0 && c < (int64_t)a.C;
-    b.fill = (valid && 0.0f >= a.thr) ? 1 : 0;
-    paste_bounds(b.x0, b.x1, a.w, a.img_w, &b.xlo, &b.xhi);
-    paste_bounds(b.y0, b.y1, a.h, a.img_h, &b.ylo, &b.yhi);
+    int64_t c;
+    const bool valid = paste_box(a.boxes + n * a.ldb, a.labels, n, a.C, a.h, a.w, a.img_h, a.img_w, a.thr, &b, &c);
     b.any = valid && b.xhi >= b.xlo && !(b.yhi < yb0 || b.ylo >= yb1);
     if (b.any) {
         const int hw = a.h * a.w;
-        const int64_t off = (n * a.C + c) * hw;
-        for (int e = tid; e < hw; e += kThreads) {
-            float v = a.dtype == IIF_BF16 ? bf16_bits_to_f32(static_cast<const uint16_t*>(a.pred)[off + e])
-                                          : static_cast<const float*>(a.pred)[off + e];
-            if (!a.activated) v = 1.0f / (1.0f + expf(-v));
-            tile[e] = v;
-        }
+        paste_load_tile(a.pred, a.dtype, a.activated, (n * a.C + c) * hw, hw, tile, tid, kThreads);
         __syncthreads();
     }
     const int64_t img0 = n * a.img_h * a.img_w;

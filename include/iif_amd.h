@@ -1112,6 +1112,49 @@ int iif_mask_targets(const iif_mask_image* images, int num_images, const float* 
 int iif_paste_masks(const void* mask_pred, int dtype, int activated, const int64_t* labels /* NULL: channel 0 */,
                     const float* boxes, int64_t ld_boxes, int64_t N, int C, int h, int w, int img_h, int img_w, float threshold,
                     uint8_t* out, void* stream);
+/* COCO run-length encoding on the device (csrc/mask_rle.hip; iif_amd/mmdet_mask_loss.py: paste_masks_rle, encode_masks,
+ * get_seg_masks_rle): what pycocotools' mask.encode returns for each mask, without the host loop and - for pasted masks - without
+ * the boolean image.  A mask of H x W is read in column-major order, pixel j = x * H + y; its counts alternate run lengths
+ * starting with a run of zeros (which may be 0 long), so they are the differences of successive transition positions (j with
+ * M[j] != M[j - 1], M[-1] := 0), opened by 0 and closed by H * W.
+ *
+ * Two steps, with one small read by the caller between them:
+ *   ..._count  transitions per (mask, column, row segment) into `workspace`, their exclusive scan in place, totals[n] = the
+ *              number of counts of mask n (int32 [N]) and the masks' offsets in the flat run buffer (kept in the workspace)
+ *   (caller)   reads totals, total = their sum, allocates positions and runs: uint32 [total] each
+ *   ..._fill   the same pixels again: transition positions into `positions`, then runs[k] = positions[k] - positions[k - 1]
+ *              within each mask.  runs holds the counts of mask 0, then of mask 1, ...; positions is scratch.
+ * workspace: iif_rle_workspace_bytes(N, H, W) bytes, 8-byte aligned, the SAME buffer untouched between the two steps; the fill
+ * step must get the arguments of the count step.  No atomics: the same bytes from call to call.  A `total` below the true sum
+ * is not an overrun: what does not fit is dropped.
+ *
+ * iif_paste_rle_*: the masks iif_paste_masks would write, decided pixel by pixel by the same definition (csrc/mask_paste.h), but
+ * evaluated only inside the conservative rectangle around each box - outside it the mask is the constant 0 >= threshold; the
+ * arguments, limits and checks of iif_paste_masks (H = img_h, W = img_w).
+ * iif_mask_rle_*: masks uint8 (any non-zero byte is 1; torch.bool's storage), N masks of H x W read IN PLACE, rows ld_row bytes
+ * apart (>= W), masks ld_mask bytes apart (>= (H - 1) * ld_row + W).  IIF_EINVAL: N < 0 or > 65535, H / W <= 0, a pitch too
+ * small, a null pointer; IIF_EUNSUPPORTED: H * W >= 2^31.
+ * Both: IIF_EINVAL for a null or misaligned workspace / totals / positions / runs (4 bytes), a workspace below
+ * iif_rle_workspace_bytes, total < N.  N == 0: IIF_OK, nothing is enqueued. */
+int64_t iif_rle_workspace_bytes(int64_t N, int H, int W);
+int iif_paste_rle_count(const void* mask_pred, int dtype, int activated, const int64_t* labels /* NULL: channel 0 */,
+                        const float* boxes, int64_t ld_boxes, int64_t N, int C, int h, int w, int img_h, int img_w, float threshold,
+                        void* workspace, int64_t workspace_bytes, int32_t* totals, void* stream);
+int iif_paste_rle_fill(const void* mask_pred, int dtype, int activated, const int64_t* labels, const float* boxes, int64_t ld_boxes,
+                       int64_t N, int C, int h, int w, int img_h, int img_w, float threshold, void* workspace,
+                       int64_t workspace_bytes, const int32_t* totals, int64_t total, uint32_t* positions, uint32_t* runs,
+                       void* stream);
+int iif_mask_rle_count(const uint8_t* masks, int64_t ld_row, int64_t ld_mask, int64_t N, int H, int W, void* workspace,
+                       int64_t workspace_bytes, int32_t* totals, void* stream);
+int iif_mask_rle_fill(const uint8_t* masks, int64_t ld_row, int64_t ld_mask, int64_t N, int H, int W, void* workspace,
+                      int64_t workspace_bytes, const int32_t* totals, int64_t total, uint32_t* positions, uint32_t* runs,
+                      void* stream);
+/* iif_rle_to_string (host code: the runs are on the host by then): pycocotools' rleToString of m counts.  Count i is written as
+ * x = counts[i] - (i > 2 ? counts[i - 2] : 0) in signed 64-bit, five bits at a time from the low end: c = x & 0x1f, x >>= 5
+ * (arithmetic), more = (c & 0x10) ? x != -1 : x != 0, byte = (c | (more ? 0x20 : 0)) + 48.  out: `cap` bytes, no terminator;
+ * *len (nullable) = the length of the string, also when it does not fit.  7 * m bytes always suffice.  IIF_EINVAL: m < 0, cap < 0,
+ * a null counts with m > 0, a null out with cap > 0, and a string longer than cap - then nothing is written past out[cap - 1]. */
+int iif_rle_to_string(const uint32_t* counts, int64_t m, char* out, int64_t cap, int64_t* len);
 
 /* The class-selected mask predictor (csrc/mask_predictor.hip; iif_amd/mmdet_mask_predictor.py): FCNMaskHead's conv_logits
  * (fcn_mask_head.py:135, a 1x1 convolution to C channels) evaluated at each RoI's label channel only - the one channel that
