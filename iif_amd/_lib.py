@@ -139,6 +139,14 @@ SIGNATURES = {
     "iif_roi_stage_targets": [_P, _I, _P, _L, _L, _L, _P, _P, _L, _F, _F, _F, _F, _I, _I, _I, _L, _L, _c.c_double, _L, _F, _I, _P, _P,
                               _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "iif_refine_bboxes": [_P, _L, _P, _P, _L, _I, _I, _P, _P, _I, _L, _P, _P, _P, _F, _I, _F, _I, _P, _P, _P],
+    "iif_grid_anchors": [_P, _P, _P],
+    "iif_grid_valid_flags": [_P, _P, _P, _P],
+    "iif_rpn_stage_workspace_bytes": [_I, _L, _L],
+    "iif_rpn_stage_targets": [_P, _P, _I, _P, _I, _F, _P, _P, _F, _F, _F, _F, _I, _I, _L, _L, _c.c_double, _P, _P, _P, _P, _P, _P, _P,
+                              _P, _P, _L, _P],
+    "iif_rpn_stage_dense": [_P, _I, _P, _P, _P, _P, _L, _L, _L, _F, _P, _P, _P, _P, _P],
+    "iif_rpn_loss_fwd": [_P, _P, _I, _P, _P, _P, _P, _L, _L, _P, _F, _F, _F, _F, _P, _P, _P],
+    "iif_rpn_loss_bwd": [_P, _P, _I, _P, _P, _P, _P, _L, _L, _P, _F, _F, _F, _F, _P, _P, _P],
     "iif_roi_extract_forward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _P],
     "iif_roi_extract_backward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _L, _P],
     "iif_mask_targets": [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P],
@@ -189,6 +197,18 @@ class RoiImage(ctypes.Structure):
                 ("img_index", ctypes.c_int32)]
 
 
+class RpnGrid(ctypes.Structure):
+    """Mirror of ``iif_rpn_grid`` (include/iif_amd.h)."""
+    _fields_ = [("num_levels", ctypes.c_int32)] + [(k, ctypes.c_int32 * 8) for k in ("W", "H", "num_base", "stride_w", "stride_h")] + [
+        ("base", ctypes.c_float * 4 * 16 * 8)]
+
+
+class RpnLossLevel(ctypes.Structure):
+    """Mirror of ``iif_rpn_loss_level`` (include/iif_amd.h)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("scores", "deltas", "grad_scores", "grad_deltas")] + [
+        (k, ctypes.c_int64 * 4) for k in ("score_strides", "delta_strides", "grad_score_strides", "grad_delta_strides")]
+
+
 class RpnLevel(ctypes.Structure):
     """Mirror of ``iif_rpn_level`` (include/iif_amd.h)."""
     _fields_ = [("scores", ctypes.c_void_p), ("deltas", ctypes.c_void_p), ("anchors", ctypes.c_void_p),
@@ -223,7 +243,8 @@ def lib():
         for name, argtypes in SIGNATURES.items():
             fn = getattr(l, name)
             fn.argtypes = argtypes
-            fn.restype = _L if name in ("iif_bn_workspace_bytes", "iif_bn3_algebra_prep_scratch_floats", "iif_rle_workspace_bytes") else _I
+            fn.restype = _L if name in ("iif_bn_workspace_bytes", "iif_bn3_algebra_prep_scratch_floats", "iif_rle_workspace_bytes",
+                                         "iif_rpn_stage_workspace_bytes") else _I
         _lib = l
     return _lib
 

@@ -16,7 +16,9 @@ the reference keeps.
 mmdet_multiclass_nms.py.  Deliberately not offered: ``soft_nms``, ``nms_match``, ``fast_nms``; more than 16 384 boxes; the two-class softmax RPN; ``rescale``; the ONNX
 branches; a tensor ``max_shape``; ``with_nms=False``; on the RPN path ``split_thr`` candidates or more per image (the
 reference's data-dependent switch to a per-level NMS).  The padded proposals feed the RoI stage without a read:
-``mmdet_roi_stage.roi_stage_targets_padded`` takes ``(dets, counts)`` as they are.  When mmdet is importable a subclass of its ``RPNHead`` registers itself as ``RPNHead``.
+``mmdet_roi_stage.roi_stage_targets_padded`` takes ``(dets, counts)`` as they are.  The head's training side (anchors, batch
+targets, the loss at the sampled anchors) is ``mmdet_anchor.AnchorGenerator`` and ``mmdet_rpn_stage.rpn_head_loss``; it is not
+wired into the class registered here.  When mmdet is importable a subclass of its ``RPNHead`` registers itself as ``RPNHead``.
 """
 import ctypes
 

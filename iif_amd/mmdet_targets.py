@@ -14,8 +14,9 @@ roi_heads/bbox_heads/bbox_head.py:122-261 (constructors, attributes, assertions,
     included) or on ``SamplingResult``s (exact sizes).
 
 Deliberately not offered: ``PseudoSampler``, OHEM and the other samplers; batch dimensions and a tensor-valued ``max_shape``
-in the coder; a mask inside the assigner itself (a synchronisation-free masked RPN path would need one: a follow-up); the ONNX
-export branches.  When mmdet is importable the classes register themselves as ``RandomSampler`` / ``DeltaXYWHBBoxCoder``.
+in the coder; a mask inside the assigner itself (``MaxIoUAssigner.assign`` still takes none: the synchronisation-free masked RPN
+path is ``mmdet_rpn_stage.rpn_stage_targets``, whose own assignment passes carry the mask for all images at once, while
+``anchor_targets_single`` stays the per-image chain); the ONNX export branches.  When mmdet is importable the classes register themselves as ``RandomSampler`` / ``DeltaXYWHBBoxCoder``.
 """
 import ctypes
 

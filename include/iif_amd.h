@@ -354,6 +354,81 @@ int iif_refine_bboxes(const float* rois, int64_t ld_rois, const int64_t* labels,
                       const float* img_hw, const float* means, const float* stds, float max_ratio, int add_ctr_clamp,
                       float ctr_clamp, int clip, float* proposals, int64_t* proposal_counts, void* stream);
 
+/* ---- The training side of the RPN head (csrc/rpn_stage.hip): anchors from a formula, batch targets without stored anchors, the
+ * loss at the sampled anchors only - what AnchorGenerator (core/anchor/anchor_generator.py) and AnchorHead.get_anchors /
+ * get_targets / loss (dense_heads/anchor_head.py:142-491) do.
+ *
+ * iif_rpn_grid: a HOST description of the anchor grid, copied into every launch.  Level l has H[l] x W[l] cells (both <= 65535),
+ *   num_base[l] <= 16 base anchors base[l][a] = <x1, y1, x2, y2> and integer strides; at most 8 levels.  Flat anchor index
+ *   i = start_l + (y W + x) num_base + a over the concatenated levels, A = sum of the levels < 2^31.  Anchor (l, y, x, a) is
+ *   base[l][a] + (x stride_w, y stride_h, x stride_w, y stride_h): one float32 add per coordinate (x stride_w < 2^24). */
+typedef struct iif_rpn_grid {
+    int32_t num_levels;
+    int32_t W[8], H[8], num_base[8], stride_w[8], stride_h[8];
+    float base[8][16][4];
+} iif_rpn_grid;
+/* anchors [A, 4] float32 on a 16-byte boundary, all levels in one launch. */
+int iif_grid_anchors(const iif_rpn_grid* grid, float* anchors, void* stream);
+/* flags [A] uint8 (0 / 1): x < valid_wh[2 l] and y < valid_wh[2 l + 1] (HOST array [num_levels, 2]: the valid width and height
+ * of each level in cells), all levels in one launch. */
+int iif_grid_valid_flags(const iif_rpn_grid* grid, const int32_t* valid_wh, uint8_t* flags, void* stream);
+
+/* Assign (iif_max_iou_assign's definition, no ignore boxes), sample (iif_random_sample's rule) and encode for all B images at
+ * once; the anchors are generated from their index and never read.
+ *   images: HOST array of B iif_roi_image (gt_bboxes, ld_gt, G; gt_labels and img_index are not read).  Any G.
+ *   Candidate i of image b takes part only if its cell is valid - x < valid_wh[(b L + l) 2], y < valid_wh[(b L + l) 2 + 1]
+ *   (HOST array [B, L, 2], each <= 65535) - and, when use_border, x1 >= border_lo, y1 >= border_lo, x2 < border_hi[2 b],
+ *   y2 < border_hi[2 b + 1] (HOST array [B, 2]: img_w + border, img_h + border; border_lo = -border).  Every other candidate
+ *   takes no part at all: not in a gt's maximum, not as a negative, not in the sampler.
+ *   keys [B, A] int32: the key of flat anchor i of image b.
+ *   pos_inds [B, num_expected_pos] / neg_inds [B, num]: flat indices, ascending, tails -1; counts [B, 2]; pos_assigned_gt_inds
+ *   [B, num_expected_pos] (tail -1); pos_bbox_targets [B, num_expected_pos, 4] (iif_bbox2delta's arithmetic, tail 0);
+ *   num_total_samples: one float32 = sum_b max(pos_b, 1) + max(neg_b, 1).
+ *   d_workspace: iif_rpn_stage_workspace_bytes(B, A, sum of G) on a 16-byte boundary; it belongs to the call until the stream
+ *   has run it.
+ * Limits: 1 <= B <= 16, num <= 1024, 0 <= num_expected_pos <= num.  FIVE enqueued operations whatever the shapes and the data:
+ * one clear of the head of the workspace, two assignment passes, the selection, the total.  Phases meet at launch boundaries;
+ * integer atomics only: no result depends on arrival order. */
+int64_t iif_rpn_stage_workspace_bytes(int B, int64_t A, int64_t total_G);
+int iif_rpn_stage_targets(const iif_rpn_grid* grid, const iif_roi_image* images, int B, const int32_t* valid_wh, int use_border,
+                          float border_lo, const float* border_hi, const int32_t* keys, float pos_iou_thr, float neg_lo,
+                          float neg_hi, float min_pos_iou, int gt_max_assign_all, int match_low_quality, int64_t num_expected_pos,
+                          int64_t num, double neg_pos_ub, const float* means, const float* stds, int64_t* pos_inds,
+                          int64_t* neg_inds, int64_t* counts, int64_t* pos_assigned_gt_inds, float* pos_bbox_targets,
+                          float* num_total_samples, void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* The dense targets of AnchorHead.get_targets after images_to_levels from the lists above, one launch, every element written
+ * once: each of labels (int64), label_weights, bbox_targets [.., 4], bbox_weights [.., 4] holds the levels one after the other,
+ * level l as [B, A_l(, 4)] at element offset B start_l.  Positives: label 0, weight pos_weight (1 when <= 0), their targets,
+ * box weights 1; negatives: label num_classes, weight 1; the rest: label num_classes, zeros. */
+int iif_rpn_stage_dense(const iif_rpn_grid* grid, int B, const int64_t* pos_inds, const int64_t* neg_inds, const int64_t* counts,
+                        const float* pos_bbox_targets, int64_t num_expected_pos, int64_t num, int64_t num_classes, float pos_weight,
+                        int64_t* labels, float* label_weights, float* bbox_targets, float* bbox_weights, void* stream);
+
+/* The RPN loss at the sampled anchors only.  levels: HOST array, one per level: the float32 score map [B, num_base, H, W] and
+ * delta map [B, 4 num_base, H, W] with their element strides (any memory format; read in place at channel a / 4 a + j), and for
+ * the backward the gradient maps with theirs.
+ *   forward (one launch, one workgroup per level, fixed summation order): loss_cls[l] = cls_loss_weight / num_total_samples *
+ *   sum over the level's sampled anchors of w BCE_with_logits(x, [positive]) (w = pos_weight on positives when > 0, else 1);
+ *   loss_bbox[l] = bbox_loss_weight / num_total_samples * sum over its positives and the four deltas of |p - t| (beta <= 0) or
+ *   SmoothL1(beta).  num_total_samples is read on the device.
+ *   backward (one launch): plain stores at the sampled positions of gradient maps THE CALLER HAS CLEARED. */
+typedef struct iif_rpn_loss_level {
+    const float* scores;
+    const float* deltas;
+    float* grad_scores;
+    float* grad_deltas;
+    int64_t score_strides[4], delta_strides[4], grad_score_strides[4], grad_delta_strides[4];
+} iif_rpn_loss_level;
+int iif_rpn_loss_fwd(const iif_rpn_grid* grid, const iif_rpn_loss_level* levels, int B, const int64_t* pos_inds,
+                     const int64_t* neg_inds, const int64_t* counts, const float* pos_bbox_targets, int64_t num_expected_pos,
+                     int64_t num, const float* num_total_samples, float pos_weight, float cls_loss_weight, float bbox_loss_weight,
+                     float beta, float* loss_cls, float* loss_bbox, void* stream);
+int iif_rpn_loss_bwd(const iif_rpn_grid* grid, const iif_rpn_loss_level* levels, int B, const int64_t* pos_inds,
+                     const int64_t* neg_inds, const int64_t* counts, const float* pos_bbox_targets, int64_t num_expected_pos,
+                     int64_t num, const float* num_total_samples, float pos_weight, float cls_loss_weight, float bbox_loss_weight,
+                     float beta, const float* grad_loss_cls, const float* grad_loss_bbox, void* stream);
+
 /* out = logits * table. Replaces classification/custom.py:37-39 (infer=True). */
 int iif_scale_logits(const void* logits, int dtype, int64_t ld_logits, const float* table,
                      int B, int C, void* out, int64_t ld_out, void* stream);
