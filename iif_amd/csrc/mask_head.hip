@@ -32,9 +32,13 @@ __global__ void __launch_bounds__(256) mask_gather_kernel(const T* pred, const i
                                                           int* status) {
     const int n = blockIdx.x;
     const int64_t lb = labels[n];
-    if (lb < 0 || lb >= C) { if (threadIdx.x == 0) atomicOr(status, 1); return; }
-    const T* p = pred + ((int64_t)n * C + lb) * hw;
     float* o = out + (int64_t)n * hw;
+    if (lb < 0 || lb >= C) {            // reported through the sticky status word; the RoI's row is zero
+        if (threadIdx.x == 0) atomicOr(status, 1);
+        for (int i = threadIdx.x; i < hw; i += 256) o[i] = 0.f;
+        return;
+    }
+    const T* p = pred + ((int64_t)n * C + lb) * hw;
     for (int i = threadIdx.x; i < hw; i += 256) o[i] = LD<T>::ld(p + i);
 }
 

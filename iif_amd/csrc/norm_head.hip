@@ -37,7 +37,8 @@ __global__ void __launch_bounds__(256) rowmap_fwd_kernel(const TI* x, int rows, 
 
 // backward of the row map: g = dL/d(out) (fp32 or T), x the forward input, n its stored norm
 //   mode 0: dx = scale * ( g/(1+n) - x * <g,x> / (n (1+n)^2) )
-//   mode 1: dx = g/m - x * <g,x> / m^3,  m = max(n, eps)
+//   mode 1: dx = g/m - x * <g,x> / m^3,  m = max(n, eps); where n < eps the map is x/eps (F.normalize clamps the norm),
+//           so the projection term is dropped there: dx = g/eps
 template <typename TI, typename TG, typename TO>
 __global__ void __launch_bounds__(256) rowmap_bwd_kernel(const TI* x, const float* norms, const TG* g, int rows, int cols,
                                                          int64_t ldx, int64_t ldg, int mode, float scale, float eps, TO* dx,
@@ -58,7 +59,7 @@ __global__ void __launch_bounds__(256) rowmap_bwd_kernel(const TI* x, const floa
     } else {
         const float m = fmaxf(n, eps);
         a = n > 0.f ? 1.0f / m : 0.f;
-        b = n > 0.f ? dot / (m * m * m) : 0.f;
+        b = (n > 0.f && n >= eps) ? dot / (m * m * m) : 0.f;
     }
     TO* o = dx + (int64_t)row * lddx;
     for (int c = lane; c < cols; c += 64) HIO<TO>::st(o + c, HIO<TG>::ld(gr + c) * a - HIO<TI>::ld(xr + c) * b);

@@ -45,13 +45,20 @@ def _prep(pred, label):
     return pred, label, n, c, hw
 
 
+def _label_status(device):
+    """The sticky label-status word the fused loss heads share: ``custom.check_label_status()`` raises on it."""
+    from . import custom
+    return custom._workspace(device, 0, False)[2]
+
+
 def gather_class_masks(mask_pred, labels):
-    """``mask_pred[range(N), labels]`` -> [N, *] fp32 (fcn_mask_head.py:289-290)."""
+    """``mask_pred[range(N), labels]`` -> [N, *] fp32 (fcn_mask_head.py:289-290).  A label outside ``[0, C)`` (the reference
+    raises) gives a row of zeros and sets the flag that ``custom.check_label_status()`` raises on; no host synchronisation."""
     pred, label, n, c, hw = _prep(mask_pred, labels)
     out = torch.empty((n,) + tuple(pred.shape[2:]), dtype=torch.float32, device=pred.device)
     if n == 0:
         return out
-    status = torch.zeros(1, dtype=torch.int32, device=pred.device)
+    status = _label_status(pred.device)
     _lib.check(_lib.lib().iif_mask_gather(_lib.ptr(pred), _lib.dtype_code(pred), _lib.ptr(label), n, c, hw, _lib.ptr(out),
                                           _lib.ptr(status), _lib.stream_ptr()), "iif_mask_gather")
     return out
@@ -65,7 +72,7 @@ class _MaskBCE(torch.autograd.Function):
         dev = p.device
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         rows = torch.empty(n, dtype=torch.float32, device=dev)
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        status = _label_status(dev)
         need = pred.requires_grad
         dpred = torch.zeros(p.shape, dtype=torch.float32, device=dev) if need else None
         _lib.check(_lib.lib().iif_mask_bce_fwd_bwd(_lib.ptr(p), _lib.dtype_code(p), _lib.ptr(t), _lib.ptr(lb), n, c, hw, 1.0,
@@ -86,7 +93,9 @@ class _MaskBCE(torch.autograd.Function):
 
 def mask_cross_entropy(pred, target, label, reduction="mean", avg_factor=None, class_weight=None, ignore_index=None):
     """cross_entropy_loss.py:112-162: BCE-with-logits on the class channel of every RoI, mean over all
-    pixels, returned with shape ``(1,)``.  Loss and gradient come out of one pass over the selected channels."""
+    pixels, returned with shape ``(1,)``.  Loss and gradient come out of one pass over the selected channels.  A label outside
+    ``[0, C)`` (the reference raises) contributes zero loss and no gradient and sets the flag that
+    ``custom.check_label_status()`` raises on."""
     assert ignore_index is None, "BCE loss does not support ignore_index"
     assert reduction == "mean" and avg_factor is None
     if class_weight is not None:

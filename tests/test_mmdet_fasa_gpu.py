@@ -91,3 +91,124 @@ def test_dynamic_sampling_runs():
     L.cum_losses = L.cum_losses * 2                                    # losses rose -> probabilities go down
     bank.dynamic_sampling(L)
     assert (bank.prob_list.data <= p0 + 1e-9).all() and (bank.prob_list.data < p0).any()
+
+
+# ------------------------------------------------------------------ strided loops of the update / generate kernels, float64
+U24 = 2.0 ** -24
+F64 = torch.float64
+FASA_C = 300                                             # the select scan crosses a 256-class chunk
+
+
+def _fasa_labels(n, step):
+    """Labels of one update: classes seen exactly once (variance 0), the background label C and a negative label (both
+    ignored), the rest spread over classes on both sides of the 256-class chunk boundary.  Step 1 revisits part of step 0's
+    classes (the moving-average branch) and brings new ones (the first-sight branch)."""
+    g = torch.Generator().manual_seed(1000 * step + n)
+    if n == 1:
+        return torch.tensor([7])                            # first sight, then the moving average of the same class
+    pool = torch.cat([torch.arange(0, 24), torch.arange(250, 262)]) + 12 * step
+    lab = pool[torch.randint(0, len(pool), (n,), generator=g)]
+    lab[0], lab[1] = FASA_C, -1
+    for i, c in enumerate((100 + step, 255, 256 + step, 299 - step)):         # exactly once each
+        lab[2 + i] = c
+    return lab
+
+
+def _fasa_update_reference(emb, lab, decay, state):
+    """One fa_update in float64 on (mean, var, used) and their error bounds, in place.  Bounds: the kernel sums a class's rows
+    in row order in fp32, so a sum gets max((n + 16) 2^-24 S, 4 |float32 CPU sum - float64|); the mean divides it by the
+    count; the centred sum of squares gets the same form plus count * (mean bound)^2 (the first-order effect of the mean's
+    error cancels: the deviations sum to zero); every other step is one rounding of its own terms (16 * 2^-24 of their
+    magnitudes); the moving average carries the bound of the state it blends."""
+    fm, fv, fu, bm, bv = state
+    n = emb.shape[0]
+    e32 = emb.float()
+    for c in torch.unique(lab).tolist():
+        if c < 0 or c >= FASA_C:
+            continue
+        idx = torch.nonzero(lab == c).squeeze(1)
+        m = len(idx)
+        e = emb[idx]
+        ssum = e.sum(0)
+        b_sum = torch.maximum((n + 16) * U24 * e.abs().sum(0), 4 * (e32[idx].sum(0).to(F64) - ssum).abs())
+        mean = ssum / m
+        b_mean = b_sum / m + 16 * U24 * mean.abs()
+        t = e - mean
+        ss = (t * t).sum(0)
+        t32 = e32[idx] - (e32[idx].sum(0) / m)
+        b_ss = torch.maximum((n + 16) * U24 * ss, 4 * ((t32 * t32).sum(0).to(F64) - ss).abs()) + m * b_mean ** 2
+        var = ss / (m - 1) if m > 1 else ss / m
+        b_var = b_ss / max(m - 1, 1) + 16 * U24 * var
+        if fu[c] > 0:
+            bm[c] = decay * b_mean + (1 - decay) * bm[c] + 16 * U24 * (decay * mean.abs() + (1 - decay) * fm[c].abs())
+            bv[c] = decay * b_var + (1 - decay) * bv[c] + 16 * U24 * (decay * var + (1 - decay) * fv[c])
+            fm[c] = decay * mean + (1 - decay) * fm[c]
+            fv[c] = decay * var + (1 - decay) * fv[c]
+        else:
+            fm[c], fv[c], bm[c], bv[c] = mean, var, b_mean, b_var
+            fu[c] += 1
+
+
+@pytest.mark.parametrize("n", [1, 257, 600])
+@pytest.mark.parametrize("d", [1, 255, 256, 257, 1024])
+def test_feature_bank_strides_against_float64(d, n):
+    """D below / at / above one pass of the 256 threads and the model's 1024; n below and above one pass of the label count;
+    embeddings with leading dimension D + 3 (NaN in the padding).  Measured on the MI355X, worst over the 15 cases: mean
+    |error| / bound 0.043 (4.6e-7 absolute), variance 0.018 (2.4e-6); classes seen once: variance exactly 0; generate within
+    16 * 2^-24 of its two terms, labels exact."""
+    from iif_amd.mmdet_fasa import FasaFeatureBank
+    C = FASA_C
+    bank = FasaFeatureBank(C, d, [100] * C, dict(decay_ratio=0.1), device=DEV)
+    decay = float(torch.tensor(0.1, dtype=torch.float32))                   # the value the kernel is handed
+    state = (torch.zeros(C, d, dtype=F64), torch.zeros(C, d, dtype=F64), torch.zeros(C, dtype=F64),
+             torch.zeros(C, d, dtype=F64), torch.zeros(C, d, dtype=F64))
+    once = set()
+    for step in range(2):
+        g = torch.Generator().manual_seed(7 * step + d)
+        emb = torch.randn(n, d, generator=g) * 1.5 + 0.3
+        lab = _fasa_labels(n, step)
+        buf = torch.full((n, d + 3), float("nan"), device=DEV)
+        buf[:, :d] = emb.to(DEV)
+        view = buf[:, :d]
+        assert view.stride(0) == d + 3
+        bank.fa_update(view, lab.to(DEV))
+        if step == 0:
+            once = {c for c in torch.unique(lab).tolist() if 0 <= c < C and int((lab == c).sum()) == 1}
+            torch.cuda.synchronize()
+            assert len(once) >= 1 and (bank.feature_std.data.cpu()[sorted(once)] == 0).all()   # seen once: variance exactly 0
+        _fasa_update_reference(emb.to(F64), lab, decay, state)
+    fm, fv, fu, bm, bv = state
+    assert torch.equal(bank.feature_used.data.cpu().to(F64), fu)
+    assert 0 < fu.sum().item() < C or n == 1
+    gm, gv = bank.feature_mean.data.cpu().to(F64), bank.feature_std.data.cpu().to(F64)
+    em, ev = (gm - fm).abs(), (gv - fv).abs()
+    print("\n  mean worst err/bound %.3f (err %.2e)  var worst err/bound %.3f (err %.2e)" %
+          ((em / bm.clamp_min(1e-300)).max().item(), em.max().item(), (ev / bv.clamp_min(1e-300)).max().item(), ev.max().item()))
+    assert (em <= bm).all() and (ev <= bv).all()           # bound 0 for classes never seen: untouched, exactly zero
+    # ---- generate, from the state the bank holds
+    normal = torch.randn(C, d, generator=torch.Generator().manual_seed(99))
+    bank.prob_list.data.fill_(0.5)
+    want_all = gm + gv.sqrt() * normal.to(F64)
+    b_all = 16 * U24 * (gm.abs() + (gv.sqrt() * normal.to(F64)).abs())
+
+    def generate(rand, expect):
+        e, l = bank.fa_generate(rand.to(DEV), normal.to(DEV))
+        if not expect:
+            assert e == [] and l == []
+            return
+        assert l.dtype == torch.int64 and l.cpu().tolist() == expect          # exact, ascending
+        assert e.shape == (len(expect), d)
+        assert ((e.cpu().to(F64) - want_all[expect]).abs() <= b_all[expect]).all()
+
+    used = [c for c in range(C) if fu[c] > 0]
+    generate(torch.full((C,), 0.25), used)                                     # everything that was ever seen
+    generate(torch.full((C,), 0.75), [])                                       # nothing
+    generate(torch.full((C,), 0.5), [])                                        # rand == prob is not below it
+    rand = torch.full((C,), 0.75)
+    rand[250:262] = 0.25
+    generate(rand, [c for c in used if 250 <= c < 262])                        # straddles the 256-class chunk
+    bank.feature_used.data.fill_(1.0)                                          # every class: slots on both sides of the chunk
+    generate(torch.full((C,), 0.25), list(range(C)))
+    rand = torch.full((C,), 0.25)
+    rand[::3] = 0.75
+    generate(rand, [c for c in range(C) if c % 3])

@@ -413,3 +413,206 @@ def worst(metrics):
             if k not in w or v > w[k][0]:
                 w[k] = (v, name)
     return w
+
+
+# ------------------------------------------------------------------ the head: pooling, classifier, loss, and their backward
+HEAD_ERRORS = {}                              # metric -> largest absolute error of the last check_head call (for reports)
+FP32_TINY = 2.0 ** -126                       # below this fp32 results may be flushed to zero
+HEAD_EXACT = ("w_cast", "wt", "w_t", "dl_cast", "dl_pad", "w_pad")          # counts / magnitudes that must be exactly 0
+
+
+def _gemm_bound(a, b):
+    """a [m, k] @ b [n, k]^T in float64 with the bound of an fp32-accumulated product (tests/head_cases.py: the reduction
+    length k is the chain), or 4 x the error of the same product in float32 on the CPU."""
+    from tests import head_cases as H
+    ref = a @ b.t()
+    s = a.abs() @ b.abs().t()
+    cpu32 = (a.float() @ b.float().t()).to(F64)
+    return ref, torch.maximum((a.shape[1] + 16) * H.U24 * s, 4 * (cpu32 - ref).abs())
+
+
+def check_head(net, cap, targets, crit):
+    """Everything between the last block and the loss of the last step, stage by stage in float64 on the CPU from the operands
+    the step itself stored (``net._saved``), so each metric sees one rounding and one accumulation.  Returns {metric: value}.
+
+    Unless noted a value is the worst |error| / bound over every element of the stage's output (<= 1 passes), with the
+    per-element bounds of tests/head_cases.py: fp32 sums get max((L + 16) 2^-24 S, 4 |float32 CPU - float64|), an output that
+    depends on a sum through a coefficient gets that bound times what multiplies it plus 16 * 2^-24 of its own terms, and
+    every store in bf16 adds 2^-8 |ref|.
+      pooled        mean over the pixels of ``final`` (L = pixels)
+      ex, xnorm     the feature map of the cosine (x scale / (1 + |x|); lr_cosine: s^2, applied by a second in-place pass, so
+                    two stores) and normed (x / max(|x|, eps)) heads and its stored row norms
+      wn, wnorm     row-normalised weights (cosine: eps 0; normed: the columns, through the transpose ``w_t``, exact)
+      w_pad         largest magnitude in the zero pad rows of the normalised weights (exactly 0)
+      w_cast, wt    elements of ``head_w`` that are not the compute-type rounding of its fp32 source / of ``head_wt`` that are
+                    not ``head_w`` transposed (exactly 0)
+      logits        features x weights (+ bias), L = in_features
+      loss, dlogits the closed form of oracle.iif_oracle.iif_ce_closed_form on the stored logits.  z = logit * table is one
+                    fp32 product, exp(z - max) carries the rounding of its argument, 2^-24 (|z| + |max| + 3 |z - max| + 16)
+                    relative (and may be flushed to 0 below 2^-126), the row sum L = C on top; the softmax and the row loss
+                    inherit both
+      dl_pad, dl_cast  pad columns of dlogits (exactly 0); elements of ``dlogits_t`` that are not the rounding of dlogits
+      dwn           (cosine / normed) dlogits_t^T x ex, L = batch
+      dw            the weight gradient against the float64 one formed from the stored dlogits_t and ex (pooled), taken back
+                    through the row normalisation with the stored norms: the bound of dwn carried through g a - w <g, w> k
+      dw_full       relative L2 of the weight gradient against the same from the unrounded dlogits (what bf16 storage of
+                    dlogits costs; bounded like ``dw`` next to ``dw_rdx`` in the unit table)
+      db, ds        (linear) column sums of dlogits, L = batch; (lr_cosine) (2 / s) <dlogits, logits>, double accumulation
+      dex, dpooled  dlogits_t x weights, L = out_padded (lr_cosine: times s^2 by a second in-place pass); back through the map
+      dgrad         the gradient that arrived at the last unit against the float64 dpooled / pixels at every pixel (the stored
+                    dpooled's bound carried over, so an error in dpooled shows here too)
+    """
+    from oracle import iif_oracle as O
+    from tests import head_cases as H
+    plan, head = net._saved, net._head
+    dt, kind = plan.dt, plan.head_kind
+    n, C, op, D = plan.n, head.out_features, head.out_padded, head.in_features
+    u24 = H.U24
+    met = {}
+
+    def P(t):
+        return t.detach().to("cpu", F64)
+
+    def ratio(name, got, ref, bound, store=None):
+        met[name], HEAD_ERRORS[name] = H.worst_ratio(P(got), ref, H.stored(bound, ref, store) if store is not None else bound)
+
+    def mismatch(name, a, b):
+        met[name] = float((a.detach().cpu() != b.detach().cpu()).sum().item())
+
+    lr = kind == "cosine" and head.lr_scale
+    s = P(head._s1d[:1]).item() if lr else None
+    # ---- pooling
+    final = P(plan.final)
+    hw = final.shape[1] * final.shape[2]
+    fin = final.reshape(n, hw, D).permute(0, 2, 1)                            # [n, D, pixels]
+    psum, b_psum = H.sum_bound(fin, torch.ones_like(fin), hw)
+    pooled_ref = psum / hw
+    ratio("pooled", plan.pooled, pooled_ref, b_psum / hw + 16 * u24 * pooled_ref.abs(), dt)
+    pooled = P(plan.pooled)
+    # ---- feature map and weights
+    if kind == "linear":
+        feat = pooled
+        wsrc = P(head._w2d)
+        bias = P(head._b1d)[:op]
+    else:
+        bias = None
+        mode, eps = (1, 1e-12) if kind == "norm" else (0, 1e-12)
+        scale = 1.0 if (kind == "norm" or lr) else float(head.scale)
+        ex, b_ex, xn, b_xn = H.rowmap_forward_bounds(pooled, mode, scale, eps)
+        if lr:                                          # stored once, then scaled in place by s^2 and stored again
+            s2 = float(torch.tensor(s, dtype=torch.float32) ** 2)
+            b_ex = s2 * H.stored(b_ex, ex, dt) + 16 * u24 * s2 * ex.abs()
+            ex = ex * s2
+        ratio("ex", plan.head_ex, ex, b_ex, dt)
+        ratio("xnorm", plan.head_xnorm, xn, b_xn)
+        feat = P(plan.head_ex)
+        if kind == "cosine":
+            wmaster, weps = P(head._w2d), 0.0
+        else:
+            mismatch("w_t", plan.head_wT, head._w2d.t())
+            wmaster, weps = P(plan.head_wT), 1e-12
+        wn, b_wn, wnorm, b_wnorm = H.rowmap_forward_bounds(wmaster, 1, 1.0, weps)
+        ratio("wn", plan.head_wsrc, wn, b_wn)
+        ratio("wnorm", plan.head_wnorm, wnorm, b_wnorm)
+        met["w_pad"] = P(plan.head_wsrc)[C:].abs().max().item() if op > C else 0.0
+        wsrc = P(plan.head_wsrc)
+    mismatch("w_cast", plan.head_w, (head._w2d if kind == "linear" else plan.head_wsrc).to(dt))
+    w = P(plan.head_w)
+    if plan.head_wt is not None:
+        mismatch("wt", plan.head_wt[:, :op], plan.head_w.t())
+    # ---- logits
+    lg, b_lg = _gemm_bound(feat, w)
+    if bias is not None:
+        lg, b_lg = lg + bias, b_lg + (D + 16) * u24 * bias.abs()
+    ratio("logits", plan.logits, lg, b_lg)
+    logits = P(plan.logits)
+    # ---- loss and dlogits from the stored logits
+    table = P(crit._table(plan.logits)).reshape(-1)[:C]
+    tg = targets.detach().cpu().long()
+    loss_ref, dl_ref, rows = O.iif_ce_closed_form(logits[:, :C], tg, table)
+    z = logits[:, :C] * table
+    zmax = z.max(1, keepdim=True).values
+    e = torch.exp(z - zmax)
+    ssum = e.sum(1, keepdim=True)
+    rel_e = u24 * (z.abs() + zmax.abs() + 3 * (z - zmax).abs() + 16)
+    b_e = e * rel_e + FP32_TINY                       # an exponential below fp32's normal range may come out as 0
+    b_ssum = b_e.sum(1, keepdim=True) + (C + 16) * u24 * ssum
+    soft = e / ssum
+    b_soft = b_e / ssum + soft * (b_ssum / ssum + 2 * u24)
+    onehot = torch.zeros_like(soft)
+    onehot[torch.arange(n), tg] = 1.0
+    b_dl = table.abs() / n * b_soft + 16 * u24 * table.abs() * (soft + onehot) / n + FP32_TINY
+    zt = z[torch.arange(n), tg]
+    b_row = (u24 * (zmax.abs() + zt.abs()[:, None]) + b_ssum / ssum
+             + 16 * u24 * (zmax.abs() + ssum.log().abs() + zt.abs()[:, None])).squeeze(1)
+    b_loss = b_row.sum() / n + (n + 16) * u24 * rows.abs().sum() / n
+    ratio("loss", plan.loss, loss_ref, b_loss)
+    ratio("dlogits", plan.dlogits[:, :C], dl_ref, b_dl)
+    met["dl_pad"] = P(plan.dlogits)[:, C:].abs().max().item() if op > C else 0.0
+    dl_full = P(plan.dlogits)
+    if dt == torch.float32:
+        dl = dl_full
+        met["dl_cast"] = 0.0
+    else:
+        mismatch("dl_cast", plan.dlogits_t, plan.dlogits.to(dt))
+        dl = P(plan.dlogits_t)
+    # ---- weight gradient
+    def through_norm(g, b_g):
+        """Row-normalisation backward of g [op, D] (with its bound) from the master weights and the stored norms."""
+        if kind == "linear":
+            return g, b_g
+        nrm = P(plan.head_wnorm)
+        dx, t1, t2, k = H._rowmap_backward_terms(wmaster, nrm, g, 1, 1.0, weps)
+        _, b = H.rowmap_backward_bounds(wmaster, nrm, g, 1, 1.0, weps)
+        m = nrm.clamp_min(weps)
+        a = torch.where(nrm > 0, 1 / torch.where(nrm > 0, m, torch.ones_like(m)), torch.zeros_like(nrm))
+        carried = a[:, None] * b_g + wmaster.abs() * (k * (wmaster.abs() * b_g).sum(1))[:, None]
+        return dx, b + carried
+
+    dwn, b_dwn = _gemm_bound(dl.t().contiguous(), feat.t().contiguous())        # [op, D], L = batch
+    if kind != "linear":
+        ratio("dwn", plan.head_dwn, dwn, b_dwn)
+    dw_ref, b_dw = through_norm(dwn, b_dwn)
+    got_dw = P(head._g2d)
+    if kind == "norm":
+        got_dw = got_dw.t()
+    ratio("dw", got_dw, dw_ref, b_dw)
+    dw_full, _ = through_norm(dl_full.t() @ feat, torch.zeros_like(b_dwn))
+    met["dw_full"] = rel_l2(got_dw, dw_full)
+    if kind == "linear":
+        ones = torch.ones_like(dl_full.t())
+        db, b_db = H.sum_bound(dl_full.t().contiguous(), ones, n)
+        ratio("db", head._gb1d[:op], db, b_db)
+    if lr:
+        ds, b_ds = H.dot_window(dl_full[:, :C], logits[:, :C], 2.0, s)
+        ratio("ds", head._gs1d[:1], ds.reshape(1), b_ds.reshape(1))
+    # ---- data gradient
+    dex, b_dex = _gemm_bound(dl, w.t().contiguous())                             # [n, D], L = out_padded
+    dpooled_t = plan._grad_pool[("dpooled",)].view(n, D)
+    if kind == "linear":
+        dp, b_dp = dex, b_dex
+        ratio("dpooled", dpooled_t, dex, b_dex, dt)
+    else:
+        if lr:
+            b_dex = s2 * H.stored(b_dex, dex, dt) + 16 * u24 * s2 * dex.abs()
+            dex = dex * s2
+        ratio("dex", plan.head_dex, dex, b_dex, dt)
+        dp, b_dp = H.rowmap_backward_bounds(pooled, P(plan.head_xnorm), P(plan.head_dex), mode, scale, eps)
+        ratio("dpooled", dpooled_t, dp, b_dp, dt)
+    last = plan.blocks[-1]["units"][-1]
+    gy = P(cap.records[id(last)]["gy"])
+    dg = (dp / hw).view(n, 1, 1, D).expand(gy.shape)
+    b_dg = (H.stored(b_dp, dp, dt) / hw).view(n, 1, 1, D).expand(gy.shape) + 16 * u24 * dg.abs()
+    ratio("dgrad", gy, dg, b_dg, dt)
+    return met
+
+
+def head_failures(met, dt):
+    """[(metric, value, bound)] above its bound: 1 for the error / bound ratios, 0 for the exact ones, and for ``dw_full`` the
+    bound ``dw`` has next to ``dw_rdx`` in the unit table (2e-2 in bf16, 1e-5 in fp32)."""
+    out = []
+    for k, v in met.items():
+        bnd = 0.0 if k in HEAD_EXACT else (2e-2 if dt == torch.bfloat16 else 1e-5) if k == "dw_full" else 1.0
+        if not (v <= bnd):
+            out.append((k, v, bnd))
+    return out
