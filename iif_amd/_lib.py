@@ -160,6 +160,9 @@ SIGNATURES = {
     "iif_mask_predict_fwd": [_P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "iif_mask_predict_bwd_input": [_P, _P, _P, _L, _P, _I, _I, _I, _I, _P, _I, _P],
     "iif_mask_predict_bwd_weight": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    "iif_normed_mask_predict_fwd": [_P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "iif_normed_mask_predict_bwd_input": [_P, _I, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _F, _P, _P],
+    "iif_normed_mask_predict_bwd_weight": [_P, _I, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P],
     "iif_mask_tail_fwd": [_P, _I, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "iif_mask_tail_bwd_rows": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "iif_mask_tail_bwd_input": [_P, _P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P],

@@ -22,7 +22,7 @@ to call.  A label outside ``[0, C)`` contributes zero loss, a zero ``dx`` slice 
 divisor stays ``N * H * W``.  Limits: ``Cin <= 2048``, ``H * W <= 4096``, ``N <= 65535``.
 
 Deliberately not offered: the full ``[N, C, H, W]`` logits (``to_conv()`` gives the convolution back), a ``predictor_cfg`` other
-than a plain convolution, ``class_weight``, float16 and a native ``channels_last`` kernel.  The deconv + ReLU in front are fused
+than a plain convolution (``NormedConv2d``: mmdet_normed_mask_predictor.py), ``class_weight``, float16 and a native ``channels_last`` kernel.  The deconv + ReLU in front are fused
 with this predictor in ``mmdet_mask_tail.py`` (``FusedMaskHeadTail``).
 """
 import torch

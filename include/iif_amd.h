@@ -1266,6 +1266,47 @@ int iif_mask_predict_bwd_weight(const void* x, int dtype, const float* g, const 
                                 int n, int c, int cin, int hw, float* scratch, float* dweight /* nullable */,
                                 float* dbias /* nullable */, void* stream);
 
+/* The class-selected mask predictor of the cosine-norm heads (csrc/normed_mask_predictor.hip;
+ * iif_amd/mmdet_normed_mask_predictor.py): predictor_cfg=dict(type='NormedConv2d', tempearture=20) - normed_predictor.py:104-124,
+ * a 1x1 kernel - evaluated at each RoI's label channel only.  Operands as for iif_mask_predict_*.  With l = labels[i],
+ * T = temperature, q = power:  r = |x[i, :, p]|_2, rho = |weight[l, :]|_2, s_x = T / (r^q + eps), s_w = 1 / (rho^q + eps),
+ * what = weight[l] * s_w, d = sum_k what[k] * x[i, k, p].
+ *
+ * iif_normed_mask_predict_fwd (one launch; two with a target)
+ *   z[i, p] = s_x * d + bias[l]                                    fp32 [n][hw], nullable when a target is given
+ *   coef_a[i, p] = s_x,  coef_b[i, p] = d * T * q * r^(q-2) / (r^q + eps)^2, exactly 0 where r == 0      fp32 [n][hw], nullable:
+ *   what the backward entries take.  target (fp32 [n][hw], nullable): g[i, p] = sigmoid(z) - target (fp32 [n][hw], nullable,
+ *   NOT divided), *loss = sum BCEWithLogits(z, target) / divisor (row partials in fp32, their sum in double) and
+ *   *inv_div = 1 / divisor, a device scalar for the backward entries.  divisor = n * hw, or with valid_rows != 0
+ *   max(1, #{i : 0 <= labels[i] < c}) * hw, counted on the device.  row_loss: scratch of n * ((hw + 63) / 64) floats.  Without a
+ *   target row_loss, loss and inv_div are not touched and g must be NULL.  A RoI with a label outside [0, c) gets z = g =
+ *   coef_a = coef_b = 0, adds nothing to the loss, and its x is not read.
+ * iif_normed_mask_predict_bwd_input (one launch)
+ *   dx[i, k, p] = u * g[i, p] * (coef_a[i, p] * what[k] - coef_b[i, p] * x[i, k, p]),  u = up * inv_div (DEVICE scalars, each
+ *   nullable = 1).  dx [n][cin][hw] in x's dtype, EVERY element written once; x is read once.  A label outside [0, c): a zero
+ *   slice, x not read.
+ * iif_normed_mask_predict_bwd_weight (two launches)
+ *   scratch[i, k] = u * sum_p g[i, p] * coef_a[i, p] * x[i, k, p],  scratch[i, cin] = u * sum_p g[i, p]       fp32 [n][cin + 1]
+ *   dwhat[j] = sum over the RoIs with labels[i] == j, in ascending i, of scratch[i, :cin];  dbias[j] likewise of scratch[i, cin]
+ *   dweight[j] = s_w * dwhat[j] - (<dwhat[j], weight[j]> * q * rho^(q-2) / (rho^q + eps)^2) * weight[j]   (no second term at rho == 0)
+ *   dweight fp32 [c][cin] and dbias fp32 [c], either nullable: EVERY row is written, zeros for a class no RoI has.
+ * All sums are fp32 in a fixed order without float atomics: the same bits from call to call.  power == 1 calls no powf.  Nothing
+ * is allocated or read back.  IIF_EINVAL before any launch: a required pointer NULL, n < 0 or > 65535, c < 1, cin outside
+ * 1 .. 2048, hw outside 1 .. 4096, ld_w < cin, an unknown dtype, power <= 0.  n == 0: IIF_OK, nothing is enqueued. */
+int iif_normed_mask_predict_fwd(const void* x, int dtype, const float* weight, int64_t ld_w, const float* bias /* nullable */,
+                                const int64_t* labels, const float* target /* nullable */, int n, int c, int cin, int hw,
+                                float temperature, float power, float eps, int valid_rows, float* z /* nullable */,
+                                float* g /* nullable */, float* coef_a /* nullable */, float* coef_b /* nullable */,
+                                float* row_loss, float* loss, float* inv_div, void* stream);
+int iif_normed_mask_predict_bwd_input(const void* x, int dtype, const float* g, const float* coef_a, const float* coef_b,
+                                      const float* up /* nullable */, const float* inv_div /* nullable */, const float* weight,
+                                      int64_t ld_w, const int64_t* labels, int n, int c, int cin, int hw, float power, float eps,
+                                      void* dx, void* stream);
+int iif_normed_mask_predict_bwd_weight(const void* x, int dtype, const float* g, const float* coef_a,
+                                       const float* up /* nullable */, const float* inv_div /* nullable */, const float* weight,
+                                       int64_t ld_w, const int64_t* labels, int n, int c, int cin, int hw, float power, float eps,
+                                       float* scratch, float* dweight /* nullable */, float* dbias /* nullable */, void* stream);
+
 /* The mask head's tail fused (csrc/mask_tail.hip; iif_amd/mmdet_mask_tail.py): FCNMaskHead's upsample (a ConvTranspose2d with
  * kernel = stride = 2, no padding), its ReLU and conv_logits at each RoI's label channel (fcn_mask_head.py:131-136), on the
  * fp32-input MFMA.  The [n][co][2h][2w] activation between the two layers and its gradient are never stored.

@@ -1,0 +1,133 @@
+"""Cases of the class-selected NormedConv2d mask predictor (iif_amd/mmdet_normed_mask_predictor.py): the seeded input recipe
+and a float64 restatement.
+
+The restatement is torch on the CPU: the two normalisations of normed_predictor.py:104-124 on the SELECTED weight rows only, an
+einsum, BCE-with-logits, autograd (whose sub-gradient of the norm at 0 is 0, as in the reference).
+tests/test_normed_mask_predictor_host.py shows that it reproduces the reference's own FCNMaskHead(predictor_cfg=NormedConv2d)
+forward + loss (tests/golden/g35_normed_mask_predictor.npz) to 1e-12; the GPU tests compare the kernels against it.
+
+Recipe (torch CPU generator, seeded per case): x = relu(randn), so every case is post-ReLU; weight ~ N(0, 8 / Cin); bias ~
+N(0, 0.01); targets Bernoulli(0.5) as floats, uniform soft targets where the case says so.  With T = 20 the logits have a
+standard deviation of about 20 / sqrt(Cin) around a class-dependent offset.
+"""
+import functools
+
+import torch
+
+EPS = 1e-6
+# name -> (N, C, Cin, H, W, labels or None (seeded random), bias, soft targets, tempearture, power, zero pixels)
+CASES = {
+    "a": (5, 7, 256, 28, 28, [0, 6, 3, 3, 0], True, False, 20, 1.0, False),   # the head's real tile; repeated and edge labels
+    "b": (9, 4, 256, 28, 28, [3] * 9, True, False, 20, 1.0, False),           # one class owns every RoI: the ordered segment sum
+    "c": (33, 80, 80, 14, 14, None, True, True, 20, 1.0, False),              # Cin not a multiple of 64; HW = 196; soft targets
+    "d": (1, 3, 3, 2, 2, [1], True, False, 20, 1.0, False),                   # everything smaller than a wave
+    "e": (3, 11, 65, 7, 9, [10, 0, 4], True, False, 20, 1.0, False),          # HW = 63: unaligned rows, vector tails, odd Cin
+    "f": (64, 1203, 256, 28, 28, None, True, False, 20, 1.0, False),          # the LVIS class count
+    "g": (6, 1, 256, 28, 28, [0] * 6, False, False, 20, 1.0, False),          # the class_agnostic head, bias=None
+    "h": (9, 4, 256, 28, 28, [3] * 9, True, False, 8, 2.0, False),            # case b with power = 2, T = 8: the powf path
+    "i": (5, 7, 256, 28, 28, [0, 6, 3, 3, 0], True, False, 20, 1.0, True),    # case a with pixels that are zero in every channel
+}
+ZERO_PIXELS = ((0, 0, 0), (0, 27, 27), (1, 13, 5), (2, 4, 4), (4, 27, 0), (4, 9, 9), (4, 9, 10))       # (roi, y, x) of case i
+UP = 2.5                                                                      # the upstream factor of the scaled-backward checks
+# labels of the valid_rows checks on case a (C = 7): none invalid, mixed (a padded row has label C; -1 is also outside), all invalid
+VALID_ROWS_LABELS = {"none": [0, 6, 3, 3, 0], "mixed": [0, 7, 3, -1, 0], "all": [7, 7, -1, 7, 7]}
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(name):
+    """(x [N, Cin, H, W], weight [C, Cin, 1, 1], bias [C] or None, labels int64 [N], targets [N, H, W]) float32, CPU.  Shared:
+    do not modify."""
+    n, c, cin, h, w, labels, has_bias, soft = CASES[name][:8]
+    g = torch.Generator().manual_seed(3500 + sorted(CASES).index(name))
+    x = torch.relu(torch.randn(n, cin, h, w, generator=g))
+    weight = torch.randn(c, cin, 1, 1, generator=g) * (8.0 / cin) ** 0.5
+    bias = torch.randn(c, generator=g) * 0.1 if has_bias else None
+    u = torch.rand(n, h, w, generator=g)
+    targets = u if soft else (u < 0.5).float()
+    lb = torch.randint(0, c, (n,), generator=g) if labels is None else torch.tensor(labels, dtype=torch.int64)
+    if CASES[name][10]:
+        for r, y, xx in ZERO_PIXELS:
+            x[r, :, y, xx] = 0
+    return x, weight, bias, lb, targets
+
+
+def cfg(name):
+    """(tempearture, power, eps) of a case."""
+    return float(CASES[name][8]), float(CASES[name][9]), EPS
+
+
+def restate64(x, weight, bias, labels, targets, tempearture=20.0, power=1.0, eps=EPS, up=1.0, valid=None, valid_rows=False):
+    """Float64 restatement on the given values (widened exactly).  Returns a dict of float64 CPU tensors: z [N, H, W], zabs
+    (s_x s_w sum_c |w x| behind every logit) and babs (|bias[l]|): the scales of its rounding bound, loss (1,), and the gradients
+    of (loss * up).sum(): dx, dweight [C, Cin], dbias [C] (zeros for bias None).  valid: bool [N], RoIs that take part (others:
+    zero loss, zero gradients) - the contract for labels outside [0, C).  The divisor is N * HW, or with valid_rows
+    max(1, #valid) * HW."""
+    x = x.detach().double().clone().requires_grad_(True)
+    c, cin = weight.shape[0], weight.shape[1]
+    w2 = weight.detach().double().reshape(c, cin).clone().requires_grad_(True)
+    b = (torch.zeros(c, dtype=torch.float64) if bias is None else bias.detach().double().clone()).requires_grad_(True)
+    n = x.shape[0]
+    valid = torch.ones(n, dtype=torch.bool) if valid is None else valid
+    lb = torch.where(valid, labels, torch.zeros_like(labels))
+    wsel = w2[lb]                                                        # [N, Cin]: the selected rows only
+    what = wsel / (wsel.norm(dim=1, keepdim=True).pow(power) + eps)
+    xn = x / (x.norm(dim=1, keepdim=True).pow(power) + eps) * tempearture
+    z = torch.einsum("nc,nchw->nhw", what, xn) + b[lb][:, None, None]
+    zabs = torch.einsum("nc,nchw->nhw", what.detach().abs(), xn.detach().abs())
+    babs = b.detach()[lb].abs()[:, None, None].expand_as(zabs)
+    t = targets.detach().double()
+    rows = z.clamp(min=0) - z * t + torch.log1p(torch.exp(-z.abs()))
+    rows = rows * valid[:, None, None].double()
+    rois = max(1, int(valid.sum())) if valid_rows else n
+    loss = (rows.sum() / (rois * rows[0].numel()))[None]
+    (loss * up).sum().backward()
+    zz = z.detach() * valid[:, None, None].double()
+    return dict(z=zz, zabs=zabs, babs=babs, loss=loss.detach(), dx=x.grad, dweight=w2.grad, dbias=b.grad)
+
+
+@functools.lru_cache(maxsize=None)
+def reference64(name, up=1.0, bf16=False):
+    """restate64 of a case (bf16: on x rounded to bfloat16 and widened exactly).  Shared: do not modify."""
+    x, weight, bias, labels, targets = inputs(name)
+    if bf16:
+        x = x.bfloat16().float()
+    t, q, eps = cfg(name)
+    return restate64(x, weight, bias, labels, targets, t, q, eps, up)
+
+
+def logit_bound(ref, cin, power):
+    """The per-element bound of the logits: the first-order bound of the fp32 dot product plus the two norms, and two roundings
+    of the result and the bias."""
+    u24 = 2.0 ** -24
+    return ((1 + power) * (cin + 2) + 16) * u24 * ref["zabs"] + 2 * u24 * (ref["babs"] + ref["z"].abs())
+
+
+def float32_reference(name, x=None):
+    """What a float32 run of the reference computes, on the CPU: oracle.mmdet_iif.normed_conv2d_1x1 + mask_cross_entropy +
+    autograd on ALL C channels.  Returns (z [N, H, W] at the labels, loss, dx, dweight [C, Cin], dbias or None)."""
+    from oracle import mmdet_iif as M
+    x0, weight, bias, labels, targets = inputs(name)
+    t, q, eps = cfg(name)
+    xs = (x0 if x is None else x).clone().requires_grad_(True)
+    ws = weight.clone().requires_grad_(True)
+    bs = None if bias is None else bias.clone().requires_grad_(True)
+    pred = M.normed_conv2d_1x1(xs, ws, bs, t, q, eps)
+    loss = M.mask_cross_entropy(pred, targets, labels)
+    loss.sum().backward()
+    c, cin = weight.shape[:2]
+    z = pred.detach()[torch.arange(xs.shape[0]), labels]
+    return z, loss.detach(), xs.grad, ws.grad.reshape(c, cin), None if bs is None else bs.grad
+
+
+def selected_rows(labels, c):
+    sel = torch.zeros(c, dtype=torch.bool)
+    sel[labels[(labels >= 0) & (labels < c)]] = True
+    return sel
+
+
+# The float32 reference's own worst error against the restatement over the cases above (float32_reference), relative to the
+# largest element of the quantity (the loss: relative to max(1, |loss|)), measured by
+# tests/test_normed_mask_predictor_host.py and rounded up: loss 8.55e-8 (case h), dx 5.07e-7 (h), dweight 5.47e-7 (f),
+# dbias 1.10e-6 (f).  The GPU tests allow the kernels 4x this, the margin of the project's other head tests.
+F32_REFERENCE_ERROR = dict(loss=8.6e-8, dx=5.1e-7, dweight=5.5e-7, dbias=1.11e-6)
+GPU_TOLERANCE = {k: 4 * v for k, v in F32_REFERENCE_ERROR.items()}
