@@ -1,0 +1,320 @@
+// The classification half of BBoxHead.loss (roi_heads/bbox_heads/bbox_head.py:266-283) without its host read: the softmax
+// cross entropy of iif_head.hip with avg_factor = max(#{label_weights > 0}, 1) counted ON THE DEVICE, and the top-1 accuracy of
+// the rows that count, out of the same launch.
+//
+// One 64-lane wave owns one row; the row (C <= 2048) lives in registers, a lane holding groups of 4 consecutive columns
+// (16 bytes of fp32, 8 of bf16) at (j * 64 + lane) * 4.  A group is one vector access when the row pitch and the base allow it
+// and the group is whole, else up to four guarded element accesses: C need not be a multiple of 4 and any pitch >= C works.
+// The softmax runs in base 2 on v_exp_f32 as iif_head.hip's does, with the exponent formed from z - max and the target's own
+// term kept out of the sum (see the row loop).  The kernels are latency / HBM-bound: no MFMA.
+//
+// A row of weight 0 (a padding row of roi_stage_targets_padded) is NOT READ: its gradient row is zeros and it takes no part in
+// the loss, the count or the accuracy, whatever its scores or its label hold (the reference multiplies it by 0, which turns a
+// non-finite padding row into NaN).  A row with a negative weight enters the loss but not the count, as in the reference.
+//
+// avg is known only when the last row is done, so the gradient is stored WITHOUT loss_weight / avg and iif_head_loss_bwd applies
+// upstream * loss_weight / avg from the device scalars in its one launch (normed_mask_predictor.hip's device-scalar pattern).
+//
+// Reduction: loss_reduce.h's ticket protocol (partials published with returning agent-scope exchanges, s_waitcnt, ticket; no
+// fence), restated here because the last block has to combine three sums - the float loss sum and the INTEGER count of valid
+// rows and of hits - into loss, acc and avg.  Thread t of the last block adds the partials of blocks t, t + 256, ... and a
+// halving tree folds the threads: a fixed order for a given N, integers exact, no float atomics, the same bits every call.
+// Only the ticket word has to be zero on entry, and it is zero again on exit.
+#include "common.h"
+
+namespace {
+
+constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kLn2 = 0.6931471805599453f;
+constexpr int kMaxBlocks = (IIF_HEAD_LOSS_WORKSPACE_BYTES / 4 - 4) / 3;       // partial triples behind the 4-word header
+static_assert(IIF_HEAD_LOSS_WORKSPACE_BYTES == 4 * (4 + 3 * kMaxBlocks), "a 4-word header and whole (sum, valid, hits) triples");
+static_assert(IIF_HEAD_LOSS_WORKSPACE_BYTES <= IIF_CE_WORKSPACE_BYTES, "the per-stream CE workspace serves this head too");
+
+__device__ __forceinline__ float fast_exp2(float v) { return __builtin_amdgcn_exp2f(v); }
+__device__ __forceinline__ float fast_log2(float v) { return __builtin_amdgcn_logf(v); }
+
+template <typename T> struct Io;
+template <> struct Io<float> {
+    static constexpr int VEC_BYTES = 16;
+    static __device__ __forceinline__ void load4(const float* p, float (&v)[4]) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    }
+    static __device__ __forceinline__ void store4(float* p, const float (&v)[4]) { *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; }
+    static __device__ __forceinline__ float load1(const float* p) { return *p; }
+    static __device__ __forceinline__ void store1(float* p, float v) { *p = v; }
+};
+template <> struct Io<unsigned short> {  // bf16 bits
+    static constexpr int VEC_BYTES = 8;
+    static __device__ __forceinline__ void load4(const unsigned short* p, float (&v)[4]) {
+        const u32x2 w = *reinterpret_cast<const u32x2*>(p);
+        v[0] = bf16_bits_to_f32(w.x & 0xffffu); v[1] = __uint_as_float(w.x & 0xffff0000u);
+        v[2] = bf16_bits_to_f32(w.y & 0xffffu); v[3] = __uint_as_float(w.y & 0xffff0000u);
+    }
+    static __device__ __forceinline__ void store4(unsigned short* p, const float (&v)[4]) {
+        *reinterpret_cast<u32x2*>(p) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+    }
+    static __device__ __forceinline__ float load1(const unsigned short* p) { return bf16_bits_to_f32(*p); }
+    static __device__ __forceinline__ void store1(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
+};
+
+struct HeadLossArgs {
+    const void* x; int64_t ldx;
+    const float* tab;                  // nullable: ones
+    const int64_t* labels;
+    const float* roww; const float* clsw;   // nullable: ones
+    int64_t ignore; float loss_weight;
+    int N, C;
+    void* dx; int64_t lddx;            // nullable: loss only
+    int32_t* status;
+    float* loss_out; float* acc_out; float* avg_out;
+    int32_t* ws;                       // [0] ticket, [1..3] unused, then (float sum, int valid, int hits) per block
+    int vec_in, vec_out;               // whole groups of x / dx are one vector access
+};
+
+// One group of 4 columns at c0 (a multiple of 4): a vector access if the row allows it.  Only the LAST group of a lane
+// (j == NCH - 1) can be ragged or missing - NCH = ceil(C / 256) - so only that one (RAGGED) tests its columns: columns that do
+// not exist read as -inf (they never win the max, add 0 to the sum and never outrank a target) and are never written.
+template <typename T, bool RAGGED>
+__device__ __forceinline__ void load_group(const T* row, int c0, int C, bool vec, float (&v)[4]) {
+    if (vec && (!RAGGED || c0 + 4 <= C)) { Io<T>::load4(row + c0, v); return; }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (!RAGGED || c0 + e < C) ? Io<T>::load1(row + c0 + e) : -INFINITY;
+}
+template <typename T, bool RAGGED>
+__device__ __forceinline__ void store_group(T* row, int c0, int C, bool vec, const float (&v)[4]) {
+    if (vec && (!RAGGED || c0 + 4 <= C)) { Io<T>::store4(row + c0, v); return; }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (!RAGGED || c0 + e < C) Io<T>::store1(row + c0 + e, v[e]);
+}
+
+// NCH: groups per lane = ceil(C / 256).  Blocks of 4 waves; a wave walks rows wave, wave + n_waves, ...
+// (launch bound: no occupancy asked for - 8 groups are 32 row values per lane, and the compiler's own allocation keeps every
+// instance free of scratch; a tighter bound would only constrain it)
+template <typename T, int NCH>
+__global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
+    __shared__ __attribute__((aligned(16))) float tab_s[NCH * 256];
+    __shared__ float red_f[256];
+    __shared__ int red_v[256], red_h[256];
+    __shared__ int last;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nwaves = gridDim.x * 4;
+    const int C = a.C;
+    for (int i = threadIdx.x; i < NCH * 256; i += 256) tab_s[i] = (a.tab != nullptr && i < C) ? a.tab[i] : 1.0f;
+    __syncthreads();
+    float wave_loss = 0.f;
+    int wave_v = 0, wave_h = 0;                    // wave-uniform
+    for (int row = blockIdx.x * 4 + wv; row < a.N; row += nwaves) {
+        asm volatile("" ::: "memory");            // keep the table reads in LDS: hoisted into registers they cost the occupancy
+        const float w = a.roww ? a.roww[row] : 1.0f;
+        T* dxr = a.dx ? static_cast<T*>(a.dx) + (int64_t)row * a.lddx : nullptr;
+        bool live = w != 0.f;                      // (a NaN weight is live, and poisons the loss as it does in the reference)
+        int l = 0;
+        if (live) {
+            const int64_t l64 = a.labels[row];
+            const bool in_range = l64 >= 0 && l64 < C;
+            if (l64 != a.ignore && !in_range && a.status && lane == 0) atomicExch(a.status, 1);
+            live = in_range && l64 != a.ignore;
+            l = live ? (int)l64 : 0;
+        }
+        wave_v += w > 0.f;
+        if (!live) {                               // wave-uniform: nothing of the row is read
+            if (dxr) {
+                const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < NCH - 1; ++j) store_group<T, false>(dxr, (j * 64 + lane) * 4, C, a.vec_out, zero);
+                store_group<T, true>(dxr, ((NCH - 1) * 64 + lane) * 4, C, a.vec_out, zero);
+            }
+            continue;
+        }
+        const T* xr = static_cast<const T*>(a.x) + (int64_t)row * a.ldx;
+        float z[NCH][4];
+#pragma unroll
+        for (int j = 0; j < NCH - 1; ++j) load_group<T, false>(xr, (j * 64 + lane) * 4, C, a.vec_in, z[j]);
+        load_group<T, true>(xr, ((NCH - 1) * 64 + lane) * 4, C, a.vec_in, z[NCH - 1]);
+        const float xt = Io<T>::load1(xr + l);
+        // top-1 on the RAW scores, iif_topk_hits' tie rule: columns that outrank the target, an equal score at a lower index included
+        int cnt = 0;
+        float m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const int c0 = (j * 64 + lane) * 4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                cnt += (z[j][e] > xt) || (z[j][e] == xt && c0 + e < l);
+                z[j][e] *= tab_s[c0 + e];
+                m = fmaxf(m, z[j][e]);
+            }
+        }
+        cnt = wave_sum_i(cnt);
+        wave_h += (w > 0.f) && cnt == 0;
+        m = wave_max(m);
+        // 2^((z - m) log2 e) with the difference formed first, so that the row maximum contributes exactly 1 (iif_head.hip's single
+        // fma z log2 e - round(m log2 e) scales the whole row by 2^residual: harmless for its lse = m + ..., not here).
+        // The target's own term e_l stays OUT of the sum: with so = sum_{c != l} e_c,
+        //   nll = log(so + e_l) - log(e_l) = log1p(so / e_l)      and      softmax_l - 1 = -so / (so + e_l),
+        // neither of which cancels when the row is a confident hit (softmax_l -> 1: log(sum) and softmax_l - 1 would be right only
+        // to ulp(1), far more than such a row's whole nll and gradient).
+        float so = 0.f;
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const int c0 = (j * 64 + lane) * 4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) z[j][e] = fast_exp2((z[j][e] - m) * kLog2e);
+            const unsigned d = (unsigned)(l - c0);
+            if (d < 4u) so += ((d == 0u ? 0.f : z[j][0]) + (d == 1u ? 0.f : z[j][1])) + ((d == 2u ? 0.f : z[j][2]) + (d == 3u ? 0.f : z[j][3]));
+            else so += (z[j][0] + z[j][1]) + (z[j][2] + z[j][3]);
+        }
+        so = wave_sum(so);
+        const float dl = xt * tab_s[l] - m;                       // <= 0, the same product the row's own element is
+        const float el = fast_exp2(dl * kLog2e);
+        const float sum = so + el, inv_s = 1.0f / sum;
+        // (el underflows only for a target ~87 below the maximum: there log(sum) - dl has nothing to cancel)
+        const float nll = el > 1e-30f ? log1pf(so / el) : kLn2 * fast_log2(sum) - dl;
+        const float cw = a.clsw ? a.clsw[l] : 1.0f;
+        wave_loss += w * (cw * nll);
+        if (dxr == nullptr) continue;
+        const float coef = w * cw, gs = coef * inv_s, gl = -(so * gs);
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const int c0 = (j * 64 + lane) * 4;
+            float p[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) p[e] = (c0 + e == l ? gl : z[j][e] * gs) * tab_s[c0 + e];
+            if (j < NCH - 1) store_group<T, false>(dxr, c0, C, a.vec_out, p);
+            else store_group<T, true>(dxr, c0, C, a.vec_out, p);
+        }
+    }
+    // ---- the block's three sums, then loss_reduce.h's protocol
+    if (lane == 0) { red_f[wv] = wave_loss; red_v[wv] = wave_v; red_h[wv] = wave_h; }
+    __syncthreads();
+    int32_t* part = a.ws + 4;
+    if (threadIdx.x == 0) {
+        float f = 0.f;
+        int v = 0, h = 0;
+        for (int i = 0; i < 4; ++i) { f += red_f[i]; v += red_v[i]; h += red_h[i]; }
+        const float p0 = __hip_atomic_exchange(reinterpret_cast<float*>(part + 3 * blockIdx.x), f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int p1 = __hip_atomic_exchange(part + 3 * blockIdx.x + 1, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int p2 = __hip_atomic_exchange(part + 3 * blockIdx.x + 2, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" : : "v"(p0), "v"(p1), "v"(p2) : "memory");
+        const int t = __hip_atomic_fetch_add(a.ws, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = (t == (int)gridDim.x - 1);
+    }
+    __syncthreads();
+    if (!last) return;
+    float f = 0.f;
+    int v = 0, h = 0;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
+        f += __hip_atomic_load(reinterpret_cast<float*>(part + 3 * i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v += __hip_atomic_load(part + 3 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        h += __hip_atomic_load(part + 3 * i + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    red_f[threadIdx.x] = f; red_v[threadIdx.x] = v; red_h[threadIdx.x] = h;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red_f[threadIdx.x] += red_f[threadIdx.x + o];
+            red_v[threadIdx.x] += red_v[threadIdx.x + o];
+            red_h[threadIdx.x] += red_h[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const int valid = red_v[0];
+        const float avg = (float)(valid > 1 ? valid : 1);
+        *a.loss_out = a.loss_weight * (red_f[0] / avg);
+        // accuracy.py:49: correct.float().sum() * (100.0 / rows), the factor a Python double rounded to float32
+        *a.acc_out = valid > 0 ? (float)red_h[0] * (float)(100.0 / (double)avg) : 0.f;
+        *a.avg_out = avg;
+        __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// out = u * (upstream * loss_weight / avg), the three factors read on the device
+template <typename T>
+__global__ void __launch_bounds__(256) head_loss_scale_kernel(const T* u, int64_t n, const float* upstream, const float* avg, float loss_weight,
+                                                              T* out, int vec) {
+    const float f = (*upstream * loss_weight) / *avg;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    if (vec) {
+        const int64_t n4 = n / 4;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+            float v[4];
+            Io<T>::load4(u + 4 * i, v);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] *= f;
+            Io<T>::store4(out + 4 * i, v);
+        }
+        for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) Io<T>::store1(out + i, Io<T>::load1(u + i) * f);
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) Io<T>::store1(out + i, Io<T>::load1(u + i) * f);
+    }
+}
+
+inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+template <typename T>
+int launch_fwd(HeadLossArgs a, hipStream_t st) {
+    a.vec_in = a.N > 0 && a.ldx % 4 == 0 && aligned(a.x, Io<T>::VEC_BYTES);
+    a.vec_out = a.dx != nullptr && a.lddx % 4 == 0 && aligned(a.dx, Io<T>::VEC_BYTES);
+    int blocks = (a.N + 3) / 4;
+    if (blocks < 1) blocks = 1;                   // N == 0: one block writes loss 0, acc 0, avg 1
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+    const dim3 grid(blocks), block(256);
+    const int nch = (a.C + 255) / 256;
+    if (nch <= 1) hipLaunchKernelGGL((head_loss_kernel<T, 1>), grid, block, 0, st, a);            // COCO: 81
+    else if (nch <= 2) hipLaunchKernelGGL((head_loss_kernel<T, 2>), grid, block, 0, st, a);
+    else if (nch <= 3) hipLaunchKernelGGL((head_loss_kernel<T, 3>), grid, block, 0, st, a);
+    else if (nch <= 4) hipLaunchKernelGGL((head_loss_kernel<T, 4>), grid, block, 0, st, a);
+    else if (nch <= 5) hipLaunchKernelGGL((head_loss_kernel<T, 5>), grid, block, 0, st, a);       // LVIS: 1204, Seesaw-sized 1205
+    else if (nch <= 6) hipLaunchKernelGGL((head_loss_kernel<T, 6>), grid, block, 0, st, a);
+    else if (nch <= 7) hipLaunchKernelGGL((head_loss_kernel<T, 7>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((head_loss_kernel<T, 8>), grid, block, 0, st, a);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int iif_head_loss_fwd(const void* scores, int dtype, int64_t ld_scores, const float* table, const int64_t* labels,
+                      const float* label_weights, const float* class_weight, int64_t ignore_index, float loss_weight, int N, int C,
+                      void* dscores, int64_t ld_dscores, float* loss_out, float* acc_out, float* avg_out, int32_t* d_status,
+                      void* d_workspace, void* stream) {
+    if (N < 0 || N > IIF_HEAD_LOSS_MAX_ROWS || C < 2) return IIF_EINVAL;
+    if (dtype != IIF_F32 && dtype != IIF_BF16) return IIF_EINVAL;
+    if (!loss_out || !acc_out || !avg_out || !d_workspace || !aligned(d_workspace, 4)) return IIF_EINVAL;
+    if (N > 0 && (!scores || !labels)) return IIF_EINVAL;
+    if (N > 0 && (ld_scores < C || (dscores && ld_dscores < C))) return IIF_EINVAL;
+    if (!aligned(scores, dtype == IIF_F32 ? 4 : 2) || !aligned(dscores, dtype == IIF_F32 ? 4 : 2)) return IIF_EINVAL;
+    if (C > IIF_HEAD_LOSS_MAX_CLASSES) return IIF_EUNSUPPORTED;
+    HeadLossArgs a{scores, ld_scores, table, labels, label_weights, class_weight, ignore_index, loss_weight, N, C,
+                   N > 0 ? dscores : nullptr, ld_dscores, d_status, loss_out, acc_out, avg_out, static_cast<int32_t*>(d_workspace), 0, 0};
+    return dtype == IIF_F32 ? launch_fwd<float>(a, as_stream(stream)) : launch_fwd<unsigned short>(a, as_stream(stream));
+}
+
+int iif_head_loss_bwd(const void* dscores, int dtype, int64_t n, const float* d_upstream, const float* d_avg, float loss_weight,
+                      void* out, void* stream) {
+    if (n < 0 || !d_upstream || !d_avg) return IIF_EINVAL;
+    if (dtype != IIF_F32 && dtype != IIF_BF16) return IIF_EINVAL;
+    if (n == 0) return IIF_OK;
+    if (!dscores || !out) return IIF_EINVAL;
+    const int es = dtype == IIF_F32 ? 4 : 2;
+    if (!aligned(dscores, es) || !aligned(out, es)) return IIF_EINVAL;
+    const int vec = aligned(dscores, 4 * es) && aligned(out, 4 * es);
+    const int64_t want = cdiv64(vec ? cdiv64(n, 4) : n, 256);
+    const int blocks = (int)(want < 2048 ? want : 2048);
+    if (dtype == IIF_F32)
+        hipLaunchKernelGGL(head_loss_scale_kernel<float>, dim3(blocks), dim3(256), 0, as_stream(stream), (const float*)dscores, n,
+                           d_upstream, d_avg, loss_weight, (float*)out, vec);
+    else
+        hipLaunchKernelGGL(head_loss_scale_kernel<unsigned short>, dim3(blocks), dim3(256), 0, as_stream(stream),
+                           (const unsigned short*)dscores, n, d_upstream, d_avg, loss_weight, (unsigned short*)out, vec);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+}  // extern "C"

@@ -195,6 +195,45 @@ int iif_bbox_reg_fwd(const void* pred, int dtype, int64_t ld_pred, const int64_t
 int iif_bbox_reg_scatter_grad(const float* dsel, const int64_t* labels, int num_classes, int N, int C, const float* g,
                               void* dpred, int dtype, int64_t ld_dpred, void* stream);
 
+/* The classification half of BBoxHead.loss (mmdet/models/roi_heads/bbox_heads/bbox_head.py:266-283) in ONE launch and with NO
+ * host read (csrc/head_loss.hip): the softmax cross entropy of iif_ce_fwd_bwd with avg_factor = max(#{label_weights > 0}, 1)
+ * counted on the device, and the top-1 accuracy (mmdet/models/losses/accuracy.py:7-51) of the rows that count.
+ * scores [N, C], row pitch ld_scores >= C (elements), IIF_F32 or IIF_BF16 (math is fp32), element-aligned;
+ * l_i = labels[i] (int64), w_i = label_weights[i] (NULL = ones), cw = class_weight (NULL = ones), table NULL = ones:
+ *   z_i    = scores_i * table
+ *   nll_i  = cw[l_i] * (logsumexp(z_i) - z_i[l_i])           0 if l_i == ignore_index
+ *   V      = #{ i : w_i > 0 },  avg = max(V, 1)
+ *   loss   = loss_weight * (sum_i w_i nll_i) / avg
+ *   hit_i  = no column of the RAW scores_i outranks column l_i (greater, or equal at a lower index: iif_topk_hits' tie rule)
+ *   acc    = float(sum_{w_i > 0} hit_i) * float(100.0 / avg)   0 when V == 0
+ *   dscores[i, c] = w_i * cw[l_i] * table[c] * (softmax(z_i)[c] - [c == l_i])     WITHOUT loss_weight / avg: iif_head_loss_bwd
+ * The scores of a row with w_i == 0 are NOT READ and its label is not looked at: its dscores row is zeros and it takes no part in loss, V
+ * or acc (the padded rows of iif_roi_stage_targets; the reference computes 0 * nll there, NaN for a non-finite row).  A row
+ * with w_i < 0 enters the loss but not V, as in the reference.  Of a row with w_i != 0, a label equal to ignore_index, or
+ * outside [0, C), contributes 0, is never a hit and gets a zero dscores row; the latter also sets d_status (int32[1] or NULL)
+ * to 1, as iif_ce_fwd_bwd does.
+ * loss_out, acc_out, avg_out: DEVICE floats, all required.  dscores: [N, C] in the scores' dtype, pitch ld_dscores >= C, or
+ * NULL (loss only).  d_workspace: IIF_HEAD_LOSS_WORKSPACE_BYTES (the IIF_CE_WORKSPACE_BYTES buffer of a stream is large
+ * enough and may be shared: same contract - its first int32 zero on entry, zero again on exit; nothing else has to be zero).
+ * V and the hit count are integer sums, the float sum is added in an order fixed by N: the same bits from call to call.
+ * N == 0 writes loss 0, acc 0, avg 1 (one launch).
+ * Before anything is launched: IIF_EINVAL for N outside 0 .. IIF_HEAD_LOSS_MAX_ROWS, C < 2, an unknown dtype, a null or
+ * misaligned output / workspace / scores / labels, a pitch smaller than C; IIF_EUNSUPPORTED for C > IIF_HEAD_LOSS_MAX_CLASSES. */
+#define IIF_HEAD_LOSS_MAX_ROWS 65535
+#define IIF_HEAD_LOSS_MAX_CLASSES 2048
+#define IIF_HEAD_LOSS_WORKSPACE_BYTES (4 * (4 + 3 * 512))
+int iif_head_loss_fwd(const void* scores, int dtype, int64_t ld_scores, const float* table, const int64_t* labels,
+                      const float* label_weights, const float* class_weight, int64_t ignore_index, float loss_weight, int N, int C,
+                      void* dscores, int64_t ld_dscores, float* loss_out, float* acc_out, float* avg_out, int32_t* d_status,
+                      void* d_workspace, void* stream);
+
+/* Backward of iif_head_loss_fwd in ONE launch: out[e] = dscores[e] * (*d_upstream * loss_weight / *d_avg) over n contiguous
+ * elements (IIF_F32 / IIF_BF16, element-aligned; 16-byte pieces when both bases allow).  d_upstream (the gradient of the
+ * scalar loss) and d_avg (iif_head_loss_fwd's avg_out) are DEVICE floats, so nothing synchronises; dscores is left intact
+ * (backward may run twice).  n == 0 is a no-op.  IIF_EINVAL: n < 0, a null or misaligned pointer, an unknown dtype. */
+int iif_head_loss_bwd(const void* dscores, int dtype, int64_t n, const float* d_upstream, const float* d_avg, float loss_weight,
+                      void* out, void* stream);
+
 /* ---- Box overlaps and max-IoU assignment (csrc/assign.hip): mmdet/core/bbox/iou_calculators/iou2d_calculator.py:75-261 and
  * mmdet/core/bbox/assigners/max_iou_assigner.py:61-213 without the [G, N] overlap matrix.
  *
