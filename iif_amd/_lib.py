@@ -60,6 +60,7 @@ SIGNATURES = {
     "iif_shortcut_a_backward_acc": [_P, _I, _I, _I, _I, _I, _I, _P, _P],
     "iif_colsum_f32": [_P, _I, _I, _L, _P, _P],
     "iif_sgd_step": [_P, _P, _P, _L, _F, _P, _F, _F, _I, _F, _P],
+    "iif_stream_plan": [_I, _L, _I, _I, _P],
     "iif_rmsprop_step": [_P, _P, _P, _P, _P, _L, _F, _P, _F, _F, _F, _F, _I, _F, _P],
     "iif_group_pack": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "iif_group_pack_batched": [_P, _I, _I, _I, _P],

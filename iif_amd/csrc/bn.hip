@@ -18,6 +18,7 @@
 #include "common.h"
 #include "vec16.h"
 #include "pool_gather.h"
+#include "stream_plan.h"
 
 namespace {
 
@@ -532,22 +533,9 @@ inline int launch_bn_finalize(const float* partial, int nblk, int C, double coun
     return IIF_OK;
 }
 
-// grid of the two normalisation passes: one trip per thread over U vectors (U = 4 where that still leaves >= 2 048 blocks).
-// In the ResNet-50 step (same-call A/B, ms per step): round 4's form (4 096 blocks looping, U = 1) 18.59 / 18.62; one trip,
-// U <= 4 18.32 / 18.33; the same with non-temporal stores 18.34 / 18.41 (alone they are the faster form, 6.6 against 6.2 TB/s;
-// in the step the consumer reads the tensor next); U = 1 one trip 19.09 / 19.04 (100 k blocks of one vector per thread: alone
-// 6.1 TB/s, in the step the other streams' blocks wait behind them); a grid capped at 4 096 / 2 048 / 1 024 blocks with U <= 4
-// 18.42 / 18.47 / 18.51.  IIF_BN_GRID_CAP=<blocks>, IIF_BN_UNROLL=<1|2|4>, IIF_BN_NT_STORES=1 select the other forms.
-struct StreamGrid { int blocks, u; bool nts; };
-inline StreamGrid stream_grid(int64_t total_vec) {
-    static const int64_t cap = [] { const char* e = getenv("IIF_BN_GRID_CAP"); return e ? atoll(e) : (1LL << 30); }();
-    static const bool nts = getenv("IIF_BN_NT_STORES") != nullptr;
-    static const int umax = [] { const char* e = getenv("IIF_BN_UNROLL"); return e ? atoi(e) : 4; }();
-    int u = total_vec >= (int64_t)4 * 256 * 2048 ? 4 : (total_vec >= (int64_t)2 * 256 * 2048 ? 2 : 1);
-    if (u > umax) u = umax;
-    const int64_t b = (total_vec + 256 * u - 1) / (256 * u);
-    return StreamGrid{(int)(b < cap ? b : cap), u, nts};
-}
+// grid of the two normalisation passes: stream_plan.h (the planning query iif_stream_plan walks the same function)
+using iif_plan::StreamGrid;
+using iif_plan::stream_grid;
 
 template <typename T>
 int bn_forward_t(const T* x, int64_t M, int C, const float* gamma, const float* beta, float eps, float momentum,
@@ -845,7 +833,7 @@ __global__ void __launch_bounds__(256) pool_bn_bwd_apply_kernel(const T* gp, con
     // Blocks go round the 8 XCDs; a pooled row is gathered by three image rows.  XCD k walks the k-th eighth of the row groups in
     // order, so neighbouring rows meet in one L2.
     const unsigned ngroups = gridDim.x, per = ngroups >> 3;
-    const unsigned grp = (ngroups & 7u) == 0 ? (blockIdx.x & 7u) * per + (blockIdx.x >> 3) : blockIdx.x;
+    const unsigned grp = iif_plan::pool_fused_remap(ngroups) ? (blockIdx.x & 7u) * per + (blockIdx.x >> 3) : blockIdx.x;
     const unsigned r0 = grp * (unsigned)rows_per_block;
     unsigned nr = (unsigned)rows_per_block;
     if (r0 + nr > (unsigned)total_rows) nr = (unsigned)total_rows - r0;
@@ -1115,9 +1103,9 @@ int iif_bn_backward_pool_fused(const void* g_pool, const uint8_t* argmax, const 
     else hipLaunchKernelGGL(bn_bwd_finalize_kernel<32>, fgrid, blk, 0, st, rows, nblk, c, (double)m, gamma, stats, dgamma, dbeta, coef);
     IIF_LAUNCH_CHECK();
     const int total_rows = n * h;
-    int rpb = 8;                     // rows per block: 28 pipelined steps per thread at 112 x 64 channels (2: 247 us, 4: 238, 8-28: 230)
-    if ((int64_t)rpb * w * (c / v) < 2048) rpb = (int)((2048 + (int64_t)w * (c / v) - 1) / ((int64_t)w * (c / v)));
-    const dim3 agrid((unsigned)((total_rows + rpb - 1) / rpb));
+    const iif_plan::PoolFusedGrid pg = iif_plan::pool_fused_grid(total_rows, w, c / v);
+    const int rpb = pg.rows_per_block;
+    const dim3 agrid((unsigned)pg.groups);
     if (dtype == IIF_F32)
         hipLaunchKernelGGL(pool_bn_bwd_apply_kernel<float>, agrid, blk, 0, st, (const float*)g_pool, argmax, (const float*)x, stats, coef,
                            (float*)dx, h, w, c, ho, wo, total_rows, rpb);

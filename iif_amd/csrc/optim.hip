@@ -8,12 +8,13 @@
 // Padding lanes of the arena (p = g = sq = buf = ga = 0) stay 0 as long as eps > 0: avg = eps there.
 // Traffic per parameter: p, g, sq read + p, sq written = 20 B; + 8 B with MOMENTUM (buf), + 8 B with CENTERED (ga).
 #include "common.h"
+#include "stream_plan.h"
 
 #include <math.h>
 
 namespace {
 
-inline int rms_blocks(int64_t n4) { const int64_t b = (n4 + 255) / 256; return (int)(b < 8192 ? (b > 0 ? b : 1) : 8192); }
+using iif_plan::rms_blocks;    // stream_plan.h
 
 template <bool MOMENTUM, bool CENTERED>
 __device__ __forceinline__ void rmsprop_elem(float& p, float g, float& sq, float& buf, float& ga, float lr, float alpha,

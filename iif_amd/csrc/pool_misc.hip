@@ -3,6 +3,7 @@
 // channel vectors per lane wherever alignment allows.
 #include "common.h"
 #include "pool_gather.h"
+#include "stream_plan.h"
 
 namespace {
 
@@ -35,7 +36,7 @@ template <> struct PT<unsigned short> {
     static __device__ __forceinline__ void store1(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
 };
 
-inline int sblocks(int64_t n) { const int64_t b = (n + 255) / 256; return (int)(b < 8192 ? (b > 0 ? b : 1) : 8192); }
+using iif_plan::sblocks;       // grid of the grid-stride kernels below: stream_plan.h
 
 // ---------------------------------------------------------------- max pool 3x3/s2/p1 (general k,s,p)
 template <typename T>
@@ -503,7 +504,7 @@ int iif_maxpool_bn_forward(const void* x, int dtype, const float* stats, int n, 
     const int cvs = c / (dtype == IIF_F32 ? 4 : 8);
     if (k == 3 && stride == 2 && pad == 1 && cvs <= 256 && 256 % cvs == 0 && (int64_t)n * ho < 0x7fffffffLL &&
         (int64_t)n * h * w * c < 0x7fffffffLL) {
-        const int rowblocks = (int)((int64_t)n * ho < 16384 ? (int64_t)n * ho : 16384);
+        const int rowblocks = iif_plan::pool_row_blocks((int64_t)n * ho);
         IIF_BY_DTYPE(dtype,
             hipLaunchKernelGGL(maxpool321_bn_fwd_kernel<float>, dim3(rowblocks), dim3(256), 0, st, (const float*)x, stats, n, h, w, c, ho, wo, (float*)y, argmax, (float*)pool_x),
             hipLaunchKernelGGL(maxpool321_bn_fwd_kernel<unsigned short>, dim3(rowblocks), dim3(256), 0, st, (const unsigned short*)x, stats, n, h, w, c, ho, wo, (unsigned short*)y, argmax, (unsigned short*)pool_x))
@@ -664,6 +665,35 @@ int iif_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t
     hipLaunchKernelGGL(sgd_kernel, dim3(sblocks(n / 4 + 1)), dim3(256), 0, as_stream(stream), params, grads, momentum_buf,
                        n, lr, d_lr, momentum, weight_decay, nesterov, grad_scale);
     IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+// The size-dependent launch decisions of the streaming kernels (stream_plan.h), walked without launching anything.
+int iif_stream_plan(int family, int64_t work, int w, int cv, int32_t* out) {
+    if (!out || work <= 0) return IIF_EINVAL;
+    int64_t blocks = 0, per_trip = 256;
+    out[1] = 1; out[2] = 0;
+    switch (family) {
+        case IIF_PLAN_BN_STREAM: {
+            const iif_plan::StreamGrid sg = iif_plan::stream_grid(work);
+            blocks = sg.blocks; out[1] = sg.u; out[2] = sg.nts ? 1 : 0; per_trip = 256 * sg.u;
+            break;
+        }
+        case IIF_PLAN_GRID_STRIDE: blocks = iif_plan::sblocks(work); break;
+        case IIF_PLAN_RMSPROP: blocks = iif_plan::rms_blocks(work); break;
+        case IIF_PLAN_SE_STREAM: blocks = iif_plan::se_stream_blocks(work); break;
+        case IIF_PLAN_STEM_POOL_ROWS: blocks = iif_plan::pool_row_blocks(work); per_trip = 1; break;
+        case IIF_PLAN_POOL_FUSED: {
+            if (w <= 0 || cv <= 0 || work > 0x7fffffffLL) return IIF_EINVAL;
+            const iif_plan::PoolFusedGrid pg = iif_plan::pool_fused_grid((int)work, w, cv);
+            out[0] = pg.groups; out[1] = pg.rows_per_block; out[2] = pg.remap ? 1 : 0;
+            out[3] = (int32_t)(work - (int64_t)(pg.groups - 1) * pg.rows_per_block);
+            return IIF_OK;
+        }
+        default: return IIF_EINVAL;
+    }
+    out[0] = (int32_t)blocks;
+    out[3] = (int32_t)((work + blocks * per_trip - 1) / (blocks * per_trip));
     return IIF_OK;
 }
 

@@ -13,6 +13,7 @@
 // Sums are accumulated in a fixed order per (sample, channel): deterministic.
 #include "common.h"
 #include "vec16.h"
+#include "stream_plan.h"
 
 namespace {
 
@@ -116,11 +117,7 @@ __global__ void __launch_bounds__(256) se_form_kernel(const T* g, const float* e
     }
 }
 
-inline unsigned stream_blocks(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    if (b > 256 * 16) b = 256 * 16;
-    return (unsigned)(b < 1 ? 1 : b);
-}
+inline unsigned stream_blocks(int64_t total) { return iif_plan::se_stream_blocks(total); }   // stream_plan.h
 inline bool bad(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 inline int vec_of(int dtype) { return dtype == IIF_F32 ? 4 : 8; }
 

@@ -753,6 +753,27 @@ int iif_colsum_f32(const float* a, int rows, int cols, int64_t ld, float* out, v
 int iif_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, float lr,
                  const float* d_lr, float momentum, float weight_decay, int nesterov,
                  float grad_scale, void* stream);
+/* Planning query of the streaming kernels: the launch decisions that depend only on the SIZE of the tensor, answered by the
+ * functions the launches themselves call (a host function; it touches no operand and launches nothing).  `work` is the number of
+ * work items as the entry counts them:
+ *   IIF_PLAN_BN_STREAM      16-byte vectors m * c / V of iif_bn_apply and of the normalisation pass of every iif_bn_backward*
+ *                           entry; follows IIF_BN_GRID_CAP / IIF_BN_UNROLL / IIF_BN_NT_STORES as the process read them;
+ *   IIF_PLAN_GRID_STRIDE    the grid-stride kernels of the pooling / cast / shortcut / im2col / transpose entries: output vectors
+ *                           (pools, im2col), elements (casts, shortcut, transpose), n / 4 + 1 for iif_sgd_step;
+ *   IIF_PLAN_RMSPROP        n / 4 + 1 for iif_rmsprop_step;
+ *   IIF_PLAN_SE_STREAM      vectors n * hw * c / V of iif_se_apply and iif_se_backward_form;
+ *   IIF_PLAN_STEM_POOL_ROWS pooled rows n * ho of iif_maxpool_bn_forward (3 x 3 / 2 / 1 with 256 % (c / V) == 0);
+ *   IIF_PLAN_POOL_FUSED     image rows n * h of iif_bn_backward_pool_fused, with w and cv = c / V (unused by the others).
+ * out[4] = { blocks, vectors per thread and trip (U), non-temporal stores (0 / 1), trips of the grid-stride loop } and for
+ * IIF_PLAN_POOL_FUSED { row groups = blocks, image rows per block, XCD remap (0 / 1), rows of the last group }.
+ * For tests: a case asks on which side of a threshold it lies instead of repeating the arithmetic. */
+#define IIF_PLAN_BN_STREAM 0
+#define IIF_PLAN_GRID_STRIDE 1
+#define IIF_PLAN_RMSPROP 2
+#define IIF_PLAN_SE_STREAM 3
+#define IIF_PLAN_STEM_POOL_ROWS 4
+#define IIF_PLAN_POOL_FUSED 5
+int iif_stream_plan(int family, int64_t work, int w, int cv, int32_t* out);
 
 /* One fused RMSprop update over a flat fp32 arena.  torch.optim.RMSprop
  * semantics as used at classification/train.py:205-207 (eps 0.0316, alpha 0.9;

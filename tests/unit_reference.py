@@ -102,16 +102,19 @@ def bn_act(x, a, b, res=None, relu=True):
     return pre.clamp_min(0) if relu else pre
 
 
-def bn_backward(gy, mask, xhat, gamma, invstd):
+def bn_backward(gy, mask, xhat, gamma, invstd, gy_sums=None):
     """BN backward with the statistics of the step: gt = gy * mask (mask None: no ReLU),
     dgamma = sum gt xhat, dbeta = sum gt, dx = gamma invstd (gt - mean(gt) - xhat mean(gt xhat)).
+    gy_sums: the gradient the two sums are formed from where that is not gy itself (the stem behind the max pool: the sums
+    come from the pooled gradients, unrounded, the normalisation pass from their gathered sum rounded to the storage type).
     Returns (dx, dgamma, dbeta, gt)."""
     c = gy.shape[-1]
     gt = gy if mask is None else gy * mask
     g2, xh = gt.reshape(-1, c), xhat.reshape(-1, c)
     m = g2.shape[0]
-    dbeta = g2.sum(0)
-    dgamma = (g2 * xh).sum(0)
+    gs = g2 if gy_sums is None else (gy_sums if mask is None else gy_sums * mask).reshape(-1, c)
+    dbeta = gs.sum(0)
+    dgamma = (gs * xh).sum(0)
     dx = (gamma * invstd) * (g2 - dbeta / m - xh * (dgamma / m))
     return dx.view(gt.shape), dgamma, dbeta, gt
 
@@ -272,12 +275,12 @@ def check_step(net, img, cap):
         res[names[id(cv)]] = m
         return xr, st
 
-    def backward(u, src, gy, mask, xsrc, st, stored_dx=True):
+    def backward(u, src, gy, mask, xsrc, st, stored_dx=True, gy_sums=None):
         """BN backward + weight gradient of unit u from the gradient that arrived at it; returns (dx, gt).  stored_dx: the
-        engine forms the weight gradient from its stored (bf16) dx, not by algebra from fp32 P / Gram."""
+        engine forms the weight gradient from its stored (bf16) dx, not by algebra from fp32 P / Gram.  gy_sums: see bn_backward."""
         cv, bn = u.conv, u.bn
         xh = (xsrc - st[0]) * st[1]
-        dx, dgam, dbet, gt = bn_backward(gy, mask, xh, P(bn.weight), st[1])
+        dx, dgam, dbet, gt = bn_backward(gy, mask, xh, P(bn.weight), st[1], gy_sums)
         m = res[names[id(cv)]]
         m["dgamma"] = rel_l2(bn._dgamma, dgam)
         m["dbeta"] = rel_l2(bn._dbeta, dbet)
@@ -384,9 +387,12 @@ def check_step(net, img, cap):
         chosen = win.gather(-1, plan.pool_idx.long().unsqueeze(-1)).squeeze(-1)
         m["pool"] = rel_max(plan.pool_out, wmax)
         m["pool_idx"] = ((wmax - chosen) / wmax.abs().clamp_min(1e-30)).max().item()
+        # the gathered sum of up to four pooled gradients is rounded to the storage type before the normalisation pass: the fused
+        # kernel rounds it in registers (bn.hip, pool_bn_bwd_apply_kernel), the unfused route stores that tensor.  The two
+        # column sums are formed from the pooled gradients themselves (pool_bwd_sums_kernel): unrounded.
         gy = maxpool_scatter(P(g_in[0]), plan.pool_idx, (stem.ho, stem.wo))
         mask = ((P(stem.x) * st[2] + st[3]) > 0).to(F64)
-        backward(stem, img64, gy, mask, P(stem.x), st)
+        backward(stem, img64, rnd(gy), mask, P(stem.x), st, gy_sums=gy)
     else:
         xr, st = forward(stem, img64, True, False)
         backward(stem, img64, P(rec[id(stem)]["gy"]), mask_of(stem), P(stem.x), st)
