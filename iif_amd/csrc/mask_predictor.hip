@@ -14,48 +14,9 @@
 // multiple of 4 and the base is aligned to 4 elements, one element per lane otherwise (HW = 63: rows 252 bytes apart).
 #include "common.h"
 #include "loss_reduce.h"
-#include "mask_class_rows.h"
+#include "mask_predict_core.h"
 
 namespace {
-
-// pixels per forward block: 64, 128 or 256.  Measured at N = 256, 28 x 28, Cin = 256 (profiles/mask_predictor.txt): 44 / 39 / 42 us
-// with x in the Infinity Cache, no difference (83 .. 86 us) behind a 1 GiB fill
-constexpr int kTile = 128;
-static_assert(kTile == 64 || kTile == 128 || kTile == 256, "whole waves of pixels, at most the block");
-constexpr int kChunk = 16;         // channels per block of the dx and dweight passes
-constexpr int kMaxHW = 4096, kMaxCin = 2048;
-
-// V consecutive elements of a channel row as floats
-template <typename T, int V> struct Row;
-template <> struct Row<float, 1> {
-    static __device__ __forceinline__ void ld(const float* p, float (&v)[1]) { v[0] = *p; }
-    static __device__ __forceinline__ void st(float* p, const float (&v)[1]) { *p = v[0]; }
-};
-template <> struct Row<float, 4> {
-    static __device__ __forceinline__ void ld(const float* p, float (&v)[4]) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-        v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
-    }
-    static __device__ __forceinline__ void st(float* p, const float (&v)[4]) {
-        f32x4 q; q[0] = v[0]; q[1] = v[1]; q[2] = v[2]; q[3] = v[3];
-        *reinterpret_cast<f32x4*>(p) = q;
-    }
-};
-template <> struct Row<unsigned short, 1> {
-    static __device__ __forceinline__ void ld(const unsigned short* p, float (&v)[1]) { v[0] = bf16_bits_to_f32(*p); }
-    static __device__ __forceinline__ void st(unsigned short* p, const float (&v)[1]) { *p = f32_to_bf16_bits(v[0]); }
-};
-template <> struct Row<unsigned short, 4> {
-    static __device__ __forceinline__ void ld(const unsigned short* p, float (&v)[4]) {
-        const u32x2 q = *reinterpret_cast<const u32x2*>(p);
-        v[0] = bf16_bits_to_f32(q[0] & 0xffffu); v[1] = __uint_as_float(q[0] & 0xffff0000u);
-        v[2] = bf16_bits_to_f32(q[1] & 0xffffu); v[3] = __uint_as_float(q[1] & 0xffff0000u);
-    }
-    static __device__ __forceinline__ void st(unsigned short* p, const float (&v)[4]) {
-        u32x2 q; q[0] = pack_bf16x2(v[0], v[1]); q[1] = pack_bf16x2(v[2], v[3]);
-        *reinterpret_cast<u32x2*>(p) = q;
-    }
-};
 
 // Forward: block (tile, n) owns kTile pixels of RoI n.  Lanes 0 .. 64 / V - 1 of a channel group cover the tile V pixels each,
 // the 256 V / kTile groups of the block take the channels g, g + 256 V / kTile, ...; the groups' partial sums are folded through LDS in group order
@@ -83,9 +44,7 @@ __global__ void __launch_bounds__(256) mask_predict_fwd_kernel(const T* __restri
         }
         return;
     }
-    const float* wrow = weight + lb * ld_w;
-    for (int c = tid; c < cin; c += 256) sw[c] = wrow[c];
-    __syncthreads();
+    stage_weight_row(weight + lb * ld_w, cin, sw);
     const int grp = tid / LPG, pl = (tid % LPG) * V;     // pixel offset of this lane inside the tile
     float acc[V];
 #pragma unroll
@@ -106,31 +65,17 @@ __global__ void __launch_bounds__(256) mask_predict_fwd_kernel(const T* __restri
     __syncthreads();
     float loss = 0.f;
     if (tid < kTile && p0 + tid < hw) {
-        float s = 0.f;
-#pragma unroll
-        for (int g = 0; g < G; ++g) s += part[g][tid];
+        float s = fold_groups(part, tid);
         if (bias) s += bias[lb];
         const int64_t o = (int64_t)n * hw + p0 + tid;
         if (z) z[o] = s;
         if (target) {
             const float t = target[o];
-            loss = fmaxf(s, 0.f) - s * t + log1pf(expf(-fabsf(s)));
-            if (g0) g0[o] = (1.0f / (1.0f + expf(-s)) - t) * inv;
+            loss = bce_with_logits(s, t);
+            if (g0) g0[o] = (sigmoidf(s) - t) * inv;
         }
     }
-    if (row_loss) {                                      // the tile is the first kTile / 64 waves
-        if (tid < kTile) {
-            loss = wave_sum(loss);
-            if ((tid & 63) == 0) wl[tid >> 6] = loss;
-        }
-        if (kTile > 64) __syncthreads();
-        if (tid == 0) {
-            float tot = 0.f;
-#pragma unroll
-            for (int i = 0; i < kTile / 64; ++i) tot += wl[i];
-            row_loss[(int64_t)n * gridDim.x + blockIdx.x] = tot;
-        }
-    }
+    if (row_loss) store_tile_loss<kTile / 64>(loss, wl, row_loss + (int64_t)n * gridDim.x + blockIdx.x);
 }
 
 // dx = g * up * weight[l, :]: block (chunk, n) writes the contiguous kChunk * hw elements of channels [c0, c0 + kChunk) of RoI n.
@@ -161,49 +106,7 @@ __global__ void __launch_bounds__(256) mask_predict_dx_kernel(const float* __res
     }
 }
 
-// Rows of the weight gradient: block (chunk, n) stages g[n, :] * up once, 16 lanes per channel sum g x over the contiguous
-// pixels, a 16-lane butterfly folds them.  scratch[n, c] for c < cin, scratch[n, cin] = sum_p g (the bias gradient's row).
-template <typename T, int V>
-__global__ void __launch_bounds__(256) mask_predict_dw_rows_kernel(const T* __restrict__ x, const float* __restrict__ g,
-                                                                   const float* __restrict__ up, const int64_t* __restrict__ labels,
-                                                                   int C, int cin, int hw, float* __restrict__ scratch) {
-    __shared__ __attribute__((aligned(16))) float sg[kMaxHW];
-    const int n = blockIdx.y, c0 = blockIdx.x * kChunk, tid = threadIdx.x;
-    const int64_t lb = labels[n];
-    if (lb < 0 || lb >= C) return;                       // no class reads this RoI's row
-    const float u = up ? *up : 1.0f;
-    for (int p = tid; p < hw; p += 256) sg[p] = g[(int64_t)n * hw + p] * u;
-    __syncthreads();
-    const int c = c0 + (tid >> 4), l16 = tid & 15;
-    const int per = hw / V;
-    float acc = 0.f, gs = 0.f;
-    if (c < cin) {
-        const T* xp = x + ((int64_t)n * cin + c) * hw;
-#pragma unroll 4
-        for (int i = l16; i < per; i += 16) {
-            float v[V];
-            Row<T, V>::ld(xp + i * V, v);
-#pragma unroll
-            for (int j = 0; j < V; ++j) acc = fmaf(sg[i * V + j], v[j], acc);
-        }
-    }
-    if (blockIdx.x == 0)                                 // (block-uniform)
-        for (int i = l16; i < hw; i += 16) gs += sg[i];
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-        acc += __shfl_xor(acc, o, 64);
-        gs += __shfl_xor(gs, o, 64);
-    }
-    float* row = scratch + (int64_t)n * (cin + 1);
-    if (l16 == 0 && c < cin) row[c] = acc;
-    if (blockIdx.x == 0 && tid == 0) row[cin] = gs;
-}
-
-inline bool geometry_ok(int n, int c, int cin, int hw) {
-    return n >= 0 && n <= 65535 && c >= 1 && cin >= 1 && cin <= kMaxCin && hw >= 1 && hw <= kMaxHW;
-}
-// 4 elements per lane: every channel row starts on a 4-element boundary
-inline bool wide_ok(const void* p, int esz, int hw) { return hw % 4 == 0 && ((uintptr_t)p % (4 * (uintptr_t)esz)) == 0; }
+// dweight / dbias: mask_predict_dw_rows_kernel<T, V, false> and mask_predict_dw_classes_kernel of mask_predict_core.h.
 
 }  // namespace
 
@@ -212,7 +115,7 @@ extern "C" {
 int iif_mask_predict_fwd(const void* x, int dtype, const float* weight, int64_t ld_w, const float* bias, const int64_t* labels,
                          const float* target, int n, int c, int cin, int hw, float* z, float* g0, float* row_loss, float* loss,
                          int* status, void* stream) {
-    if (!geometry_ok(n, c, cin, hw) || ld_w < cin || (dtype != IIF_F32 && dtype != IIF_BF16)) return IIF_EINVAL;
+    if (!geometry_ok(n, c, cin, hw) || ld_w < cin || !dtype_ok(dtype)) return IIF_EINVAL;
     if (!x || !weight || !labels || !status || (!z && !target)) return IIF_EINVAL;
     if (target ? (!row_loss || !loss) : (g0 != nullptr)) return IIF_EINVAL;
     if (n == 0) return IIF_OK;
@@ -222,11 +125,11 @@ int iif_mask_predict_fwd(const void* x, int dtype, const float* weight, int64_t 
     const double invd = 1.0 / ((double)n * (double)hw);
     const float inv = (float)invd;
     float* rows = target ? row_loss : nullptr;
-#define IIF_MP_FWD(T, V) hipLaunchKernelGGL((mask_predict_fwd_kernel<T, V>), grid, dim3(256), 0, st, (const T*)x, weight, ld_w, bias, \
-                                            labels, target, c, cin, hw, inv, z, g0, rows, status)
-    if (dtype == IIF_F32) { if (wide_ok(x, 4, hw)) IIF_MP_FWD(float, 4); else IIF_MP_FWD(float, 1); }
-    else { if (wide_ok(x, 2, hw)) IIF_MP_FWD(unsigned short, 4); else IIF_MP_FWD(unsigned short, 1); }
-#undef IIF_MP_FWD
+    dispatch_row(dtype, wide_ok(x, dtype, hw), [&](auto t, auto v) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_predict_fwd_kernel<T, decltype(v)::value>), grid, dim3(256), 0, st, (const T*)x, weight, ld_w, bias,
+                           labels, target, c, cin, hw, inv, z, g0, rows, status);
+    });
     IIF_LAUNCH_CHECK();
     if (target) {
         hipLaunchKernelGGL(rows_reduce_kernel<double>, dim3(1), dim3(256), 0, st, row_loss, n * tiles, invd, loss);
@@ -237,32 +140,32 @@ int iif_mask_predict_fwd(const void* x, int dtype, const float* weight, int64_t 
 
 int iif_mask_predict_bwd_input(const float* g, const float* up, const float* weight, int64_t ld_w, const int64_t* labels, int n,
                                int c, int cin, int hw, void* dx, int dtype, void* stream) {
-    if (!geometry_ok(n, c, cin, hw) || ld_w < cin || (dtype != IIF_F32 && dtype != IIF_BF16)) return IIF_EINVAL;
+    if (!geometry_ok(n, c, cin, hw) || ld_w < cin || !dtype_ok(dtype)) return IIF_EINVAL;
     if (!g || !weight || !labels || !dx) return IIF_EINVAL;
     if (n == 0) return IIF_OK;
     hipStream_t st = as_stream(stream);
     const dim3 grid((cin + kChunk - 1) / kChunk, n);
-#define IIF_MP_DX(T, V) hipLaunchKernelGGL((mask_predict_dx_kernel<T, V>), grid, dim3(256), 0, st, g, up, weight, ld_w, labels, c, cin, \
-                                           hw, (T*)dx)
-    if (dtype == IIF_F32) { if (wide_ok(dx, 4, hw)) IIF_MP_DX(float, 4); else IIF_MP_DX(float, 1); }
-    else { if (wide_ok(dx, 2, hw)) IIF_MP_DX(unsigned short, 4); else IIF_MP_DX(unsigned short, 1); }
-#undef IIF_MP_DX
+    dispatch_row(dtype, wide_ok(dx, dtype, hw), [&](auto t, auto v) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_predict_dx_kernel<T, decltype(v)::value>), grid, dim3(256), 0, st, g, up, weight, ld_w, labels, c,
+                           cin, hw, (T*)dx);
+    });
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }
 
 int iif_mask_predict_bwd_weight(const void* x, int dtype, const float* g, const float* up, const int64_t* labels, int n, int c,
                                 int cin, int hw, float* scratch, float* dweight, float* dbias, void* stream) {
-    if (!geometry_ok(n, c, cin, hw) || (dtype != IIF_F32 && dtype != IIF_BF16)) return IIF_EINVAL;
+    if (!geometry_ok(n, c, cin, hw) || !dtype_ok(dtype)) return IIF_EINVAL;
     if (!x || !g || !labels || !scratch || (!dweight && !dbias)) return IIF_EINVAL;
     if (n == 0) return IIF_OK;
     hipStream_t st = as_stream(stream);
     const dim3 grid((cin + kChunk - 1) / kChunk, n);
-#define IIF_MP_DW(T, V) hipLaunchKernelGGL((mask_predict_dw_rows_kernel<T, V>), grid, dim3(256), 0, st, (const T*)x, g, up, labels, c, cin, \
-                                           hw, scratch)
-    if (dtype == IIF_F32) { if (wide_ok(x, 4, hw)) IIF_MP_DW(float, 4); else IIF_MP_DW(float, 1); }
-    else { if (wide_ok(x, 2, hw)) IIF_MP_DW(unsigned short, 4); else IIF_MP_DW(unsigned short, 1); }
-#undef IIF_MP_DW
+    dispatch_row(dtype, wide_ok(x, dtype, hw), [&](auto t, auto v) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_predict_dw_rows_kernel<T, decltype(v)::value, false>), grid, dim3(256), 0, st, (const T*)x, g,
+                           (const float*)nullptr, up, (const float*)nullptr, labels, c, cin, hw, scratch);
+    });
     IIF_LAUNCH_CHECK();
     hipLaunchKernelGGL(mask_predict_dw_classes_kernel, dim3(c), dim3(256), 0, st, scratch, labels, n, cin, dweight, dbias);
     IIF_LAUNCH_CHECK();

@@ -16,17 +16,18 @@
 //             g * weight[l, co] * sign; every element of df written once
 //   dup       block (64 ci, 128 columns, RoI range): [Ci][pixels] x [pixels][4 Co] with the same generated operand, one partial
 //             per RoI range, summed in range order; dup_bias from the column sums of the generated operand
-// dweight / dbias: the per-class segment sum of mask_class_rows.h on the rows.  No float atomics: the same bits from call to call.
+// dweight / dbias: the per-class segment sum of mask_predict_core.h on the rows.  No float atomics: the same bits from call to call.
 #include "common.h"
 #include "loss_reduce.h"
-#include "mask_class_rows.h"
+#include "mask_predict_core.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-constexpr int kMaxC = 1024, kMaxHW = 1024;   // Ci, Co; input pixels per RoI
+constexpr int kMaxC = 1024, kMaxInHW = 1024; // Ci, Co; input pixels per RoI
 constexpr int kPix = 64;                     // pixels per block: two 32-row MFMA tiles
+static_assert(kPix >= kMinTile, "the wrappers allocate one row partial per kMinTile pixels");
 constexpr int kCols = 128;                   // columns per chunk: one 32-column MFMA tile per wave; forward / rows: two chunks
 constexpr int kSlab = 32;                    // Ci values staged per round
 
@@ -172,16 +173,11 @@ __global__ void __launch_bounds__(256, 2) mask_tail_fwd_kernel(const T* __restri
         if (z) z[o] = s;
         if (target) {
             const float t = target[o];
-            loss = fmaxf(s, 0.f) - s * t + log1pf(expf(-fabsf(s)));
-            if (g0) g0[o] = (1.0f / (1.0f + expf(-s)) - t) * inv;
+            loss = bce_with_logits(s, t);
+            if (g0) g0[o] = (sigmoidf(s) - t) * inv;
         }
     }
-    if (row_loss) {
-        loss = wave_sum(loss);
-        if (lane == 0) wl[wave] = loss;
-        __syncthreads();
-        if (tid == 0) row_loss[(int64_t)n * gridDim.x + blockIdx.x] = ((wl[0] + wl[1]) + wl[2]) + wl[3];
-    }
+    if (row_loss) store_tile_loss<4>(loss, wl, row_loss + (int64_t)n * gridDim.x + blockIdx.x);
 }
 
 // g[n, :] * up of one RoI as sg[p][ab], zeros from pixel hw to pixel `fill`
@@ -203,7 +199,7 @@ __global__ void __launch_bounds__(256, 2) mask_tail_rows_kernel(const T* __restr
                                                              int ci, int co, int w, int hw, unsigned int* __restrict__ signs,
                                                              float* __restrict__ rows) {
     __shared__ float sA[kSlab * 64];
-    __shared__ float sg[kMaxHW * 4];
+    __shared__ float sg[kMaxInHW * 4];
     const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
     const int64_t lb = labels[n];
     if (lb < 0 || lb >= C) return;                       // g counts as zero there: neither the bits nor the row are read
@@ -343,7 +339,7 @@ __global__ void __launch_bounds__(256) mask_tail_dup_kernel(const T* __restrict_
                                                             int w, int hw, int per, float* __restrict__ partial,
                                                             float* __restrict__ colsum) {
     __shared__ float sA[64 * 65];
-    __shared__ float sg[kMaxHW * 4];
+    __shared__ float sg[kMaxInHW * 4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, li = lane & 31;
     const int ci0 = blockIdx.x * 64, sp = blockIdx.z, ld = 4 * co, nsub32 = (hw + 31) / 32;
     const int j = blockIdx.y * kCols + wave * 32 + li, cidx = j >> 2, ab = j & 3;
@@ -428,10 +424,8 @@ __global__ void __launch_bounds__(256) mask_tail_dup_sum_kernel(const float* __r
 }
 
 inline bool geometry_ok(int n, int c, int ci, int co, int h, int w) {
-    return n >= 0 && n <= 65535 && c >= 1 && ci >= 1 && ci <= kMaxC && co >= 1 && co <= kMaxC && h >= 1 && w >= 1 &&
-           (int64_t)h * w <= kMaxHW;
+    return rois_ok(n, c) && dim_ok(ci, kMaxC) && dim_ok(co, kMaxC) && h >= 1 && w >= 1 && (int64_t)h * w <= kMaxInHW;
 }
-inline bool dtype_ok(int dtype) { return dtype == IIF_F32 || dtype == IIF_BF16; }
 
 }  // namespace
 
@@ -449,10 +443,11 @@ int iif_mask_tail_fwd(const void* f, int dtype, const float* up_weight, const fl
     const dim3 grid(tiles, n);
     const double invd = 1.0 / ((double)n * 4.0 * (double)hw);
     float* rows = target ? row_loss : nullptr;
-#define IIF_MT_FWD(T) hipLaunchKernelGGL((mask_tail_fwd_kernel<T>), grid, dim3(256), 0, st, (const T*)f, up_weight, up_bias, weight, \
-                                         ld_w, bias, labels, target, c, ci, co, w, hw, (float)invd, z, g0, rows, status)
-    if (dtype == IIF_F32) IIF_MT_FWD(float); else IIF_MT_FWD(unsigned short);
-#undef IIF_MT_FWD
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_tail_fwd_kernel<T>), grid, dim3(256), 0, st, (const T*)f, up_weight, up_bias, weight, ld_w, bias,
+                           labels, target, c, ci, co, w, hw, (float)invd, z, g0, rows, status);
+    });
     IIF_LAUNCH_CHECK();
     if (target) {
         hipLaunchKernelGGL(rows_reduce_kernel<double>, dim3(1), dim3(256), 0, st, row_loss, n * tiles, invd, loss);
@@ -469,10 +464,11 @@ int iif_mask_tail_bwd_rows(const void* f, int dtype, const float* up_weight, con
     if (n == 0) return IIF_OK;
     hipStream_t st = as_stream(stream);
     const dim3 grid((4 * co + 2 * kCols - 1) / (2 * kCols), n);
-#define IIF_MT_ROWS(T) hipLaunchKernelGGL((mask_tail_rows_kernel<T>), grid, dim3(256), 0, st, (const T*)f, up_weight, up_bias, g, up, \
-                                          labels, c, ci, co, w, h * w, signs, rows)
-    if (dtype == IIF_F32) IIF_MT_ROWS(float); else IIF_MT_ROWS(unsigned short);
-#undef IIF_MT_ROWS
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_tail_rows_kernel<T>), grid, dim3(256), 0, st, (const T*)f, up_weight, up_bias, g, up, labels, c, ci,
+                           co, w, h * w, signs, rows);
+    });
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }
@@ -487,10 +483,11 @@ int iif_mask_tail_bwd_input(const float* g, const float* up, const float* up_wei
     hipStream_t st = as_stream(stream);
     const int hw = h * w;
     const dim3 grid((hw + kPix - 1) / kPix, n);
-#define IIF_MT_DF(T) hipLaunchKernelGGL((mask_tail_df_kernel<T>), grid, dim3(256), 0, st, g, up, up_weight, weight, ld_w, labels, signs, \
-                                        c, ci, co, w, hw, (T*)df)
-    if (dtype == IIF_F32) IIF_MT_DF(float); else IIF_MT_DF(unsigned short);
-#undef IIF_MT_DF
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_tail_df_kernel<T>), grid, dim3(256), 0, st, g, up, up_weight, weight, ld_w, labels, signs, c, ci, co,
+                           w, hw, (T*)df);
+    });
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }
@@ -515,10 +512,11 @@ int iif_mask_tail_bwd_params(const void* f, int dtype, const float* g, const flo
     const int splits = iif_mask_tail_splits(n, ci, co), per = (n + splits - 1) / splits;
     const dim3 grid((ci + 63) / 64, (4 * co + kCols - 1) / kCols, splits);
     float* colsum = partial + (int64_t)splits * ci * 4 * co;
-#define IIF_MT_DUP(T) hipLaunchKernelGGL((mask_tail_dup_kernel<T>), grid, dim3(256), 0, st, (const T*)f, g, up, weight, ld_w, labels, \
-                                         signs, n, c, ci, co, w, h * w, per, partial, colsum)
-    if (dtype == IIF_F32) IIF_MT_DUP(float); else IIF_MT_DUP(unsigned short);
-#undef IIF_MT_DUP
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_tail_dup_kernel<T>), grid, dim3(256), 0, st, (const T*)f, g, up, weight, ld_w, labels, signs, n, c,
+                           ci, co, w, h * w, per, partial, colsum);
+    });
     IIF_LAUNCH_CHECK();
     const int64_t total = (int64_t)ci * 4 * co + co;
     hipLaunchKernelGGL(mask_tail_dup_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, partial, colsum, splits, ci,
@@ -529,7 +527,7 @@ int iif_mask_tail_bwd_params(const void* f, int dtype, const float* g, const flo
 
 int iif_mask_tail_bwd_classes(const float* rows, const int64_t* labels, int n, int c, int co, float* dweight, float* dbias,
                               void* stream) {
-    if (n < 0 || n > 65535 || c < 1 || co < 1 || co > kMaxC) return IIF_EINVAL;
+    if (!rois_ok(n, c) || !dim_ok(co, kMaxC)) return IIF_EINVAL;
     if (!rows || !labels || (!dweight && !dbias)) return IIF_EINVAL;
     if (n == 0) return IIF_OK;
     hipLaunchKernelGGL(mask_predict_dw_classes_kernel, dim3(c), dim3(256), 0, as_stream(stream), rows, labels, n, co, dweight, dbias);

@@ -14,45 +14,9 @@
 // stored, nothing is read back.  power == 1 (every config) never calls powf.  x and dx are NCHW-contiguous, 4 elements per lane
 // where HW is a multiple of 4 and the base is aligned, one otherwise.
 #include "common.h"
+#include "mask_predict_core.h"
 
 namespace {
-
-constexpr int kTile = 128;         // pixels per forward block, as mask_predictor.hip
-static_assert(kTile == 64 || kTile == 128 || kTile == 256, "whole waves of pixels, at most the block");
-constexpr int kChunk = 16;         // channels per block of the dx and dweight passes
-constexpr int kMaxHW = 4096, kMaxCin = 2048;
-
-// V consecutive elements of a channel row as floats (the loaders of mask_predictor.hip, which stays as it is)
-template <typename T, int V> struct Row;
-template <> struct Row<float, 1> {
-    static __device__ __forceinline__ void ld(const float* p, float (&v)[1]) { v[0] = *p; }
-    static __device__ __forceinline__ void st(float* p, const float (&v)[1]) { *p = v[0]; }
-};
-template <> struct Row<float, 4> {
-    static __device__ __forceinline__ void ld(const float* p, float (&v)[4]) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-        v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
-    }
-    static __device__ __forceinline__ void st(float* p, const float (&v)[4]) {
-        f32x4 q; q[0] = v[0]; q[1] = v[1]; q[2] = v[2]; q[3] = v[3];
-        *reinterpret_cast<f32x4*>(p) = q;
-    }
-};
-template <> struct Row<unsigned short, 1> {
-    static __device__ __forceinline__ void ld(const unsigned short* p, float (&v)[1]) { v[0] = bf16_bits_to_f32(*p); }
-    static __device__ __forceinline__ void st(unsigned short* p, const float (&v)[1]) { *p = f32_to_bf16_bits(v[0]); }
-};
-template <> struct Row<unsigned short, 4> {
-    static __device__ __forceinline__ void ld(const unsigned short* p, float (&v)[4]) {
-        const u32x2 q = *reinterpret_cast<const u32x2*>(p);
-        v[0] = bf16_bits_to_f32(q[0] & 0xffffu); v[1] = __uint_as_float(q[0] & 0xffff0000u);
-        v[2] = bf16_bits_to_f32(q[1] & 0xffffu); v[3] = __uint_as_float(q[1] & 0xffff0000u);
-    }
-    static __device__ __forceinline__ void st(unsigned short* p, const float (&v)[4]) {
-        u32x2 q; q[0] = pack_bf16x2(v[0], v[1]); q[1] = pack_bf16x2(v[2], v[3]);
-        *reinterpret_cast<u32x2*>(p) = q;
-    }
-};
 
 // v^q; power == 1 takes the path without powf
 __device__ __forceinline__ float powq(float v, float q) { return q == 1.0f ? v : powf(v, q); }
@@ -60,22 +24,6 @@ __device__ __forceinline__ float powq(float v, float q) { return q == 1.0f ? v :
 __device__ __forceinline__ float back_coef(float d, float v, float q, float eps) {
     const float den = powq(v, q) + eps;
     return q == 1.0f ? (d / v) / (den * den) : d * q * powf(v, q - 2.0f) / (den * den);
-}
-
-// Sum over the 256 threads of a block in a fixed order (butterfly inside a wave, the four waves in index order); every thread
-// gets the sum.  red: 4 floats of LDS that nothing else uses until the next barrier after the call.
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-// |row|^2 of cin floats: thread t adds the squares of elements t, t + 256, ..., then block_sum.  The forward, the dx pass and
-// the per-class pass all use this one order, so they agree on rho to the bit.
-__device__ __forceinline__ float block_sumsq(const float* row, int cin, float* red) {
-    float s = 0.f;
-    for (int c = threadIdx.x; c < cin; c += 256) { const float w = row[c]; s = fmaf(w, w, s); }
-    return block_sum(s, red);
 }
 
 // Forward: block (tile, n) owns kTile pixels of RoI n, as mask_predict_fwd_kernel; each channel group carries sum w x AND
@@ -105,9 +53,7 @@ __global__ void __launch_bounds__(256) normed_predict_fwd_kernel(const T* __rest
         }
         return;
     }
-    const float* wrow = weight + lb * ld_w;
-    for (int c = tid; c < cin; c += 256) sw[c] = wrow[c];
-    __syncthreads();
+    stage_weight_row(weight + lb * ld_w, cin, sw);
     const float rho = sqrtf(block_sumsq(sw, cin, red));
     const float s_w = 1.0f / (powq(rho, q) + eps);
     const int grp = tid / LPG, pl = (tid % LPG) * V;     // pixel offset of this lane inside the tile
@@ -136,14 +82,8 @@ __global__ void __launch_bounds__(256) normed_predict_fwd_kernel(const T* __rest
     __syncthreads();
     float loss = 0.f;
     if (tid < kTile && p0 + tid < hw) {
-        float d = 0.f, r2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-            d += part[0][k][tid];
-            r2 += part[1][k][tid];
-        }
-        d *= s_w;
-        const float r = sqrtf(r2);
+        const float d = fold_groups(part[0], tid) * s_w;
+        const float r = sqrtf(fold_groups(part[1], tid));
         const float s_x = temp / (powq(r, q) + eps);
         float s = s_x * d;
         if (bias) s += bias[lb];
@@ -153,23 +93,11 @@ __global__ void __launch_bounds__(256) normed_predict_fwd_kernel(const T* __rest
         if (cb) cb[o] = r > 0.f ? temp * back_coef(d, r, q, eps) : 0.f;
         if (target) {
             const float t = target[o];
-            loss = fmaxf(s, 0.f) - s * t + log1pf(expf(-fabsf(s)));
-            if (g) g[o] = 1.0f / (1.0f + expf(-s)) - t;
+            loss = bce_with_logits(s, t);
+            if (g) g[o] = sigmoidf(s) - t;
         }
     }
-    if (row_loss) {                                      // the tile is the first kTile / 64 waves
-        if (tid < kTile) {
-            loss = wave_sum(loss);
-            if ((tid & 63) == 0) wl[tid >> 6] = loss;
-        }
-        if (kTile > 64) __syncthreads();
-        if (tid == 0) {
-            float tot = 0.f;
-#pragma unroll
-            for (int i = 0; i < kTile / 64; ++i) tot += wl[i];
-            row_loss[(int64_t)n * gridDim.x + blockIdx.x] = tot;
-        }
-    }
+    if (row_loss) store_tile_loss<kTile / 64>(loss, wl, row_loss + (int64_t)n * gridDim.x + blockIdx.x);
 }
 
 // One block: the row partials summed in double in a fixed order, the divisor - n hw, or with valid_rows max(1, #{labels in
@@ -254,54 +182,10 @@ __global__ void __launch_bounds__(256) normed_predict_dx_kernel(const T* __restr
     }
 }
 
-// Rows of the weight gradient: block (chunk, n) stages u g A of its RoI once, 16 lanes per channel sum it against x over the
-// contiguous pixels, a 16-lane butterfly folds them.  scratch[n, c] for c < cin; scratch[n, cin] = u sum_p g (without A).
-template <typename T, int V>
-__global__ void __launch_bounds__(256) normed_predict_dw_rows_kernel(const T* __restrict__ x, const float* __restrict__ g,
-                                                                     const float* __restrict__ ca, const float* __restrict__ up,
-                                                                     const float* __restrict__ inv_div,
-                                                                     const int64_t* __restrict__ labels, int C, int cin, int hw,
-                                                                     float* __restrict__ scratch) {
-    __shared__ __attribute__((aligned(16))) float sg[kMaxHW];
-    __shared__ float s0[kMaxHW];
-    const int n = blockIdx.y, c0 = blockIdx.x * kChunk, tid = threadIdx.x;
-    const int64_t lb = labels[n];
-    if (lb < 0 || lb >= C) return;                       // no class reads this RoI's row
-    const float u = (up ? *up : 1.0f) * (inv_div ? *inv_div : 1.0f);
-    for (int p = tid; p < hw; p += 256) {
-        const int64_t o = (int64_t)n * hw + p;
-        const float gu = g[o] * u;
-        sg[p] = gu * ca[o];
-        if (blockIdx.x == 0) s0[p] = gu;
-    }
-    __syncthreads();
-    const int c = c0 + (tid >> 4), l16 = tid & 15;
-    const int per = hw / V;
-    float acc = 0.f, gs = 0.f;
-    if (c < cin) {
-        const T* xp = x + ((int64_t)n * cin + c) * hw;
-#pragma unroll 4
-        for (int i = l16; i < per; i += 16) {
-            float v[V];
-            Row<T, V>::ld(xp + i * V, v);
-#pragma unroll
-            for (int j = 0; j < V; ++j) acc = fmaf(sg[i * V + j], v[j], acc);
-        }
-    }
-    if (blockIdx.x == 0)                                 // (block-uniform)
-        for (int i = l16; i < hw; i += 16) gs += s0[i];
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-        acc += __shfl_xor(acc, o, 64);
-        gs += __shfl_xor(gs, o, 64);
-    }
-    float* row = scratch + (int64_t)n * (cin + 1);
-    if (l16 == 0 && c < cin) row[c] = acc;
-    if (blockIdx.x == 0 && tid == 0) row[cin] = gs;
-}
+// The per-RoI rows of the weight gradient: mask_predict_dw_rows_kernel<T, V, true> of mask_predict_core.h.
 
-// One block per class k: the ascending list of the class's RoIs (ballot and prefix count over the labels, 2048 at a time, as
-// mask_predict_dw_classes_kernel), dwhat[k] = the sum of their scratch rows in list order, kept in LDS, then
+// One block per class k: the ascending list of the class's RoIs (class_roi_list, 2048 labels at a time; pieces outside columns,
+// so every list is built once), dwhat[k] = the sum of their scratch rows in list order (add_listed_rows), kept in LDS, then
 //   dweight[k] = s_w dwhat - (<dwhat, w[k]> q rho^(q-2) / (rho^q + eps)^2) w[k]      (no second term where rho == 0)
 // and dbias[k] = the sum of column cin.  A class no RoI has gets zeros without a look at its weights.
 __global__ void __launch_bounds__(256) normed_predict_dw_classes_kernel(const float* __restrict__ scratch,
@@ -309,45 +193,17 @@ __global__ void __launch_bounds__(256) normed_predict_dw_classes_kernel(const fl
                                                                         const float* __restrict__ weight, int64_t ld_w, int n,
                                                                         int cin, float q, float eps, float* __restrict__ dweight,
                                                                         float* __restrict__ dbias) {
-    constexpr int kPiece = 2048;
     __shared__ int list[kPiece];
     __shared__ int wcnt[4];
     __shared__ float dwh[kMaxCin + 1];
     __shared__ float red[2][4];
-    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, ld = cin + 1;
+    const int k = blockIdx.x, tid = threadIdx.x, ld = cin + 1;
     for (int col = tid; col < ld; col += 256) dwh[col] = 0.f;    // each thread owns its columns: no barrier needed for dwh
     int total = 0;                                       // block-uniform
     for (int n0 = 0; n0 < n; n0 += kPiece) {
-        const int m = min(kPiece, n - n0);
-        int cnt = 0;                                     // block-uniform
-        for (int i0 = 0; i0 < m; i0 += 256) {
-            const int i = i0 + tid;
-            const bool hit = i < m && labels[n0 + i] == k;
-            const unsigned long long b = __ballot(hit);
-            __syncthreads();                             // the previous round's wcnt (and, first round, the previous list) is read
-            if (lane == 0) wcnt[wv] = __popcll(b);
-            __syncthreads();
-            int off = cnt;
-            for (int w = 0; w < wv; ++w) off += wcnt[w];
-            if (hit) list[off + __popcll(b & ((1ull << lane) - 1ull))] = n0 + i;
-            cnt += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        }
-        __syncthreads();
+        const int cnt = class_roi_list(labels, n0, min(kPiece, n - n0), k, list, wcnt);
         total += cnt;
-        for (int col = tid; col < ld; col += 256) {
-            const float* sc = scratch + col;
-            float acc = dwh[col];
-            int j = 0;
-            for (; j + 8 <= cnt; j += 8) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = sc[(int64_t)list[j + u] * ld];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc += v[u];
-            }
-            for (; j < cnt; ++j) acc += sc[(int64_t)list[j] * ld];
-            dwh[col] = acc;
-        }
+        for (int col = tid; col < ld; col += 256) dwh[col] = add_listed_rows(scratch + col, ld, list, cnt, dwh[col]);
     }
     if (dbias && tid == (cin & 255)) dbias[k] = total ? dwh[cin] : 0.f;      // the owner of column cin
     if (!dweight) return;
@@ -365,13 +221,6 @@ __global__ void __launch_bounds__(256) normed_predict_dw_classes_kernel(const fl
     for (int col = tid; col < cin; col += 256) dweight[(int64_t)k * cin + col] = fmaf(-coef, wrow[col], s_w * dwh[col]);
 }
 
-inline bool geometry_ok(int n, int c, int cin, int hw) {
-    return n >= 0 && n <= 65535 && c >= 1 && cin >= 1 && cin <= kMaxCin && hw >= 1 && hw <= kMaxHW;
-}
-inline bool dtype_ok(int dtype) { return dtype == IIF_F32 || dtype == IIF_BF16; }
-// 4 elements per lane: every channel row starts on a 4-element boundary
-inline bool wide_ok(const void* p, int esz, int hw) { return hw % 4 == 0 && ((uintptr_t)p % (4 * (uintptr_t)esz)) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -388,11 +237,11 @@ int iif_normed_mask_predict_fwd(const void* x, int dtype, const float* weight, i
     const int tiles = (hw + kTile - 1) / kTile;
     const dim3 grid(tiles, n);
     float* rows = target ? row_loss : nullptr;
-#define IIF_NMP_FWD(T, V) hipLaunchKernelGGL((normed_predict_fwd_kernel<T, V>), grid, dim3(256), 0, st, (const T*)x, weight, ld_w, bias, \
-                                             labels, target, c, cin, hw, temperature, power, eps, z, g, coef_a, coef_b, rows)
-    if (dtype == IIF_F32) { if (wide_ok(x, 4, hw)) IIF_NMP_FWD(float, 4); else IIF_NMP_FWD(float, 1); }
-    else { if (wide_ok(x, 2, hw)) IIF_NMP_FWD(unsigned short, 4); else IIF_NMP_FWD(unsigned short, 1); }
-#undef IIF_NMP_FWD
+    dispatch_row(dtype, wide_ok(x, dtype, hw), [&](auto t, auto v) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((normed_predict_fwd_kernel<T, decltype(v)::value>), grid, dim3(256), 0, st, (const T*)x, weight, ld_w, bias,
+                           labels, target, c, cin, hw, temperature, power, eps, z, g, coef_a, coef_b, rows);
+    });
     IIF_LAUNCH_CHECK();
     if (target) {
         hipLaunchKernelGGL(normed_predict_finish_kernel, dim3(1), dim3(256), 0, st, row_loss, n * tiles, labels, n, c, hw,
@@ -411,11 +260,11 @@ int iif_normed_mask_predict_bwd_input(const void* x, int dtype, const float* g, 
     if (n == 0) return IIF_OK;
     hipStream_t st = as_stream(stream);
     const dim3 grid((cin + kChunk - 1) / kChunk, n);
-#define IIF_NMP_DX(T, V) hipLaunchKernelGGL((normed_predict_dx_kernel<T, V>), grid, dim3(256), 0, st, (const T*)x, g, coef_a, coef_b, up, \
-                                            inv_div, weight, ld_w, labels, c, cin, hw, power, eps, (T*)dx)
-    if (dtype == IIF_F32) { if (wide_ok(x, 4, hw) && wide_ok(dx, 4, hw)) IIF_NMP_DX(float, 4); else IIF_NMP_DX(float, 1); }
-    else { if (wide_ok(x, 2, hw) && wide_ok(dx, 2, hw)) IIF_NMP_DX(unsigned short, 4); else IIF_NMP_DX(unsigned short, 1); }
-#undef IIF_NMP_DX
+    dispatch_row(dtype, wide_ok(x, dtype, hw) && wide_ok(dx, dtype, hw), [&](auto t, auto v) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((normed_predict_dx_kernel<T, decltype(v)::value>), grid, dim3(256), 0, st, (const T*)x, g, coef_a, coef_b,
+                           up, inv_div, weight, ld_w, labels, c, cin, hw, power, eps, (T*)dx);
+    });
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }
@@ -429,11 +278,11 @@ int iif_normed_mask_predict_bwd_weight(const void* x, int dtype, const float* g,
     if (n == 0) return IIF_OK;
     hipStream_t st = as_stream(stream);
     const dim3 grid((cin + kChunk - 1) / kChunk, n);
-#define IIF_NMP_DW(T, V) hipLaunchKernelGGL((normed_predict_dw_rows_kernel<T, V>), grid, dim3(256), 0, st, (const T*)x, g, coef_a, up, \
-                                            inv_div, labels, c, cin, hw, scratch)
-    if (dtype == IIF_F32) { if (wide_ok(x, 4, hw)) IIF_NMP_DW(float, 4); else IIF_NMP_DW(float, 1); }
-    else { if (wide_ok(x, 2, hw)) IIF_NMP_DW(unsigned short, 4); else IIF_NMP_DW(unsigned short, 1); }
-#undef IIF_NMP_DW
+    dispatch_row(dtype, wide_ok(x, dtype, hw), [&](auto t, auto v) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_predict_dw_rows_kernel<T, decltype(v)::value, true>), grid, dim3(256), 0, st, (const T*)x, g, coef_a,
+                           up, inv_div, labels, c, cin, hw, scratch);
+    });
     IIF_LAUNCH_CHECK();
     hipLaunchKernelGGL(normed_predict_dw_classes_kernel, dim3(c), dim3(256), 0, st, scratch, labels, weight, ld_w, n, cin, power, eps,
                        dweight, dbias);

@@ -31,7 +31,11 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 
-_MAX_CIN, _MAX_HW, _MAX_N, _TILE = 2048, 4096, 65535, 64
+_MAX_CIN, _MAX_HW, _MAX_N = 2048, 4096, 65535
+# Pixels per row partial of the loss: the SMALLEST tile any forward kernel of the family may use (kMinTile in
+# csrc/mask_predict_core.h, which checks kTile = 128 and the tail's kPix = 64 against it), so n * ceil(hw / _TILE) floats are an
+# upper bound of what a forward writes.
+_TILE = 64
 
 
 def _prep(x, weight, bias, labels):
@@ -104,6 +108,38 @@ def _up(g):
     return g.detach().reshape(1).to(torch.float32).contiguous()
 
 
+def _needs(*tensors):
+    """Which of the tensors (None allowed) ask for a gradient."""
+    return tuple(t is not None and t.requires_grad for t in tensors)
+
+
+def _is_empty(x):
+    """N == 0: no kernel runs; the callers check the other arguments and return _empty_result."""
+    return isinstance(x, torch.Tensor) and x.dim() == 4 and x.size(0) == 0
+
+
+def _empty_result(x, params, shape):
+    """N == 0: a zero of `shape` that is still connected to x and every parameter (the reference returns mask_pred.sum())."""
+    z = x.sum().float()
+    for p in params:
+        if p is not None:
+            z = z + p.sum() * 0
+    return z * x.new_zeros(shape, dtype=torch.float32) if 0 in shape else z.reshape(shape)
+
+
+def _copy_params(dst, src):
+    """weight and bias of src into dst, bit for bit; a bias src does not have leaves dst's as it is."""
+    with torch.no_grad():
+        dst.weight.copy_(src.weight)
+        if src.bias is not None:
+            dst.bias.copy_(src.bias)
+
+
+def _is_plain_1x1(conv):
+    return conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1 \
+        and conv.dilation == (1, 1)
+
+
 class _Logits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, labels, wshape):
@@ -113,8 +149,8 @@ class _Logits(torch.autograd.Function):
         _lib.check(_lib.lib().iif_mask_predict_fwd(_lib.ptr(xc), _lib.dtype_code(xc), _lib.ptr(w2), _ld(w2), _lib.ptr(b), _lib.ptr(lb), 0,
                                                    n, c, cin, hw, _lib.ptr(z), 0, 0, 0, _lib.ptr(status), _lib.stream_ptr()),
                    "iif_mask_predict_fwd")
-        need_wb = weight.requires_grad or (bias is not None and bias.requires_grad)
-        ctx.save_for_backward(xc if need_wb else None, w2 if x.requires_grad else None, lb)
+        need_x, need_w, need_b = _needs(x, weight, bias)
+        ctx.save_for_backward(xc if need_w or need_b else None, w2 if need_x else None, lb)
         ctx.dims = (n, c, cin, hw, (tuple(x.shape), x.dtype), wshape)
         return z
 
@@ -138,16 +174,15 @@ class _Loss(torch.autograd.Function):
         _lib.require_gpu(targets)
         t = targets.detach().reshape(n, hw).to(torch.float32).contiguous()
         dev = xc.device
-        need = x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)
+        need_x, need_w, need_b = _needs(x, weight, bias)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         rows = torch.empty(n * ((hw + _TILE - 1) // _TILE), dtype=torch.float32, device=dev)
-        g0 = torch.empty((n, hw), dtype=torch.float32, device=dev) if need else None
+        g0 = torch.empty((n, hw), dtype=torch.float32, device=dev) if need_x or need_w or need_b else None
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         _lib.check(_lib.lib().iif_mask_predict_fwd(_lib.ptr(xc), _lib.dtype_code(xc), _lib.ptr(w2), _ld(w2), _lib.ptr(b), _lib.ptr(lb),
                                                    _lib.ptr(t), n, c, cin, hw, 0, _lib.ptr(g0), _lib.ptr(rows), _lib.ptr(loss),
                                                    _lib.ptr(status), _lib.stream_ptr()), "iif_mask_predict_fwd")
-        need_wb = weight.requires_grad or (bias is not None and bias.requires_grad)
-        ctx.save_for_backward(xc if need_wb else None, w2 if x.requires_grad else None, lb, g0)
+        ctx.save_for_backward(xc if need_w or need_b else None, w2 if need_x else None, lb, g0)
         ctx.dims = (n, c, cin, hw, (tuple(x.shape), x.dtype), wshape)
         return loss
 
@@ -163,22 +198,14 @@ class _Loss(torch.autograd.Function):
         return dx, None if dw is None else dw.reshape(wshape), db, None, None, None
 
 
-def _empty_result(x, weight, bias, shape):
-    """N == 0: a zero of `shape` that is still connected to x, weight and bias (the reference returns mask_pred.sum())."""
-    z = x.sum().float() + weight.sum() * 0
-    if bias is not None:
-        z = z + bias.sum() * 0
-    return z * x.new_zeros(shape, dtype=torch.float32) if 0 in shape else z.reshape(shape)
-
-
 def class_mask_logits(x, weight, bias, labels):
     """``conv_logits(x)[range(N), labels][:, None]`` -> ``[N, 1, H, W]`` float32 without the other channels.  ``x [N, Cin, H, W]``
     float32 / bfloat16; ``weight [C, Cin]`` or ``[C, Cin, 1, 1]`` float32; ``bias [C]`` float32 or ``None``; ``labels [N]``
     integer.  Differentiable in ``x``, ``weight`` and ``bias`` (not twice).  A non-contiguous or ``channels_last`` ``x`` costs one
     layout copy."""
-    if isinstance(x, torch.Tensor) and x.dim() == 4 and x.size(0) == 0:
+    if _is_empty(x):
         _prep(x, weight, bias, labels)
-        return _empty_result(x, weight, bias, (0, 1) + tuple(x.shape[2:]))
+        return _empty_result(x, (weight, bias), (0, 1) + tuple(x.shape[2:]))
     return _Logits.apply(x, weight, bias, labels, tuple(weight.shape))
 
 
@@ -189,17 +216,16 @@ def class_mask_loss(x, weight, bias, labels, targets):
     is computed and stored; the upstream gradient is applied on the device.  ``targets [N, H, W]``.  ``N == 0``: a zero connected
     to ``x``, ``weight`` and ``bias`` (the reference's ``mask_pred.sum()``).  A non-contiguous or ``channels_last`` ``x`` costs one
     layout copy."""
-    if isinstance(x, torch.Tensor) and x.dim() == 4 and x.size(0) == 0:
+    if _is_empty(x):
         _prep(x, weight, bias, labels)
-        return _empty_result(x, weight, bias, (1,))
+        return _empty_result(x, (weight, bias), (1,))
     return _Loss.apply(x, weight, bias, labels, targets, tuple(weight.shape))
 
 
-class ClassSelectedMaskPredictor(nn.Module):
-    """Stands where ``FCNMaskHead.conv_logits`` stood (fcn_mask_head.py:106-111, ``predictor_cfg=dict(type='Conv')``): the same
-    parameters - ``weight [C, Cin, 1, 1]``, ``bias [C]``, ``C = 1`` for a ``class_agnostic`` head - under the same ``state_dict``
-    keys as ``nn.Conv2d(Cin, C, 1)``, so a reference checkpoint's ``mask_head.conv_logits.*`` loads unchanged, and the
-    reference's initialisation (``kaiming_normal_(mode='fan_out', nonlinearity='relu')``, zero bias, fcn_mask_head.py:123-125)."""
+class _SelectedPredictor(nn.Module):
+    """What the class-selected predictor modules share: ``weight [C, Cin, 1, 1]`` and ``bias [C]`` (``C = 1`` for a
+    ``class_agnostic`` head) with the initialisation ``FCNMaskHead.init_weights`` gives ``conv_logits``, the label mapping of the
+    ``class_agnostic`` head, and the two ends of ``from_conv`` / ``to_conv``."""
 
     def __init__(self, in_channels, num_classes, class_agnostic=False):
         super().__init__()
@@ -214,7 +240,29 @@ class ClassSelectedMaskPredictor(nn.Module):
         nn.init.constant_(self.bias, 0)
 
     def _labels(self, labels):
+        """The weight row of each RoI: its label, or row 0 of a ``class_agnostic`` head."""
         return torch.zeros_like(labels) if self.class_agnostic else labels
+
+    @classmethod
+    def _from_conv(cls, conv, class_agnostic, **kwargs):
+        """A module of conv's shape, device and dtype with conv's parameters."""
+        agnostic = conv.out_channels == 1 if class_agnostic is None else class_agnostic
+        m = cls(conv.in_channels, conv.out_channels, class_agnostic=agnostic, **kwargs)
+        m.to(device=conv.weight.device, dtype=conv.weight.dtype)
+        _copy_params(m, conv)
+        return m
+
+    def _into_conv(self, conv):
+        conv.to(device=self.weight.device, dtype=self.weight.dtype)
+        _copy_params(conv, self)
+        return conv
+
+
+class ClassSelectedMaskPredictor(_SelectedPredictor):
+    """Stands where ``FCNMaskHead.conv_logits`` stood (fcn_mask_head.py:106-111, ``predictor_cfg=dict(type='Conv')``): the same
+    parameters - ``weight [C, Cin, 1, 1]``, ``bias [C]``, ``C = 1`` for a ``class_agnostic`` head - under the same ``state_dict``
+    keys as ``nn.Conv2d(Cin, C, 1)``, so a reference checkpoint's ``mask_head.conv_logits.*`` loads unchanged, and the
+    reference's initialisation (``kaiming_normal_(mode='fan_out', nonlinearity='relu')``, zero bias, fcn_mask_head.py:123-125)."""
 
     def forward(self, x, labels):
         """The selected logits ``[N, 1, H, W]``: ``pos_labels`` in training, ``det_labels`` at test time."""
@@ -227,26 +275,13 @@ class ClassSelectedMaskPredictor(nn.Module):
     @classmethod
     def from_conv(cls, conv, class_agnostic=None):
         """From the reference head's ``conv_logits``; the parameters are copied bit for bit."""
-        if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.padding != (0, 0) \
-                or conv.groups != 1 or conv.dilation != (1, 1):
+        if not isinstance(conv, nn.Conv2d) or not _is_plain_1x1(conv):
             raise NotImplementedError("a plain 1x1 nn.Conv2d expected")
-        agnostic = conv.out_channels == 1 if class_agnostic is None else class_agnostic
-        m = cls(conv.in_channels, conv.out_channels, class_agnostic=agnostic)
-        m.to(device=conv.weight.device, dtype=conv.weight.dtype)
-        with torch.no_grad():
-            m.weight.copy_(conv.weight)
-            if conv.bias is not None:
-                m.bias.copy_(conv.bias)
-        return m
+        return cls._from_conv(conv, class_agnostic)
 
     def to_conv(self):
         """The ``nn.Conv2d`` with these parameters: the full ``[N, C, H, W]`` logits for whoever needs them."""
-        conv = nn.Conv2d(self.in_channels, self.weight.size(0), 1)
-        conv.to(device=self.weight.device, dtype=self.weight.dtype)
-        with torch.no_grad():
-            conv.weight.copy_(self.weight)
-            conv.bias.copy_(self.bias)
-        return conv
+        return self._into_conv(nn.Conv2d(self.in_channels, self.weight.size(0), 1))
 
     def extra_repr(self):
         return "in_channels=%d, num_classes=%d, class_agnostic=%s" % (self.in_channels, self.num_classes, self.class_agnostic)

@@ -36,9 +36,9 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .mmdet_mask_predictor import _ld, _up
+from .mmdet_mask_predictor import _TILE, _copy_params, _empty_result, _is_empty, _is_plain_1x1, _ld, _needs, _up
 
-_MAX_C, _MAX_HW, _MAX_N, _TILE = 1024, 1024, 65535, 64
+_MAX_C, _MAX_HW, _MAX_N = 1024, 1024, 65535
 
 
 def _prep(f, up_weight, up_bias, weight, bias, labels):
@@ -155,24 +155,19 @@ def _det(t):
     return None if t is None else t.detach()
 
 
-def _needs(ctx, up_bias, bias):
-    nf, nuw, nub, nw, nb = ctx.needs_input_grad[:5]
-    return nf, nuw, nub and up_bias, nw, nb and bias
-
-
 class _Logits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, f, up_weight, up_bias, weight, bias, labels, wshape):
         saved, dims, z, _ = _forward(f.detach(), up_weight.detach(), _det(up_bias), weight.detach(), _det(bias), labels, None, False)
         ctx.save_for_backward(*saved)
-        ctx.meta = (dims, wshape, up_bias is not None, bias is not None)
+        ctx.meta = (dims, wshape)
         return z
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gz):
-        dims, wshape, has_ub, has_b = ctx.meta
-        needs = _needs(ctx, has_ub, has_b)
+        dims, wshape = ctx.meta
+        needs = ctx.needs_input_grad[:5]                 # (False for a bias that is None)
         if not any(needs):
             return (None,) * 7
         n, hw4 = dims[0], 4 * dims[4] * dims[5]
@@ -184,37 +179,24 @@ class _Logits(torch.autograd.Function):
 class _Loss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, f, up_weight, up_bias, weight, bias, labels, targets, wshape):
-        need = any(t is not None and t.requires_grad for t in (f, up_weight, up_bias, weight, bias))
+        need = any(_needs(f, up_weight, up_bias, weight, bias))
         saved, dims, loss, g0 = _forward(f.detach(), up_weight.detach(), _det(up_bias), weight.detach(), _det(bias), labels, targets,
                                          need)
         if need:
             ctx.save_for_backward(*saved, g0)
-        ctx.meta = (dims, wshape, up_bias is not None, bias is not None, need)
+        ctx.meta = (dims, wshape, need)
         return loss
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gl):
-        dims, wshape, has_ub, has_b, need = ctx.meta
-        needs = _needs(ctx, has_ub, has_b)
+        dims, wshape, need = ctx.meta
+        needs = ctx.needs_input_grad[:5]                 # (False for a bias that is None)
         if not need or not any(needs):
             return (None,) * 8
         *saved, g0 = ctx.saved_tensors
         df, duw, dub, dw, db = _backward(saved, dims, g0, _up(gl), needs)
         return df, duw, dub, None if dw is None else dw.reshape(wshape), db, None, None, None
-
-
-def _empty_result(f, params, shape):
-    """N == 0: a zero of `shape` that is still connected to every input (the reference returns mask_pred.sum())."""
-    z = f.sum().float()
-    for p in params:
-        if p is not None:
-            z = z + p.sum() * 0
-    return z * f.new_zeros(shape, dtype=torch.float32) if 0 in shape else z.reshape(shape)
-
-
-def _is_empty(f):
-    return isinstance(f, torch.Tensor) and f.dim() == 4 and f.size(0) == 0
 
 
 def upsampled_class_mask_logits(f, up_weight, up_bias, weight, bias, labels):
@@ -289,30 +271,24 @@ class FusedMaskHeadTail(nn.Module):
         if not isinstance(u, nn.ConvTranspose2d) or u.kernel_size != (2, 2) or u.stride != (2, 2) or u.padding != (0, 0) \
                 or u.output_padding != (0, 0) or u.groups != 1 or u.dilation != (1, 1):
             raise NotImplementedError("a 2x2 / stride-2 / no-padding nn.ConvTranspose2d expected")
-        if not isinstance(c, nn.Conv2d) or c.kernel_size != (1, 1) or c.stride != (1, 1) or c.padding != (0, 0) or c.groups != 1 \
-                or c.dilation != (1, 1):
+        if not isinstance(c, nn.Conv2d) or not _is_plain_1x1(c):
             raise NotImplementedError("a plain 1x1 nn.Conv2d expected")
         if c.in_channels != u.out_channels:
             raise ValueError("conv_logits takes %d channels, upsample gives %d" % (c.in_channels, u.out_channels))
         agnostic = c.out_channels == 1 if class_agnostic is None else class_agnostic
         m = cls(u.in_channels, u.out_channels, c.out_channels, class_agnostic=agnostic)
         m.to(device=c.weight.device, dtype=c.weight.dtype)
-        with torch.no_grad():
-            for dst, src in ((m.upsample, u), (m.conv_logits, c)):
-                dst.weight.copy_(src.weight)
-                if src.bias is not None:
-                    dst.bias.copy_(src.bias)
+        _copy_params(m.upsample, u)
+        _copy_params(m.conv_logits, c)
         return m
 
     def to_modules(self):
         """``(nn.ConvTranspose2d, nn.Conv2d)`` with these parameters: the composed path for whoever needs it."""
         u = nn.ConvTranspose2d(self.in_channels, self.conv_out_channels, 2, stride=2)
         c = nn.Conv2d(self.conv_out_channels, self.conv_logits.weight.size(0), 1)
-        with torch.no_grad():
-            for dst, src in ((u, self.upsample), (c, self.conv_logits)):
-                dst.to(device=src.weight.device, dtype=src.weight.dtype)
-                dst.weight.copy_(src.weight)
-                dst.bias.copy_(src.bias)
+        for dst, src in ((u, self.upsample), (c, self.conv_logits)):
+            dst.to(device=src.weight.device, dtype=src.weight.dtype)
+            _copy_params(dst, src)
         return u, c
 
     def extra_repr(self):

@@ -32,7 +32,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .mmdet_mask_predictor import _TILE, _empty_result, _ld, _prep, _up
+from .mmdet_mask_predictor import _TILE, _SelectedPredictor, _empty_result, _is_empty, _is_plain_1x1, _ld, _needs, _prep, _up
 
 
 def _cfg(tempearture, power, eps):
@@ -66,17 +66,12 @@ def _backward(x, weight, labels, g, ca, cb, up, inv, dims, cfg, need_x, need_w, 
     return dx, dw, db
 
 
-def _needs(x, weight, bias):
-    need_x = x.requires_grad
-    need_wb = weight.requires_grad or (bias is not None and bias.requires_grad)
-    return need_x, need_wb
-
-
 class _Logits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, labels, wshape, cfg):
         xc, w2, b, lb, n, c, cin, hw = _prep(x.detach(), weight.detach(), None if bias is None else bias.detach(), labels)
-        need_x, need_wb = _needs(x, weight, bias)
+        need_x, need_w, need_b = _needs(x, weight, bias)
+        need_wb = need_w or need_b
         dev = xc.device
         z = torch.empty((n, 1) + tuple(x.shape[2:]), dtype=torch.float32, device=dev)
         coef = torch.empty((2 if need_x else 1 if need_wb else 0, n, hw), dtype=torch.float32, device=dev)
@@ -111,7 +106,8 @@ class _Loss(torch.autograd.Function):
         _lib.require_gpu(targets)
         t = targets.detach().reshape(n, hw).to(torch.float32).contiguous()
         dev = xc.device
-        need_x, need_wb = _needs(x, weight, bias)
+        need_x, need_w, need_b = _needs(x, weight, bias)
+        need_wb = need_w or need_b
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         inv = torch.empty(1, dtype=torch.float32, device=dev)                      # 1 / divisor, written by the forward
         rows = torch.empty(n * ((hw + _TILE - 1) // _TILE), dtype=torch.float32, device=dev)
@@ -145,9 +141,9 @@ def normed_class_mask_logits(x, weight, bias, labels, tempearture=20, power=1.0,
     ``labels [N]`` integer.  Differentiable in ``x``, ``weight`` and ``bias`` (not twice).  A RoI with a label outside ``[0, C)``
     gets zeros.  A non-contiguous or ``channels_last`` ``x`` costs one layout copy."""
     cfg = _cfg(tempearture, power, eps)
-    if isinstance(x, torch.Tensor) and x.dim() == 4 and x.size(0) == 0:
+    if _is_empty(x):
         _prep(x, weight, bias, labels)
-        return _empty_result(x, weight, bias, (0, 1) + tuple(x.shape[2:]))
+        return _empty_result(x, (weight, bias), (0, 1) + tuple(x.shape[2:]))
     return _Logits.apply(x, weight, bias, labels, tuple(weight.shape), cfg)
 
 
@@ -158,13 +154,13 @@ def normed_class_mask_loss(x, weight, bias, labels, targets, tempearture=20, pow
     applied on the device.  ``valid_rows``: divide by ``max(1, #{n: 0 <= labels[n] < C}) * H * W`` instead of ``N * H * W``.
     ``targets [N, H, W]``.  ``N == 0``: a zero connected to ``x``, ``weight`` and ``bias``."""
     cfg = _cfg(tempearture, power, eps)
-    if isinstance(x, torch.Tensor) and x.dim() == 4 and x.size(0) == 0:
+    if _is_empty(x):
         _prep(x, weight, bias, labels)
-        return _empty_result(x, weight, bias, (1,))
+        return _empty_result(x, (weight, bias), (1,))
     return _Loss.apply(x, weight, bias, labels, targets, tuple(weight.shape), cfg, bool(valid_rows))
 
 
-class ClassSelectedNormedMaskPredictor(nn.Module):
+class ClassSelectedNormedMaskPredictor(_SelectedPredictor):
     """Stands where ``FCNMaskHead.conv_logits`` stood in a head built with ``predictor_cfg=dict(type='NormedConv2d', ...)``
     (fcn_mask_head.py:106-111): the same parameters - ``weight [C, Cin, 1, 1]``, ``bias [C]``, ``C = 1`` for a ``class_agnostic``
     head - under the ``state_dict`` keys of the reference's ``NormedConv2d(Cin, C, 1)``, so a checkpoint's
@@ -173,25 +169,14 @@ class ClassSelectedNormedMaskPredictor(nn.Module):
     accepted and kept: for a 1x1 kernel both settings are the same normalisation."""
 
     def __init__(self, in_channels, num_classes, class_agnostic=False, tempearture=20, power=1.0, eps=1e-6, norm_over_kernel=False):
-        super().__init__()
-        self.in_channels, self.num_classes, self.class_agnostic = int(in_channels), int(num_classes), bool(class_agnostic)
-        self.tempearture, self.power, self.eps, self.norm_over_kernel = tempearture, power, eps, bool(norm_over_kernel)
         _cfg(tempearture, power, eps)
-        out_channels = 1 if self.class_agnostic else self.num_classes
-        self.weight = nn.Parameter(torch.empty(out_channels, self.in_channels, 1, 1))
-        self.bias = nn.Parameter(torch.empty(out_channels))
-        self.init_weights()
-
-    def init_weights(self):
-        nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
-        nn.init.constant_(self.bias, 0)
+        super().__init__(in_channels, num_classes, class_agnostic)
+        self.tempearture, self.power, self.eps, self.norm_over_kernel = tempearture, power, eps, bool(norm_over_kernel)
 
     def _labels(self, labels, valid_rows=False):
-        if not self.class_agnostic:
-            return labels
-        if valid_rows:                                   # channel 0 for a real class, still invalid for a padded row
+        if self.class_agnostic and valid_rows:           # channel 0 for a real class, still invalid for a padded row
             return torch.where((labels >= 0) & (labels < self.num_classes), torch.zeros_like(labels), torch.full_like(labels, -1))
-        return torch.zeros_like(labels)
+        return super()._labels(labels)
 
     def forward(self, x, labels):
         """The selected logits ``[N, 1, H, W]``: ``pos_labels`` in training, ``det_labels`` at test time."""
@@ -208,30 +193,17 @@ class ClassSelectedNormedMaskPredictor(nn.Module):
         parameters are copied bit for bit."""
         if not isinstance(conv, nn.Conv2d) or not all(hasattr(conv, k) for k in ("tempearture", "power", "eps")):
             raise NotImplementedError("a NormedConv2d expected")
-        if conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.padding != (0, 0) or conv.groups != 1 \
-                or conv.dilation != (1, 1):
+        if not _is_plain_1x1(conv):
             raise NotImplementedError("a plain 1x1 NormedConv2d expected")
-        agnostic = conv.out_channels == 1 if class_agnostic is None else class_agnostic
-        m = cls(conv.in_channels, conv.out_channels, class_agnostic=agnostic, tempearture=conv.tempearture, power=conv.power,
-                eps=conv.eps, norm_over_kernel=getattr(conv, "norm_over_kernel", False))
-        m.to(device=conv.weight.device, dtype=conv.weight.dtype)
-        with torch.no_grad():
-            m.weight.copy_(conv.weight)
-            if conv.bias is not None:
-                m.bias.copy_(conv.bias)
-        return m
+        return cls._from_conv(conv, class_agnostic, tempearture=conv.tempearture, power=conv.power, eps=conv.eps,
+                              norm_over_kernel=getattr(conv, "norm_over_kernel", False))
 
     def to_conv(self):
         """The dense ``iif_amd.mmdet_normed_predictor.NormedConv2d`` with these parameters: the full ``[N, C, H, W]`` logits for
         whoever needs them."""
         from .mmdet_normed_predictor import NormedConv2d
-        conv = NormedConv2d(self.in_channels, self.weight.size(0), 1, tempearture=self.tempearture, power=self.power, eps=self.eps,
-                            norm_over_kernel=self.norm_over_kernel)
-        conv.to(device=self.weight.device, dtype=self.weight.dtype)
-        with torch.no_grad():
-            conv.weight.copy_(self.weight)
-            conv.bias.copy_(self.bias)
-        return conv
+        return self._into_conv(NormedConv2d(self.in_channels, self.weight.size(0), 1, tempearture=self.tempearture, power=self.power,
+                                            eps=self.eps, norm_over_kernel=self.norm_over_kernel))
 
     def extra_repr(self):
         return "in_channels=%d, num_classes=%d, class_agnostic=%s, tempearture=%s, power=%s, eps=%s" % (

@@ -20,6 +20,9 @@ CASES = {
     "e": (3, 11, 65, 7, 9, [10, 0, 4], True, False),            # HW = 63: rows not 16-byte aligned, vector tails, odd Cin
     "f": (64, 1203, 256, 28, 28, None, True, False),            # the LVIS class count: >= 1139 zero rows of dweight
     "g": (6, 1, 256, 28, 28, [0] * 6, False, False),            # the class_agnostic head, bias=None
+    # s: the smallest N that sends the per-class list builder through a second 2048-RoI piece (eight full rounds of 256, then 3 RoIs);
+    # every class owns RoIs on both sides of the boundary; the eight-wide row sum runs with its remainder loop
+    "s": (2051, 3, 3, 2, 2, [i % 3 for i in range(2051)], True, False),
 }
 UP = 2.5                                                        # the upstream factor of the scaled-backward checks
 

@@ -28,8 +28,11 @@ CASES = {
     "f": (6, 1, 256, 256, 14, 14, [0] * 6, False, False),       # the class_agnostic head, bias=None
     "g": (5, 7, 300, 130, 7, 7, None, True, True),              # Co > 128 and no tile multiple
     "r": (3, 5, 256, 256, 14, 14, [4, 0, 0], True, False),      # a's shape, plain randn inputs
+    # s: the smallest N that sends the per-class list builder through a second 2048-RoI piece (eight full rounds of 256, then 3 RoIs);
+    # every class owns RoIs on both sides of the boundary; the eight-wide row sum runs with its remainder loop
+    "s": (2051, 3, 3, 3, 2, 2, [i % 3 for i in range(2051)], True, False),
 }
-GRID_CASES = ("a", "b", "c", "d", "e", "f", "g")
+GRID_CASES = ("a", "b", "c", "d", "e", "f", "g", "s")
 UP = 2.5                                                        # the upstream factor of the scaled-backward checks
 GRADS = ("df", "dup_weight", "dup_bias", "dweight", "dbias")
 

@@ -26,6 +26,9 @@ CASES = {
     "g": (6, 1, 256, 28, 28, [0] * 6, False, False, 20, 1.0, False),          # the class_agnostic head, bias=None
     "h": (9, 4, 256, 28, 28, [3] * 9, True, False, 8, 2.0, False),            # case b with power = 2, T = 8: the powf path
     "i": (5, 7, 256, 28, 28, [0, 6, 3, 3, 0], True, False, 20, 1.0, True),    # case a with pixels that are zero in every channel
+    # s: the smallest N that sends the per-class list builder through a second 2048-RoI piece (eight full rounds of 256, then 3 RoIs);
+    # every class owns RoIs on both sides of the boundary; the eight-wide row sum runs with its remainder loop
+    "s": (2051, 3, 3, 2, 2, [i % 3 for i in range(2051)], True, False, 20, 1.0, False),
 }
 ZERO_PIXELS = ((0, 0, 0), (0, 27, 27), (1, 13, 5), (2, 4, 4), (4, 27, 0), (4, 9, 9), (4, 9, 10))       # (roi, y, x) of case i
 UP = 2.5                                                                      # the upstream factor of the scaled-backward checks
