@@ -203,6 +203,31 @@ class RoiImage(ctypes.Structure):
                 ("img_index", ctypes.c_int32)]
 
 
+def roi_images(gt_bboxes_list, gt_labels_list=None):
+    """The ``RoiImage`` array of a batch call, image ``b`` with ``img_index`` b: float32 ``[G, 4]`` boxes (made contiguous where
+    the row strides do not fit) and, if given, one int64 label per box.  Returns ``(images, held)``; the caller keeps ``held``
+    alive until the launch is enqueued."""
+    B = len(gt_bboxes_list)
+    images = (RoiImage * B)()
+    held = []
+    for b, g in enumerate(gt_bboxes_list):
+        G = int(g.shape[0])
+        g = g.detach()
+        if G and (g.stride(1) != 1 or (G > 1 and g.stride(0) < 4)):
+            g = g.contiguous()
+        held.append(g)
+        l = None
+        if gt_labels_list is not None:
+            l = gt_labels_list[b].reshape(-1).to(torch.int64).contiguous()
+            held.append(l)
+        images[b].gt_bboxes = ptr(g) if G else None
+        images[b].ld_gt = g.stride(0) if G > 1 else 4
+        images[b].gt_labels = ptr(l) if (G and l is not None) else None
+        images[b].G = G
+        images[b].img_index = b
+    return images, held
+
+
 class RpnGrid(ctypes.Structure):
     """Mirror of ``iif_rpn_grid`` (include/iif_amd.h)."""
     _fields_ = [("num_levels", ctypes.c_int32)] + [(k, ctypes.c_int32 * 8) for k in ("W", "H", "num_base", "stride_w", "stride_h")] + [

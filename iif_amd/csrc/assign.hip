@@ -8,16 +8,17 @@
 //   iif_bbox_overlaps    the stand-alone calculator: 'iou' / 'iof' / 'giou', pairwise [M, N] or aligned [N], one lane per output.
 //   iif_max_iou_assign   no [G, N] array anywhere.  One lane per candidate box; the ground-truth (and ignore) boxes pass through
 //                        LDS in chunks of kChunk, so any G works.
-//     pass 1  per candidate: is it ignored (max iof against the ignore boxes > ignore_iof_thr), its maximum overlap and the
-//             LOWEST gt index that attains it.  Per gt: the maximum over the non-ignored candidates and the LOWEST candidate that
+//     pass 1  (assign_pass1_chunks, assign_common.h) per candidate: is it ignored (max iof against the ignore boxes >
+//             ignore_iof_thr), its maximum overlap and the LOWEST gt index that attains it.  Per gt: the maximum over the non-ignored candidates and the LOWEST candidate that
 //             attains it, as a 64-bit INTEGER maximum of (bits(overlap) + 1) << 32 | ~candidate: an LDS atomic per overlapping
 //             pair that beats the running LDS value, then one global atomic per gt and block that has one.  Overlaps are >= +0, so
 //             their bits order as unsigned integers; 0 is "no candidate" (the reference's -1) and orders below bits(0.0) + 1.
 //             Pairs that do not intersect (nearly all of them) issue nothing: their overlap is exactly +0, and what they contribute
 //             to a gt's maximum - "0.0, at the lowest non-ignored candidate" - is ONE extra workspace slot for all gts.
-//     pass 2  (match_low_quality only; without it pass 1 finishes the assignment in the same launch) applies the reference's steps
-//             in its order and recomputes the pairs it needs with the same inline function, hence to the same bits: a candidate
-//             can only equal gt i's maximum if that maximum is <= the candidate's own, which leaves few pairs.
+//     pass 2  (match_low_quality only; without it pass 1 finishes the assignment in the same launch; step4_stage_chunk and
+//             step4_hit, assign_common.h) applies the reference's steps in its order and recomputes the pairs it needs with the
+//             same inline function, hence to the same bits: a candidate can only equal gt i's maximum if that maximum is <= the
+//             candidate's own, which leaves few pairs.
 //   Three enqueued operations at most: the workspace clear, pass 1, pass 2.  No float atomics: nothing depends on arrival order.
 //
 // Arithmetic: every step of the reference is one IEEE float32 operation, done here in its order (the build passes
@@ -33,7 +34,8 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kChunk = 256;                   // gt / ignore boxes per LDS chunk: one per thread of the block
+constexpr int kChunk = kAssignChunk;          // gt / ignore boxes per LDS chunk: one per thread of the block
+static_assert(kThreads == kAssignChunk, "assign_pass1_chunks / step4_stage_chunk stage one box per thread");
 constexpr unsigned kOvMaxBlocks = 1u << 16;   // grid cap of the calculator (grid-stride beyond)
 
 enum { kIoU = 0, kIoF = 1, kGIoU = 2 };
@@ -46,7 +48,7 @@ struct AssignArgs {
     int assign_all, ign_wrt_cand, low_quality;
     const int64_t* gt_labels;
     int64_t* gt_inds; float* max_ov; int64_t* labels;
-    unsigned long long* ws;                                 // [G + 1], zero on entry (low_quality only)
+    u64* ws;                                                // [G + 1], zero on entry (low_quality only)
 };
 
 __device__ __forceinline__ void store_result(const AssignArgs& a, int64_t idx, int64_t gi) {
@@ -55,10 +57,8 @@ __device__ __forceinline__ void store_result(const AssignArgs& a, int64_t idx, i
 }
 
 __global__ void __launch_bounds__(kThreads) assign_pass1_kernel(AssignArgs a) {
-    __shared__ Box s_box[kChunk];
-    __shared__ float s_area[kChunk];
-    __shared__ unsigned long long s_max[kChunk];
-    __shared__ unsigned s_low;                              // ~(lowest non-ignored candidate of the block), 0 = none
+    __shared__ Pass1Lds s;
+    __shared__ unsigned s_low;                              // assign_pass1_chunks' slot
     const int tid = threadIdx.x;
     const int64_t idx = (int64_t)blockIdx.x * kThreads + tid;
     const bool live = idx < a.N;
@@ -75,7 +75,6 @@ __global__ void __launch_bounds__(kThreads) assign_pass1_kernel(AssignArgs a) {
         c = load_box(a.b + idx * a.ldb, a.vec_b != 0);
         ca = box_area(c);
     }
-    if (tid == 0) s_low = 0u;
 
     // ---- ignored: max over the ignore boxes of iof > ignore_iof_thr (:108-118).  The threshold is > 0 here, so a pair that
     // does not intersect (iof = +0) never decides.
@@ -86,15 +85,15 @@ __global__ void __launch_bounds__(kThreads) assign_pass1_kernel(AssignArgs a) {
             __syncthreads();
             if (tid < cn) {
                 const Box q = load_box(a.ig + (int64_t)(i0 + tid) * a.ldi, false);
-                s_box[tid] = q;
-                s_area[tid] = box_area(q);
+                s.box[tid] = q;
+                s.area[tid] = box_area(q);
             }
             __syncthreads();
             if (live) {
                 for (int j = 0; j < cn; ++j) {
-                    const float inter = box_inter(c, s_box[j]);
+                    const float inter = box_inter(c, s.box[j]);
                     if (inter > 0.0f) {
-                        const float fg = a.ign_wrt_cand ? ca : s_area[j];
+                        const float fg = a.ign_wrt_cand ? ca : s.area[j];
                         if (inter / fmaxf(fg, kAssignEps) > a.ign_thr) ignored = true;
                     }
                 }
@@ -102,60 +101,11 @@ __global__ void __launch_bounds__(kThreads) assign_pass1_kernel(AssignArgs a) {
         }
     }
 
-    // ---- the candidate's maximum over the gts; the gts' maxima over the candidates
+    // ---- the candidate's maximum over the gts; the gts' maxima over the candidates that are not ignored
     float best = ignored ? -1.0f : 0.0f;                    // an ignored candidate has overlap -1 with every gt
     int arg = 0;
     const bool lq = a.low_quality != 0;
-    for (int g0 = 0; g0 < a.G; g0 += kChunk) {
-        const int cn = min(kChunk, a.G - g0);
-        __syncthreads();
-        if (tid < cn) {
-            const Box q = load_box(a.g + (int64_t)(g0 + tid) * a.ldg, false);
-            s_box[tid] = q;
-            s_area[tid] = box_area(q);
-            s_max[tid] = 0ull;
-        }
-        __syncthreads();
-        if (live && !ignored) {
-            for (int j = 0; j < cn; ++j) {
-                float inter;
-                const float v = pair_iou(s_box[j], s_area[j], c, ca, inter);
-                if (inter > 0.0f) {
-                    if (v > best) { best = v; arg = g0 + j; }               // strict: ties stay with the lowest gt
-                    if (lq) {
-                        const unsigned long long p = pack_max(v, (unsigned)idx);
-                        if (p > __hip_atomic_load(&s_max[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-                            __hip_atomic_fetch_max(&s_max[j], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                }
-            }
-        }
-        if (lq) {
-            __syncthreads();
-            if (tid < cn) {
-                const unsigned long long p = s_max[tid];
-                unsigned long long* slot = a.ws + g0 + tid;
-                if (p != 0ull && p > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                    __hip_atomic_fetch_max(slot, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
-
-    if (lq) {
-        // the lowest non-ignored candidate: it holds every gt's maximum of 0.0 where no candidate intersects the gt
-        const bool cand = live && !ignored;
-        const unsigned long long m = __ballot(cand);
-        if (cand && (threadIdx.x & 63) == (unsigned)__ffsll((long long)m) - 1u)
-            __hip_atomic_fetch_max(&s_low, ~(unsigned)idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __syncthreads();
-        if (tid == 0 && s_low != 0u) {
-            const unsigned long long p = (1ull << 32) | (unsigned long long)s_low;             // = pack_max(0.0f, lowest)
-            unsigned long long* slot = a.ws + a.G;
-            if (p > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                __hip_atomic_fetch_max(slot, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-
+    assign_pass1_chunks(s, &s_low, a.g, a.ldg, a.G, c, ca, (unsigned)idx, live && !ignored, lq, a.ws, best, arg);
     if (live) {
         a.max_ov[idx] = best;
         if (lq) a.gt_inds[idx] = arg;                       // parked for pass 2
@@ -165,12 +115,8 @@ __global__ void __launch_bounds__(kThreads) assign_pass1_kernel(AssignArgs a) {
 
 // Step 4 (:185-200) on top of steps 1 - 3.  max_ov / gt_inds hold pass 1's per-candidate maximum and argmax.
 __global__ void __launch_bounds__(kThreads) assign_pass2_kernel(AssignArgs a) {
-    __shared__ Box s_box[kChunk];
-    __shared__ float s_area[kChunk];
-    __shared__ float s_gmax[kChunk];                        // the gt's maximum, NaN if it is below min_pos_iou (matches nothing)
-    __shared__ int s_garg[kChunk];                          // the candidate that attains it, -1 likewise
-    const int tid = threadIdx.x;
-    const int64_t idx = (int64_t)blockIdx.x * kThreads + tid;
+    __shared__ Pass2Lds s;
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const bool live = idx < a.N;
     float mo = 0.0f, ca = 0.0f;
     Box c = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -184,42 +130,13 @@ __global__ void __launch_bounds__(kThreads) assign_pass2_kernel(AssignArgs a) {
         }
     }
     const bool ignored = mo == -1.0f;                       // overlaps are >= 0 otherwise
-    const unsigned long long zero_slot = a.ws[a.G];
+    const u64 zero_slot = a.ws[a.G];
     for (int g0 = 0; g0 < a.G; g0 += kChunk) {
         const int cn = min(kChunk, a.G - g0);
-        __syncthreads();
-        if (tid < cn) {
-            unsigned long long p = a.ws[g0 + tid];
-            p = p > zero_slot ? p : zero_slot;
-            // no non-ignored candidate at all: the reference's row is all -1, its max -1 at index 0
-            const float gm = p ? __uint_as_float((unsigned)(p >> 32) - 1u) : -1.0f;
-            const int ga = p ? (int)~(unsigned)p : 0;
-            const bool active = gm >= a.min_pos;
-            s_gmax[tid] = active ? gm : __uint_as_float(0x7fc00000u);
-            s_garg[tid] = active ? ga : -1;
-            if (a.assign_all) {
-                const Box q = load_box(a.g + (int64_t)(g0 + tid) * a.ldg, false);
-                s_box[tid] = q;
-                s_area[tid] = box_area(q);
-            }
-        }
-        __syncthreads();
+        step4_stage_chunk<false>(s, a.ws, zero_slot, a.min_pos, a.g, a.ldg, g0, cn, a.assign_all != 0);
         if (!live) continue;
-        if (a.assign_all) {
-            for (int j = 0; j < cn; ++j) {
-                const float gm = s_gmax[j];
-                if (!(gm <= mo)) continue;                  // overlap(j, this) <= mo < gm, or gt j takes no part
-                bool hit = true;                            // ignored: mo = -1, so gm = -1 = this candidate's overlap with j
-                if (!ignored) {
-                    float inter;
-                    hit = pair_iou(s_box[j], s_area[j], c, ca, inter) == gm;
-                }
-                if (hit) gi = g0 + j + 1;                   // ascending: the highest gt wins, as in the reference's loop
-            }
-        } else {
-            for (int j = 0; j < cn; ++j)
-                if (s_garg[j] == (int)idx) gi = g0 + j + 1;
-        }
+        const int hit = step4_hit(s.box, s.area, s.gmax, s.garg, g0, cn, a.assign_all != 0, c, ca, mo, (int)idx, ignored);
+        if (hit) gi = hit;
     }
     if (live) store_result(a, idx, gi);
 }
@@ -327,7 +244,7 @@ int iif_max_iou_assign(const float* bboxes, int64_t ld_bboxes, int64_t N, const 
     a.assign_all = gt_max_assign_all != 0; a.ign_wrt_cand = ignore_wrt_candidates != 0; a.low_quality = two_pass;
     a.gt_labels = gt_labels;
     a.gt_inds = gt_inds; a.max_ov = max_overlaps; a.labels = labels;
-    a.ws = static_cast<unsigned long long*>(d_workspace);
+    a.ws = static_cast<u64*>(d_workspace);
     hipStream_t st = as_stream(stream);
     const unsigned blocks = (unsigned)cdiv64(N, kThreads);
     if (two_pass) {

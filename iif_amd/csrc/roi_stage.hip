@@ -9,12 +9,14 @@
 //                        and keys in registers), the ground-truth boxes and their maxima live in LDS.  No global workspace, no
 //                        clear, no ticket.
 //     assign   iif_max_iou_assign's definition (assign.hip's header comment) on the proposals alone, with the same inline
-//              functions (assign_common.h): per-gt maxima are 64-bit INTEGER maxima of (bits(overlap) + 1) << 32 | ~proposal in
-//              LDS.  Then the ground truth goes in front as add_gt_ does: candidate c < G is gt c with gt_inds c + 1.
-//     sample   iif_random_sample's rule: a class with more members than its budget keeps the k smallest (key, index) pairs.  The
-//              threshold key is found by a radix select over four digits of the 31 key bits (LDS histograms); one ordered
-//              sweep (block scans, tile by tile in index order) then ranks the members with exactly that key and gives every
-//              kept candidate its slot, so the lists are ascending.  Any keys work, all equal included.
+//              functions (assign_common.h: pair_update, decode_max, step4_hit over the LDS-resident ground truth): per-gt maxima
+//              are 64-bit INTEGER maxima of (bits(overlap) + 1) << 32 | ~proposal in LDS.  Then the ground truth goes in front
+//              as add_gt_ does: candidate c < G is gt c with gt_inds c + 1.
+//     sample   iif_random_sample's rule and budgets (sample_core.h), by another route: a class with more members than its
+//              budget keeps the k smallest (key, index) pairs.  The threshold key is found by a radix select over four digits of
+//              the 31 key bits (LDS histograms); one ordered sweep (block scans, tile by tile in index order) then ranks the
+//              members with exactly that key and gives every kept candidate its slot, so the lists are ascending.  Any keys
+//              work, all equal included.
 //     targets  the thread that owns a kept candidate writes its row: iif_roi_targets' rows, plus pos_is_gt and the
 //              positives-only rows for the mask branch.
 //   iif_refine_bboxes    BBoxHead.refine_bboxes + regress_by_class (bbox_head.py:380-496) on the padded rows of one stage: decode
@@ -24,19 +26,19 @@
 // Integer atomics only: no result depends on arrival order.
 #include "common.h"
 #include "assign_common.h"
+#include "sample_core.h"
 
 namespace {
 
-constexpr int kThreads = 1024;
+constexpr int kThreads = kSelThreads;
+static_assert(kThreads == 1024, "thread t owns the candidates t, t + 1024, ...; block_scan_excl is written for kSelThreads");
 constexpr int kMaxImages = 16;
 constexpr int kMaxProposals = 4096;
 constexpr int kMaxGt = 1024;
 constexpr int kMaxNum = 1024;
 constexpr int kSlots = (kMaxProposals + kMaxGt) / kThreads;     // candidates per thread
 constexpr int kDigits = 4;
-constexpr int kBins = 256;
-
-typedef unsigned long long u64;
+constexpr int kDigitBins = 256;                                // per digit of the radix select (sample_core.h: kBins)
 
 struct RoiImage { const float* gt; int64_t ldg; const int64_t* gt_labels; int G; float img; };
 
@@ -52,39 +54,6 @@ struct StageArgs {
     int64_t* counts; uint8_t* pos_is_gt; float* pos_rois; int64_t* pos_gt_inds; int64_t* pos_labels;
 };
 
-// Exclusive prefix sums over the block's 1024 threads of two 32-bit counts packed in one word; `total` is the block's sum.
-// s_w: 17 words of LDS, reusable after the call returns.
-__device__ __forceinline__ u64 block_scan_excl(u64 v, u64* s_w, u64& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    if (wv == 0) {
-        const u64 x = lane < kThreads / 64 ? s_w[lane] : 0ull;
-        u64 xi = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u64 t = __shfl_up(xi, o, 64);
-            if (lane >= o) xi += t;
-        }
-        if (lane < kThreads / 64) s_w[lane] = xi - x;
-        if (lane == 63) s_w[kThreads / 64] = xi;
-    }
-    __syncthreads();
-    const u64 res = s_w[wv] + inc - v;
-    total = s_w[kThreads / 64];
-    __syncthreads();
-    return res;
-}
-
-__device__ __forceinline__ unsigned half_of(u64 v, int c) { return c ? (unsigned)(v >> 32) : (unsigned)v; }
-__device__ __forceinline__ u64 one_of(int c) { return c ? (1ull << 32) : 1ull; }
-
 // digit d (0 = most significant) of a 31-bit key: 8, 8, 8 and 7 bits
 __device__ __forceinline__ int digit_shift(int d) { return d == 0 ? 23 : (d == 1 ? 15 : (d == 2 ? 7 : 0)); }
 __device__ __forceinline__ unsigned digit_of(unsigned key, int d) { return (key >> digit_shift(d)) & (d == 3 ? 127u : 255u); }
@@ -97,7 +66,7 @@ __global__ void __launch_bounds__(kThreads) roi_stage_kernel(StageArgs a) {
     __shared__ u64 s_max[kMaxGt];
     __shared__ float s_gmax[kMaxGt];                        // the gt's maximum, NaN if it is below min_pos_iou (matches nothing)
     __shared__ int s_garg[kMaxGt];                          // the proposal that attains it, -1 likewise
-    __shared__ unsigned s_hist[2 * kBins];
+    __shared__ unsigned s_hist[2 * kDigitBins];
     __shared__ u64 s_scan[kThreads / 64 + 1];
     __shared__ long long s_k[2], s_m[2];
     __shared__ unsigned s_prefix[2], s_rem[2];
@@ -149,18 +118,7 @@ __global__ void __launch_bounds__(kThreads) roi_stage_kernel(StageArgs a) {
         if (G == 0) { gi[k] = 0; continue; }                // no ground truth: everything is background (:146-162)
         float best = 0.0f;
         int ar = 0;
-        for (int j = 0; j < G; ++j) {
-            float inter;
-            const float v = pair_iou(s_box[j], s_area[j], bx[k], ca[k], inter);
-            if (inter > 0.0f) {
-                if (v > best) { best = v; ar = j; }         // strict: ties stay with the lowest gt
-                if (lq) {
-                    const u64 p = pack_max(v, (unsigned)i);
-                    if (p > __hip_atomic_load(&s_max[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-                        __hip_atomic_fetch_max(&s_max[j], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            }
-        }
+        for (int j = 0; j < G; ++j) pair_update(s_box[j], s_area[j], j, bx[k], ca[k], (unsigned)i, lq, &s_max[j], best, ar);
         mo[k] = best; arg[k] = ar;
         gi[k] = (int)base_assign(a, best, ar);
     }
@@ -169,41 +127,21 @@ __global__ void __launch_bounds__(kThreads) roi_stage_kernel(StageArgs a) {
         // Step 4 (:185-200).  Proposal 0 holds every gt's maximum of 0.0 where no proposal intersects the gt.
         __syncthreads();
         const u64 zero_slot = n > 0 ? pack_max(0.0f, 0u) : 0ull;
-        for (int j = tid; j < G; j += kThreads) {
-            u64 p = s_max[j];
-            p = p > zero_slot ? p : zero_slot;
-            const float gm = p ? __uint_as_float((unsigned)(p >> 32) - 1u) : -1.0f;
-            const int ga = p ? (int)~(unsigned)p : 0;
-            const bool active = gm >= a.min_pos;
-            s_gmax[j] = active ? gm : __uint_as_float(0x7fc00000u);
-            s_garg[j] = active ? ga : -1;
-        }
+        for (int j = tid; j < G; j += kThreads) decode_max<false>(s_max[j], zero_slot, a.min_pos, s_gmax[j], s_garg[j]);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < kSlots; ++k) {
             const int c = tid + k * kThreads;
             if (c >= M || c < front) continue;
-            const int i = c - front;
-            int g2 = gi[k];
-            if (a.assign_all) {
-                for (int j = 0; j < G; ++j) {
-                    const float gm = s_gmax[j];
-                    if (!(gm <= mo[k])) continue;           // overlap(j, this) <= mo < gm, or gt j takes no part
-                    float inter;
-                    if (pair_iou(s_box[j], s_area[j], bx[k], ca[k], inter) == gm) g2 = j + 1;   // ascending: the highest gt wins
-                }
-            } else {
-                for (int j = 0; j < G; ++j)
-                    if (s_garg[j] == i) g2 = j + 1;
-            }
-            gi[k] = g2;
+            const int hit = step4_hit(s_box, s_area, s_gmax, s_garg, 0, G, a.assign_all != 0, bx[k], ca[k], mo[k], c - front, false);
+            if (hit) gi[k] = hit;
         }
     }
 
     // ---- sampling: keys, class totals, budgets
     unsigned key[kSlots];
     int cls[kSlots];                                        // 0 positive, 1 negative, -1 takes no part
-    for (int i = tid; i < 2 * kBins; i += kThreads) s_hist[i] = 0u;
+    for (int i = tid; i < 2 * kDigitBins; i += kThreads) s_hist[i] = 0u;
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < kSlots; ++k) {
@@ -213,21 +151,15 @@ __global__ void __launch_bounds__(kThreads) roi_stage_kernel(StageArgs a) {
         if (c < M && gi[k] >= 0) {
             cls[k] = gi[k] > 0 ? 0 : 1;
             key[k] = (unsigned)a.keys[(int64_t)b * a.ld_keys + c] & 0x7fffffffu;
-            atomicAdd(&s_hist[cls[k] * kBins + (int)digit_of(key[k], 0)], 1u);
+            atomicAdd(&s_hist[cls[k] * kDigitBins + (int)digit_of(key[k], 0)], 1u);
         }
     }
     __syncthreads();
     if (tid == 0) {
         long long tot[2] = {0, 0};
-        for (int i = 0; i < kBins; ++i) { tot[0] += s_hist[i]; tot[1] += s_hist[kBins + i]; }
-        const long long kp = tot[0] < a.nep ? tot[0] : a.nep;                 // base_sampler.py:83-89
-        long long budget = a.num - kp;                                        // :90-95
-        if (a.ub >= 0.0) {
-            const double capd = a.ub * (double)(kp > 1 ? kp : 1);
-            if (capd < (double)budget) budget = (long long)capd;              // int(): truncation
-        }
-        const long long kn = tot[1] < budget ? tot[1] : budget;
-        s_k[0] = kp; s_k[1] = kn; s_m[0] = tot[0]; s_m[1] = tot[1];
+        for (int i = 0; i < kDigitBins; ++i) { tot[0] += s_hist[i]; tot[1] += s_hist[kDigitBins + i]; }
+        const Budgets bu = sample_budgets(tot[0], tot[1], a.nep, a.num, a.ub);
+        s_k[0] = bu.kp; s_k[1] = bu.kn; s_m[0] = tot[0]; s_m[1] = tot[1];
     }
     __syncthreads();
     const long long kk[2] = {s_k[0], s_k[1]};
@@ -243,21 +175,21 @@ __global__ void __launch_bounds__(kThreads) roi_stage_kernel(StageArgs a) {
     if (sel[0] || sel[1]) {
         for (int d = 0; d < kDigits; ++d) {
             if (d > 0) {
-                for (int i = tid; i < 2 * kBins; i += kThreads) s_hist[i] = 0u;
+                for (int i = tid; i < 2 * kDigitBins; i += kThreads) s_hist[i] = 0u;
                 __syncthreads();
                 const unsigned pre[2] = {s_prefix[0], s_prefix[1]};
 #pragma unroll
                 for (int k = 0; k < kSlots; ++k)
                     if (cls[k] >= 0 && sel[cls[k]] && prefix_of(key[k], d) == pre[cls[k]])
-                        atomicAdd(&s_hist[cls[k] * kBins + (int)digit_of(key[k], d)], 1u);
+                        atomicAdd(&s_hist[cls[k] * kDigitBins + (int)digit_of(key[k], d)], 1u);
                 __syncthreads();
             }
             if (tid < 2 && sel[tid]) {
                 const unsigned r = s_rem[tid];
                 unsigned cum = 0u;
-                const int bins = d == 3 ? 128 : kBins;
+                const int bins = d == 3 ? 128 : kDigitBins;
                 for (int i = 0; i < bins; ++i) {
-                    const unsigned h = s_hist[tid * kBins + i];
+                    const unsigned h = s_hist[tid * kDigitBins + i];
                     if (cum < r && r <= cum + h) {
                         s_prefix[tid] = (s_prefix[tid] << (d == 3 ? 7 : 8)) | (unsigned)i;
                         s_rem[tid] = r - cum;

@@ -10,17 +10,17 @@
 //                        of the sampled positives, for all B images (blockIdx.y), FIVE enqueued operations whatever B, the number of
 //                        levels, G and the data:
 //     clear    one hipMemsetAsync over the head of the workspace (per-gt maxima, key histograms, tickets).
-//     pass 1   assign.hip's pass 1, one lane per flat anchor index: the anchor is GENERATED from its index (base anchors and level
-//              table arrive by value), the gts pass through LDS in chunks of 256, per-gt maxima are 64-bit integer maxima of
-//              (bits(overlap) + 1) << 32 | ~index.  A candidate that is not valid for the image (valid_flags on its pad_shape;
-//              anchor_inside_flags on its img_shape for allowed_border >= 0) takes no part at all: no maximum, not the "lowest
-//              candidate" slot, later no class in the sampler.  The reference compacts these away; compaction is monotone, so
-//              "lowest index wins" means the same in both index spaces.
-//     pass 2   assign.hip's pass 2 (steps 1 - 4 in the reference's order) and targets.hip's histogram of the top 12 key bits per
-//              class: LDS atomics, flushed with integer global atomics.
-//     select   targets.hip's select kernel per image: budgets, threshold bins, one word per candidate; the last block of an image
-//              (a ticket per image, no waiting) finds the threshold key, sweeps in index order, writes the ascending index lists
-//              and - as the block that resolves the boundary - the encode of the positives it places.
+//     pass 1   assign_pass1_chunks (assign_common.h), one lane per flat anchor index: the anchor is GENERATED from its index (base
+//              anchors and level table arrive by value), the gts pass through LDS in chunks of 256, per-gt maxima are 64-bit
+//              integer maxima of (bits(overlap) + 1) << 32 | ~index.  A candidate that is not valid for the image (valid_flags on
+//              its pad_shape; anchor_inside_flags on its img_shape for allowed_border >= 0) takes no part at all: no maximum, not
+//              the "lowest candidate" slot, later no class in the sampler.  The reference compacts these away; compaction is
+//              monotone, so "lowest index wins" means the same in both index spaces.
+//     pass 2   steps 1 - 4 in the reference's order (base_assign, step4_stage_chunk, step4_hit: assign_common.h) and the
+//              histogram of the top 12 key bits per class (sample_core.h): LDS atomics, flushed with integer global atomics.
+//     select   sample_select_core (sample_core.h) per image: budgets, threshold bins, one word per candidate; the last block of an
+//              image (a ticket per image, no waiting) finds the threshold key, sweeps in index order, writes the ascending index
+//              lists and - as the block that resolves the boundary - the encode of the positives it places.
 //     total    num_total_samples = sum_b max(pos_b, 1) + max(neg_b, 1) as a float32 on the device.
 //   Phases meet at launch boundaries only.  Integer atomics only: the same bits from call to call.
 //   iif_rpn_stage_dense  the four dense per-level tensors of get_targets after images_to_levels, from the index lists: one lane
@@ -31,23 +31,19 @@
 //   iif_rpn_loss_bwd     one launch: plain stores at the sampled positions of a gradient arena the caller cleared.
 #include "common.h"
 #include "assign_common.h"
+#include "sample_core.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kChunk = 256;
-constexpr int kSelThreads = 1024;
-constexpr int kBins = 4096;
-constexpr int kLowBits = 19;
-constexpr unsigned kLowMask = (1u << kLowBits) - 1u;
+constexpr int kChunk = kAssignChunk;
+static_assert(kThreads == kAssignChunk, "assign_pass1_chunks / step4_stage_chunk stage one box per thread");
 constexpr int kMaxImages = 16;
 constexpr int kMaxLevels = 8;
 constexpr int kMaxBase = 16;
 constexpr int kMaxNum = 1024;
 constexpr int kPass2MaxBlocks = 512;
 constexpr int kSelMaxBlocks = 64;
-
-typedef unsigned long long u64;
 
 struct Lvl { int start, W, H, nb, sx, sy; };
 struct Grid { int L, A; Lvl lv[kMaxLevels]; };
@@ -138,15 +134,12 @@ __device__ __forceinline__ bool takes_part(const StageArgs& a, const Img& im, co
 }
 
 __global__ void __launch_bounds__(kThreads) rpn_pass1_kernel(StageArgs a) {
-    __shared__ Box s_box[kChunk];
-    __shared__ float s_area[kChunk];
-    __shared__ u64 s_max[kChunk];
-    __shared__ unsigned s_low;                              // ~(lowest candidate of the block that takes part), 0 = none
-    const int tid = threadIdx.x;
+    __shared__ Pass1Lds s;
+    __shared__ unsigned s_low;                              // assign_pass1_chunks' slot
     const int b = blockIdx.y;
     const Img& im = a.im[b];
     const int G = im.G;
-    const int i = blockIdx.x * kThreads + tid;
+    const int i = blockIdx.x * kThreads + threadIdx.x;
     const bool live = i < a.g.A;
     Box c = {0.0f, 0.0f, 0.0f, 0.0f};
     bool cand = false;
@@ -161,69 +154,16 @@ __global__ void __launch_bounds__(kThreads) rpn_pass1_kernel(StageArgs a) {
         if (live) { mo[i] = 0.0f; arg_out[i] = cand ? 0 : -1; }
         return;
     }
-    const float ca = box_area(c);
-    if (tid == 0) s_low = 0u;
     float best = 0.0f;
     int arg = 0;
-    const bool lq = a.low_quality != 0;
-    u64* ws = a.maxima + im.ws_off;
-    for (int g0 = 0; g0 < G; g0 += kChunk) {
-        const int cn = min(kChunk, G - g0);
-        __syncthreads();
-        if (tid < cn) {
-            const Box q = load_box(im.gt + (int64_t)(g0 + tid) * im.ldg, false);
-            s_box[tid] = q;
-            s_area[tid] = box_area(q);
-            s_max[tid] = 0ull;
-        }
-        __syncthreads();
-        if (cand) {
-            for (int j = 0; j < cn; ++j) {
-                float inter;
-                const float v = pair_iou(s_box[j], s_area[j], c, ca, inter);
-                if (inter > 0.0f) {
-                    if (v > best) { best = v; arg = g0 + j; }               // strict: ties stay with the lowest gt
-                    if (lq) {
-                        const u64 p = pack_max(v, (unsigned)i);
-                        if (p > __hip_atomic_load(&s_max[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-                            __hip_atomic_fetch_max(&s_max[j], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                }
-            }
-        }
-        if (lq) {
-            __syncthreads();
-            if (tid < cn) {
-                const u64 p = s_max[tid];
-                u64* slot = ws + g0 + tid;
-                if (p != 0ull && p > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                    __hip_atomic_fetch_max(slot, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
-    if (lq) {
-        // the lowest candidate that takes part: it holds every gt's maximum of 0.0 where no candidate intersects the gt
-        const u64 m = __ballot(cand);
-        if (cand && (threadIdx.x & 63) == (unsigned)__ffsll((long long)m) - 1u)
-            __hip_atomic_fetch_max(&s_low, ~(unsigned)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __syncthreads();
-        if (tid == 0 && s_low != 0u) {
-            const u64 p = (1ull << 32) | (u64)s_low;                         // = pack_max(0.0f, lowest)
-            u64* slot = ws + G;
-            if (p > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                __hip_atomic_fetch_max(slot, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    assign_pass1_chunks(s, &s_low, im.gt, im.ldg, G, c, box_area(c), (unsigned)i, cand, a.low_quality != 0, a.maxima + im.ws_off, best, arg);
     if (live) { mo[i] = best; arg_out[i] = cand ? arg : -1; }
 }
 
 // Steps 1 - 4 on pass 1's per-candidate maximum and argmax (the argmax slot becomes gt_inds: -1 takes no part, 0 negative,
 // j + 1 gt j), and the histogram of the top 12 key bits per class.
 __global__ void __launch_bounds__(kThreads) rpn_pass2_kernel(StageArgs a) {
-    __shared__ Box s_box[kChunk];
-    __shared__ float s_area[kChunk];
-    __shared__ float s_gmax[kChunk];                        // the gt's maximum, NaN if it matches nothing
-    __shared__ int s_garg[kChunk];
+    __shared__ Pass2Lds s;
     __shared__ unsigned s_hist[2 * kBins];
     const int tid = threadIdx.x;
     const int b = blockIdx.y;
@@ -234,7 +174,7 @@ __global__ void __launch_bounds__(kThreads) rpn_pass2_kernel(StageArgs a) {
     const int32_t* keys = a.keys + (int64_t)b * a.g.A;
     const u64* ws = a.maxima + im.ws_off;
     const bool lq = a.low_quality != 0 && G > 0;
-    for (int k = tid; k < 2 * kBins; k += kThreads) s_hist[k] = 0u;
+    hist_clear<kThreads>(s_hist);
     __syncthreads();
     const int tiles = (a.g.A + kThreads - 1) / kThreads;
     const u64 zero_slot = lq ? ws[G] : 0ull;
@@ -257,304 +197,51 @@ __global__ void __launch_bounds__(kThreads) rpn_pass2_kernel(StageArgs a) {
         if (lq) {
             for (int g0 = 0; g0 < G; g0 += kChunk) {
                 const int cn = min(kChunk, G - g0);
-                __syncthreads();
-                if (tid < cn) {
-                    u64 p = ws[g0 + tid];
-                    p = p > zero_slot ? p : zero_slot;
-                    const float gm = p ? __uint_as_float((unsigned)(p >> 32) - 1u) : -1.0f;
-                    const int ga = p ? (int)~(unsigned)p : -1;
-                    const bool active = p != 0ull && gm >= a.min_pos;       // p == 0: no candidate takes part in this image
-                    s_gmax[tid] = active ? gm : __uint_as_float(0x7fc00000u);
-                    s_garg[tid] = active ? ga : -1;
-                    if (a.assign_all) {
-                        const Box q = load_box(im.gt + (int64_t)(g0 + tid) * im.ldg, false);
-                        s_box[tid] = q;
-                        s_area[tid] = box_area(q);
-                    }
-                }
-                __syncthreads();
+                step4_stage_chunk<true>(s, ws, zero_slot, a.min_pos, im.gt, im.ldg, g0, cn, a.assign_all != 0);
                 if (!cand) continue;
-                if (a.assign_all) {
-                    for (int j = 0; j < cn; ++j) {
-                        const float gm = s_gmax[j];
-                        if (!(gm <= mo)) continue;          // overlap(j, this) <= mo < gm, or gt j takes no part
-                        float inter;
-                        if (pair_iou(s_box[j], s_area[j], c, ca, inter) == gm) gi = g0 + j + 1;   // ascending: the highest gt wins
-                    }
-                } else {
-                    for (int j = 0; j < cn; ++j)
-                        if (s_garg[j] == i) gi = g0 + j + 1;
-                }
+                const int hit = step4_hit(s.box, s.area, s.gmax, s.garg, g0, cn, a.assign_all != 0, c, ca, mo, i, false);
+                if (hit) gi = hit;
             }
         }
         if (live) {
             gi_io[i] = gi;
-            if (gi >= 0) {
-                const unsigned key = (unsigned)keys[i] & 0x7fffffffu;
-                atomicAdd(&s_hist[(gi > 0 ? 0 : kBins) + (int)(key >> kLowBits)], 1u);
-            }
+            if (gi >= 0) hist_add(s_hist, gi > 0 ? 0 : 1, sample_key(keys[i]));
         }
     }
     __syncthreads();
-    unsigned* hist = a.hist + (int64_t)b * 2 * kBins;
-    for (int k = tid; k < 2 * kBins; k += kThreads)
-        if (s_hist[k] != 0u) atomicAdd(hist + k, s_hist[k]);
+    hist_flush<kThreads>(s_hist, a.hist + (int64_t)b * 2 * kBins);
 }
 
-// Exclusive prefix sums over the block's 1024 threads of two 32-bit counts packed in one word; `total` is the block's sum.
-__device__ __forceinline__ u64 block_scan_excl(u64 v, u64* s_w, u64& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
+// sample_select_core's policy for image b: the class from pass 2's int gt_inds, no flags, and - as the block that resolves the
+// boundary - the encode of each positive it places into pos_gt / pos_bt, zeros in their tails.
+struct RpnSelect : SelectViews {
+    static constexpr bool kFlags = false;
+    const StageArgs& a; const Img& im; const int* gi; const int32_t* keys; int64_t row0;
+    __device__ __forceinline__ RpnSelect(const StageArgs& a_, int b) : a(a_), im(a_.im[b]) {
+        N = a.g.A; nep = a.nep; num = a.num; ub = a.ub;
+        hist = a.hist + (int64_t)b * 2 * kBins; ticket = a.tickets + b; w = a.w + (int64_t)b * a.As;
+        row0 = (int64_t)b * a.nep;
+        pos_inds = a.pos_inds + row0; neg_inds = a.neg_inds + (int64_t)b * a.num; counts = a.counts + 2 * b;
+        gi = a.gi + (int64_t)b * a.As; keys = a.keys + (int64_t)b * N;
     }
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    if (wv == 0) {
-        const u64 x = lane < kSelThreads / 64 ? s_w[lane] : 0ull;
-        u64 xi = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u64 t = __shfl_up(xi, o, 64);
-            if (lane >= o) xi += t;
-        }
-        if (lane < kSelThreads / 64) s_w[lane] = xi - x;
-        if (lane == 63) s_w[kSelThreads / 64] = xi;
+    __device__ __forceinline__ int cls(int64_t i) const { const int g = gi[i]; return g < 0 ? -1 : (g > 0 ? 0 : 1); }
+    __device__ __forceinline__ unsigned key(int64_t i) const { return sample_key(keys[i]); }
+    __device__ __forceinline__ void placed(unsigned slot, int64_t idx) const {
+        int gt = gi[idx] - 1;
+        gt = gt < 0 ? 0 : (gt >= im.G ? im.G - 1 : gt);                // a positive has 1 <= gt_inds <= G
+        const Box anchor = make_anchor(a.g, a.bs, locate(a.g, (int)idx));
+        const Box gb = load_box(im.gt + (int64_t)gt * im.ldg, false);
+        a.pos_gt[row0 + slot] = gt;
+        *reinterpret_cast<f32x4*>(a.pos_bt + 4 * (row0 + slot)) = encode_delta(anchor, gb, a.nm);
     }
-    __syncthreads();
-    const u64 res = s_w[wv] + inc - v;
-    total = s_w[kSelThreads / 64];
-    __syncthreads();
-    return res;
-}
+    __device__ __forceinline__ void padded(int j) const {
+        const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+        a.pos_gt[row0 + j] = -1;
+        *reinterpret_cast<f32x4*>(a.pos_bt + 4 * (row0 + j)) = z;
+    }
+};
 
-__device__ __forceinline__ unsigned half_of(u64 v, int c) { return c ? (unsigned)(v >> 32) : (unsigned)v; }
-
-// four consecutive words of the per-candidate array from 4 g on (0 past the end)
-__device__ __forceinline__ u32x4 load_words(const unsigned* w, int64_t g, int N) {
-    const int64_t i = 4 * g;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (i + 3 < N) return *reinterpret_cast<const u32x4*>(w + i);
-    if (i < N) v.x = w[i];
-    if (i + 1 < N) v.y = w[i + 1];
-    if (i + 2 < N) v.z = w[i + 2];
-    return v;
-}
-
-__device__ __forceinline__ void find_bin(u64 mine, u64 ex, const unsigned* r, int* s_bin, unsigned* s_rem) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const unsigned e = half_of(ex, c), h = half_of(mine, c);
-        if (r[c] > 0u && e < r[c] && r[c] <= e + h) {
-            s_bin[c] = threadIdx.x;
-            s_rem[c] = r[c] - e;
-        }
-    }
-}
-
-// targets.hip's sample_select_kernel for image blockIdx.y, with the encode of the positives in the last block's sweep.
-__global__ void __launch_bounds__(kSelThreads) rpn_select_kernel(StageArgs a) {
-    __shared__ u64 s_scan[kSelThreads / 64 + 1];
-    __shared__ unsigned s_h[2 * 1024];
-    __shared__ int s_T[2], s_T2[2], s_T3[2];
-    __shared__ unsigned s_r[2], s_r2[2], s_r3[2];
-    __shared__ bool s_last;
-    const int tid = threadIdx.x;
-    const int b = blockIdx.y;
-    const Img& im = a.im[b];
-    const int N = a.g.A;
-    const unsigned* hist = a.hist + (int64_t)b * 2 * kBins;
-    const int* gi_in = a.gi + (int64_t)b * a.As;
-    const int32_t* keys = a.keys + (int64_t)b * N;
-    unsigned* w = a.w + (int64_t)b * a.As;
-    int64_t* pos_inds = a.pos_inds + (int64_t)b * a.nep;
-    int64_t* neg_inds = a.neg_inds + (int64_t)b * a.num;
-
-    // ---- class totals, budgets, threshold bins: every block for itself (thread t owns bins 4 t .. 4 t + 3 of both classes)
-    const u32x4 h0 = reinterpret_cast<const u32x4*>(hist)[tid];
-    const u32x4 h1 = reinterpret_cast<const u32x4*>(hist + kBins)[tid];
-    const unsigned c0 = h0.x + h0.y + h0.z + h0.w, c1 = h1.x + h1.y + h1.z + h1.w;
-    u64 total;
-    const u64 ex = block_scan_excl((u64)c0 | ((u64)c1 << 32), s_scan, total);
-    const long long P = (unsigned)total, Q = (unsigned)(total >> 32);
-    const long long kp = P < a.nep ? P : a.nep;                       // base_sampler.py:83-89
-    long long budget = a.num - kp;                                    // :90-95
-    if (a.ub >= 0.0) {
-        const double capd = a.ub * (double)(kp > 1 ? kp : 1);
-        if (capd < (double)budget) budget = (long long)capd;          // int(): truncation
-    }
-    const long long kn = Q < budget ? Q : budget;
-    const long long k[2] = {kp, kn}, M[2] = {P, Q};
-    if (tid < 2) {
-        s_T[tid] = k[tid] <= 0 ? -1 : kBins;                           // nothing / everything of the class, unless found below
-        s_r[tid] = 0u;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        if (k[c] > 0 && k[c] < M[c]) {
-            const u32x4 hh = c ? h1 : h0;
-            const unsigned hv[4] = {hh.x, hh.y, hh.z, hh.w};
-            long long cum = half_of(ex, c);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (cum < k[c] && k[c] <= cum + hv[j]) {
-                    s_T[c] = 4 * tid + j;
-                    s_r[c] = (unsigned)(k[c] - cum);
-                }
-                cum += hv[j];
-            }
-        }
-    }
-    __syncthreads();
-    const int T[2] = {s_T[0], s_T[1]};
-    const unsigned r[2] = {s_r[0], s_r[1]};
-
-    // ---- the grid-wide pass: one word per candidate (0 nothing, 1 / 2 selected, 3 + class << 19 | low key bits: boundary)
-    const int step = (int)gridDim.x * kSelThreads;
-    for (int i = (int)blockIdx.x * kSelThreads + tid; i < N; i += step) {
-        const int gi = gi_in[i];
-        unsigned ww = 0u;
-        if (gi >= 0) {
-            const int cls = gi > 0 ? 0 : 1;
-            const unsigned key = (unsigned)keys[i] & 0x7fffffffu;
-            const int bin = (int)(key >> kLowBits);
-            if (bin < T[cls]) ww = 1u + cls;
-            else if (bin == T[cls]) ww = 3u + (((unsigned)cls << kLowBits) | (key & kLowMask));
-        }
-        w[i] = ww;
-    }
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned t = __hip_atomic_fetch_add(a.tickets + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == gridDim.x - 1u;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-
-    // ---- the last block of the image, alone: the threshold key of each class among its boundary candidates
-    const int64_t groups = ((int64_t)N + 3) / 4;
-    if (tid < 2) { s_T2[tid] = 0; s_T3[tid] = 0; s_r2[tid] = 0u; s_r3[tid] = 0u; }
-    s_h[tid] = 0u;
-    s_h[1024 + tid] = 0u;
-    __syncthreads();
-    if (r[0] > 0u || r[1] > 0u) {
-        for (int64_t g = tid; g < groups; g += kSelThreads) {
-            const u32x4 v = load_words(w, g, N);
-            const unsigned e4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (e4[j] >= 3u) {
-                    const unsigned e = e4[j] - 3u;
-                    atomicAdd(&s_h[(e >> kLowBits) * 1024u + ((e & kLowMask) >> 9)], 1u);
-                }
-        }
-        __syncthreads();
-        const u64 mine = (u64)s_h[tid] | ((u64)s_h[1024 + tid] << 32);
-        u64 tot;
-        const u64 ex2 = block_scan_excl(mine, s_scan, tot);
-        find_bin(mine, ex2, r, s_T2, s_r2);
-        __syncthreads();
-        const int T2[2] = {s_T2[0], s_T2[1]};
-        const unsigned r2[2] = {s_r2[0], s_r2[1]};
-        s_h[tid] = 0u;
-        __syncthreads();
-        for (int64_t g = tid; g < groups; g += kSelThreads) {
-            const u32x4 v = load_words(w, g, N);
-            const unsigned e4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (e4[j] >= 3u) {
-                    const unsigned e = e4[j] - 3u;
-                    const unsigned cls = e >> kLowBits, low = e & kLowMask;
-                    if ((int)(low >> 9) == T2[cls]) atomicAdd(&s_h[cls * 512u + (low & 511u)], 1u);
-                }
-        }
-        __syncthreads();
-        const u64 mine3 = tid < 512 ? ((u64)s_h[tid] | ((u64)s_h[512 + tid] << 32)) : 0ull;
-        const u64 ex3 = block_scan_excl(mine3, s_scan, tot);
-        find_bin(mine3, ex3, r2, s_T3, s_r3);
-        __syncthreads();
-    }
-    unsigned K[2], r3[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        K[c] = ((unsigned)s_T2[c] << 9) | (unsigned)s_T3[c];
-        r3[c] = s_r3[c];
-    }
-
-    // ---- the ordered sweep: tile by tile in index order; among the candidates with exactly the threshold key the first r3
-    u64 run_eq = 0ull, run_sel = 0ull;
-    const int64_t tiles = (groups + kSelThreads - 1) / kSelThreads;
-    for (int64_t t = 0; t < tiles; ++t) {
-        const int64_t g = t * kSelThreads + tid;
-        const u32x4 v = load_words(w, g, N);
-        const unsigned e4[4] = {v.x, v.y, v.z, v.w};
-        int cls4[4], kind4[4];                                         // kind: 0 not selected, 1 selected, 2 has the threshold key
-        u64 eq = 0ull;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            cls4[j] = 0; kind4[j] = 0;
-            if (e4[j] == 1u || e4[j] == 2u) { cls4[j] = (int)e4[j] - 1; kind4[j] = 1; }
-            else if (e4[j] >= 3u) {
-                const unsigned e = e4[j] - 3u;
-                const unsigned low = e & kLowMask;
-                cls4[j] = (int)(e >> kLowBits);
-                if (low < K[cls4[j]]) kind4[j] = 1;
-                else if (low == K[cls4[j]]) { kind4[j] = 2; eq += cls4[j] ? (1ull << 32) : 1ull; }
-            }
-        }
-        u64 tot;
-        u64 rank = block_scan_excl(eq, s_scan, tot) + run_eq;
-        run_eq += tot;
-        u64 sel = 0ull;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (kind4[j] == 2) {
-                kind4[j] = half_of(rank, cls4[j]) < r3[cls4[j]] ? 1 : 0;
-                rank += cls4[j] ? (1ull << 32) : 1ull;
-            }
-            if (kind4[j] == 1) sel += cls4[j] ? (1ull << 32) : 1ull;
-        }
-        u64 at = block_scan_excl(sel, s_scan, tot) + run_sel;
-        run_sel += tot;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t idx = 4 * g + j;
-            if (kind4[j] != 1) continue;
-            const unsigned slot = half_of(at, cls4[j]);
-            at += cls4[j] ? (1ull << 32) : 1ull;
-            if (cls4[j] == 1) {
-                if ((long long)slot < kn) neg_inds[slot] = idx;
-                continue;
-            }
-            if ((long long)slot >= kp) continue;                       // cannot happen: the select takes exactly k
-            pos_inds[slot] = idx;
-            int gt = gi_in[idx] - 1;
-            gt = gt < 0 ? 0 : (gt >= im.G ? im.G - 1 : gt);            // a positive has 1 <= gt_inds <= G
-            const Box anchor = make_anchor(a.g, a.bs, locate(a.g, (int)idx));
-            const Box gb = load_box(im.gt + (int64_t)gt * im.ldg, false);
-            const int64_t row = (int64_t)b * a.nep + slot;
-            a.pos_gt[row] = gt;
-            *reinterpret_cast<f32x4*>(a.pos_bt + 4 * row) = encode_delta(anchor, gb, a.nm);
-        }
-    }
-    const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (long long j = kp + tid; j < a.nep; j += kSelThreads) {
-        pos_inds[j] = -1;
-        a.pos_gt[(int64_t)b * a.nep + j] = -1;
-        *reinterpret_cast<f32x4*>(a.pos_bt + 4 * ((int64_t)b * a.nep + j)) = z;
-    }
-    for (long long j = kn + tid; j < a.num; j += kSelThreads) neg_inds[j] = -1;
-    if (tid == 0) {
-        a.counts[2 * b] = kp;
-        a.counts[2 * b + 1] = kn;
-    }
-}
+__global__ void __launch_bounds__(kSelThreads) rpn_select_kernel(StageArgs a) { sample_select_core(RpnSelect(a, blockIdx.y)); }
 
 __global__ void __launch_bounds__(64) rpn_total_kernel(const int64_t* counts, int B, float* out) {
     const int lane = threadIdx.x;

@@ -9,15 +9,9 @@
 //                        members than its budget k keeps the k SMALLEST (key, index) pairs - equal keys go to the lower index.
 //     clear   the 2 x 4096 counters and the ticket.
 //     pass 1  (grid) histogram of the top 12 key bits per class: LDS atomics, flushed with integer global atomics.
-//     pass 2  (grid) every block scans the counters: class totals, hence both budgets (the negative budget follows from the
-//             positive total), each class's threshold bin T and the number r it must still take from that bin.  A candidate
-//             below T is selected outright, one in T is a BOUNDARY candidate; pass 2 leaves one word per candidate in the
-//             workspace (0 nothing, 1 / 2 selected, 3 + class << 19 | low 19 key bits: boundary) and the flags of all but the
-//             boundary candidates.  The last block to finish (a ticket) then works alone on those words: two more digit
-//             histograms (10 and 9 bits) give each class's threshold KEY and the number to take among the candidates that
-//             have exactly that key; one ordered sweep (block scans, tile by tile) takes them in index order and writes the
-//             index lists - ascending because the sweep is - and the boundary candidates' flags.  The boundary may be all N
-//             candidates (equal keys): nothing here depends on its length.
+//     pass 2  (grid) sample_select_core (sample_core.h, where the select is described) on the int64 gt_inds, with the flags:
+//             budgets and threshold bins per block, one word per candidate, and the last block to finish (a ticket) resolves
+//             the boundary bin and writes the ascending index lists.
 //     Each of gt_inds and keys is read twice (pass 1, pass 2).  Integer atomics only: the result does not depend on arrival order.
 //   iif_anchor_targets   dense_heads/anchor_head.py:224-265 with unmap_outputs: defaults, scatter, encode, unmap; one lane per
 //                        anchor of the full set.
@@ -28,20 +22,15 @@
 // -ffp-contract=off; `/` is the correctly rounded division); logf / expf are the device library's.
 #include "common.h"
 #include "box_coder.h"
+#include "sample_core.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kSelThreads = 1024;             // both sampler kernels; the last block's sweep is written for exactly this
-constexpr int kBins = 4096;                   // top 12 of the 31 key bits
-constexpr int kLowBits = 19;
-constexpr unsigned kLowMask = (1u << kLowBits) - 1u;
 constexpr int kSampleMaxBlocks = 64;
 constexpr int kTicketWord = 2 * kBins;        // workspace, in 32-bit words: [0, 8192) counters, [8192] ticket
 constexpr int kWordsOffset = 65536 / 4;       // the per-candidate words start 64 KiB in
 constexpr unsigned kMaxBlocks = 1u << 16;
-
-typedef unsigned long long u64;
 
 struct EncArgs { const float* p; int64_t ldp; int vecp; const float* g; int64_t ldg; int vecg; int64_t n; Norm nm; float* out; };
 
@@ -85,254 +74,34 @@ struct SampleArgs {
 __global__ void __launch_bounds__(kSelThreads) sample_hist_kernel(SampleArgs a) {
     __shared__ unsigned h[2 * kBins];
     const int tid = threadIdx.x;
-    for (int i = tid; i < 2 * kBins; i += kSelThreads) h[i] = 0u;
+    hist_clear<kSelThreads>(h);
     __syncthreads();
     const int64_t step = (int64_t)gridDim.x * kSelThreads;
     for (int64_t i = (int64_t)blockIdx.x * kSelThreads + tid; i < a.N; i += step) {
         const int64_t gi = a.gt_inds[i];
-        if (gi >= 0) {
-            const unsigned key = (unsigned)a.keys[i] & 0x7fffffffu;
-            atomicAdd(&h[(gi > 0 ? 0 : kBins) + (int)(key >> kLowBits)], 1u);
-        }
+        if (gi >= 0) hist_add(h, gi > 0 ? 0 : 1, sample_key(a.keys[i]));
     }
     __syncthreads();
-    for (int i = tid; i < 2 * kBins; i += kSelThreads)
-        if (h[i] != 0u) atomicAdd(a.hist + i, h[i]);
+    hist_flush<kSelThreads>(h, a.hist);
 }
 
-// Exclusive prefix sums over the block's 1024 threads of two 32-bit counts packed in one word (neither half reaches 2^31);
-// `total` is the block's sum.  s_w: 17 words of LDS; reusable after the call returns.
-__device__ __forceinline__ u64 block_scan_excl(u64 v, u64* s_w, u64& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    if (wv == 0) {
-        const u64 x = lane < kSelThreads / 64 ? s_w[lane] : 0ull;
-        u64 xi = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u64 t = __shfl_up(xi, o, 64);
-            if (lane >= o) xi += t;
-        }
-        if (lane < kSelThreads / 64) s_w[lane] = xi - x;
-        if (lane == 63) s_w[kSelThreads / 64] = xi;
-    }
-    __syncthreads();
-    const u64 res = s_w[wv] + inc - v;
-    total = s_w[kSelThreads / 64];
-    __syncthreads();
-    return res;
-}
-
-__device__ __forceinline__ unsigned half_of(u64 v, int c) { return c ? (unsigned)(v >> 32) : (unsigned)v; }
-
-// four consecutive words of the per-candidate array from 4 g on (0 past the end)
-__device__ __forceinline__ u32x4 load_words(const unsigned* w, int64_t g, int N) {
-    const int64_t i = 4 * g;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (i + 3 < N) return *reinterpret_cast<const u32x4*>(w + i);
-    if (i < N) v.x = w[i];
-    if (i + 1 < N) v.y = w[i + 1];
-    if (i + 2 < N) v.z = w[i + 2];
-    return v;
-}
-
-// the bin of `h` (this thread's count of bin threadIdx.x, per class) in which the r-th smallest of a class falls, r >= 1
-__device__ __forceinline__ void find_bin(u64 mine, u64 ex, const unsigned* r, int* s_bin, unsigned* s_rem) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const unsigned e = half_of(ex, c), h = half_of(mine, c);
-        if (r[c] > 0u && e < r[c] && r[c] <= e + h) {
-            s_bin[c] = threadIdx.x;
-            s_rem[c] = r[c] - e;
-        }
-    }
-}
+// sample_select_core's policy for one flat candidate set: the class from int64 gt_inds, the flags written, nothing else per positive
+struct FlatSelect : SelectViews {
+    static constexpr bool kFlags = true;
+    const int64_t* gt_inds; const int32_t* keys; int8_t* flags;
+    __device__ __forceinline__ int cls(int64_t i) const { const int64_t gi = gt_inds[i]; return gi < 0 ? -1 : (gi > 0 ? 0 : 1); }
+    __device__ __forceinline__ unsigned key(int64_t i) const { return sample_key(keys[i]); }
+    __device__ __forceinline__ void placed(unsigned, int64_t) const {}
+    __device__ __forceinline__ void padded(int) const {}
+};
 
 __global__ void __launch_bounds__(kSelThreads) sample_select_kernel(SampleArgs a) {
-    __shared__ u64 s_scan[kSelThreads / 64 + 1];
-    __shared__ unsigned s_h[2 * 1024];
-    __shared__ int s_T[2], s_T2[2], s_T3[2];
-    __shared__ unsigned s_r[2], s_r2[2], s_r3[2];
-    __shared__ bool s_last;
-    const int tid = threadIdx.x;
-
-    // ---- class totals, budgets, threshold bins: every block for itself (thread t owns bins 4 t .. 4 t + 3 of both classes)
-    const u32x4 h0 = reinterpret_cast<const u32x4*>(a.hist)[tid];
-    const u32x4 h1 = reinterpret_cast<const u32x4*>(a.hist + kBins)[tid];
-    const unsigned c0 = h0.x + h0.y + h0.z + h0.w, c1 = h1.x + h1.y + h1.z + h1.w;
-    u64 total;
-    const u64 ex = block_scan_excl((u64)c0 | ((u64)c1 << 32), s_scan, total);
-    const long long P = (unsigned)total, Q = (unsigned)(total >> 32);
-    const long long kp = P < a.nep ? P : a.nep;                       // base_sampler.py:83-89
-    long long budget = a.num - kp;                                    // :90-95
-    if (a.ub >= 0.0) {
-        const double capd = a.ub * (double)(kp > 1 ? kp : 1);
-        if (capd < (double)budget) budget = (long long)capd;          // int(): truncation
-    }
-    const long long kn = Q < budget ? Q : budget;
-    const long long k[2] = {kp, kn}, M[2] = {P, Q};
-    if (tid < 2) {
-        s_T[tid] = k[tid] <= 0 ? -1 : kBins;                           // nothing / everything of the class, unless found below
-        s_r[tid] = 0u;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        if (k[c] > 0 && k[c] < M[c]) {
-            const u32x4 hh = c ? h1 : h0;
-            const unsigned hv[4] = {hh.x, hh.y, hh.z, hh.w};
-            long long cum = half_of(ex, c);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (cum < k[c] && k[c] <= cum + hv[j]) {
-                    s_T[c] = 4 * tid + j;
-                    s_r[c] = (unsigned)(k[c] - cum);
-                }
-                cum += hv[j];
-            }
-        }
-    }
-    __syncthreads();
-    const int T[2] = {s_T[0], s_T[1]};
-    const unsigned r[2] = {s_r[0], s_r[1]};
-
-    // ---- the grid-wide pass: one word per candidate, the flags of all but the boundary candidates
-    const int64_t step = (int64_t)gridDim.x * kSelThreads;
-    for (int64_t i = (int64_t)blockIdx.x * kSelThreads + tid; i < a.N; i += step) {
-        const int64_t gi = a.gt_inds[i];
-        unsigned ww = 0u;
-        bool boundary = false;
-        if (gi >= 0) {
-            const int cls = gi > 0 ? 0 : 1;
-            const unsigned key = (unsigned)a.keys[i] & 0x7fffffffu;
-            const int bin = (int)(key >> kLowBits);
-            if (bin < T[cls]) ww = 1u + cls;
-            else if (bin == T[cls]) { ww = 3u + (((unsigned)cls << kLowBits) | (key & kLowMask)); boundary = true; }
-        }
-        a.w[i] = ww;
-        if (!boundary) a.flags[i] = (int8_t)ww;
-    }
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == gridDim.x - 1u;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-
-    // ---- the last block, alone: the threshold key of each class among its boundary candidates, low 19 bits in two digits
-    const int64_t groups = ((int64_t)a.N + 3) / 4;
-    if (tid < 2) { s_T2[tid] = 0; s_T3[tid] = 0; s_r2[tid] = 0u; s_r3[tid] = 0u; }
-    s_h[tid] = 0u;
-    s_h[1024 + tid] = 0u;
-    __syncthreads();
-    if (r[0] > 0u || r[1] > 0u) {
-        for (int64_t g = tid; g < groups; g += kSelThreads) {
-            const u32x4 v = load_words(a.w, g, a.N);
-            const unsigned e4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (e4[j] >= 3u) {
-                    const unsigned e = e4[j] - 3u;
-                    atomicAdd(&s_h[(e >> kLowBits) * 1024u + ((e & kLowMask) >> 9)], 1u);
-                }
-        }
-        __syncthreads();
-        const u64 mine = (u64)s_h[tid] | ((u64)s_h[1024 + tid] << 32);
-        u64 tot;
-        const u64 ex2 = block_scan_excl(mine, s_scan, tot);
-        find_bin(mine, ex2, r, s_T2, s_r2);
-        __syncthreads();
-        const int T2[2] = {s_T2[0], s_T2[1]};
-        const unsigned r2[2] = {s_r2[0], s_r2[1]};
-        s_h[tid] = 0u;
-        __syncthreads();
-        for (int64_t g = tid; g < groups; g += kSelThreads) {
-            const u32x4 v = load_words(a.w, g, a.N);
-            const unsigned e4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (e4[j] >= 3u) {
-                    const unsigned e = e4[j] - 3u;
-                    const unsigned cls = e >> kLowBits, low = e & kLowMask;
-                    if ((int)(low >> 9) == T2[cls]) atomicAdd(&s_h[cls * 512u + (low & 511u)], 1u);
-                }
-        }
-        __syncthreads();
-        const u64 mine3 = tid < 512 ? ((u64)s_h[tid] | ((u64)s_h[512 + tid] << 32)) : 0ull;
-        const u64 ex3 = block_scan_excl(mine3, s_scan, tot);
-        find_bin(mine3, ex3, r2, s_T3, s_r3);
-        __syncthreads();
-    }
-    unsigned K[2], r3[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        K[c] = ((unsigned)s_T2[c] << 9) | (unsigned)s_T3[c];
-        r3[c] = s_r3[c];
-    }
-
-    // ---- the ordered sweep: tile by tile in index order; among the candidates with exactly the threshold key the first r3
-    u64 run_eq = 0ull, run_sel = 0ull;
-    const int64_t tiles = (groups + kSelThreads - 1) / kSelThreads;
-    for (int64_t t = 0; t < tiles; ++t) {
-        const int64_t g = t * kSelThreads + tid;
-        const u32x4 v = load_words(a.w, g, a.N);
-        const unsigned e4[4] = {v.x, v.y, v.z, v.w};
-        int cls4[4], kind4[4];                                         // kind: 0 not selected, 1 selected, 2 has the threshold key
-        u64 eq = 0ull;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            cls4[j] = 0; kind4[j] = 0;
-            if (e4[j] == 1u || e4[j] == 2u) { cls4[j] = (int)e4[j] - 1; kind4[j] = 1; }
-            else if (e4[j] >= 3u) {
-                const unsigned e = e4[j] - 3u;
-                const unsigned low = e & kLowMask;
-                cls4[j] = (int)(e >> kLowBits);
-                if (low < K[cls4[j]]) kind4[j] = 1;
-                else if (low == K[cls4[j]]) { kind4[j] = 2; eq += cls4[j] ? (1ull << 32) : 1ull; }
-            }
-        }
-        u64 tot;
-        u64 rank = block_scan_excl(eq, s_scan, tot) + run_eq;
-        run_eq += tot;
-        u64 sel = 0ull;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (kind4[j] == 2) {
-                kind4[j] = half_of(rank, cls4[j]) < r3[cls4[j]] ? 1 : 0;
-                rank += cls4[j] ? (1ull << 32) : 1ull;
-            }
-            if (kind4[j] == 1) sel += cls4[j] ? (1ull << 32) : 1ull;
-        }
-        u64 at = block_scan_excl(sel, s_scan, tot) + run_sel;
-        run_sel += tot;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t idx = 4 * g + j;
-            if (e4[j] >= 3u) a.flags[idx] = (int8_t)(kind4[j] == 1 ? 1 + cls4[j] : 0);
-            if (kind4[j] == 1) {
-                const unsigned slot = half_of(at, cls4[j]);
-                if (cls4[j] == 0) { if ((long long)slot < a.nep) a.pos_inds[slot] = idx; }
-                else if ((long long)slot < a.num) a.neg_inds[slot] = idx;
-                at += cls4[j] ? (1ull << 32) : 1ull;
-            }
-        }
-    }
-    for (long long j = kp + tid; j < a.nep; j += kSelThreads) a.pos_inds[j] = -1;
-    for (long long j = kn + tid; j < a.num; j += kSelThreads) a.neg_inds[j] = -1;
-    if (tid == 0) {
-        a.counts[0] = kp;
-        a.counts[1] = kn;
-    }
+    FlatSelect p;
+    p.N = a.N; p.nep = a.nep; p.num = a.num; p.ub = a.ub;
+    p.hist = a.hist; p.ticket = a.ticket; p.w = a.w;
+    p.pos_inds = a.pos_inds; p.neg_inds = a.neg_inds; p.counts = a.counts;
+    p.gt_inds = a.gt_inds; p.keys = a.keys; p.flags = a.flags;
+    sample_select_core(p);
 }
 
 // ------------------------------------------------------------------------------------------------ target builders

@@ -140,19 +140,7 @@ def roi_stage_targets_padded(proposals, proposal_counts, gt_bboxes_list, gt_labe
         keys = torch.randint(0, 2 ** 31, (B, gmax + P), dtype=torch.int32, device=dev)
     else:
         keys = keys.contiguous()
-    images = (_lib.RoiImage * B)()
-    held = []
-    for b, (g, l) in enumerate(zip(gt_bboxes_list, gt_labels_list)):
-        g = g.detach()
-        if Gs[b] and (g.stride(1) != 1 or (Gs[b] > 1 and g.stride(0) < 4)):
-            g = g.contiguous()
-        l = l.reshape(-1).to(torch.int64).contiguous()
-        held += [g, l]
-        images[b].gt_bboxes = _lib.ptr(g) if Gs[b] else None
-        images[b].ld_gt = g.stride(0) if Gs[b] > 1 else 4
-        images[b].gt_labels = _lib.ptr(l) if Gs[b] else None
-        images[b].G = Gs[b]
-        images[b].img_index = b
+    images, held = _lib.roi_images(gt_bboxes_list, gt_labels_list)
     neg_lo, neg_hi = assigner._neg_range()
     means, stds = _coder_norm(coder)
     f32, i64 = torch.float32, torch.int64

@@ -105,19 +105,8 @@ def rpn_stage_targets(featmap_sizes, anchor_generator, pad_shapes, img_shapes, g
         for b in range(B):
             img_h, img_w = img_shapes[b][:2]
             hi[2 * b], hi[2 * b + 1] = float(img_w + allowed_border), float(img_h + allowed_border)
-    images = (_lib.RoiImage * B)()
-    held = []
+    images, held = _lib.roi_images(gt_bboxes_list)
     Gs = [int(g.shape[0]) for g in gt_bboxes_list]
-    for b, g in enumerate(gt_bboxes_list):
-        g = g.detach()
-        if Gs[b] and (g.stride(1) != 1 or (Gs[b] > 1 and g.stride(0) < 4)):
-            g = g.contiguous()
-        held.append(g)
-        images[b].gt_bboxes = _lib.ptr(g) if Gs[b] else None
-        images[b].ld_gt = g.stride(0) if Gs[b] > 1 else 4
-        images[b].gt_labels = None
-        images[b].G = Gs[b]
-        images[b].img_index = b
     if keys is None:
         keys = torch.randint(0, 2 ** 31, (B, A), dtype=torch.int32, device=dev)
     else:

@@ -205,6 +205,19 @@ def test_rows_equal_the_chain_bit_for_bit(valid, G):
         assert_equals_chain(t, gen, featmaps, [pad], [pad], gts, asg, smp, coder, keys, -1)
 
 
+def test_row_with_every_key_in_one_bin_equals_the_chain():
+    """tc.one_bin_keys on a row of A = 4100 anchors: two sweep tiles of the select, every candidate a boundary candidate, tied keys."""
+    from iif_amd.mmdet_rpn_stage import rpn_stage_targets
+    valid = tc.ONE_BIN_N - 3
+    gen, featmaps, pad = row_generator(valid)
+    gts = [T(row_gts(257, valid, 9650))]
+    keys = T(tc.one_bin_keys()).reshape(1, tc.ONE_BIN_N)
+    for num, frac, ub in tc.ONE_BIN_BUDGETS:
+        asg, smp, coder = parts(num=num, frac=frac, ub=ub, means=tc.MEANS[1], stds=tc.STDS[1])
+        t = rpn_stage_targets(featmaps, gen, [pad], [pad], gts, asg, smp, coder, allowed_border=-1, keys=keys)
+        assert_equals_chain(t, gen, featmaps, [pad], [pad], gts, asg, smp, coder, keys, -1)
+
+
 @pytest.mark.parametrize("border", [-1, 0])
 def test_three_images_and_equal_keys_equal_the_chain(border):
     from iif_amd.mmdet_rpn_stage import rpn_stage_targets

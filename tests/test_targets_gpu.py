@@ -102,6 +102,20 @@ def test_sampler_with_colliding_keys_equals_the_restatement(kind):
         check_padded(p, N, pos, neg, int(num * frac), num)
 
 
+def test_sampler_with_every_key_in_one_bin_equals_the_restatement():
+    """tc.one_bin_keys: two sweep tiles, every candidate a boundary candidate, the threshold key found by the two low-digit
+    histograms and tied (test_targets_host.py checks that the selection cuts through the tie)."""
+    from iif_amd.mmdet_targets import RandomSampler
+    keys, gi = tc.one_bin_keys(), tc.one_bin_gt_inds()
+    N = gi.size
+    bboxes = torch.zeros((N, 4), device=DEV)
+    gts = torch.zeros((tc.G_DEFAULT, 4), device=DEV)
+    for num, frac, ub in tc.ONE_BIN_BUDGETS:
+        pos, neg = tc.sample_np(gi, keys, num, frac, ub)
+        p = RandomSampler(num, frac, neg_pos_ub=ub, add_gt_as_proposals=False).sample_padded(assign_result(gi), bboxes, gts, keys=T(keys))
+        check_padded(p, N, pos, neg, int(num * frac), num)
+
+
 def test_sampler_edge_sizes():
     """No candidates at all, a zero budget, and a budget of everything."""
     from iif_amd.mmdet_targets import RandomSampler

@@ -57,6 +57,19 @@ def test_selection_rule_with_colliding_keys():
     assert pos.tolist() == [1, 2] and neg.tolist() == [4]
 
 
+def test_one_bin_case_cuts_through_a_tie_at_the_threshold_key():
+    """What the GPU tests on tc.one_bin_keys rely on: one bin of the top 12 key bits, both classes over budget, and for each
+    budget a class whose threshold key has more members than the selection takes from them."""
+    keys, gi = tc.one_bin_keys(), tc.one_bin_gt_inds()
+    assert keys.size == 4100 and np.unique(keys >> 19).size == 1 and np.array_equal(keys[4::5], keys[3::5])
+    ties = []
+    for num, frac, ub in tc.ONE_BIN_BUDGETS:
+        pos, neg = tc.sample_np(gi, keys, num, frac, ub)
+        assert 0 < pos.size < (gi > 0).sum() and 0 < neg.size < (gi == 0).sum()
+        ties.append(tc.threshold_ties(gi, keys, pos, neg))
+    assert ties == [[0, 1], [1, 0]]
+
+
 @pytest.mark.parametrize("name", list(tc.ENCODE_CASES))
 def test_encode_restatement_against_the_fixture(golden, name):
     g = golden(FIXTURE)
