@@ -36,6 +36,7 @@ SIGNATURES = {
     "iif_mix_rows": [_P, _I, _P, _F, _I, _L, _P, _P],
     "iif_conv_igemm": [_P, _P, _P, _P, _P, _P, _P],
     "iif_conv_wgrad": [_P, _P, _P, _P, _P, _L, _I, _P],
+    "iif_conv_wgrad_plan": [_P, _I, _L, _I, _P],
     "iif_conv_igemm_bnstats": [_P, _P, _P, _P, _P, _P, _P, _L, _P, _P],
     "iif_bn_finalize_stats": [_P, _I, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _L, _P],
     "iif_bn_finalize_stats_fused": [_P, _I, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _L, _P, _P],

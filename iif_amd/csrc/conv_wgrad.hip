@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "wgrad_plan.h"
 #ifndef IIF_WG_AUX_X
 #define IIF_WG_AUX_X 0
 #endif
@@ -1019,165 +1020,100 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* ws, int 
 // slab traffic of a launch is (blocks in the round) x (tile bytes): 75 MB written + read again by the nine-tap kernel, 32 MB
 // by the 256 x 128 1x1 kernel, ~4 GB of the step's 73 (profiles/r5_d_pmc_hbm_traffic.csv).  Two half rounds side by side
 // keep the device as full with half of that.
-inline int share_of(int splits_req) { return splits_req < 0 ? -splits_req : 1; }
+// (share_of, the automatic rounds, the workspace fit and the choice between one pass and two stages: wgrad_plan.h)
+using iif_plan::WgPlan;
+using iif_plan::WgShape;
 
 inline int reduce_slabs(float* ws, int64_t ws_bytes, int splits, int64_t slab, int rows, int ldw, int K, float* dw, hipStream_t st) {
-    const int64_t total4 = slab / 4;
-    const int blocks = (int)(cdiv64(total4, 256) < 2048 ? cdiv64(total4, 256) : 2048);
-    // few elements x many slabs: sum chunks of 16 slabs in parallel first (into the slab area itself:
-    // chunk c writes slab c, which only chunk 0 reads, and chunk 0's own slab 0 is read before written
-    // by the same thread), then one pass over the <= ceil(splits/16) chunk sums
-    if (splits > 32 && blocks * 256 < 65536) {
-        const int chunk = 16, nch = (splits + chunk - 1) / chunk;
-        float* stage = ws + (int64_t)splits * slab;       // needs nch more slabs of workspace
-        if ((int64_t)(splits + nch) * slab * 4 <= ws_bytes) {
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks, nch), dim3(256), 0, st, ws, splits, chunk, slab, rows, ldw, K, stage, slab);
-            IIF_LAUNCH_CHECK();
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks, 1), dim3(256), 0, st, stage, nch, nch, slab, rows, ldw, K, dw, (int64_t)0);
-            IIF_LAUNCH_CHECK();
-            return IIF_OK;
-        }
+    const iif_plan::ReducePlan r = iif_plan::reduce_plan(splits, slab, ws_bytes);
+    const int blocks = r.blocks;
+    // few elements x many slabs: sum chunks of 16 slabs in parallel first, chunk c into slab c of a stage area BEHIND the
+    // `splits` slabs (no slab is overwritten), then one pass over the ceil(splits/16) chunk sums
+    if (r.stages == 2) {
+        const int chunk = 16, nch = r.nch;
+        float* stage = ws + (int64_t)splits * slab;       // nch more slabs of workspace (reduce_plan checked the room)
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks, nch), dim3(256), 0, st, ws, splits, chunk, slab, rows, ldw, K, stage, slab);
+        IIF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks, 1), dim3(256), 0, st, stage, nch, nch, slab, rows, ldw, K, dw, (int64_t)0);
+        IIF_LAUNCH_CHECK();
+        return IIF_OK;
     }
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks, 1), dim3(256), 0, st, ws, splits, splits, slab, rows, ldw, K, dw, (int64_t)0);
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }
 
+// what wgrad_plan.h reads of a launch
+inline WgShape shape_of(const WgArgs& a, int esz, int64_t x_bytes, int64_t dy_bytes, bool stacked = false, int cd2 = 0) {
+    WgShape s{};
+    s.N = a.N; s.Hs = a.Hs; s.Ws = a.Ws; s.Cs = a.Cs; s.Hd = a.Hd; s.Wd = a.Wd; s.Cd = a.Cd; s.R = a.R; s.S = a.S;
+    s.sshift = a.sshift; s.pad = a.pad; s.ldw = a.ldw; s.M = a.M; s.K = a.K; s.groups = a.groups; s.xpitch = a.xpitch;
+    s.ypitch = a.ypitch; s.esz = esz; s.cd2 = cd2; s.stacked = stacked; s.gram = a.x == a.dy && !stacked;
+    s.x_bytes = x_bytes; s.dy_bytes = dy_bytes;
+    return s;
+}
+
 // all nine taps per block (conv3x3_wgrad_halo_kernel): 3x3 / stride 1 / pad 1, dense, bf16, channels in 64s, W <= 61
-inline int launch_wgrad_halo(const WgArgs& a, float* dw, float* ws, int64_t ws_bytes, int splits_req, int64_t x_bytes,
+inline int launch_wgrad_halo(const WgArgs& a, const WgPlan& p, float* dw, float* ws, int64_t ws_bytes, int64_t x_bytes,
                              int64_t dy_bytes, hipStream_t st) {
     WgHaloArgs h{};
     h.x = a.x; h.dy = a.dy; h.N = a.N; h.H = a.Hd; h.W = a.Wd; h.Cs = a.xpitch; h.Cd = a.ypitch; h.ldw = a.ldw;
     h.grouped = a.groups > 1;
-    h.ci_tiles = h.grouped ? a.groups : a.Cs / 64; h.co_tiles = h.grouped ? 1 : a.Cd / 64;
-    h.HB = a.Wd + 3 <= 32 ? 32 : 64;
-    const int64_t vt = (int64_t)a.N * (a.Hd + 2) * (a.Wd + 2);
-    if (vt > 0x7fff0000LL) return -100;            // beyond the 32-bit virtual index: caller falls back
-    h.nsteps = (int)((vt + 31) / 32);
-    const int tiles = h.ci_tiles * h.co_tiles;
-    int splits = splits_req;
-    if (splits <= 0) {
-        const int per_cu = 2;
-        // grouped layers (ResNeXt: the weight gradient is block-diagonal, 8 chunks x 147 KB at 14 x 14 against 51 MB of operands) take
-        // a quarter of a round: ResNeXt-101 20.80 / 20.87 (full) -> 20.37 (half) -> 20.36 / 20.29 (quarter) -> 21.0 (eighth) ms per step;
-        // dense layers keep the full round (ResNet-50: 16.57 -> 16.65 with half)
-        static const int halo_div = [] { const char* e = getenv("IIF_WGRAD_HALO_DIV"); return e ? atoi(e) : 1; }();
-        static const int halo_gdiv = [] { const char* e = getenv("IIF_WGRAD_HALO_GROUPED_DIV"); return e ? atoi(e) : 4; }();
-        const int hdiv = h.grouped ? halo_gdiv : halo_div;
-        splits = 256 * per_cu / share_of(splits_req) / tiles / (hdiv > 0 ? hdiv : 1);
-        if (splits < 1) splits = 1;
-        const int max_by_work = h.nsteps / 8 > 0 ? h.nsteps / 8 : 1;
-        if (splits > max_by_work) splits = max_by_work;
-    }
-    const int64_t slab = (int64_t)a.groups * a.Cd * a.ldw;
-    const int64_t fit = ws ? ws_bytes / (slab * 4) : 0;
-    if (splits > fit) splits = (int)fit;
-    if (splits < 1) splits = 1;
-    if (splits > h.nsteps) splits = h.nsteps;
-    if (splits > 65535) splits = 65535;
-    h.steps_per_split = (h.nsteps + splits - 1) / splits;
-    splits = (h.nsteps + h.steps_per_split - 1) / h.steps_per_split;
-    h.slab = splits > 1 ? slab : 0;
+    h.ci_tiles = p.ntiles; h.co_tiles = p.ktiles;
+    h.HB = p.HB;
+    h.nsteps = p.nsteps;
+    const int splits = p.splits;
+    h.steps_per_split = p.steps_per_split;
+    h.slab = splits > 1 ? p.slab : 0;
     h.out = splits > 1 ? ws : dw;
     h.nsplits = splits;
-    const dim3 grid((unsigned)(tiles * ((splits + 7) / 8) * 8));
+    const dim3 grid((unsigned)p.blocks);               // tiles x splits rounded up to 8
     // 8-block x ring, 4-block dy ring, two block pairs in flight (48 KB, two blocks per CU).  Deeper rings were
     // measured: <8,8,4> equal at W <= 29, <16,8,6> (one block per CU) 10 % slower at 56x56 -- the issue phase is
     // bound by the DMA path, not by latency.
     hipLaunchKernelGGL((conv3x3_wgrad_halo_kernel<8, 4, 2>), grid, dim3(256), 0, st, h, (unsigned)x_bytes, (unsigned)dy_bytes);
     IIF_LAUNCH_CHECK();
-    if (splits > 1) return reduce_slabs(ws, ws_bytes, splits, slab, a.groups * a.Cd, a.ldw, a.K, dw, st);
+    if (splits > 1) return reduce_slabs(ws, ws_bytes, splits, p.slab, p.rows, a.ldw, a.K, dw, st);
     return IIF_OK;
 }
 
 // all sixteen taps per block for the space-to-depth stem (conv4x4_s2d_wgrad_kernel)
-inline int launch_wgrad_stem(const WgArgs& a, float* dw, float* ws, int64_t ws_bytes, int splits_req, int64_t x_bytes,
+inline int launch_wgrad_stem(const WgArgs& a, const WgPlan& p, float* dw, float* ws, int64_t ws_bytes, int64_t x_bytes,
                              int64_t dy_bytes, hipStream_t st) {
     WgStemArgs h{};
     h.x = a.x; h.dy = a.dy; h.N = a.N; h.H = a.Hd; h.W = a.Wd; h.ldw = a.ldw;
-    const int Wp = a.Wd + 3;
-    h.LB = (2 * Wp + 2 + 31) / 32;
-    h.LEAD = h.LB + (31 + Wp + 1) / 32;
-    if (h.LEAD + 2 > 14) return -100;                // the 16-block x ring cannot hold the window: caller falls back
-    const int64_t vt = (int64_t)a.N * (a.Hd + 3) * Wp;
-    if (vt > 0x7fff0000LL) return -100;
-    h.nsteps = (int)((vt + 31) / 32);
-    int splits = splits_req;
-    if (splits <= 0) {
-        const int per_cu = 2;
-        splits = 256 * per_cu / share_of(splits_req);
-        const int max_by_work = h.nsteps / 8 > 0 ? h.nsteps / 8 : 1;
-        if (splits > max_by_work) splits = max_by_work;
-    }
-    const int64_t slab = (int64_t)a.Cd * a.ldw;
-    const int64_t fit = ws ? ws_bytes / (slab * 4) : 0;
-    if (splits > fit) splits = (int)fit;
-    if (splits < 1) splits = 1;
-    if (splits > h.nsteps) splits = h.nsteps;
-    if (splits > 65535) splits = 65535;
-    h.steps_per_split = (h.nsteps + splits - 1) / splits;
-    splits = (h.nsteps + h.steps_per_split - 1) / h.steps_per_split;
-    h.slab = splits > 1 ? slab : 0;
+    h.LB = p.LB;
+    h.LEAD = p.LEAD;
+    h.nsteps = p.nsteps;
+    const int splits = p.splits;
+    h.steps_per_split = p.steps_per_split;
+    h.slab = splits > 1 ? p.slab : 0;
     h.out = splits > 1 ? ws : dw;
     h.nsplits = splits;
-    hipLaunchKernelGGL(conv4x4_s2d_wgrad_kernel, dim3((unsigned)(((splits + 7) / 8) * 8)), dim3(256), 0, st, h, (unsigned)x_bytes,
+    hipLaunchKernelGGL(conv4x4_s2d_wgrad_kernel, dim3((unsigned)p.blocks), dim3(256), 0, st, h, (unsigned)x_bytes,
                        (unsigned)dy_bytes);
     IIF_LAUNCH_CHECK();
-    if (splits > 1) return reduce_slabs(ws, ws_bytes, splits, slab, a.Cd, a.ldw, a.K, dw, st);
+    if (splits > 1) return reduce_slabs(ws, ws_bytes, splits, p.slab, p.rows, a.ldw, a.K, dw, st);
     return IIF_OK;
 }
 
-// 1x1 / stride 1 (wgrad1x1_body): tile by the channel counts, one co-resident round of splits as below
-inline int launch_wgrad_1x1(const WgArgs& g, float* dw, float* ws, int64_t ws_bytes, int splits_req, int64_t x_bytes, int64_t dy_bytes,
+// 1x1 / stride 1 (wgrad1x1_body): tile by the channel counts, one co-resident round of splits (wg_plan_1x1)
+inline int launch_wgrad_1x1(const WgArgs& g, const WgPlan& p, float* dw, float* ws, int64_t ws_bytes, int64_t x_bytes, int64_t dy_bytes,
                             hipStream_t st, const unsigned char* dy2 = nullptr, int cd2 = 0) {
     W1Args a{};
     a.x = g.x; a.dy = g.dy; a.M = g.M; a.Cs = g.Cs; a.Cd = g.Cd; a.ldw = g.ldw;
     a.dy2 = dy2; a.Cd1 = dy2 ? g.Cd - cd2 : g.Cd; a.Cd2 = cd2;
-    // (stacked: the first tensor's channels fill whole tiles; the second's last tile may be partly empty)
-    const int bc = dy2 ? (a.Cd1 % 256 == 0 ? 256 : 128) : ((g.Cd >= 256 && g.Cd % 256 == 0) ? 256 : (g.Cd <= 64 ? 64 : 128));
-    static const bool no_wide = getenv("IIF_WGRAD_NO_64X256") != nullptr;
-    const int bnw = (g.Cs <= 64 && bc == 64) ? 64 : ((bc == 64 && g.Cs > 128 && g.Cs % 256 == 0 && !no_wide) ? 256 : 128);      // (256 x 64 as two 4-wave blocks per CU was slower than 256 x 128 with half of its columns empty: 0.115 against 0.106 ms at 56 x 56)
-    a.ktiles = (g.Cd + bc - 1) / bc;
-    a.ntiles = (g.Cs + bnw - 1) / bnw;
-    a.nsteps = (g.M + 31) / 32;
-    const int tiles = a.ktiles * a.ntiles;
-    // blocks per CU by LDS (3 stages of 32 x (bnw + bc) x 2 bytes) and registers: 256 x 128: one 8-wave block (72 KB);
-    // 128 x 128: three (48 KB); 64 x {128, 64}: four
-    const int per_cu = bc == 256 ? 1 : (bc == 128 ? 3 : (bnw == 256 ? 2 : 4));
-    int splits = splits_req;
-    const int64_t slab = (int64_t)g.Cd * g.ldw;
-    if (splits <= 0) {
-        splits = 256 * per_cu / share_of(splits_req) / tiles;
-        if (splits < 1) splits = 1;
-        const int max_by_work = a.nsteps / 8 > 0 ? a.nsteps / 8 : 1;
-        if (splits > max_by_work) splits = max_by_work;
-        // Small outputs write splits x their own size in slabs: a Gram matrix a2^T a2 (16-256 KB) 16-48 MB, P = g~^T a2 of the
-        // 56 x 56 stage (64 KB) 16 MB - more than the operands at 14 x 14.  Round 5, same-call A/B of the step (ms): default splits
-        // 18.02; Gram 1/4 + other outputs <= 256 KB 1/2: 17.78; Gram 1/8: 17.77; 1/2 for EVERY 1x1 weight gradient 17.86 and for
-        // the nine-tap kernel 17.90 (their streams become the critical path).  Gram (x == dy) is forward data a block ahead on the
-        // shortcut stream: nothing waits for it.  IIF_WGRAD_GRAM_DIV / IIF_WGRAD_SMALL_DIV = 1 restore the full round of splits.
-        static const int small_div = [] { const char* e = getenv("IIF_WGRAD_SMALL_DIV"); return e ? atoi(e) : 2; }();
-        static const int gram_div = [] { const char* e = getenv("IIF_WGRAD_GRAM_DIV"); return e ? atoi(e) : 8; }();
-        const bool gram = g.x == g.dy && dy2 == nullptr;
-        static const int small_kb = [] { const char* e = getenv("IIF_WGRAD_SMALL_KB"); return e ? atoi(e) : 256; }();
-        // (late round 6: outputs up to 4 MB - the 14 x 14 / 7 x 7 1x1 layers - take half a round too: 16.75 / 16.80 / 16.84 -> 16.73 / 16.71 /
-        // 16.78 ms per step in one call, their slabs halved; a quarter round: 17.2.  IIF_WGRAD_MID_DIV=1 restores the full round)
-        static const int mid_div = [] { const char* e = getenv("IIF_WGRAD_MID_DIV"); return e ? atoi(e) : 2; }();
-        const int div = gram ? gram_div : (slab * 4 <= ((int64_t)small_kb << 10) ? small_div : (slab * 4 <= (4 << 20) ? mid_div : 1));
-        if (div > 1 && splits > 8) { splits /= div; if (splits < 8) splits = 8; }       // (never more splits than before)
-    }
-    const int64_t fit = ws ? ws_bytes / (slab * 4) : 0;
-    if (splits > fit) splits = (int)fit;
-    if (splits < 1) splits = 1;
-    if (splits > a.nsteps) splits = a.nsteps > 0 ? a.nsteps : 1;
-    if (splits > 65535) splits = 65535;
-    a.steps_per_split = (a.nsteps + splits - 1) / splits;
-    splits = (a.nsteps + a.steps_per_split - 1) / a.steps_per_split;
-    if (splits < 1) splits = 1;
+    const int bc = p.bc, bnw = p.bnw;
+    a.ktiles = p.ktiles;
+    a.ntiles = p.ntiles;
+    a.nsteps = p.nsteps;
+    const int splits = p.splits;
+    const int64_t slab = p.slab;
+    a.steps_per_split = p.steps_per_split;
     a.slab = splits > 1 ? slab : 0;
     a.out = splits > 1 ? ws : dw;
     a.nsplits = splits;
-    const dim3 grid((unsigned)(tiles * ((splits + 7) / 8) * 8));
+    const dim3 grid((unsigned)p.blocks);               // tiles x splits rounded up to 8
     const unsigned xb = (unsigned)x_bytes, yb = (unsigned)dy_bytes;
     if (bc == 256) hipLaunchKernelGGL(wgrad1x1_256x128_kernel, grid, dim3(512), 0, st, a, xb, yb);
     else if (bc == 128) hipLaunchKernelGGL(wgrad1x1_128x128_kernel, grid, dim3(256), 0, st, a, xb, yb);
@@ -1192,69 +1128,29 @@ inline int launch_wgrad_1x1(const WgArgs& g, float* dw, float* ws, int64_t ws_by
 template <typename T>
 int launch_wgrad(WgArgs a, float* dw, float* ws, int64_t ws_bytes, int splits_req, int64_t x_bytes, int64_t dy_bytes,
                  hipStream_t st) {
-    constexpr int ROWS = WT<T>::ROWS;
-    // 256-channel tiles (8 waves): bf16, dense, >= 256 output channels, the LDS-DMA path
-    // (IIF_CONV_REGSTAGE: every launch on the register-staged kernel, the fallback for operands >= 2 GiB; tests)
-    const bool force_v1 = getenv("IIF_CONV_REGSTAGE") != nullptr;       // (read per call: a test flips it)
-    const bool dma_ok = !force_v1 && x_bytes < 0x7ffffff0LL && dy_bytes < 0x7ffffff0LL;
+    // kernel family, tile and split-K round: wgrad_plan.h (the planning query iif_conv_wgrad_plan walks the same function)
+    if (!ws) ws_bytes = 0;
+    const WgPlan p = iif_plan::wgrad_plan(shape_of(a, (int)sizeof(T), x_bytes, dy_bytes), ws_bytes, splits_req);
+    if (p.rc != IIF_OK) return p.rc;
     if constexpr (sizeof(T) == 2) {
-        // dense: channels in 64s; grouped: 64-channel chunks (the nine-tap tile IS a chunk)
-        const bool shape = a.groups == 1 ? (a.Cs % 64 == 0 && a.Cd % 64 == 0 && a.xpitch == a.Cs && a.ypitch == a.Cd)
-                                         : (a.Cs == 64 && a.Cd == 64 && a.ldw >= 576);
-        const bool halo = dma_ok && shape && a.R == 3 && a.S == 3 && a.sshift == 0 && a.pad == 1 && a.Hs == a.Hd &&
-                          a.Ws == a.Wd && a.Wd + 3 <= 64;
-        if (halo) {
-            const int rc = launch_wgrad_halo(a, dw, ws, ws_bytes, splits_req, x_bytes, dy_bytes, st);
-            if (rc != -100) return rc;
-        }
-        const bool stem = dma_ok && a.groups == 1 && a.R == 4 && a.S == 4 && a.sshift == 0 && a.pad == 2 && a.Hs == a.Hd &&
-                          a.Ws == a.Wd && a.Cs == 16 && a.Cd == 64 && a.xpitch == 16 && a.ypitch == 64;
-        if (stem) {
-            const int rc = launch_wgrad_stem(a, dw, ws, ws_bytes, splits_req, x_bytes, dy_bytes, st);
-            if (rc != -100) return rc;
-        }
+        if (p.family == IIF_WGRAD_NINETAP) return launch_wgrad_halo(a, p, dw, ws, ws_bytes, x_bytes, dy_bytes, st);
+        if (p.family == IIF_WGRAD_STEM) return launch_wgrad_stem(a, p, dw, ws, ws_bytes, x_bytes, dy_bytes, st);
+        if (p.family == IIF_WGRAD_1X1) return launch_wgrad_1x1(a, p, dw, ws, ws_bytes, x_bytes, dy_bytes, st);
     }
-    if constexpr (sizeof(T) == 2) {
-        if (dma_ok && a.R == 1 && a.S == 1 && a.sshift == 0 && a.pad == 0 && a.groups == 1 && a.Hs == a.Hd && a.Ws == a.Wd &&
-            a.xpitch == a.Cs && a.ypitch == a.Cd)
-            return launch_wgrad_1x1(a, dw, ws, ws_bytes, splits_req, x_bytes, dy_bytes, st);
-    }
-    bool wide = sizeof(T) == 2 && dma_ok && a.groups == 1 && a.Cd >= 256 && a.Cd % 256 == 0;
-    const int bc = wide ? 256 : (a.Cd <= 64 ? 64 : 128);
-    a.ktiles = (a.Cd + bc - 1) / bc;
-    a.ntiles = (a.K + 127) / 128;
-    a.nsteps = (a.M + ROWS - 1) / ROWS;
-    const int tiles = a.ktiles * a.ntiles;
-    int splits = splits_req;
-    if (splits <= 0) {
-        // one full co-resident round: 256 CUs x (3 | 4) workgroups (LDS 48 | 36 KB each), so every
-        // workgroup gets the same number of steps and there is no tail round
-        // blocks per CU: 4 (64-channel tile), 3 (128), and ONE 8-wave block for the 256-channel tile: two per CU write twice
-        // the split-K slabs for nothing (step 20.67 -> 20.62 ms at one; 0.75 / 1.25 per CU leave a tail round: 21.2 / 20.8;
-        // round 3, scripts removed).
-        const int slots = 256 * (bc == 256 ? 1 : (bc == 128 ? 3 : 4)) / share_of(splits_req);
-        splits = slots / (tiles * a.groups);
-        if (splits < 1) splits = 1;
-        const int max_by_work = a.nsteps / 8 > 0 ? a.nsteps / 8 : 1;
-        if (splits > max_by_work) splits = max_by_work;
-    }
-    const int64_t slab = (int64_t)a.groups * a.Cd * a.ldw;
-    const int64_t fit = ws ? ws_bytes / (slab * 4) : 0;
-    if (splits > fit) splits = (int)fit;
-    if (splits < 1) splits = 1;
-    if (splits > a.nsteps) splits = a.nsteps > 0 ? a.nsteps : 1;
-    if (splits > 65535) splits = 65535;
-    a.steps_per_split = (a.nsteps + splits - 1) / splits;
-    splits = (a.nsteps + a.steps_per_split - 1) / a.steps_per_split;
-    if (splits < 1) splits = 1;
+    const int bc = p.bc;
+    a.ktiles = p.ktiles;
+    a.ntiles = p.ntiles;
+    a.nsteps = p.nsteps;
+    const int tiles = p.tiles;
+    const int splits = p.splits;
+    const int64_t slab = p.slab;
+    a.steps_per_split = p.steps_per_split;
     a.slab = splits > 1 ? slab : 0;
     a.out = splits > 1 ? ws : dw;
     a.nsplits = splits;
     const dim3 grid(tiles, splits);
-    const dim3 grid1d((unsigned)(tiles * ((splits + 7) / 8) * 8), (unsigned)a.groups);
-    if (a.groups > 1 && !dma_ok)
-        return IIF_EUNSUPPORTED;
-    const bool dma = dma_ok;
+    const dim3 grid1d((unsigned)(p.blocks / a.groups), (unsigned)a.groups);      // tiles x splits rounded up to 8, per group
+    const bool dma = p.family == IIF_WGRAD_DMA;
     if (dma) {
         const unsigned xb = (unsigned)x_bytes, yb = (unsigned)dy_bytes;
         if (bc == 64) hipLaunchKernelGGL((conv_wgrad_dma_kernel<T, 64>), grid1d, dim3(256), 0, st, a, xb, yb);
@@ -1270,11 +1166,8 @@ int launch_wgrad(WgArgs a, float* dw, float* ws, int64_t ws_bytes, int splits_re
     return IIF_OK;
 }
 
-}  // namespace
-
-extern "C" int iif_conv_wgrad(const iif_conv_desc* d, const void* x, const void* dy, float* dw, void* workspace,
-                              int64_t workspace_bytes, int splits, void* stream) {
-    if (!d || !x || !dy || !dw) return IIF_EINVAL;
+// the descriptor checks of iif_conv_wgrad (operand pointers aside) and the launch arguments it describes
+int wgrad_args_of(const iif_conv_desc* d, int64_t workspace_bytes, WgArgs& a, int64_t& x_bytes, int64_t& dy_bytes) {
     if (d->n <= 0 || d->hs <= 0 || d->ws <= 0 || d->cs <= 0 || d->hd <= 0 || d->wd <= 0 || d->cd <= 0 ||
         d->r <= 0 || d->s <= 0 || d->pad < 0 || workspace_bytes < 0)
         return IIF_EINVAL;
@@ -1283,22 +1176,45 @@ extern "C" int iif_conv_wgrad(const iif_conv_desc* d, const void* x, const void*
     if (d->transposed) return IIF_EINVAL;
     const int pe = d->dtype == IIF_F32 ? 4 : 8;
     if (d->cs % pe != 0 || d->cd % pe != 0 || d->ldw % 4 != 0 || d->ldw < d->r * d->s * d->cs) return IIF_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dw) |
-         reinterpret_cast<uintptr_t>(workspace)) & 15)
-        return IIF_EUNSUPPORTED;
     const int64_t M = (int64_t)d->n * d->hd * d->wd;
     if (M > 0x7fffff00LL || (int64_t)d->n * d->hs * d->ws > 0x7fffff00LL) return IIF_EUNSUPPORTED;
-    WgArgs a{};
-    a.x = (const unsigned char*)x; a.dy = (const unsigned char*)dy;
     a.N = d->n; a.Hs = d->hs; a.Ws = d->ws; a.Cs = d->cs; a.Hd = d->hd; a.Wd = d->wd; a.Cd = d->cd;
     a.R = d->r; a.S = d->s; a.sshift = d->stride - 1; a.pad = d->pad; a.ldw = d->ldw; a.M = (int)M;
     a.K = d->r * d->s * d->cs;
     a.groups = d->groups > 1 ? d->groups : 1;
     a.xpitch = a.groups * d->cs; a.ypitch = a.groups * d->cd;
     if (a.groups > 65535) return IIF_EUNSUPPORTED;
-    hipStream_t st = as_stream(stream);
     const int64_t esz = d->dtype == IIF_F32 ? 4 : 2;
-    const int64_t x_bytes = (int64_t)d->n * d->hs * d->ws * a.xpitch * esz, dy_bytes = M * a.ypitch * esz;
+    x_bytes = (int64_t)d->n * d->hs * d->ws * a.xpitch * esz;
+    dy_bytes = M * a.ypitch * esz;
+    return IIF_OK;
+}
+
+// ... and of iif_wgrad1x1_stacked
+int stacked_args_of(int64_t m, int cs, int cd1, int cd2, int ldw, int64_t workspace_bytes, WgArgs& a) {
+    if (m <= 0 || cs <= 0 || cd1 <= 0 || cd2 <= 0 || workspace_bytes < 0) return IIF_EINVAL;
+    if (cs % 8 || cd1 % 128 || cd2 % 8 || ldw % 4 || ldw < cs) return IIF_EUNSUPPORTED;
+    if (m > 0x7fffff00LL || m * cs * 2 >= 0x7f000000LL || m * cd1 * 2 >= 0x7f000000LL || m * cd2 * 2 >= 0x7f000000LL) return IIF_EUNSUPPORTED;
+    a.N = 1; a.Hs = 1; a.Ws = (int)m; a.Cs = cs; a.Hd = 1; a.Wd = (int)m; a.Cd = cd1 + cd2;
+    a.R = 1; a.S = 1; a.sshift = 0; a.pad = 0; a.ldw = ldw; a.M = (int)m; a.K = cs; a.groups = 1;
+    a.xpitch = cs; a.ypitch = cd1;
+    return IIF_OK;
+}
+
+}  // namespace
+
+extern "C" int iif_conv_wgrad(const iif_conv_desc* d, const void* x, const void* dy, float* dw, void* workspace,
+                              int64_t workspace_bytes, int splits, void* stream) {
+    if (!d || !x || !dy || !dw) return IIF_EINVAL;
+    WgArgs a{};
+    int64_t x_bytes = 0, dy_bytes = 0;
+    const int rc = wgrad_args_of(d, workspace_bytes, a, x_bytes, dy_bytes);
+    if (rc != IIF_OK) return rc;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dw) |
+         reinterpret_cast<uintptr_t>(workspace)) & 15)
+        return IIF_EUNSUPPORTED;
+    a.x = (const unsigned char*)x; a.dy = (const unsigned char*)dy;
+    hipStream_t st = as_stream(stream);
     if (d->dtype == IIF_BF16)
         return launch_wgrad<unsigned short>(a, dw, (float*)workspace, workspace_bytes, splits, x_bytes, dy_bytes, st);
     return launch_wgrad<float>(a, dw, (float*)workspace, workspace_bytes, splits, x_bytes, dy_bytes, st);
@@ -1306,26 +1222,54 @@ extern "C" int iif_conv_wgrad(const iif_conv_desc* d, const void* x, const void*
 
 extern "C" int iif_wgrad1x1_stacked(const void* x, const void* dy, const void* dy2, int64_t m, int cs, int cd1, int cd2, int ldw,
                                     float* out, void* workspace, int64_t workspace_bytes, int splits, void* stream) {
-    if (!x || !dy || !dy2 || !out || m <= 0 || cs <= 0 || cd1 <= 0 || cd2 <= 0 || workspace_bytes < 0) return IIF_EINVAL;
-    if (cs % 8 || cd1 % 128 || cd2 % 8 || ldw % 4 || ldw < cs) return IIF_EUNSUPPORTED;
+    if (!x || !dy || !dy2 || !out) return IIF_EINVAL;
+    WgArgs a{};
+    const int rc = stacked_args_of(m, cs, cd1, cd2, ldw, workspace_bytes, a);
+    if (rc != IIF_OK) return rc;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dy2) |
          reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 15)
         return IIF_EUNSUPPORTED;
-    if (m > 0x7fffff00LL || m * cs * 2 >= 0x7f000000LL || m * cd1 * 2 >= 0x7f000000LL || m * cd2 * 2 >= 0x7f000000LL) return IIF_EUNSUPPORTED;
-    WgArgs a{};
     a.x = (const unsigned char*)x; a.dy = (const unsigned char*)dy;
-    a.N = 1; a.Hs = 1; a.Ws = (int)m; a.Cs = cs; a.Hd = 1; a.Wd = (int)m; a.Cd = cd1 + cd2;
-    a.R = 1; a.S = 1; a.sshift = 0; a.pad = 0; a.ldw = ldw; a.M = (int)m; a.K = cs; a.groups = 1;
-    a.xpitch = cs; a.ypitch = cd1;
-    return launch_wgrad_1x1(a, out, (float*)workspace, workspace_bytes, splits, m * cs * 2, m * cd1 * 2, as_stream(stream),
+    if (!workspace) workspace_bytes = 0;
+    const WgPlan p = iif_plan::wgrad_plan(shape_of(a, 2, m * cs * 2, m * cd1 * 2, true, cd2), workspace_bytes, splits);
+    return launch_wgrad_1x1(a, p, out, (float*)workspace, workspace_bytes, m * cs * 2, m * cd1 * 2, as_stream(stream),
                             (const unsigned char*)dy2, cd2);
+}
+
+// The decision iif_conv_wgrad (cd2 == 0; cd2 == -1: with x and dy one tensor, the Gram matrix) or iif_wgrad1x1_stacked (cd2 > 0,
+// d its 1x1 descriptor with cd = cd1) takes for these arguments, walked without launching anything (wgrad_plan.h).
+extern "C" int iif_conv_wgrad_plan(const iif_conv_desc* d, int cd2, int64_t workspace_bytes, int splits, int32_t* out) {
+    if (!d || !out || cd2 < -1) return IIF_EINVAL;
+    WgArgs a{};
+    int64_t x_bytes = 0, dy_bytes = 0;
+    int rc = wgrad_args_of(d, workspace_bytes, a, x_bytes, dy_bytes);
+    if (rc != IIF_OK) return rc;
+    const bool stacked = cd2 > 0;
+    if (stacked) {
+        if (d->dtype != IIF_BF16 || d->r != 1 || d->s != 1 || d->stride != 1 || d->pad != 0 || a.groups != 1 || d->hs != d->hd ||
+            d->ws != d->wd)
+            return IIF_EUNSUPPORTED;
+        rc = stacked_args_of(a.M, d->cs, d->cd, cd2, d->ldw, workspace_bytes, a);
+        if (rc != IIF_OK) return rc;
+        x_bytes = (int64_t)a.M * d->cs * 2; dy_bytes = (int64_t)a.M * d->cd * 2;
+    }
+    WgShape s = shape_of(a, d->dtype == IIF_F32 ? 4 : 2, x_bytes, dy_bytes, stacked, stacked ? cd2 : 0);
+    s.gram = cd2 == -1;
+    if (s.gram && (d->cs != d->cd || d->hs != d->hd || d->ws != d->wd)) return IIF_EINVAL;      // not one tensor
+    const WgPlan p = iif_plan::wgrad_plan(s, workspace_bytes, splits);
+    if (p.rc != IIF_OK) return p.rc;
+    out[0] = p.family; out[1] = p.bc; out[2] = p.bnw; out[3] = p.tiles; out[4] = p.nsteps; out[5] = p.splits;
+    out[6] = p.steps_per_split; out[7] = (int32_t)p.blocks; out[8] = p.stages; out[9] = p.nch;
+    return IIF_OK;
 }
 
 // sum of n fp32 slabs [rows, ld] (columns < cols) in slab order into out - the split-K reduction of this file for slabs written by
 // another kernel (the P / Gram by-product of iif_conv_igemm_dgrad_masksum_rx_pg).  slab_floats: floats available behind `slabs`;
-// the two-stage form needs ceil(n / 16) slabs of room behind the n slabs and is used when there is.
+// the two-stage form needs ceil(n / 16) slabs of room behind the n slabs and is used when there is.  The kernel moves 4-float
+// vectors and tests the first column of each against `cols`: cols % 4 != 0 would write up to three columns past it, so it is
+// refused (every caller's `cols` is a channel count in 8s).
 extern "C" int iif_slab_sum(float* slabs, int64_t slab_floats, int n, int rows, int ld, int cols, float* out, void* stream) {
-    if (!slabs || !out || n < 1 || rows < 1 || ld < cols || cols < 1 || (ld & 3)) return IIF_EINVAL;
+    if (!slabs || !out || n < 1 || rows < 1 || ld < cols || cols < 1 || (ld & 3) || (cols & 3)) return IIF_EINVAL;
     if ((reinterpret_cast<uintptr_t>(slabs) | reinterpret_cast<uintptr_t>(out)) & 15) return IIF_EINVAL;
     const int64_t slab = (int64_t)rows * ld;
     if ((int64_t)n * slab > slab_floats) return IIF_EINVAL;

@@ -1,6 +1,7 @@
 """Thin tensor-level wrappers over the C ABI (one call = one kernel launch on
 torch's current HIP stream).  Layout everywhere: activations NHWC, weights
 [Cout][R][S][Cin] rows with pitch ``ldw``.  No fallbacks: GPU tensors only."""
+import collections
 import ctypes
 
 import torch
@@ -163,6 +164,20 @@ def conv_wgrad(x, dy, r, s, stride, pad, ldw=None, out=None, workspace=None, spl
     check(lib().iif_conv_wgrad(ctypes.byref(d), ptr(x), ptr(dy), ptr(out), ptr(workspace), wsb, splits, stream_ptr()),
           "iif_conv_wgrad")
     return out
+
+
+WGRAD_FAMILIES = ("regstage", "dma", "1x1", "ninetap", "stem")          # IIF_WGRAD_* of include/iif_amd.h
+WgradPlan = collections.namedtuple("WgradPlan", "family bc bnw tiles nsteps splits steps_per_split blocks stages chunks")
+
+
+def conv_wgrad_plan(n, hs, ws, cs, hd, wd, cd, r, s, stride, pad, ldw, dtype, groups=1, workspace_bytes=0, splits=0, cd2=0):
+    """What conv_wgrad (cd2 = 0; -1: x is dy) or wgrad1x1_stacked (cd2 > 0, cd = cd1) launches for these arguments
+    (iif_conv_wgrad_plan; host only, per-group channel counts as conv_wgrad's descriptor)."""
+    d = _desc(n, hs, ws, cs, hd, wd, cd, r, s, stride, pad, 0, ldw, _lib.IIF_F32 if dtype == torch.float32 else _lib.IIF_BF16,
+              _lib.IIF_F32, groups)
+    out = (ctypes.c_int32 * 10)()
+    check(lib().iif_conv_wgrad_plan(ctypes.byref(d), cd2, workspace_bytes, splits, ctypes.addressof(out)), "iif_conv_wgrad_plan")
+    return WgradPlan(WGRAD_FAMILIES[out[0]], *out[1:])
 
 
 def wgrad1x1_stacked(x2d, dy2d, dy2_2d, out, workspace, splits=0):

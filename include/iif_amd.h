@@ -639,6 +639,52 @@ int iif_wgrad1x1_stacked(const void* x, const void* dy, const void* dy2, int64_t
                          int ldw, float* out, void* workspace, int64_t workspace_bytes, int splits,
                          void* stream);
 
+/* The split-K decision of a weight-gradient launch as a value: what iif_conv_wgrad(d, ..., workspace_bytes, splits) would
+ * launch, decided on the host, nothing launched, no device needed.  cd2 = 0: iif_conv_wgrad; cd2 = -1: the same with x and dy
+ * one tensor (the Gram matrix; cs == cd); cd2 > 0: iif_wgrad1x1_stacked with d its 1x1 descriptor (n * hd * wd = m, cd = cd1).
+ * workspace_bytes = 0 stands for no workspace.  The argument checks are the entry's own (operand pointers aside).
+ *
+ * The rule.  With groups = max(d->groups, 1), K = r * s * cs, M = n * hd * wd, and unless IIF_CONV_REGSTAGE is set or an operand
+ * (n * hs * ws * groups * cs, or M * groups * cd, elements) reaches 0x7ffffff0 bytes - then every launch is REGSTAGE - bf16 takes
+ *   NINETAP  3 x 3 / stride 1 / pad 1 with hs x ws = hd x wd, wd <= 61, dense channels in 64s or grouped 64 -> 64 chunks with
+ *            ldw >= 576; tiles = (cs / 64) * (cd / 64) (grouped: groups) of 64 x 64; steps of 32 PADDED pixels,
+ *            nsteps = ceil(n * (hd + 2) * (wd + 2) / 32); 2 blocks per CU;
+ *   STEM     4 x 4 / stride 1 / pad 2, dense 16 -> 64 with hs x ws = hd x wd and a window that fits the ring:
+ *            ceil((2 * (wd + 3) + 2) / 32) + floor((wd + 35) / 32) <= 12; one 64 x 256 tile, nsteps = ceil(n * (hd + 3) * (wd + 3) / 32);
+ *            2 blocks per CU;
+ *   1X1      1 x 1 / stride 1 / pad 0, dense: output-channel tile 256 (cd a multiple of 256; stacked: cd1 is), 64 (cd <= 64; never
+ *            stacked) or 128; input-column tile 64 (64-channel tile and cs <= 64), 256 (64-channel tile, cs a multiple of 256;
+ *            not under IIF_WGRAD_NO_64X256) or 128; tiles = ceil(cd_total / bc) * ceil(cs / bnw); nsteps = ceil(M / 32);
+ *            blocks per CU: 1 (256), 3 (128), 2 (64 x 256), 4;
+ * and everything else, fp32 included, takes
+ *   DMA / REGSTAGE  output-channel tile 256 (DMA, bf16, dense, cd a multiple of 256), 64 (cd <= 64) or 128, by 128 of the K columns;
+ *            tiles = ceil(cd / bc) * ceil(K / 128) PER GROUP; nsteps = ceil(M / 32) (fp32: 16); blocks per CU: 1, 4, 3.
+ *            (REGSTAGE has no grouped form: IIF_EUNSUPPORTED.)
+ * A NINETAP / STEM shape with more than 0x7fff0000 padded pixels falls through to the families below it.
+ * splits > 0 is the request.  splits <= 0 asks for one co-resident round of 1 / max(1, -splits) of the device:
+ *   256 * blocks_per_cu / share / (tiles * groups), at least 1 and at most max(1, nsteps / 8) (integer divisions, left to right;
+ *   the NINETAP tile count already counts the groups, the STEM has no lower clamp to apply);
+ *   NINETAP divides that by IIF_WGRAD_HALO_DIV (1), grouped by IIF_WGRAD_HALO_GROUPED_DIV (4), before the two clamps;
+ *   1X1, after the clamps and if more than 8 are left, divides by IIF_WGRAD_GRAM_DIV (8) for the Gram matrix, else by
+ *   IIF_WGRAD_SMALL_DIV (2) for a slab of at most IIF_WGRAD_SMALL_KB (256) KiB, else by IIF_WGRAD_MID_DIV (2) for one of at most
+ *   4 MiB - but never to fewer than 8.  (These switches are read once per process.)
+ * Then, with slab = groups * cd_total * ldw floats: at most workspace_bytes / (slab * 4) splits, at least 1, at most nsteps and
+ * 65 535; steps_per_split = ceil(nsteps / splits), and the realised count is ceil(nsteps / steps_per_split): the last split may
+ * be shorter, none is empty.  One split writes dw itself.  The grid is padded to tiles * (splits rounded up to 8) blocks, DMA: times
+ * groups (REGSTAGE: tiles x splits, unpadded); the padding blocks write nothing.
+ * More than one split: the slabs are summed in slab order by one pass, or - splits > 32, ceil(slab / 1024) < 256 (a slab under
+ * about 1 MiB) and (splits + chunks) * slab * 4 <= workspace_bytes with chunks = ceil(splits / 16) - in two stages: chunk c of 16
+ * consecutive slabs into slab c of a stage area BEHIND the splits slabs, then the chunk sums in order.
+ *
+ * out[10] = { family, output-channel tile, input-column tile, tiles (as counted above), nsteps, realised splits, steps_per_split,
+ *             blocks launched, reduction stages (0: one split, 1, 2), chunks of the first stage (0 unless 2 stages) }. */
+#define IIF_WGRAD_REGSTAGE 0
+#define IIF_WGRAD_DMA 1
+#define IIF_WGRAD_1X1 2
+#define IIF_WGRAD_NINETAP 3
+#define IIF_WGRAD_STEM 4
+int iif_conv_wgrad_plan(const iif_conv_desc* d, int cd2, int64_t workspace_bytes, int splits, int32_t* out);
+
 /* Training-mode batch norm, NHWC activation viewed as x[m, c] (m = N*H*W).
  * Replaces F.batch_norm(training=True) + ReLU + residual add and their autograd
  * backward under resnet_pytorch.py:152-167 / resnet_cifar.py:133-138.
@@ -1032,7 +1078,9 @@ int iif_conv_igemm_dgrad_masksum_rx_pg(const iif_conv_desc* d, const void* src, 
                                        void* stream);
 /* out[r][c] = sum over the n slabs [rows, ld] of slabs[s][r][c], c < cols, in slab order (the split-K reduction of
  * iif_conv_wgrad for slabs another kernel wrote).  slab_floats: floats available behind `slabs`; with room for ceil(n / 16)
- * more slabs behind the n the reduction runs in two parallel stages. */
+ * more slabs behind the n the reduction runs in two parallel stages (n > 32 and a slab under about 1 MiB, as iif_conv_wgrad_plan
+ * describes).  Columns >= cols of out are not written.  ld % 4 == 0 and cols % 4 == 0 (the sum moves 4-float vectors), slabs and
+ * out 16-byte aligned; otherwise IIF_EINVAL. */
 int iif_slab_sum(float* slabs, int64_t slab_floats, int n, int rows, int ld, int cols, float* out, void* stream);
 int iif_conv_igemm_dgrad2_bnbwd(const iif_conv_desc* d, const void* src, const void* src2, int cs2, const void* wgt,
                                 const float* bias, void* dst, const void* up_x, const unsigned char* up_bits,
