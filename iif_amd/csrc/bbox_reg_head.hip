@@ -31,6 +31,7 @@
 // bit-identical from call to call.  Indexing is 64-bit.
 #include "common.h"
 #include "loss_reduce.h"
+#include "vec16.h"
 
 namespace {
 
@@ -79,45 +80,6 @@ __device__ __forceinline__ void one(const FwdArgs& a, float p, float t, float w,
 
 __device__ __forceinline__ bool positive(int64_t lab, int64_t num_classes) { return lab >= 0 && lab < num_classes; }
 
-template <typename T, int V> struct PredIO;
-template <> struct PredIO<float, 4> {
-    static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-};
-template <> struct PredIO<unsigned short, 4> {              // bf16 bits, 8 bytes
-    static __device__ __forceinline__ void load(const unsigned short* p, float (&v)[4]) {
-        const u32x2 t = *reinterpret_cast<const u32x2*>(p);
-        v[0] = bf16_bits_to_f32(t.x & 0xffffu); v[1] = __uint_as_float(t.x & 0xffff0000u);
-        v[2] = bf16_bits_to_f32(t.y & 0xffffu); v[3] = __uint_as_float(t.y & 0xffff0000u);
-    }
-};
-template <> struct PredIO<float, 1> {
-    static __device__ __forceinline__ void load(const float* p, float (&v)[1]) { v[0] = *p; }
-};
-template <> struct PredIO<unsigned short, 1> {
-    static __device__ __forceinline__ void load(const unsigned short* p, float (&v)[1]) { v[0] = bf16_bits_to_f32(*p); }
-};
-
-template <int V>
-__device__ __forceinline__ void load_f32(const float* p, float (&v)[V]) {
-    if constexpr (V == 1) {
-        v[0] = *p;
-    } else {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-}
-template <int V>
-__device__ __forceinline__ void store_f32(float* p, const float (&v)[V]) {
-    if constexpr (V == 1) {
-        *p = v[0];
-    } else {
-        *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-    }
-}
-
 // The V elements from flat index e on (V = 4: e is a multiple of 4, one box).  Returns the sum of their weighted losses.
 template <typename T, int V>
 __device__ __forceinline__ float unit(const FwdArgs& a, int64_t e) {
@@ -133,7 +95,7 @@ __device__ __forceinline__ float unit(const FwdArgs& a, int64_t e) {
     float p[V], t[V], w[V], l[V], g[V];
     load_f32<V>(a.tgt + e, t);
     if (a.w) load_f32<V>(a.w + e, w);
-    if (pos) PredIO<T, V>::load(src, p);
+    if (pos) VTn<T, V>::load(src, p);
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < V; ++k) {
@@ -181,8 +143,6 @@ __device__ __forceinline__ f32x4 slot_value(const ScatterArgs& a, int64_t i, uns
     return v;
 }
 
-__device__ __forceinline__ u32x2 pack_bf16x4(const f32x4& v) { return u32x2{pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)}; }
-
 // dpred contiguous ([N, 4C], pitch 4C) on a 16-byte boundary.  S = class slots per 16-byte piece: 1 (fp32) or 2 (bf16).
 template <typename T, int S>
 __global__ void __launch_bounds__(kThreads) bbox_reg_scatter_vec_kernel(ScatterArgs a) {
@@ -220,9 +180,9 @@ __global__ void __launch_bounds__(kThreads) bbox_reg_scatter_vec_kernel(ScatterA
             if constexpr (S == 1) {
                 *reinterpret_cast<f32x4*>(d + v * 4) = slot_value(a, iv[j][0], cv[j][0], lab[j][0], g);
             } else {
-                const u32x2 lo = pack_bf16x4(slot_value(a, iv[j][0], cv[j][0], lab[j][0], g));
-                const u32x2 hi = pack_bf16x4(slot_value(a, iv[j][1], cv[j][1], lab[j][1], g));
-                *reinterpret_cast<u32x4*>(d + v * 8) = u32x4{lo.x, lo.y, hi.x, hi.y};
+                const f32x4 lo = slot_value(a, iv[j][0], cv[j][0], lab[j][0], g), hi = slot_value(a, iv[j][1], cv[j][1], lab[j][1], g);
+                // (packed before the address is formed: the two orders schedule differently)
+                *reinterpret_cast<u32x4*>(d + v * 8) = VT<T>::pack({lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w});
             }
         }
     }
@@ -231,7 +191,8 @@ __global__ void __launch_bounds__(kThreads) bbox_reg_scatter_vec_kernel(ScatterA
         const int64_t slots = (int64_t)a.N * a.C;
         if ((slots & 1) && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
             const int64_t il = a.N - 1;
-            *reinterpret_cast<u32x2*>(d + (slots - 1) * 4) = pack_bf16x4(slot_value(a, il, C - 1, a.labels[il], g));
+            const f32x4 v = slot_value(a, il, C - 1, a.labels[il], g);
+            *reinterpret_cast<u32x2*>(d + (slots - 1) * 4) = VT<T>::pack4({v.x, v.y, v.z, v.w});
         }
     }
 }
@@ -250,8 +211,7 @@ __global__ void __launch_bounds__(kThreads) bbox_reg_scatter_elem_kernel(Scatter
         const int64_t lab = a.labels[i];
         float v = 0.0f;
         if (positive(lab, a.num_classes) && (a.agnostic ? 0 : lab) == (col >> 2)) v = g * a.dsel[4 * i + (col & 3)];
-        if constexpr (std::is_same<T, float>::value) d[i * a.ld + col] = v;
-        else d[i * a.ld + col] = f32_to_bf16_bits(v);
+        VT<T>::store1(d + i * a.ld + col, v);
     }
 }
 

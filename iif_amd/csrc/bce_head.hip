@@ -20,19 +20,19 @@
 //     (coalesced dword / word accesses, addresses i ld + c).  Correct for every layout, not the fast path.
 // Indexing is 64-bit throughout; there is no upper limit on C.
 //
-// Per element (x = logit; sp = softplus, s = sigmoid(x), q = 1 - s from the stable forms of sigmoid_head.hip):
+// Per element (x = logit; sp = softplus, s = sigmoid(x), q = 1 - s from the stable element of head_math.h):
 //   labels:  y = 0: l = sp(x),  dl/dx = s          y = 1: l = pw_c sp(-x),  dl/dx = -pw_c q
 //   dense :  l = (1 - y) sp(x) + pw_c y sp(-x),   dl/dx = (1 - y) s - pw_c y q
 // which is torch's (1 - y) x + (1 + (pw - 1) y) sp(-x) with x + sp(-x) written as sp(x): exact at every |x|.
 // The scalar loss leaves the same launch by the ticketed reduction of loss_reduce.h: no float atomics, bit-identical from
 // call to call.
 #include "common.h"
+#include "head_math.h"
 #include "loss_reduce.h"
+#include "vec16.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 constexpr int kThreads = 256;
 
 struct Args {
@@ -50,24 +50,6 @@ struct Args {
     unsigned qs, rs;              // grid stride in elements = qs * C + rs
 };
 
-// softplus(x), softplus(-x), sigmoid(x), 1 - sigmoid(x): the forms of sigmoid_head.hip (log1p(e) = ln(u) + (e - (u - 1)) / u
-// with u = 1 + e keeps the digits of a small e; 1 - s is never formed by subtraction)
-struct Elem { float spp, spn, s, q; };
-
-__device__ __forceinline__ Elem elem(float x) {
-    const float e = __builtin_amdgcn_exp2f(-fabsf(x) * kLog2e);
-    const float u = 1.0f + e;
-    const float r = __builtin_amdgcn_rcpf(u);
-    const float l1p = __builtin_amdgcn_logf(u) * kLn2 + (e - (u - 1.0f)) * r;
-    const float er = e * r;
-    Elem p;
-    p.spp = fmaxf(x, 0.0f) + l1p;
-    p.spn = fmaxf(-x, 0.0f) + l1p;
-    p.s = x >= 0.0f ? r : er;
-    p.q = x >= 0.0f ? er : r;
-    return p;
-}
-
 // weight (0 for an ignored row) and target column (-1: none, a background row) of row i
 __device__ __forceinline__ void load_row(const Args& a, int64_t i, float& wi, int& t) {
     const int64_t lab = a.labels[i];
@@ -80,7 +62,7 @@ __device__ __forceinline__ void load_row(const Args& a, int64_t i, float& wi, in
 // unscaled weighted loss l and d l / d x of one element.  DENSE: y / ew are its target and weight; else wi / t its row's.
 template <bool DENSE>
 __device__ __forceinline__ void one(const Args& a, float x, int c, float wi, int t, float y, float ew, float& l, float& d) {
-    const Elem p = elem(x);
+    const SigmoidElem p = sigmoid_elem(x);
     if constexpr (DENSE) {
         const float pw = a.cw ? a.cw[c] : 1.0f;
         l = ((1.0f - y) * p.spp + pw * y * p.spn) * ew;
@@ -95,63 +77,6 @@ __device__ __forceinline__ void one(const Args& a, float x, int c, float wi, int
         }
         l *= wi;
         d *= wi;
-    }
-}
-
-template <typename T, int V> struct IO;
-template <> struct IO<float, 4> {
-    using Raw = f32x4;
-    static __device__ __forceinline__ Raw load(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-    static __device__ __forceinline__ void unpack(const Raw& t, float (&v)[4]) { v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[4]) { *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; }
-};
-template <> struct IO<float, 1> {
-    using Raw = float;
-    static __device__ __forceinline__ Raw load(const float* p) { return *p; }
-    static __device__ __forceinline__ void unpack(const Raw& t, float (&v)[1]) { v[0] = t; }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[1]) { *p = v[0]; }
-};
-template <> struct IO<unsigned short, 8> {               // bf16 bits
-    using Raw = u32x4;
-    static __device__ __forceinline__ Raw load(const unsigned short* p) { return *reinterpret_cast<const u32x4*>(p); }
-    static __device__ __forceinline__ void unpack(const Raw& w, float (&v)[8]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { v[2 * q] = bf16_bits_to_f32(w[q] & 0xffffu); v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u); }
-    }
-    static __device__ __forceinline__ void store(unsigned short* p, const float (&v)[8]) {
-        u32x4 w;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) w[q] = pack_bf16x2(v[2 * q], v[2 * q + 1]);
-        *reinterpret_cast<u32x4*>(p) = w;
-    }
-};
-template <> struct IO<unsigned short, 1> {
-    using Raw = unsigned short;
-    static __device__ __forceinline__ Raw load(const unsigned short* p) { return *p; }
-    static __device__ __forceinline__ void unpack(const Raw& t, float (&v)[1]) { v[0] = bf16_bits_to_f32(t); }
-    static __device__ __forceinline__ void store(unsigned short* p, const float (&v)[1]) { *p = f32_to_bf16_bits(v[0]); }
-};
-
-// V consecutive floats of a contiguous fp32 array (the element losses, dense targets and weights), 16 bytes at a time
-template <int V>
-__device__ __forceinline__ void load_f32(const float* p, float (&v)[V]) {
-    if constexpr (V == 1) {
-        v[0] = *p;
-    } else {
-#pragma unroll
-        for (int q = 0; q < V / 4; ++q) {
-            const f32x4 t = reinterpret_cast<const f32x4*>(p)[q];
-            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-        }
-    }
-}
-template <int V>
-__device__ __forceinline__ void store_f32(float* p, const float (&v)[V]) {
-    if constexpr (V == 1) {
-        *p = v[0];
-    } else {
-#pragma unroll
-        for (int q = 0; q < V / 4; ++q) reinterpret_cast<f32x4*>(p)[q] = f32x4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
     }
 }
 
@@ -176,14 +101,14 @@ __global__ void __launch_bounds__(kThreads) bce_det_kernel(Args a) {
     for (int64_t v0 = gtid; v0 < a.nv; v0 += U * T_) {
         int64_t iv[U];
         unsigned cv[U];
-        typename IO<T, V>::Raw raw[U];
+        typename VTn<T, V>::Raw raw[U];
 #pragma unroll
         for (int j = 0; j < U; ++j) {
             iv[j] = i; cv[j] = c;
             i += a.qs; c += a.rs;
             if (c >= C) { c -= C; ++i; }
             const int64_t v = v0 + j * T_;
-            if (v < a.nv) raw[j] = IO<T, V>::load(V == 1 ? x + iv[j] * a.ldx + cv[j] : x + a.h + v * V);
+            if (v < a.nv) raw[j] = VTn<T, V>::raw(V == 1 ? x + iv[j] * a.ldx + cv[j] : x + a.h + v * V);
         }
 #pragma unroll
         for (int j = 0; j < U; ++j) {
@@ -191,7 +116,7 @@ __global__ void __launch_bounds__(kThreads) bce_det_kernel(Args a) {
             if (v >= a.nv) continue;
             const int64_t e = V == 1 ? v : a.h + v * V;                    // flat logical index of the first element
             float xv[V], lv[V], dv[V], yv[V], wv[V];
-            IO<T, V>::unpack(raw[j], xv);
+            VTn<T, V>::unpack(raw[j], xv);
             int64_t ii = iv[j];
             int ci = (int)cv[j];
             float wi = 1.0f;
@@ -215,7 +140,7 @@ __global__ void __launch_bounds__(kThreads) bce_det_kernel(Args a) {
                     }
                 }
             }
-            if (dx) IO<T, V>::store(V == 1 ? dx + iv[j] * a.lddx + cv[j] : dx + e, dv);
+            if (dx) VTn<T, V>::store(V == 1 ? dx + iv[j] * a.lddx + cv[j] : dx + e, dv);
             if (a.elems) store_f32<V>(a.elems + e, lv);
         }
     }
@@ -232,10 +157,10 @@ __global__ void __launch_bounds__(kThreads) bce_det_kernel(Args a) {
             int t = -1;
             if constexpr (!DENSE) load_row(a, ii, wi, t);
             float xv[1];
-            IO<T, 1>::unpack(IO<T, 1>::load(x + e), xv);
+            VTn<T, 1>::load(x + e, xv);
             one<DENSE>(a, xv[0], ci, wi, t, DENSE ? a.tgt[e] : 0.0f, (DENSE && a.ew) ? a.ew[e] : 1.0f, l, d);
             acc += l;
-            if (dx) { const float dd[1] = {d * a.scale}; IO<T, 1>::store(dx + e, dd); }
+            if (dx) { const float dd[1] = {d * a.scale}; VTn<T, 1>::store(dx + e, dd); }
             if (a.elems) a.elems[e] = l;
         }
     }

@@ -18,10 +18,11 @@
 #include <limits.h>
 
 #include "common.h"
+#include "head_math.h"
+#include "vec16.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kMaxBins = 256;
 constexpr int kWpb = 4;                       // waves per block
 // rows beyond 4 x kMaxBlocks are walked by the same waves (fewer block flushes).  Measured at [65536, 1000] fp32 with a table:
@@ -29,9 +30,6 @@ constexpr int kWpb = 4;                       // waves per block
 constexpr unsigned kMaxBlocks = 1024;
 constexpr int kSlots = 6;                     // LDS: rows, out_of_range, hits[4], then 3 x nb bin slots
 
-__device__ __forceinline__ float fast_exp2(float v) { return __builtin_amdgcn_exp2f(v); }
-__device__ __forceinline__ float load1(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float load1(const unsigned short* p, int64_t i) { return bf16_bits_to_f32(p[i]); }
 
 struct EvalArgs {
     const void* x; int64_t ldx;
@@ -117,37 +115,10 @@ __device__ __forceinline__ void finish_row(const EvalArgs& a, long long* s, cons
 // One lane holds V consecutive columns per chunk: 16 bytes of fp32 (4) or bf16 (8); a bf16 row with C % 8 == 4 ends on
 // an 8-byte half vector in some lane.  Only the last chunk (NCH - 1) can be ragged.  The lane's table entries are loop
 // invariant and stay in registers; the next row's loads are issued before the current row is reduced.
-template <typename T> struct Row;
-template <> struct Row<float> {
-    static constexpr int V = 4;
-    using Raw = u32x4;
-    static __device__ __forceinline__ Raw load(const float* p, int nv) {
-        return nv > 0 ? *reinterpret_cast<const u32x4*>(p) : u32x4{0u, 0u, 0u, 0u};
-    }
-    static __device__ __forceinline__ void unpack(const Raw& w, float (&v)[4]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = __uint_as_float(w[q]);
-    }
-};
-template <> struct Row<unsigned short> {
-    static constexpr int V = 8;
-    using Raw = u32x4;
-    typedef u32x4 u32x4_a8 __attribute__((aligned(8)));     // rows of a [B, 1204] bf16 matrix start on 8-byte boundaries
-    static __device__ __forceinline__ Raw load(const unsigned short* p, int nv) {
-        u32x4 w = u32x4{0u, 0u, 0u, 0u};
-        if (nv == 8) w = *reinterpret_cast<const u32x4_a8*>(p);
-        else if (nv == 4) { const u32x2 h = *reinterpret_cast<const u32x2*>(p); w.x = h.x; w.y = h.y; }
-        return w;
-    }
-    static __device__ __forceinline__ void unpack(const Raw& w, float (&v)[8]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { v[2 * q] = bf16_bits_to_f32(w[q] & 0xffffu); v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u); }
-    }
-};
 
 template <typename T, int NCH, bool TAB>
 __global__ void __launch_bounds__(256) eval_reg_kernel(EvalArgs a) {
-    constexpr int V = Row<T>::V;
+    constexpr int V = VT<T>::V;
     constexpr int JL = NCH - 1;
     __shared__ long long s_acc[kSlots + 3 * kMaxBins];
     __shared__ double s_edges[kMaxBins + 1];
@@ -156,12 +127,12 @@ __global__ void __launch_bounds__(256) eval_reg_kernel(EvalArgs a) {
     int row = blockIdx.x * kWpb + (threadIdx.x >> 6);
     const int left = a.C - (JL * 64 + lane) * V;        // columns of the last chunk this lane owns: V, 4 (bf16) or 0
     const int nl = left >= V ? V : (left > 0 ? left : 0);
-    typename Row<T>::Raw xr[NCH];
+    typename VT<T>::Raw xr[NCH];
     auto load_row = [&](int r) {
         const T* xp = static_cast<const T*>(a.x) + (int64_t)r * a.ldx;
 #pragma unroll
-        for (int j = 0; j < JL; ++j) xr[j] = Row<T>::load(xp + (j * 64 + lane) * V, V);
-        xr[JL] = Row<T>::load(xp + (JL * 64 + lane) * V, nl);
+        for (int j = 0; j < JL; ++j) xr[j] = VT<T>::raw_row(xp + (j * 64 + lane) * V, V);
+        xr[JL] = VT<T>::raw_row(xp + (JL * 64 + lane) * V, nl);
     };
     if (row < a.B) load_row(row);                     // wave-uniform; in flight while the block stages its LDS
     float tb[NCH][V];
@@ -183,7 +154,7 @@ __global__ void __launch_bounds__(256) eval_reg_kernel(EvalArgs a) {
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             float xv[V];
-            Row<T>::unpack(xr[j], xv);
+            VT<T>::unpack(xr[j], xv);
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 const bool valid = j < JL || e < nl;
@@ -231,11 +202,11 @@ __global__ void __launch_bounds__(256) eval_stream_kernel(EvalArgs a) {
         const T* x = static_cast<const T*>(a.x) + (int64_t)row * a.ldx;
         const int64_t t = a.tgt[row];
         const bool ok = t >= 0 && t < a.C;
-        const float zt = ok ? load1(x, t) * (TAB ? a.tab[t] : 1.0f) : 0.f;
+        const float zt = ok ? VT<T>::load1(x + t) * (TAB ? a.tab[t] : 1.0f) : 0.f;
         float m = -INFINITY, s = 0.f;
         int mi = lane < a.C ? lane : INT_MAX, cnt = 0;
         for (int c = lane; c < a.C; c += 64) {
-            const float z = load1(x, c) * (TAB ? a.tab[c] : 1.0f);
+            const float z = VT<T>::load1(x + c) * (TAB ? a.tab[c] : 1.0f);
             cnt += (z > zt) | ((z == zt) & (c < (int)t));
             if (z > m) {
                 s = s * fast_exp2((m - z) * kLog2e) + 1.0f;
@@ -263,7 +234,7 @@ template <typename T>
 int launch(const EvalArgs& a, hipStream_t st) {
     const unsigned want = (unsigned)((a.B + kWpb - 1) / kWpb);
     const dim3 grid(want < kMaxBlocks ? want : kMaxBlocks);
-    constexpr int V = Row<T>::V;
+    constexpr int V = VT<T>::V;
     constexpr int PA = sizeof(T) == 2 ? 8 : 16;                 // row start alignment in bytes (4 elements)
     const bool reg = a.C % 4 == 0 && a.C <= 2048 && a.ldx % 4 == 0 && aligned(a.x, PA) && (!a.tab || aligned(a.tab, 16));
     if (reg) {

@@ -21,42 +21,16 @@
 // halving tree folds the threads: a fixed order for a given N, integers exact, no float atomics, the same bits every call.
 // Only the ticket word has to be zero on entry, and it is zero again on exit.
 #include "common.h"
+#include "head_math.h"
+#include "vec16.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 constexpr int kMaxBlocks = (IIF_HEAD_LOSS_WORKSPACE_BYTES / 4 - 4) / 3;       // partial triples behind the 4-word header
 static_assert(IIF_HEAD_LOSS_WORKSPACE_BYTES == 4 * (4 + 3 * kMaxBlocks), "a 4-word header and whole (sum, valid, hits) triples");
 static_assert(IIF_HEAD_LOSS_WORKSPACE_BYTES <= IIF_CE_WORKSPACE_BYTES, "the per-stream CE workspace serves this head too");
 
-__device__ __forceinline__ float fast_exp2(float v) { return __builtin_amdgcn_exp2f(v); }
-__device__ __forceinline__ float fast_log2(float v) { return __builtin_amdgcn_logf(v); }
-
-template <typename T> struct Io;
-template <> struct Io<float> {
-    static constexpr int VEC_BYTES = 16;
-    static __device__ __forceinline__ void load4(const float* p, float (&v)[4]) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    static __device__ __forceinline__ void store4(float* p, const float (&v)[4]) { *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; }
-    static __device__ __forceinline__ float load1(const float* p) { return *p; }
-    static __device__ __forceinline__ void store1(float* p, float v) { *p = v; }
-};
-template <> struct Io<unsigned short> {  // bf16 bits
-    static constexpr int VEC_BYTES = 8;
-    static __device__ __forceinline__ void load4(const unsigned short* p, float (&v)[4]) {
-        const u32x2 w = *reinterpret_cast<const u32x2*>(p);
-        v[0] = bf16_bits_to_f32(w.x & 0xffffu); v[1] = __uint_as_float(w.x & 0xffff0000u);
-        v[2] = bf16_bits_to_f32(w.y & 0xffffu); v[3] = __uint_as_float(w.y & 0xffff0000u);
-    }
-    static __device__ __forceinline__ void store4(unsigned short* p, const float (&v)[4]) {
-        *reinterpret_cast<u32x2*>(p) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-    }
-    static __device__ __forceinline__ float load1(const unsigned short* p) { return bf16_bits_to_f32(*p); }
-    static __device__ __forceinline__ void store1(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
-};
+template <typename T> constexpr int kVecBytes = 4 * (int)sizeof(T);      // a group of 4 columns
 
 struct HeadLossArgs {
     const void* x; int64_t ldx;
@@ -77,16 +51,16 @@ struct HeadLossArgs {
 // not exist read as -inf (they never win the max, add 0 to the sum and never outrank a target) and are never written.
 template <typename T, bool RAGGED>
 __device__ __forceinline__ void load_group(const T* row, int c0, int C, bool vec, float (&v)[4]) {
-    if (vec && (!RAGGED || c0 + 4 <= C)) { Io<T>::load4(row + c0, v); return; }
+    if (vec && (!RAGGED || c0 + 4 <= C)) { VT<T>::load4(row + c0, v); return; }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (!RAGGED || c0 + e < C) ? Io<T>::load1(row + c0 + e) : -INFINITY;
+    for (int e = 0; e < 4; ++e) v[e] = (!RAGGED || c0 + e < C) ? VT<T>::load1(row + c0 + e) : -INFINITY;
 }
 template <typename T, bool RAGGED>
 __device__ __forceinline__ void store_group(T* row, int c0, int C, bool vec, const float (&v)[4]) {
-    if (vec && (!RAGGED || c0 + 4 <= C)) { Io<T>::store4(row + c0, v); return; }
+    if (vec && (!RAGGED || c0 + 4 <= C)) { VT<T>::store4(row + c0, v); return; }
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-        if (!RAGGED || c0 + e < C) Io<T>::store1(row + c0 + e, v[e]);
+        if (!RAGGED || c0 + e < C) VT<T>::store1(row + c0 + e, v[e]);
 }
 
 // NCH: groups per lane = ceil(C / 256).  Blocks of 4 waves; a wave walks rows wave, wave + n_waves, ...
@@ -133,7 +107,7 @@ __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
 #pragma unroll
         for (int j = 0; j < NCH - 1; ++j) load_group<T, false>(xr, (j * 64 + lane) * 4, C, a.vec_in, z[j]);
         load_group<T, true>(xr, ((NCH - 1) * 64 + lane) * 4, C, a.vec_in, z[NCH - 1]);
-        const float xt = Io<T>::load1(xr + l);
+        const float xt = VT<T>::load1(xr + l);
         // top-1 on the RAW scores, iif_topk_hits' tie rule: columns that outrank the target, an equal score at a lower index included
         int cnt = 0;
         float m = -INFINITY;
@@ -242,14 +216,14 @@ __global__ void __launch_bounds__(256) head_loss_scale_kernel(const T* u, int64_
         const int64_t n4 = n / 4;
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
             float v[4];
-            Io<T>::load4(u + 4 * i, v);
+            VT<T>::load4(u + 4 * i, v);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] *= f;
-            Io<T>::store4(out + 4 * i, v);
+            VT<T>::store4(out + 4 * i, v);
         }
-        for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) Io<T>::store1(out + i, Io<T>::load1(u + i) * f);
+        for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) VT<T>::store1(out + i, VT<T>::load1(u + i) * f);
     } else {
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) Io<T>::store1(out + i, Io<T>::load1(u + i) * f);
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) VT<T>::store1(out + i, VT<T>::load1(u + i) * f);
     }
 }
 
@@ -257,8 +231,8 @@ inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(
 
 template <typename T>
 int launch_fwd(HeadLossArgs a, hipStream_t st) {
-    a.vec_in = a.N > 0 && a.ldx % 4 == 0 && aligned(a.x, Io<T>::VEC_BYTES);
-    a.vec_out = a.dx != nullptr && a.lddx % 4 == 0 && aligned(a.dx, Io<T>::VEC_BYTES);
+    a.vec_in = a.N > 0 && a.ldx % 4 == 0 && aligned(a.x, kVecBytes<T>);
+    a.vec_out = a.dx != nullptr && a.lddx % 4 == 0 && aligned(a.dx, kVecBytes<T>);
     int blocks = (a.N + 3) / 4;
     if (blocks < 1) blocks = 1;                   // N == 0: one block writes loss 0, acc 0, avg 1
     if (blocks > kMaxBlocks) blocks = kMaxBlocks;

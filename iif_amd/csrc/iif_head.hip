@@ -17,80 +17,15 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "head_math.h"
 #include "loss_reduce.h"
+#include "vec16.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-__device__ __forceinline__ float fast_exp2(float v) { return __builtin_amdgcn_exp2f(v); }
-__device__ __forceinline__ float fast_log2(float v) { return __builtin_amdgcn_logf(v); }
-
-// ---------------------------------------------------------------- element I/O
-template <typename T> struct Io;
-template <> struct Io<float> {
-    static __device__ __forceinline__ f32x4 load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-    static __device__ __forceinline__ void store4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-    static __device__ __forceinline__ float load1(const float* p) { return *p; }
-    static __device__ __forceinline__ void store1(float* p, float v) { *p = v; }
-};
-template <> struct Io<unsigned short> {  // bf16 bits
-    static __device__ __forceinline__ f32x4 load4(const unsigned short* p) {
-        u32x2 w = *reinterpret_cast<const u32x2*>(p);
-        f32x4 r;
-        r.x = bf16_bits_to_f32(w.x & 0xffffu); r.y = __uint_as_float(w.x & 0xffff0000u);
-        r.z = bf16_bits_to_f32(w.y & 0xffffu); r.w = __uint_as_float(w.y & 0xffff0000u);
-        return r;
-    }
-    static __device__ __forceinline__ void store4(unsigned short* p, f32x4 v) {
-        u32x2 w; w.x = pack_bf16x2(v.x, v.y); w.y = pack_bf16x2(v.z, v.w);
-        *reinterpret_cast<u32x2*>(p) = w;
-    }
-    static __device__ __forceinline__ float load1(const unsigned short* p) { return bf16_bits_to_f32(*p); }
-    static __device__ __forceinline__ void store1(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
-};
-
-// One lane's V consecutive columns of a row as V floats: 16 bytes per lane for both element types (4 fp32 / 8 bf16), so
-// every wave instruction moves whole 1-KB runs.  `nv` (0 < nv <= V, multiple of 4) is the number of columns that exist:
-// the bf16 row tail of a class count that is 4 but not 0 modulo 8 (1204) is an 8-byte access.
-template <typename T> struct RowIo;
-// A row is fetched as RAW 16-byte vectors and unpacked where it is used, so rows in flight cost 4 registers per lane and
-// chunk whatever the element type: DEPTH rows are kept in flight per wave (bf16 rows are half the bytes, so two of them
-// give a CU the same bytes in flight as one fp32 row: with one, [65536, 1000] bf16 ran at 3.2 TB/s against 4.9 for fp32).
-template <> struct RowIo<float> {
-    static constexpr int V = 4, DEPTH = 1;
-    using Raw = f32x4;
-    static __device__ __forceinline__ Raw load_raw(const float* p, int) { return *reinterpret_cast<const f32x4*>(p); }
-    static __device__ __forceinline__ void unpack(const Raw& t, float (&v)[4]) { v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    static __device__ __forceinline__ void store(float* p, int, const float (&v)[4]) {
-        *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-    }
-};
-template <> struct RowIo<unsigned short> {
-    static constexpr int V = 8, DEPTH = 2;
-    using Raw = u32x4;
-    // 8-byte aligned 16-byte vectors: the rows of a CONTIGUOUS [B, C] matrix with C % 8 == 4 (LVIS: 1204) start on alternate
-    // 8-byte boundaries; gfx950 runs with unaligned access enabled, so the access stays one dwordx4 (round 3 / 4 advice: such a
-    // matrix used to fall back to the streaming kernel)
-    typedef u32x4 u32x4_a8 __attribute__((aligned(8)));
-    static __device__ __forceinline__ Raw load_raw(const unsigned short* p, int nv) {
-        u32x4 w = u32x4{0u, 0u, 0u, 0u};
-        if (nv == 8) w = *reinterpret_cast<const u32x4_a8*>(p);
-        else { const u32x2 h = *reinterpret_cast<const u32x2*>(p); w.x = h.x; w.y = h.y; }
-        return w;
-    }
-    static __device__ __forceinline__ void unpack(const Raw& w, float (&v)[8]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { v[2 * q] = bf16_bits_to_f32(w[q] & 0xffffu); v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u); }
-    }
-    static __device__ __forceinline__ void store(unsigned short* p, int nv, const float (&v)[8]) {
-        u32x4 w;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) w[q] = pack_bf16x2(v[2 * q], v[2 * q + 1]);
-        if (nv == 8) *reinterpret_cast<u32x4_a8*>(p) = w;
-        else *reinterpret_cast<u32x2*>(p) = u32x2{w.x, w.y};
-    }
-};
+// Rows go through VT<T> (vec16.h): one lane's V consecutive columns of a row are 16 bytes for both element types (4 fp32 / 8
+// bf16), so every wave instruction moves whole 1-KB runs, and a row is fetched raw and unpacked where it is used.
+template <typename T> constexpr int kDepth = sizeof(T) == 2 ? 2 : 1;      // rows in flight per wave (vec16.h, raw: two bf16 rows)
 
 struct CeArgs {
     const void* x; int64_t ldx;
@@ -143,8 +78,8 @@ __device__ __forceinline__ RowCoef row_coef(const CeArgs& a, int row) {
 // (launch bound: 16 row values per lane = C <= 1024 fit 80 registers, i.e. 6 waves per SIMD, when the allocator is told so; at 7 the
 // round-4 loop spills 9-14 registers)
 template <typename T, int NCH, int MODE>
-__global__ void __launch_bounds__(256, (NCH * RowIo<T>::V <= 16 ? 6 : 1)) row_reg_kernel(CeArgs a, float* sm_out, int64_t ld_sm) {
-    constexpr int V = RowIo<T>::V;                     // columns per lane and chunk: 16 bytes of T
+__global__ void __launch_bounds__(256, (NCH * VT<T>::V <= 16 ? 6 : 1)) row_reg_kernel(CeArgs a, float* sm_out, int64_t ld_sm) {
+    constexpr int V = VT<T>::V;                        // columns per lane and chunk: 16 bytes of T
     constexpr int EPD = V / 4;                         // elements per dword of the raw vector
     constexpr unsigned NEG = sizeof(T) == 2 ? 0xFF80FF80u : 0xFF800000u;       // -inf in every element of a dword
     constexpr int JL = NCH - 1;                        // the only chunk that can be ragged
@@ -153,23 +88,23 @@ __global__ void __launch_bounds__(256, (NCH * RowIo<T>::V <= 16 ? 6 : 1)) row_re
     const int wpb = blockDim.x >> 6;
     const int nwaves = gridDim.x * wpb;
     int row = blockIdx.x * wpb + (threadIdx.x >> 6);
-    constexpr int DEPTH = RowIo<T>::DEPTH;            // rows in flight per wave
-    typename RowIo<T>::Raw xr[DEPTH][NCH];
+    constexpr int DEPTH = kDepth<T>;                   // rows in flight per wave
+    typename VT<T>::RawF xr[DEPTH][NCH];
     // columns of the last chunk that exist for this lane: V, or 4 on the tail of a bf16 row with C % 8 == 4, or 0
     const int left = a.C - (JL * 64 + lane) * V;
     const int nl = left >= V ? V : (left > 0 ? left : 0);
     const bool half_tail = MODE != 2 && (a.C % V) != 0;     // block-uniform: some lane's last vector is an 8-byte half (bf16, C % 8 == 4)
-    auto load_row = [&](int r, typename RowIo<T>::Raw (&dst)[NCH]) {
+    auto load_row = [&](int r, typename VT<T>::RawF (&dst)[NCH]) {
         const T* xp = static_cast<const T*>(a.x) + (int64_t)r * a.ldx;
 #pragma unroll
-        for (int j = 0; j < JL; ++j) dst[j] = RowIo<T>::load_raw(xp + (j * 64 + lane) * V, V);
+        for (int j = 0; j < JL; ++j) dst[j] = VT<T>::raw_row_some(xp + (j * 64 + lane) * V, V);
         if (half_tail) {                               // rare shape: per-lane access width
-            if (nl > 0) dst[JL] = RowIo<T>::load_raw(xp + (JL * 64 + lane) * V, nl);
+            if (nl > 0) dst[JL] = VT<T>::raw_row_some(xp + (JL * 64 + lane) * V, nl);
         } else {                                       // unconditional: a lane without columns re-reads the row's first vector
-            dst[JL] = RowIo<T>::load_raw(xp + (nl > 0 ? (JL * 64 + lane) * V : 0), V);
+            dst[JL] = VT<T>::raw_row_some(xp + (nl > 0 ? (JL * 64 + lane) * V : 0), V);
         }
     };
-    auto mask_tail = [&](typename RowIo<T>::Raw& t) {  // -inf into the columns that do not exist
+    auto mask_tail = [&](typename VT<T>::RawF& t) {  // -inf into the columns that do not exist
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             if (q * EPD >= nl) t[q] = __builtin_bit_cast(decltype(t[q] + t[q]), NEG);
@@ -222,8 +157,7 @@ __global__ void __launch_bounds__(256, (NCH * RowIo<T>::V <= 16 ? 6 : 1)) row_re
                         const auto el = xr[0][j][q];          // by value: bit_cast of a vector-element lvalue reads element 0
                         w = __builtin_amdgcn_readlane(__builtin_bit_cast(unsigned, el), tl);
                     }
-            if constexpr (sizeof(T) == 2) xt = (te & 1) ? __uint_as_float(w & 0xffff0000u) : bf16_bits_to_f32(w & 0xffffu);
-            else xt = __uint_as_float(w);
+            xt = VT<T>::dword_elem(w, te);
         }
         float z[NCH][V];
         float m = -INFINITY;
@@ -231,7 +165,7 @@ __global__ void __launch_bounds__(256, (NCH * RowIo<T>::V <= 16 ? 6 : 1)) row_re
         for (int j = 0; j < NCH; ++j) {
             const float* tp = tab_s + (j * 64 + lane) * V;
             float xv[V];
-            RowIo<T>::unpack(xr[0][j], xv);
+            VT<T>::unpack(xr[0][j], xv);
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 z[j][e] = xv[e] * tp[e];
@@ -280,8 +214,8 @@ __global__ void __launch_bounds__(256, (NCH * RowIo<T>::V <= 16 ? 6 : 1)) row_re
             if (t_ok) r = lse - xt * tab_s[(int)ta_cur];
         } else {
             rc = row_coef(a, row);
-            if (rc.ta >= 0) r += rc.wa * (lse - Io<T>::load1(x + rc.ta) * tab_s[rc.ta]);
-            if (rc.tb >= 0) r += rc.wb * (lse - Io<T>::load1(x + rc.tb) * tab_s[rc.tb]);
+            if (rc.ta >= 0) r += rc.wa * (lse - VT<T>::load1(x + rc.ta) * tab_s[rc.ta]);
+            if (rc.tb >= 0) r += rc.wb * (lse - VT<T>::load1(x + rc.tb) * tab_s[rc.tb]);
         }
         if (lane == 0) a.loss_row[row] = rc.rw * r;
         wave_loss += rc.rw * r;
@@ -306,7 +240,7 @@ __global__ void __launch_bounds__(256, (NCH * RowIo<T>::V <= 16 ? 6 : 1)) row_re
                 }
 #pragma unroll
                 for (int e = 0; e < V; ++e) p[e] *= tp[e];
-                RowIo<T>::store(dx + c0, n, p);
+                VT<T>::store_row_some(dx + c0, n, p);
             }
         }
     }
@@ -322,21 +256,21 @@ __global__ void __launch_bounds__(256) row_stream_kernel(CeArgs a, float* sm_out
     if (row < a.B) {                              // wave-uniform
         const T* x = static_cast<const T*>(a.x) + (int64_t)row * a.ldx;
         float m = -INFINITY;
-        for (int c = lane; c < a.C; c += 64) m = fmaxf(m, Io<T>::load1(x + c) * (a.tab[c] * kLog2e));
+        for (int c = lane; c < a.C; c += 64) m = fmaxf(m, VT<T>::load1(x + c) * (a.tab[c] * kLog2e));
         m = wave_max(m);
         float s = 0.f;
-        for (int c = lane; c < a.C; c += 64) s += fast_exp2(Io<T>::load1(x + c) * (a.tab[c] * kLog2e) - m);
+        for (int c = lane; c < a.C; c += 64) s += fast_exp2(VT<T>::load1(x + c) * (a.tab[c] * kLog2e) - m);
         s = wave_sum(s);
         const float inv_s = 1.0f / s;
         if (MODE == 1) {
             float* o = sm_out + (int64_t)row * ld_sm;
-            for (int c = lane; c < a.C; c += 64) o[c] = fast_exp2(Io<T>::load1(x + c) * (a.tab[c] * kLog2e) - m) * inv_s;
+            for (int c = lane; c < a.C; c += 64) o[c] = fast_exp2(VT<T>::load1(x + c) * (a.tab[c] * kLog2e) - m) * inv_s;
         } else {
             const float lse = kLn2 * (m + fast_log2(s));
             const RowCoef rc = row_coef(a, row);
             float r = 0.f;
-            if (rc.ta >= 0) r += rc.wa * (lse - Io<T>::load1(x + rc.ta) * a.tab[rc.ta]);
-            if (rc.tb >= 0) r += rc.wb * (lse - Io<T>::load1(x + rc.tb) * a.tab[rc.tb]);
+            if (rc.ta >= 0) r += rc.wa * (lse - VT<T>::load1(x + rc.ta) * a.tab[rc.ta]);
+            if (rc.tb >= 0) r += rc.wb * (lse - VT<T>::load1(x + rc.tb) * a.tab[rc.tb]);
             if (lane == 0) a.loss_row[row] = rc.rw * r;
             wave_loss = rc.rw * r;
             if (a.dx != nullptr) {
@@ -345,10 +279,10 @@ __global__ void __launch_bounds__(256) row_stream_kernel(CeArgs a, float* sm_out
                 const float gs = g * (rc.wa + rc.wb) * inv_s, ga = g * rc.wa, gb = g * rc.wb;
                 for (int c = lane; c < a.C; c += 64) {
                     const float tc = a.tab[c];
-                    float p = fast_exp2(Io<T>::load1(x + c) * (tc * kLog2e) - m) * gs;
+                    float p = fast_exp2(VT<T>::load1(x + c) * (tc * kLog2e) - m) * gs;
                     if (c == rc.ta) p -= ga;
                     if (c == rc.tb) p -= gb;
-                    Io<T>::store1(dx + c, p * tc);
+                    VT<T>::store1(dx + c, p * tc);
                 }
             }
         }
@@ -364,7 +298,7 @@ __global__ void __launch_bounds__(256) scale_rows_kernel(const T* x, int64_t ldx
     if (row >= B) return;
     const T* xr = x + (int64_t)row * ldx;
     T* o = out + (int64_t)row * ldo;
-    for (int c = lane; c < C; c += 64) Io<T>::store1(o + c, Io<T>::load1(xr + c) * tab[c]);
+    for (int c = lane; c < C; c += 64) VT<T>::store1(o + c, VT<T>::load1(xr + c) * tab[c]);
 }
 
 template <typename T>
@@ -377,10 +311,10 @@ __global__ void __launch_bounds__(256) topk_hits_kernel(const T* x, int64_t ldx,
     const int64_t t = tgt[row];
     if (t < 0 || t >= C) return;
     const T* xr = x + (int64_t)row * ldx;
-    const float zt = Io<T>::load1(xr + t) * (tab ? tab[t] : 1.0f);
+    const float zt = VT<T>::load1(xr + t) * (tab ? tab[t] : 1.0f);
     int cnt = 0;
     for (int c = lane; c < C; c += 64) {
-        const float z = Io<T>::load1(xr + c) * (tab ? tab[c] : 1.0f);
+        const float z = VT<T>::load1(xr + c) * (tab ? tab[c] : 1.0f);
         cnt += (z > zt) || (z == zt && c < (int)t);
     }
     cnt = wave_sum_i(cnt);
@@ -395,7 +329,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) scale_by_scalar_kernel(const T* x, int64_t n, const float* s, T* out) {
     const float f = *s;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        Io<T>::store1(out + i, Io<T>::load1(x + i) * f);
+        VT<T>::store1(out + i, VT<T>::load1(x + i) * f);
 }
 
 inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
@@ -417,8 +351,8 @@ int launch_rows(CeArgs a, float* sm_out, int64_t ld_sm, hipStream_t st, bool* in
     if (maxb > kCePartialSlots) maxb = kCePartialSlots;
     const dim3 pgrid(grid.x < maxb ? grid.x : maxb);
     // rows in 16-byte lane vectors: 4 fp32 / 8 bf16 columns; a bf16 row may end on a half vector (C % 8 == 4: 1204)
-    constexpr int V = RowIo<T>::V;
-    // (bf16 rows need 8-byte alignment only - RowIo<unsigned short>: a contiguous [B, 1204] matrix qualifies)
+    constexpr int V = VT<T>::V;
+    // (bf16 rows need 8-byte alignment only - vec16.h, raw_row_some: a contiguous [B, 1204] matrix qualifies)
     constexpr int RA = sizeof(T) == 2 ? 4 : V;            // row pitch granule in elements, = 8 / 16 bytes
     constexpr int PA = sizeof(T) == 2 ? 8 : 16;
     bool vec = (a.C % 4 == 0) && (a.C <= 2048) && (a.ldx % RA == 0) && aligned(a.x, PA) && aligned(a.tab, 16);

@@ -9,12 +9,9 @@
 // by one block in a fixed order (deterministic).
 #include "common.h"
 #include "loss_reduce.h"
+#include "vec16.h"
 
 namespace {
-
-template <typename T> struct LD;
-template <> struct LD<float> { static __device__ __forceinline__ float ld(const float* p) { return *p; } };
-template <> struct LD<unsigned short> { static __device__ __forceinline__ float ld(const unsigned short* p) { return bf16_bits_to_f32(*p); } };
 
 __device__ __forceinline__ float block_sum(float v, float* sh) {
     v = wave_sum(v);
@@ -39,7 +36,7 @@ __global__ void __launch_bounds__(256) mask_gather_kernel(const T* pred, const i
         return;
     }
     const T* p = pred + ((int64_t)n * C + lb) * hw;
-    for (int i = threadIdx.x; i < hw; i += 256) o[i] = LD<T>::ld(p + i);
+    for (int i = threadIdx.x; i < hw; i += 256) o[i] = VT<T>::load1(p + i);
 }
 
 // loss_i = max(x,0) - x*t + log1p(exp(-|x|))   (F.binary_cross_entropy_with_logits);  d/dx = sigmoid(x) - t
@@ -57,7 +54,7 @@ __global__ void __launch_bounds__(256) mask_bce_kernel(const T* pred, const floa
     const float* t = target + (int64_t)n * hw;
     float acc = 0.f;
     for (int i = threadIdx.x; i < hw; i += 256) {
-        const float x = LD<T>::ld(pred + base + i), y = t[i];
+        const float x = VT<T>::load1(pred + base + i), y = t[i];
         acc += fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
         if (dpred) {
             const float s = 1.0f / (1.0f + expf(-x));

@@ -1,13 +1,14 @@
 // What the class-selected mask predictor kernels share: the plain 1x1 predictor (mask_predictor.hip), its NormedConv2d variant
 // (normed_mask_predictor.hip) and the fused mask head tail (mask_tail.hip).  Each piece exists once, here:
 //   host    the argument checks and the (dtype, vector width) dispatch of the C entries
-//   loads   Row<T, V>: V consecutive elements of a channel row as floats
+//   loads   VTn<T, V> (vec16.h): V consecutive elements of a channel row as floats
 //   forward the weight-row staging, the group fold, the BCE term, the sigmoid and the fold of a tile's loss into its row partial
 //   dweight the per-RoI row kernel of the two 1x1 predictors, the ascending list of a class's RoIs and the ordered sum of the
 //           listed rows, the plain per-class kernel (scratch [n][cin + 1] -> dweight [C][cin], dbias [C])
 // Every sum here has ONE order, which the callers' outputs depend on to the bit.
 #pragma once
 #include "common.h"
+#include "vec16.h"
 
 namespace {
 
@@ -41,38 +42,6 @@ template <typename F> inline void dispatch_dtype(int dtype, F launch) {
 template <typename F> inline void dispatch_row(int dtype, bool wide, F launch) {
     dispatch_dtype(dtype, [&](auto t) { if (wide) launch(t, Width<4>()); else launch(t, Width<1>()); });
 }
-
-// V consecutive elements of a channel row as floats
-template <typename T, int V> struct Row;
-template <> struct Row<float, 1> {
-    static __device__ __forceinline__ void ld(const float* p, float (&v)[1]) { v[0] = *p; }
-    static __device__ __forceinline__ void st(float* p, const float (&v)[1]) { *p = v[0]; }
-};
-template <> struct Row<float, 4> {
-    static __device__ __forceinline__ void ld(const float* p, float (&v)[4]) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-        v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
-    }
-    static __device__ __forceinline__ void st(float* p, const float (&v)[4]) {
-        f32x4 q; q[0] = v[0]; q[1] = v[1]; q[2] = v[2]; q[3] = v[3];
-        *reinterpret_cast<f32x4*>(p) = q;
-    }
-};
-template <> struct Row<unsigned short, 1> {
-    static __device__ __forceinline__ void ld(const unsigned short* p, float (&v)[1]) { v[0] = bf16_bits_to_f32(*p); }
-    static __device__ __forceinline__ void st(unsigned short* p, const float (&v)[1]) { *p = f32_to_bf16_bits(v[0]); }
-};
-template <> struct Row<unsigned short, 4> {
-    static __device__ __forceinline__ void ld(const unsigned short* p, float (&v)[4]) {
-        const u32x2 q = *reinterpret_cast<const u32x2*>(p);
-        v[0] = bf16_bits_to_f32(q[0] & 0xffffu); v[1] = __uint_as_float(q[0] & 0xffff0000u);
-        v[2] = bf16_bits_to_f32(q[1] & 0xffffu); v[3] = __uint_as_float(q[1] & 0xffff0000u);
-    }
-    static __device__ __forceinline__ void st(unsigned short* p, const float (&v)[4]) {
-        u32x2 q; q[0] = pack_bf16x2(v[0], v[1]); q[1] = pack_bf16x2(v[2], v[3]);
-        *reinterpret_cast<u32x2*>(p) = q;
-    }
-};
 
 // Sum over the 256 threads of a block in a fixed order (butterfly inside a wave, the four waves in index order); every thread
 // gets the sum.  red: 4 floats of LDS that nothing else uses until the next barrier after the call.
@@ -162,7 +131,7 @@ __global__ void __launch_bounds__(256) mask_predict_dw_rows_kernel(const T* __re
 #pragma unroll 4
         for (int i = l16; i < per; i += 16) {
             float v[V];
-            Row<T, V>::ld(xp + i * V, v);
+            VTn<T, V>::load(xp + i * V, v);
 #pragma unroll
             for (int j = 0; j < V; ++j) acc = fmaf(sg[i * V + j], v[j], acc);
         }

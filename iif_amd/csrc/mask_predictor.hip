@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) mask_predict_fwd_kernel(const T* __restri
 #pragma unroll 8
         for (int c = grp; c < cin; c += G) {
             float v[V];
-            Row<T, V>::ld(xp + (int64_t)c * hw, v);
+            VTn<T, V>::load(xp + (int64_t)c * hw, v);
             const float wc = sw[c];
 #pragma unroll
             for (int j = 0; j < V; ++j) acc[j] = fmaf(wc, v[j], acc[j]);
@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(256) mask_predict_dx_kernel(const float* __res
         float v[V];
 #pragma unroll
         for (int j = 0; j < V; ++j) v[j] = sg[p + j] * wc;
-        Row<T, V>::st(out + (int64_t)i * V, v);
+        VTn<T, V>::store(out + (int64_t)i * V, v);
     }
 }
 

@@ -31,10 +31,6 @@ static_assert(kPix >= kMinTile, "the wrappers allocate one row partial per kMinT
 constexpr int kCols = 128;                   // columns per chunk: one 32-column MFMA tile per wave; forward / rows: two chunks
 constexpr int kSlab = 32;                    // Ci values staged per round
 
-__device__ __forceinline__ float ldf(const float* p) { return *p; }
-__device__ __forceinline__ float ldf(const unsigned short* p) { return bf16_bits_to_f32(*p); }
-__device__ __forceinline__ void stf(float* p, float v) { *p = v; }
-__device__ __forceinline__ void stf(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
 __device__ __forceinline__ int crow(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }   // C/D row of register r
 // the output pixel (2i + a, 2j + b) of input pixel p = i * w + j in a [2h][2w] map
 __device__ __forceinline__ int out_pixel(int p, int ab, int w) {
@@ -50,7 +46,7 @@ __device__ __forceinline__ void load_slab(const T* __restrict__ fn, int ci, int 
 #pragma unroll
     for (int rr = 0; rr < kSlab / 4; ++rr) {
         const int k = k0 + rr * 4 + row0;
-        stg[rr] = (pok && k < ci) ? ldf(fn + (int64_t)k * hw + p0 + px) : 0.f;
+        stg[rr] = (pok && k < ci) ? VT<T>::load1(fn + (int64_t)k * hw + p0 + px) : 0.f;
     }
 }
 
@@ -276,7 +272,7 @@ __global__ void __launch_bounds__(256) mask_tail_df_kernel(const float* __restri
     if (lb < 0 || lb >= C) {                             // block-uniform: a zero slice
         const int px = tid & 63;
         if (p0 + px < hw)
-            for (int c = tid >> 6; c < ci; c += 4) stf(dfn + (int64_t)c * hw + p0 + px, 0.f);
+            for (int c = tid >> 6; c < ci; c += 4) VT<T>::store1(dfn + (int64_t)c * hw + p0 + px, 0.f);
         return;
     }
     for (int c = tid; c < kMaxC; c += 256) sw[c] = c < co ? weight[lb * ld_w + c] : 0.f;
@@ -323,7 +319,7 @@ __global__ void __launch_bounds__(256) mask_tail_df_kernel(const float* __restri
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int c = cc * 32 + crow(r, half);
-                if (c < ci && p < hw) stf(dfn + (int64_t)c * hw + p, s ? acc[1][r] : acc[0][r]);
+                if (c < ci && p < hw) VT<T>::store1(dfn + (int64_t)c * hw + p, s ? acc[1][r] : acc[0][r]);
             }
         }
     }
@@ -359,7 +355,7 @@ __global__ void __launch_bounds__(256) mask_tail_dup_kernel(const T* __restrict_
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) {
             const int c = rr * 4 + sc0;
-            stg[rr] = (pok && ci0 + c < ci) ? ldf(fn + (int64_t)c * hw) : 0.f;
+            stg[rr] = (pok && ci0 + c < ci) ? VT<T>::load1(fn + (int64_t)c * hw) : 0.f;
         }
     };
     if (total > 0) load(0);

@@ -4,18 +4,9 @@
 // The GEMMs run on iif_conv_igemm / iif_conv_wgrad; these kernels are the per-row maps and their
 // backward.  One 64-lane wave per row, fp32 math, shuffle reductions; HBM/latency-bound, tiny.
 #include "common.h"
+#include "vec16.h"
 
 namespace {
-
-template <typename T> struct HIO;
-template <> struct HIO<float> {
-    static __device__ __forceinline__ float ld(const float* p) { return *p; }
-    static __device__ __forceinline__ void st(float* p, float v) { *p = v; }
-};
-template <> struct HIO<unsigned short> {
-    static __device__ __forceinline__ float ld(const unsigned short* p) { return bf16_bits_to_f32(*p); }
-    static __device__ __forceinline__ void st(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
-};
 
 // mode 0: out = x * scale/(1+n)      (cosine feature map)
 // mode 1: out = x / max(n, eps)      (F.normalize; rows of zeros stay zero)
@@ -27,11 +18,11 @@ __global__ void __launch_bounds__(256) rowmap_fwd_kernel(const TI* x, int rows, 
     if (row >= rows) return;
     const TI* xr = x + (int64_t)row * ldx;
     float ss = 0.f;
-    for (int c = lane; c < cols; c += 64) { const float v = HIO<TI>::ld(xr + c); ss = fmaf(v, v, ss); }
+    for (int c = lane; c < cols; c += 64) { const float v = VT<TI>::load1(xr + c); ss = fmaf(v, v, ss); }
     const float n = sqrtf(wave_sum(ss));
     const float coef = mode == 0 ? scale / (1.0f + n) : (n > 0.f ? 1.0f / fmaxf(n, eps) : 0.f);
     TO* o = out + (int64_t)row * ldo;
-    for (int c = lane; c < cols; c += 64) HIO<TO>::st(o + c, HIO<TI>::ld(xr + c) * coef);
+    for (int c = lane; c < cols; c += 64) VT<TO>::store1(o + c, VT<TI>::load1(xr + c) * coef);
     if (lane == 0 && norms) norms[row] = n;
 }
 
@@ -49,7 +40,7 @@ __global__ void __launch_bounds__(256) rowmap_bwd_kernel(const TI* x, const floa
     const TI* xr = x + (int64_t)row * ldx;
     const TG* gr = g + (int64_t)row * ldg;
     float dot = 0.f;
-    for (int c = lane; c < cols; c += 64) dot = fmaf(HIO<TG>::ld(gr + c), HIO<TI>::ld(xr + c), dot);
+    for (int c = lane; c < cols; c += 64) dot = fmaf(VT<TG>::load1(gr + c), VT<TI>::load1(xr + c), dot);
     dot = wave_sum(dot);
     const float n = norms[row];
     float a, b;
@@ -62,7 +53,7 @@ __global__ void __launch_bounds__(256) rowmap_bwd_kernel(const TI* x, const floa
         b = (n > 0.f && n >= eps) ? dot / (m * m * m) : 0.f;
     }
     TO* o = dx + (int64_t)row * lddx;
-    for (int c = lane; c < cols; c += 64) HIO<TO>::st(o + c, HIO<TG>::ld(gr + c) * a - HIO<TI>::ld(xr + c) * b);
+    for (int c = lane; c < cols; c += 64) VT<TO>::store1(o + c, VT<TG>::load1(gr + c) * a - VT<TI>::load1(xr + c) * b);
 }
 
 

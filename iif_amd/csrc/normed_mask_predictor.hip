@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(256) normed_predict_fwd_kernel(const T* __rest
 #pragma unroll 8
         for (int c = grp; c < cin; c += G) {
             float v[V];
-            Row<T, V>::ld(xp + (int64_t)c * hw, v);
+            VTn<T, V>::load(xp + (int64_t)c * hw, v);
             const float wc = sw[c];
 #pragma unroll
             for (int j = 0; j < V; ++j) {
@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(256) normed_predict_dx_kernel(const T* __restr
         float v[V];
 #pragma unroll
         for (int j = 0; j < V; ++j) v[j] = 0.f;
-        for (int i = tid; i < total; i += 256) Row<T, V>::st(out + (int64_t)i * V, v);
+        for (int i = tid; i < total; i += 256) VTn<T, V>::store(out + (int64_t)i * V, v);
         return;
     }
     const float u = (up ? *up : 1.0f) * (inv_div ? *inv_div : 1.0f);
@@ -175,10 +175,10 @@ __global__ void __launch_bounds__(256) normed_predict_dx_kernel(const T* __restr
         const int c = i / per, p = (i - c * per) * V;
         const float wc = swc[c];
         float v[V];
-        Row<T, V>::ld(in + (int64_t)i * V, v);
+        VTn<T, V>::load(in + (int64_t)i * V, v);
 #pragma unroll
         for (int j = 0; j < V; ++j) v[j] = fmaf(-sb[p + j], v[j], sa[p + j] * wc);
-        Row<T, V>::st(out + (int64_t)i * V, v);
+        VTn<T, V>::store(out + (int64_t)i * V, v);
     }
 }
 

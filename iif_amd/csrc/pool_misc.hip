@@ -7,42 +7,13 @@
 
 namespace {
 
-template <typename T> struct PT;
-template <> struct PT<float> {
-    static constexpr int V = 4;
-    static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
-        *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-    }
-    static __device__ __forceinline__ float load1(const float* p) { return *p; }
-    static __device__ __forceinline__ void store1(float* p, float v) { *p = v; }
-};
-template <> struct PT<unsigned short> {
-    static constexpr int V = 8;
-    static __device__ __forceinline__ void load(const unsigned short* p, float (&v)[8]) {
-        const u32x4 t = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { v[2 * i] = bf16_bits_to_f32(t[i] & 0xffffu); v[2 * i + 1] = __uint_as_float(t[i] & 0xffff0000u); }
-    }
-    static __device__ __forceinline__ void store(unsigned short* p, const float (&v)[8]) {
-        u32x4 t;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) t[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-        *reinterpret_cast<u32x4*>(p) = t;
-    }
-    static __device__ __forceinline__ float load1(const unsigned short* p) { return bf16_bits_to_f32(*p); }
-    static __device__ __forceinline__ void store1(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
-};
-
 using iif_plan::sblocks;       // grid of the grid-stride kernels below: stream_plan.h
 
 // ---------------------------------------------------------------- max pool 3x3/s2/p1 (general k,s,p)
 template <typename T>
 __global__ void __launch_bounds__(256) maxpool_fwd_kernel(const T* x, int N, int H, int W, int C, int k, int s, int p,
                                                           int Ho, int Wo, T* y, unsigned char* idx) {
-    constexpr int V = PT<T>::V;
+    constexpr int V = VT<T>::V;
     const int cv = C / V;
     const int64_t total = (int64_t)N * Ho * Wo * cv;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -62,7 +33,7 @@ __global__ void __launch_bounds__(256) maxpool_fwd_kernel(const T* x, int N, int
                 const int w = wo * s - p + kw;
                 if ((unsigned)w >= (unsigned)W) continue;
                 float v[V];
-                PT<T>::load(x + (((int64_t)n * H + h) * W + w) * C + c, v);
+                VT<T>::load(x + (((int64_t)n * H + h) * W + w) * C + c, v);
 #pragma unroll
                 for (int q = 0; q < V; ++q)
                     if (first || v[q] > best[q] || v[q] != v[q]) { best[q] = v[q]; bi[q] = (unsigned char)(kh * k + kw); }
@@ -70,7 +41,7 @@ __global__ void __launch_bounds__(256) maxpool_fwd_kernel(const T* x, int N, int
             }
         }
         const int64_t o = (((int64_t)n * Ho + ho) * Wo + wo) * C + c;
-        PT<T>::store(y + o, best);
+        VT<T>::store(y + o, best);
 #pragma unroll
         for (int q = 0; q < V; ++q) idx[o + q] = bi[q];
     }
@@ -82,7 +53,7 @@ __global__ void __launch_bounds__(256) maxpool_fwd_kernel(const T* x, int N, int
 template <typename T>
 __global__ void __launch_bounds__(256) maxpool_bn_fwd_kernel(const T* x, const float* stats, int N, int H, int W, int C, int k,
                                                              int s, int p, int Ho, int Wo, T* y, unsigned char* idx, T* px) {
-    constexpr int V = PT<T>::V;
+    constexpr int V = VT<T>::V;
     const int cv = C / V;
     const int64_t total = (int64_t)N * Ho * Wo * cv;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -102,19 +73,19 @@ __global__ void __launch_bounds__(256) maxpool_bn_fwd_kernel(const T* x, const f
                 const int w = wo * s - p + kw;
                 if ((unsigned)w >= (unsigned)W) continue;
                 float v[V];
-                PT<T>::load(x + (((int64_t)n * H + h) * W + w) * C + c, v);
+                VT<T>::load(x + (((int64_t)n * H + h) * W + w) * C + c, v);
 #pragma unroll
                 for (int q = 0; q < V; ++q) {
                     float t = fmaxf(fmaf(ca[q], v[q], cb[q]), 0.f);
-                    if constexpr (sizeof(T) == 2) t = bf16_bits_to_f32(f32_to_bf16_bits(t));
+                    t = VT<T>::round_trip(t);
                     if (first || t > best[q] || t != t) { best[q] = t; bx[q] = v[q]; bi[q] = (unsigned char)(kh * k + kw); }
                 }
                 first = false;
             }
         }
         const int64_t o = (((int64_t)n * Ho + ho) * Wo + wo) * C + c;
-        PT<T>::store(y + o, best);
-        if (px) PT<T>::store(px + o, bx);
+        VT<T>::store(y + o, best);
+        if (px) VT<T>::store(px + o, bx);
 #pragma unroll
         for (int q = 0; q < V; ++q) idx[o + q] = bi[q];
     }
@@ -127,7 +98,7 @@ __global__ void __launch_bounds__(256) maxpool_bn_fwd_kernel(const T* x, const f
 template <typename T>
 __global__ void __launch_bounds__(256) maxpool321_bn_fwd_kernel(const T* x, const float* stats, int N, int H, int W, int C, int Ho,
                                                                 int Wo, T* y, unsigned char* idx, T* px) {
-    constexpr int V = PT<T>::V;
+    constexpr int V = VT<T>::V;
     const unsigned cv = C / V, rowv = (unsigned)Wo * cv;
     const int c = (int)(threadIdx.x % cv) * V;
     float ca[V], cb[V];
@@ -148,7 +119,7 @@ __global__ void __launch_bounds__(256) maxpool321_bn_fwd_kernel(const T* x, cons
                     const int h = h0 + kh, w = w0 + kw;
                     ok[kh * 3 + kw] = (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
                     const int hc = h < 0 ? 0 : (h >= H ? H - 1 : h), wc = w < 0 ? 0 : (w >= W ? W - 1 : w);
-                    PT<T>::load(x + (((int64_t)n * H + hc) * W + wc) * C + c, v[kh * 3 + kw]);
+                    VT<T>::load(x + (((int64_t)n * H + hc) * W + wc) * C + c, v[kh * 3 + kw]);
                 }
             float best[V], bx[V];
             unsigned bi[V];
@@ -161,14 +132,14 @@ __global__ void __launch_bounds__(256) maxpool321_bn_fwd_kernel(const T* x, cons
 #pragma unroll
                 for (int q = 0; q < V; ++q) {
                     float t = fmaxf(fmaf(ca[q], v[t9][q], cb[q]), 0.f);
-                    if constexpr (sizeof(T) == 2) t = bf16_bits_to_f32(f32_to_bf16_bits(t));
+                    t = VT<T>::round_trip(t);
                     if (first || t > best[q] || t != t) { best[q] = t; bx[q] = v[t9][q]; bi[q] = (unsigned)t9; }
                 }
                 first = false;
             }
             const int64_t o = ((int64_t)row * Wo + wo) * C + c;
-            PT<T>::store(y + o, best);
-            if (px) PT<T>::store(px + o, bx);          // the RAW value at the arg max: what the backward's column sums start from
+            VT<T>::store(y + o, best);
+            if (px) VT<T>::store(px + o, bx);          // the RAW value at the arg max: what the backward's column sums start from
             if constexpr (V == 8) {
                 const unsigned lo = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24), hi = bi[4] | (bi[5] << 8) | (bi[6] << 16) | (bi[7] << 24);
                 *reinterpret_cast<uint2*>(idx + o) = make_uint2(lo, hi);
@@ -182,7 +153,7 @@ __global__ void __launch_bounds__(256) maxpool321_bn_fwd_kernel(const T* x, cons
 template <typename T>
 __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const T* gy, const unsigned char* idx, int N, int H, int W,
                                                           int C, int k, int s, int p, int Ho, int Wo, T* dx) {
-    constexpr int V = PT<T>::V;
+    constexpr int V = VT<T>::V;
     const int cv = C / V;
     const int64_t total = (int64_t)N * H * W * cv;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -204,7 +175,7 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const T* gy, const uns
                 const int code = (h - (ho * s - p)) * k + (w - (wo * s - p));
                 const int64_t o = (((int64_t)n * Ho + ho) * Wo + wo) * C + c;
                 float g[V];
-                PT<T>::load(gy + o, g);
+                VT<T>::load(gy + o, g);
                 // the V argmax codes of this vector in one load (o is a multiple of V)
                 unsigned long long codes;
                 if constexpr (V == 8) codes = *reinterpret_cast<const unsigned long long*>(idx + o);
@@ -213,7 +184,7 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const T* gy, const uns
                 for (int q = 0; q < V; ++q)
                     if ((int)((codes >> (8 * q)) & 0xffu) == code) acc[q] += g[q];
             }
-        PT<T>::store(dx + (((int64_t)n * H + h) * W + w) * C + c, acc);
+        VT<T>::store(dx + (((int64_t)n * H + h) * W + w) * C + c, acc);
     }
 }
 
@@ -221,7 +192,7 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const T* gy, const uns
 template <typename T>
 __global__ void __launch_bounds__(256) maxpool321_bwd_kernel(const T* gy, const unsigned char* idx, int N, int H, int W,
                                                              int C, int Ho, int Wo, T* dx) {
-    constexpr int V = PT<T>::V;
+    constexpr int V = VT<T>::V;
     const unsigned cv = C / V, rowv = (unsigned)W * cv;
     // one image row per block pass: h is uniform, only 32-bit index arithmetic
     for (unsigned row = blockIdx.x; row < (unsigned)(N * H); row += gridDim.x) {
@@ -230,7 +201,7 @@ __global__ void __launch_bounds__(256) maxpool321_bwd_kernel(const T* gy, const 
             const unsigned w = j / cv, c = (j - w * cv) * V;
             float acc[V];
             pool321_gather<T>(gy, idx, (int)n, (int)h, (int)w, (int)c, C, Ho, Wo, acc);
-            PT<T>::store(dx + ((int64_t)row * W + w) * C + c, acc);
+            VT<T>::store(dx + ((int64_t)row * W + w) * C + c, acc);
         }
     }
 }
@@ -238,7 +209,7 @@ __global__ void __launch_bounds__(256) maxpool321_bwd_kernel(const T* gy, const 
 // ---------------------------------------------------------------- global average pool
 template <typename T>
 __global__ void __launch_bounds__(256) avgpool_fwd_kernel(const T* x, int N, int HW, int C, T* y) {
-    constexpr int V = PT<T>::V;
+    constexpr int V = VT<T>::V;
     const int cv = C / V;
     const int64_t total = (int64_t)N * cv;
     const float inv = 1.0f / (float)HW;
@@ -250,19 +221,19 @@ __global__ void __launch_bounds__(256) avgpool_fwd_kernel(const T* x, int N, int
         for (int q = 0; q < V; ++q) acc[q] = 0.f;
         for (int j = 0; j < HW; ++j) {
             float v[V];
-            PT<T>::load(x + ((int64_t)n * HW + j) * C + c, v);
+            VT<T>::load(x + ((int64_t)n * HW + j) * C + c, v);
 #pragma unroll
             for (int q = 0; q < V; ++q) acc[q] += v[q];
         }
 #pragma unroll
         for (int q = 0; q < V; ++q) acc[q] *= inv;
-        PT<T>::store(y + (int64_t)n * C + c, acc);
+        VT<T>::store(y + (int64_t)n * C + c, acc);
     }
 }
 
 template <typename T>
 __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const T* gy, int N, int HW, int C, T* dx) {
-    constexpr int V = PT<T>::V;
+    constexpr int V = VT<T>::V;
     const int cv = C / V;
     const int64_t total = (int64_t)N * HW * cv;
     const float inv = 1.0f / (float)HW;
@@ -270,10 +241,10 @@ __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const T* gy, int N, in
         const int c = (int)(i % cv) * V;
         const int n = (int)(i / ((int64_t)HW * cv));
         float g[V];
-        PT<T>::load(gy + (int64_t)n * C + c, g);
+        VT<T>::load(gy + (int64_t)n * C + c, g);
 #pragma unroll
         for (int q = 0; q < V; ++q) g[q] *= inv;
-        PT<T>::store(dx + i * V, g);
+        VT<T>::store(dx + i * V, g);
     }
 }
 
@@ -282,7 +253,7 @@ __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const T* gy, int N, in
 template <typename T>
 __global__ void __launch_bounds__(256) im2col_kernel(const float* img, int N, int Cin, int H, int W, int R, int S,
                                                      int stride, int pad, int Ho, int Wo, int kp, T* out) {
-    constexpr int V = PT<T>::V;
+    constexpr int V = VT<T>::V;
     const int gv = kp / V;
     const int K = R * S * Cin;
     const int64_t total = (int64_t)N * Ho * Wo * gv;
@@ -306,7 +277,7 @@ __global__ void __launch_bounds__(256) im2col_kernel(const float* img, int N, in
             }
             v[q] = t;
         }
-        PT<T>::store(out + i * V, v);
+        VT<T>::store(out + i * V, v);
     }
 }
 
@@ -314,12 +285,12 @@ __global__ void __launch_bounds__(256) im2col_kernel(const float* img, int N, in
 template <typename T>
 __global__ void __launch_bounds__(256) cast_from_f32_kernel(const float* src, T* dst, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        PT<T>::store1(dst + i, src[i]);
+        VT<T>::store1(dst + i, src[i]);
 }
 template <typename T>
 __global__ void __launch_bounds__(256) cast_to_f32_kernel(const T* src, float* dst, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        dst[i] = PT<T>::load1(src + i);
+        dst[i] = VT<T>::load1(src + i);
 }
 // w: fp32 [Cout][ldw] (r,s,c) -> wt: T [Cin][ldwt] (r,s,k); pad columns zeroed
 template <typename T>
@@ -333,7 +304,7 @@ __global__ void __launch_bounds__(256) weight_transpose_kernel(const float* w, i
             const int tap = col / Cout, k = col - tap * Cout;
             v = w[(int64_t)k * ldw + tap * Cin + c];
         }
-        PT<T>::store1(wt + i, v);
+        VT<T>::store1(wt + i, v);
     }
 }
 
@@ -368,13 +339,13 @@ __global__ void __launch_bounds__(256) weight_transpose_batched_kernel(const flo
     __syncthreads();
     for (int j = ty; j < 32; j += 8) {                                 // rows c0+j of wt, columns tap*cout + k0 + tx
         const int c = c0 + j, k = k0 + tx;
-        if (c < d.cin && k < d.cout) PT<T>::store1(wt + (int64_t)c * d.ldwt + tap * d.cout + k, tile[tx][j]);
+        if (c < d.cin && k < d.cout) VT<T>::store1(wt + (int64_t)c * d.ldwt + tap * d.cout + k, tile[tx][j]);
     }
     if (kt == kt_n - 1 && tap == d.rs - 1) {                            // zero the row padding [rs*cout, ldwt)
         const int padn = d.ldwt - d.rs * d.cout;
         for (int i = threadIdx.x; i < 32 * padn; i += 256) {
             const int c = c0 + i / padn, col = d.rs * d.cout + i % padn;
-            if (c < d.cin) PT<T>::store1(wt + (int64_t)c * d.ldwt + col, 0.f);
+            if (c < d.cin) VT<T>::store1(wt + (int64_t)c * d.ldwt + col, 0.f);
         }
     }
 }
@@ -392,8 +363,8 @@ __global__ void __launch_bounds__(256) shortcut_a_fwd_kernel(const T* x, int N, 
         const int n = (int)(pix / Ho);
         float v = 0.f;
         const int ci = c - cpad;
-        if (ci >= 0 && ci < Cin) v = PT<T>::load1(x + (((int64_t)n * H + 2 * ho) * W + 2 * wo) * Cin + ci);
-        PT<T>::store1(y + i, v);
+        if (ci >= 0 && ci < Cin) v = VT<T>::load1(x + (((int64_t)n * H + 2 * ho) * W + 2 * wo) * Cin + ci);
+        VT<T>::store1(y + i, v);
     }
 }
 // dx[n,h,w,ci] += g[n,h/2,w/2,ci+cpad] at even (h,w)
@@ -408,8 +379,8 @@ __global__ void __launch_bounds__(256) shortcut_a_bwd_kernel(const T* g, int N, 
         const int ho = (int)(pix % Ho);
         const int n = (int)(pix / Ho);
         const int64_t o = (((int64_t)n * H + 2 * ho) * W + 2 * wo) * Cin + ci;
-        const float gv = PT<T>::load1(g + (((int64_t)n * Ho + ho) * Wo + wo) * Cout + ci + cpad);
-        PT<T>::store1(dx + o, PT<T>::load1(dx + o) + gv);
+        const float gv = VT<T>::load1(g + (((int64_t)n * Ho + ho) * Wo + wo) * Cout + ci + cpad);
+        VT<T>::store1(dx + o, VT<T>::load1(dx + o) + gv);
     }
 }
 
@@ -721,7 +692,7 @@ __global__ void __launch_bounds__(256) group_pack_kernel(const float* m, int C, 
                 v = m[(int64_t)k * ldm + tap * cg + (c % cg)];
             }
         }
-        PT<T>::store1(out + i, v);
+        VT<T>::store1(out + i, v);
     }
 }
 // every grouped layer's packed copies in ONE launch (ResNeXt-101: 66 launches per step, ~0.9 ms of host time at the start
@@ -743,7 +714,7 @@ __global__ void __launch_bounds__(256) group_pack_batched_kernel(const GroupPack
                 v = e.m[(int64_t)k * e.ldm + tap * e.cg + (c % e.cg)];
             }
         }
-        PT<T>::store1(out + i, v);
+        VT<T>::store1(out + i, v);
     }
 }
 // dense-in-chunk weight gradient [cout][ldp] -> master layout [cout][ldm] (only the in-group entries exist)
@@ -840,12 +811,12 @@ __global__ void __launch_bounds__(256) s2d_kernel(const float* img, int N, int C
         }
         for (int c = 0; c < C; ++c) {
             const float* p = img + (((int64_t)n * C + c) * H + 2 * y) * W + 2 * x;
-            PT<T>::store1(o + c, p[0]);
-            PT<T>::store1(o + C + c, p[1]);
-            PT<T>::store1(o + 2 * C + c, p[W]);
-            PT<T>::store1(o + 3 * C + c, p[W + 1]);
+            VT<T>::store1(o + c, p[0]);
+            VT<T>::store1(o + C + c, p[1]);
+            VT<T>::store1(o + 2 * C + c, p[W]);
+            VT<T>::store1(o + 3 * C + c, p[W + 1]);
         }
-        for (int q = 4 * C; q < cpad; ++q) PT<T>::store1(o + q, 0.f);
+        for (int q = 4 * C; q < cpad; ++q) VT<T>::store1(o + q, 0.f);
     }
 }
 // master [K][ldm] rows of (r, s, c) over R x R taps -> packed [K][A*A*cpad] rows of (a, b, q), A = (R+1)/2
@@ -862,7 +833,7 @@ __global__ void __launch_bounds__(256) stem_pack_kernel(const float* m, int K, i
             const int r = 2 * a + (sub >> 1) - 1, s = 2 * b + (sub & 1) - 1;
             if (r >= 0 && r < R && s >= 0 && s < R) v = m[(int64_t)k * ldm + (r * R + s) * C + c];
         }
-        PT<T>::store1(out + i, v);
+        VT<T>::store1(out + i, v);
     }
 }
 __global__ void __launch_bounds__(256) stem_unpack_kernel(const float* p, int K, int C, int R, int cpad, int ldm, float* m) {

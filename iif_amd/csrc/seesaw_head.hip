@@ -13,14 +13,10 @@
 #include <math.h>
 
 #include "common.h"
+#include "head_math.h"
 #include "loss_reduce.h"
 
 namespace {
-
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-__device__ __forceinline__ float fast_exp2(float v) { return __builtin_amdgcn_exp2f(v); }
-__device__ __forceinline__ float fast_log2(float v) { return __builtin_amdgcn_logf(v); }
 
 constexpr int kMaxCols = 2048;              // C + 2 <= 2048: the row stays in registers (<= 32 values per lane)
 constexpr int kMaxLossBlocks = 1024;        // partial slots of the workspace

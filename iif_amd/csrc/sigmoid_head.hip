@@ -12,31 +12,25 @@
 // logits' 16-byte phase on every row for that (same address modulo 16, same row pitch modulo 16 bytes); otherwise every
 // element goes through the one-per-lane path.
 //
-// Per element (x = logit, e = exp(-|x|), u = 1 + e, r = 1/u; sp(v) = softplus(v)):
-//   log1p(e) = ln(u) + (e - (u - 1)) * r        (u - 1 is exact: the bracket is u's rounding error, so small e keeps
-//                                                 its digits without a polynomial or a second reciprocal)
-//   sp(x) = max(x, 0) + log1p(e),  sp(-x) = max(-x, 0) + log1p(e)
-//   s = sigmoid(x) = x >= 0 ? r : e*r,  q = 1 - s = x >= 0 ? e*r : r       (1 - s is never formed)
+// Per element (x = logit; sp(v) = softplus(v), s = sigmoid(x), q = 1 - s: the stable element of head_math.h):
 //   gamma == 0:  y=0: l = sp(x),             dl/dx = s
 //                y=1: l = sp(-x),            dl/dx = -q
 //   gamma  > 0:  y=0: l = s^g sp(x),         dl/dx = s^g (s + g q sp(x))          s^g = exp(-g sp(-x))
 //                y=1: l = q^g sp(-x),        dl/dx = -q^g (g s sp(-x) + q)       q^g = exp(-g sp(x))
-// gamma 1 and 2 are multiplies.  Three transcendentals per element (v_exp_f32, v_rcp_f32, v_log_f32), four for
-// other gamma.  Unlike the reference (nn.BCELoss clamps log(s) at -100 after s has rounded to 1 in fp32), this is the
-// exact function at every |x|: see DESIGN.md, "Sigmoid BCE / focal head".
+// gamma 1 and 2 are multiplies.  Three transcendentals per element (the element's), four for other gamma.  Unlike the
+// reference (nn.BCELoss clamps log(s) at -100 after s has rounded to 1 in fp32), this is the exact function at every |x|: see
+// DESIGN.md, "Sigmoid BCE / focal head".
 // Every column is first evaluated as a y = 0 column; the lane(s) owning a target column patch it (mixup: two targets,
 // lam * L(y_a) + (1 - lam) * L(y_b) per element).
 // The scalar loss comes out of the same launch by the ticketed reduction of loss_reduce.h.
 #include "common.h"
+#include "head_math.h"
 #include "loss_reduce.h"
+#include "vec16.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 constexpr int kLdsWeights = 8192;              // class weights staged in LDS up to this many classes (32 KB)
-
-__device__ __forceinline__ float exp_neg(float v) { return __builtin_amdgcn_exp2f(-v * kLog2e); }   // e^-v
 
 struct Args {
     const void* x; int64_t ldx;
@@ -55,24 +49,8 @@ struct Args {
 };
 
 // y = 0 and y = 1 loss / gradient of one element.  GM: 0 -> gamma 0, 1 / 2 -> gamma 1 / 2, 3 -> any other gamma > 0.
-struct Elem { float spp, spn, s, q; };
-
-__device__ __forceinline__ Elem elem(float x) {
-    const float e = exp_neg(fabsf(x));
-    const float u = 1.0f + e;
-    const float r = __builtin_amdgcn_rcpf(u);
-    const float l1p = __builtin_amdgcn_logf(u) * kLn2 + (e - (u - 1.0f)) * r;
-    const float er = e * r;
-    Elem p;
-    p.spp = fmaxf(x, 0.0f) + l1p;
-    p.spn = fmaxf(-x, 0.0f) + l1p;
-    p.s = x >= 0.0f ? r : er;
-    p.q = x >= 0.0f ? er : r;
-    return p;
-}
-
 template <int GM>
-__device__ __forceinline__ void neg_term(const Elem& p, float g, float& l, float& d) {      // y = 0
+__device__ __forceinline__ void neg_term(const SigmoidElem& p, float g, float& l, float& d) {      // y = 0
     if constexpr (GM == 0) { l = p.spp; d = p.s; return; }
     const float m = GM == 1 ? p.s : (GM == 2 ? p.s * p.s : exp_neg(g * p.spn));
     l = m * p.spp;
@@ -80,7 +58,7 @@ __device__ __forceinline__ void neg_term(const Elem& p, float g, float& l, float
 }
 
 template <int GM>
-__device__ __forceinline__ void pos_term(const Elem& p, float g, float& l, float& d) {      // y = 1
+__device__ __forceinline__ void pos_term(const SigmoidElem& p, float g, float& l, float& d) {      // y = 1
     if constexpr (GM == 0) { l = p.spn; d = -p.q; return; }
     const float m = GM == 1 ? p.q : (GM == 2 ? p.q * p.q : exp_neg(g * p.spp));
     l = m * p.spn;
@@ -94,11 +72,11 @@ __device__ __forceinline__ void pos_term(const Elem& p, float g, float& l, float
 template <int GM, int N>
 __device__ __forceinline__ void columns(const Args& a, int wsrc, const float* w_lds, const float (&x)[N], int c0, int ta,
                                         int tb, float gs, float& acc, float (&d)[N]) {
-    Elem p[N];
+    SigmoidElem p[N];
     float l[N], w[N];
 #pragma unroll
     for (int e = 0; e < N; ++e) {
-        p[e] = elem(x[e]);
+        p[e] = sigmoid_elem(x[e]);
         neg_term<GM>(p[e], a.gamma, l[e], d[e]);
         w[e] = wsrc == 1 ? w_lds[c0 + e] : (wsrc == 2 ? a.w[c0 + e] : 1.0f);
         l[e] *= a.a0;
@@ -124,38 +102,10 @@ __device__ __forceinline__ void columns(const Args& a, int wsrc, const float* w_
     }
 }
 
-template <typename T> struct Vec;
-template <> struct Vec<float> {
-    static constexpr int V = 4;
-    using Raw = f32x4;
-    static __device__ __forceinline__ Raw load(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-    static __device__ __forceinline__ void unpack(const Raw& t, float (&v)[4]) { v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[4]) { *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; }
-    static __device__ __forceinline__ float load1(const float* p) { return *p; }
-    static __device__ __forceinline__ void store1(float* p, float v) { *p = v; }
-};
-template <> struct Vec<unsigned short> {                 // bf16 bits
-    static constexpr int V = 8;
-    using Raw = u32x4;
-    static __device__ __forceinline__ Raw load(const unsigned short* p) { return *reinterpret_cast<const u32x4*>(p); }
-    static __device__ __forceinline__ void unpack(const Raw& w, float (&v)[8]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { v[2 * q] = bf16_bits_to_f32(w[q] & 0xffffu); v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u); }
-    }
-    static __device__ __forceinline__ void store(unsigned short* p, const float (&v)[8]) {
-        u32x4 w;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) w[q] = pack_bf16x2(v[2 * q], v[2 * q + 1]);
-        *reinterpret_cast<u32x4*>(p) = w;
-    }
-    static __device__ __forceinline__ float load1(const unsigned short* p) { return bf16_bits_to_f32(*p); }
-    static __device__ __forceinline__ void store1(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
-};
-
 // U lane vectors in flight per wave and body step: 4 KB of logits per wave (4 fp32 / 2 bf16 vectors per lane).
 template <typename T, int GM>
 __global__ void __launch_bounds__(256) sigmoid_focal_kernel(Args a) {
-    constexpr int V = Vec<T>::V, U = sizeof(T) == 2 ? 2 : 4;
+    constexpr int V = VT<T>::V, U = sizeof(T) == 2 ? 2 : 4;
     extern __shared__ float w_lds[];
     const int lane = threadIdx.x & 63;
     const int wpb = blockDim.x >> 6;
@@ -187,29 +137,29 @@ __global__ void __launch_bounds__(256) sigmoid_focal_kernel(Args a) {
         }
         float acc = 0.f;
         for (int v0 = 0; v0 < nb; v0 += 64 * U) {
-            typename Vec<T>::Raw raw[U];
+            typename VT<T>::Raw raw[U];
 #pragma unroll
             for (int j = 0; j < U; ++j) {
                 const int v = v0 + j * 64 + lane;
-                if (v < nb) raw[j] = Vec<T>::load(x + h + v * V);
+                if (v < nb) raw[j] = VT<T>::raw(x + h + v * V);
             }
 #pragma unroll
             for (int j = 0; j < U; ++j) {
                 const int v = v0 + j * 64 + lane;
                 if (v < nb) {
                     float xv[V], d[V];
-                    Vec<T>::unpack(raw[j], xv);
+                    VT<T>::unpack(raw[j], xv);
                     columns<GM, V>(a, wsrc, w_lds, xv, h + v * V, (int)ta, (int)tb, gs, acc, d);
-                    if (dx) Vec<T>::store(dx + h + v * V, d);
+                    if (dx) VT<T>::store(dx + h + v * V, d);
                 }
             }
         }
         const int ns = a.C - nb * V;                              // head + tail elements
         for (int k = lane; k < ns; k += 64) {
             const int c = k < h ? k : k + nb * V;
-            float xv[1] = {Vec<T>::load1(x + c)}, d[1];
+            float xv[1] = {VT<T>::load1(x + c)}, d[1];
             columns<GM, 1>(a, wsrc, w_lds, xv, c, (int)ta, (int)tb, gs, acc, d);
-            if (dx) Vec<T>::store1(dx + c, d[0]);
+            if (dx) VT<T>::store1(dx + c, d[0]);
         }
         acc = bad ? 0.0f : wave_sum(acc);
         if (lane == 0) a.loss_row[r] = acc;
