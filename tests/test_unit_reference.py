@@ -1,6 +1,7 @@
 """The float64 per-unit reference of tests/unit_reference.py against torch autograd in float64 (no device needed): the GPU
 checks in tests/test_step_units_gpu.py are only as good as this reference, so its convolutions, BN backward with a ReLU mask
-and a residual, x-hat conventions, max-pool scatter and option-A shortcut are pinned here to float64 rounding."""
+and a residual, x-hat conventions, max-pool scatter, option-A shortcut and squeeze-and-excitation stages are pinned here to float64
+rounding."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -118,6 +119,89 @@ def test_option_a_shortcut_against_autograd():
     gs = torch.randn(ref.shape, generator=g, dtype=F64)
     (gx,) = torch.autograd.grad(ref, x, gs)
     _close(U.shortcut_a_bwd(gs, tuple(x.shape)), gx)
+
+
+@pytest.mark.parametrize("residual", ["identity", "normalised_shortcut", "none"])
+@pytest.mark.parametrize("c,hid,side", [(16, 4, 8), (64, 16, 3), (256, 16, 14)])
+def test_se_block_stages_against_autograd(c, hid, side, residual):
+    """o = bn(x), e = sigmoid(W2 relu(W1 mean_hw(o))), y = relu(o e + identity): every SE reference function (squeeze sums, q,
+    h, e, the apply, S1 / S2, dz2, dz1, the offset o, both weight gradients, the form G) against autograd, then G through the
+    reference's BN backward without a mask, and the masked gradient through the identity / the normalised shortcut."""
+    g = torch.Generator().manual_seed(c + 3 * side + len(residual))
+    n, hw = 3, side * side
+    R = lambda *s: torch.randn(*s, generator=g, dtype=F64)      # noqa: E731
+    x = (R(n, side, side, c) * 2 + 0.5).requires_grad_()
+    gamma = (torch.rand(c, generator=g, dtype=F64) + 0.5).requires_grad_()
+    beta = (R(c) * 0.3).requires_grad_()
+    w1 = (R(hid, c) * 2 / c ** 0.5).requires_grad_()
+    w2 = (R(c, hid) * 2 / hid ** 0.5).requires_grad_()
+    xd = (R(n, side, side, c) + 1).requires_grad_()
+    gam_d = (torch.rand(c, generator=g, dtype=F64) + 0.5).requires_grad_()
+    bet_d = R(c).requires_grad_()
+
+    def bn(t, ga, be):
+        return F.batch_norm(t.reshape(-1, c), None, None, ga, be, training=True, eps=1e-5).view(t.shape)
+
+    o = bn(x, gamma, beta)
+    oa, ob = o + 0, o + 0                      # the two ways o reaches y: scaled by the gate, and through the squeeze
+    q = ob.mean((1, 2))
+    z1 = q @ w1.t()
+    h = z1.clamp_min(0)
+    z2 = h @ w2.t()
+    e = torch.sigmoid(z2)
+    res = {"identity": xd, "normalised_shortcut": bn(xd, gam_d, bet_d), "none": None}[residual]
+    pre = oa * e[:, None, None, :]
+    y = (pre if res is None else pre + res).clamp_min(0)
+    for t in (oa, ob, z1, z2) + (() if res is None else (res,)):
+        t.retain_grad()
+    gy = R(*y.shape)
+    y.backward(gy)
+
+    D = lambda t: t.detach()                   # noqa: E731
+    mean, invstd = U.bn_stats(D(x))
+    a = D(gamma) * invstd
+    b = D(beta) - mean * a
+    sums = U.se_squeeze(D(x))
+    _close(sums, D(x).sum((1, 2)))
+    qr = U.se_q(sums, a, b, hw)
+    _close(qr, q)
+    hr = U.se_h(qr, D(w1))
+    _close(hr, h)
+    er = U.se_e(hr, D(w2))
+    _close(er, e)
+    rres = None
+    if residual == "identity":
+        rres = D(xd)
+    elif residual == "normalised_shortcut":
+        mean_d, inv_d = U.bn_stats(D(xd))
+        a_d = D(gam_d) * inv_d
+        rres = D(xd) * a_d + (D(bet_d) - mean_d * a_d)
+    yr = U.se_apply(D(x), a, b, er, rres)
+    _close(yr, y)
+    gt = gy * (yr > 0).to(F64)
+    s1, s2 = U.se_backward_sums(gt, D(x))
+    dz2 = U.se_dz2(s1, s2, a, b, er)
+    _close(dz2, z2.grad)
+    dz1 = U.se_dz1(dz2, D(w2), hr)
+    _close(dz1, z1.grad)
+    off = U.se_offset(dz1, D(w1), hw)
+    _close(off[:, None, None, :].expand(ob.grad.shape), ob.grad)
+    _close(U.se_dw(dz1, qr), w1.grad)
+    _close(U.se_dw(dz2, hr), w2.grad)
+    G = U.se_form(gt, er, off)
+    _close(G, oa.grad + ob.grad)
+    dx, dgam, dbet, _ = U.bn_backward(G, None, (D(x) - mean) * invstd, D(gamma), invstd)
+    _close(dx, x.grad)
+    _close(dgam, gamma.grad)
+    _close(dbet, beta.grad)
+    if residual == "identity":
+        _close(gt, xd.grad)
+    elif residual == "normalised_shortcut":
+        _close(gt, res.grad)
+        dxd, dgd, dbd, _ = U.bn_backward(gt, None, (D(xd) - mean_d) * inv_d, D(gam_d), inv_d)
+        _close(dxd, xd.grad)
+        _close(dgd, gam_d.grad)
+        _close(dbd, bet_d.grad)
 
 
 @pytest.mark.parametrize("dt,vec", [(torch.bfloat16, 8), (torch.float32, 4)])

@@ -23,6 +23,26 @@ Metrics (all dimensionless):
           dgrad_max its max-abs error over the max; both gated by the upstream unit's ReLU (producers may store it gated)
   pool, pool_idx (stem of an ImageNet network): max-pooled output, and how far below its window's maximum the chosen
           element lies (relative to the window maximum)
+
+Squeeze-and-excitation blocks (y = relu((a x + b) e + residual), e = sigmoid(W2 relu(W1 mean_hw(a x + b)))) add one entry
+``<block>.se`` per block.  ``StepCapture`` also wraps ``_Plan._se_backward`` (the block-output gradient g as it arrives, the
+same buffer after the in-place mask, the returned G), and every stage is evaluated from what the step stored for the stage
+before it (``b["se"]``: sums, q, h, e, s1, s2, dz2, dz1, o), as ``check_head`` does, so one ReLU or sigmoid decision never
+compounds:
+  se_sums, se_s1, se_s2   the per-sample sums over the pixels of the stored x, of the masked g~ = g [y > 0] and of g~ x: worst
+          |error| / bound per element, bound max((HW + 16) 2^-24 sum |term|, 4 |float32 CPU - float64|) (<= 1 passes)
+  se_q    max |q - q_ref| / max |q_ref| from the stored sums and the unit's statistics (1e-5)
+  se_h    max |h - h_ref| / max(1, max |h_ref|) from the stored q and the fp32 W1 (2e-5);  se_e  max |e - e_ref| from the
+          stored h and the fp32 W2 (2e-6)
+  y, y_l2, bits (under the last unit's name)  relu((a x + b) e + residual) from the stored x, statistics and e
+  se_gmask   elements of the masked g left in place that are not g [y > 0] (exactly 0)
+  se_dz2, se_dz1, se_o, se_dw1, se_dw2   relative L2 of each stage from the stored result of the stage before it, over
+          max(2e-5, 4 x the relative L2 of the same stage in float32 on the CPU) (<= 1 passes)
+  se_pad  non-zero elements in the pad columns of both SE gradient rows and the arena padding behind them (exactly 0)
+  se_G    max |G - round(g~ e + o)| / max |G| from the masked g, the stored e and o
+The last unit of an SE block then takes the captured G with no ReLU mask, and the identity path (identity, option-A shortcut
+or the shortcut unit) takes the masked g.  ``SE_GATE`` keeps max |o| / max |G| per block from the float64 chain alone: how
+visible the gate path is under one rounding of G.
 """
 import contextlib
 
@@ -136,6 +156,66 @@ def shortcut_a_bwd(g, in_shape):
     return dx
 
 
+# ------------------------------------------------------------------ squeeze-and-excitation around a block's last BN
+# o = a x + b (the last BN of the block), e = sigmoid(W2 relu(W1 mean_hw(o))), y = relu(o e + residual).  Every function is one
+# stage of the engine's SE forward / backward and works in the dtype of its operands (float64 for the reference, float32 on the
+# CPU for the error a stage has by itself).  x, g: [N, H, W, C]; everything else [N, C] / [N, hidden]; W1 [hidden, C],
+# W2 [C, hidden].
+def se_squeeze(x):
+    """Per-sample channel sums over the pixels."""
+    return x.sum((1, 2))
+
+
+def se_q(sums, a, b, hw):
+    """mean_hw(a x + b): the BN affine commutes with the mean."""
+    return a * sums / hw + b
+
+
+def se_h(q, w1):
+    return (q @ w1.t()).clamp_min(0)
+
+
+def se_e(h, w2):
+    return torch.sigmoid(h @ w2.t())
+
+
+def se_apply(x, a, b, e, res=None):
+    """y = relu((a x + b) e [+ res])."""
+    pre = (x * a + b) * e[:, None, None, :]
+    if res is not None:
+        pre = pre + res
+    return pre.clamp_min(0)
+
+
+def se_backward_sums(gt, x):
+    """S1 = sum_hw g~, S2 = sum_hw g~ x of the masked block-output gradient g~ = g [y > 0]."""
+    return gt.sum((1, 2)), (gt * x).sum((1, 2))
+
+
+def se_dz2(s1, s2, a, b, e):
+    """de = sum_hw g~ (a x + b) = a S2 + b S1, through the sigmoid."""
+    return (a * s2 + b * s1) * e * (1 - e)
+
+
+def se_dz1(dz2, w2, h):
+    return (dz2 @ w2) * (h > 0).to(dz2.dtype)
+
+
+def se_offset(dz1, w1, hw):
+    """The gradient that reaches every pixel of the BN output through the squeeze."""
+    return (dz1 @ w1) / hw
+
+
+def se_dw(dz, v):
+    """dW1 = dz1^T q, dW2 = dz2^T h."""
+    return dz.t() @ v
+
+
+def se_form(gt, e, o):
+    """G = d(loss) / d(BN output) = g~ e + o."""
+    return gt * e[:, None, None, :] + o[:, None, None, :]
+
+
 def maxpool_windows(y, k=3, stride=2, pad=1):
     """[N, Ho, Wo, C, k*k] candidates of every pooling window (-inf outside the image), code kh * k + kw."""
     z = F.pad(nchw(y), (pad, pad, pad, pad), value=float("-inf"))
@@ -180,7 +260,8 @@ def rel_max(a, b):
 class StepCapture(object):
     """Records, per unit, the gradient that arrived at ``_Plan._unit_backward`` (``gy``, cloned before the call), the data
     gradient it returned (``out``, cloned after it) and whether the call went the BN3-algebra way (``alg``: the fused sums
-    waiting for this unit came with their rows, ``_bn3_algebra``)."""
+    waiting for this unit came with their rows, ``_bn3_algebra``), and per SE block what went into and came out of
+    ``_Plan._se_backward`` (``se_key``)."""
 
     def __init__(self):
         self.records = {}
@@ -189,6 +270,7 @@ class StepCapture(object):
     def active(self):
         from iif_amd import resnet_engine
         orig = resnet_engine._Plan._unit_backward
+        orig_se = resnet_engine._Plan._se_backward
         rec = self.records
 
         def wrapped(plan, u, gy, *args, **kw):
@@ -199,11 +281,26 @@ class StepCapture(object):
             rec[id(u)] = {"gy": g0, "out": None if out is None else out.clone(), "alg": alg}
             return out
 
+        def wrapped_se(plan, b, last, g, *args, **kw):
+            g0 = g.clone()
+            G = orig_se(plan, b, last, g, *args, **kw)
+            rec[se_key(last)] = {"g": g0, "gm": g.clone(), "G": G.clone()}
+            return G
+
         resnet_engine._Plan._unit_backward = wrapped
+        resnet_engine._Plan._se_backward = wrapped_se
         try:
             yield self
         finally:
             resnet_engine._Plan._unit_backward = orig
+            resnet_engine._Plan._se_backward = orig_se
+
+
+def se_key(last):
+    """Record key of the SE block whose last unit is ``last`` (``g``: the block-output gradient as it arrived, ``gm``: the same
+    buffer after ``_se_backward`` masked it in place, ``G``: the returned gradient of the BN output, before the unit's own BN
+    backward overwrites that buffer)."""
+    return ("se", id(last))
 
 
 def run_step(net, x, y, crit, capture=None):
@@ -229,11 +326,15 @@ def routes(plan, cap):
             "rx": sum(1 for u in alg if plan._route(u).backward == "rx"), "nostore": sum(1 for r in rs if r.forward == "nostore"),
             "twopass": sum(1 for r in rs if r.forward == "twopass"), "pg": sum(1 for r in rs if r.gram == "producer"),
             "pro": sum(1 for r in rs if r.prologue), "pro_rows": sum(1 for r in rs if r.csum_rows),
+            "se": sum(1 for b in plan.blocks if "se" in b and se_key(b["units"][-1]) in cap.records),
             "ds_alg": len(ds_alg), "pool_fused_bwd": bool(plan.pool_fused and plan.pool_x is not None),
             "wg_stream": plan.wg_stream is not None, "ds_stream": plan.ds_stream is not None}
 
 
 # ------------------------------------------------------------------ the checker
+SE_GATE = {}            # "<block>.se" -> max |o| / max |G| of the last check_step call, both from the float64 reference alone
+
+
 def check_step(net, img, cap):
     """Evaluate every conv+BN unit of the last step in float64 from the inputs that step used; {name: {metric: value}}."""
     plan = net._saved
@@ -254,8 +355,9 @@ def check_step(net, img, cap):
     def dw_arena(cv):
         return cv._g2d[:, :cv.kdim].reshape(cv.cout, cv.k, cv.k, cv.cg).permute(0, 3, 1, 2).to(F64)
 
-    def forward(u, src, x_stored, unrounded_stats, res_t=None, y_check=True):
-        """Statistics / stored output / activated output of unit u; returns (x_ref, the stats block as float64)."""
+    def forward(u, src, x_stored, unrounded_stats, res_t=None, y_check=True, gate=None):
+        """Statistics / stored output / activated output of unit u; returns (x_ref, the stats block as float64).
+        gate: the stored excitation e [N, C] of an SE block's last unit (y = relu((a x + b) e + res))."""
         cv = u.conv
         m = {}
         xr = conv_fwd(src, weight(cv), cv.stride, cv.pad, cv.groups)
@@ -267,7 +369,7 @@ def check_step(net, img, cap):
             m["x"] = rel_max(u.x, xr)
         if y_check and u.y is not None:
             xs = P(u.x) if x_stored else rnd(xr)
-            yr = bn_act(xs, st[2], st[3], res_t)
+            yr = bn_act(xs, st[2], st[3], res_t) if gate is None else se_apply(xs, st[2], st[3], gate, res_t)
             m["y"] = rel_max(u.y, yr)
             m["y_l2"] = rel_l2(u.y, yr)
             pos = u.y > 0
@@ -301,19 +403,92 @@ def check_step(net, img, cap):
     def mask_of(u):
         return None if u is None else (u.y > 0).to(F64)
 
+    def se_check(b, last, st):
+        """The SE stages of block b around its last unit, each from the operands the step stored for it (b["se"], the capture's
+        record); metrics under ``<block>.se``.  Returns the masked block-output gradient g~ (float64)."""
+        from tests import head_cases as H
+        S, se = b["se"], b["blk"].se
+        l1, l2 = se.excitation[0], se.excitation[2]
+        n, hw, c, hid = last.n, last.ho * last.wo, se.c, se.hidden
+        bname = names[id(b["blk"])] + ".se"
+        m = res[bname] = {}
+        r = rec[se_key(last)]
+
+        def C(t):
+            return t.detach().to("cpu", F64)
+
+        def rows(t):                          # [N, H, W, C] -> [N, C, pixels] on the CPU: the sums run over the last axis
+            return C(t).reshape(n, hw, c).permute(0, 2, 1)
+
+        def stage(key, got, fn, *ops):
+            """Relative L2 of ``got`` against fn(*ops) in float64 over max(2e-5, 4 x the relative L2 of the same stage in
+            float32 on the CPU from the same operands): <= 1 passes."""
+            ref = fn(*ops)
+            r32 = fn(*[o.float() if torch.is_tensor(o) else o for o in ops]).to(F64)
+            m[key] = rel_l2(C(got), ref) / max(2e-5, 4 * rel_l2(r32, ref))
+            return ref
+
+        a, bb = C(st[2]), C(st[3])
+        w1, w2 = C(l1.weight), C(l2.weight)
+        xs = rows(last.x)
+        ones = torch.ones_like(xs)
+        # ---- forward: squeeze of the stored x, q / h / e each from the stored stage before it
+        sref, sbnd = H.sum_bound(xs, ones, hw)
+        m["se_sums"] = H.worst_ratio(C(S["sums"]), sref, sbnd)[0]
+        qr = se_q(C(S["sums"]), a, bb, hw)
+        m["se_q"] = ((C(S["q"]) - qr).abs().max() / qr.abs().max().clamp_min(1e-300)).item()
+        hr = se_h(C(S["q"]), w1)
+        m["se_h"] = ((C(S["h"]) - hr).abs().max() / max(1.0, hr.abs().max().item())).item()
+        m["se_e"] = (C(S["e"]) - se_e(C(S["h"]), w2)).abs().max().item()
+        # ---- backward: the in-place mask, the two sums over the masked gradient, the excitation's backward stage by stage
+        m["se_gmask"] = float((r["gm"] != r["g"] * (last.y > 0)).sum().item())
+        gm = rows(r["gm"])
+        s1r, b1 = H.sum_bound(gm, ones, hw)
+        s2r, b2 = H.sum_bound(gm, xs, hw)
+        m["se_s1"] = H.worst_ratio(C(S["s1"]), s1r, b1)[0]
+        m["se_s2"] = H.worst_ratio(C(S["s2"]), s2r, b2)[0]
+        e_s, h_s, q_s = C(S["e"]), C(S["h"]), C(S["q"])
+        stage("se_dz2", S["dz2"], se_dz2, C(S["s1"]), C(S["s2"]), a, bb, e_s)
+        stage("se_dz1", S["dz1"], se_dz1, C(S["dz2"]), w2, h_s)
+        stage("se_o", S["o"], se_offset, C(S["dz1"]), w1, hw)
+        stage("se_dw1", l1._g2d[:, :c], se_dw, C(S["dz1"]), q_s)
+        stage("se_dw2", l2._g2d[:, :hid], se_dw, C(S["dz2"]), h_s)
+        pad = 0
+        for lin in (l1, l2):                             # pad columns of the gradient rows and the arena's padding behind them
+            o, nrow, pitch = net._offsets[(id(lin), "weight")]
+            tail = net._grad_arena[o + nrow * pitch:o + (nrow * pitch + 15) // 16 * 16]
+            pad += int((lin._g2d[:, lin.in_features:] != 0).sum().item()) + int((tail != 0).sum().item())
+        m["se_pad"] = float(pad)
+        gm64 = P(r["gm"])
+        Gr = rnd(se_form(gm64, P(S["e"]), P(S["o"])))
+        m["se_G"] = rel_max(r["G"], Gr)
+        # how visible the gate path is in G, from float64 alone (the whole chain from the float64 sums and the stored e, h)
+        o_chain = se_offset(se_dz1(se_dz2(s1r, s2r, a, bb, e_s), w2, h_s), w1, hw)
+        G_chain = gm * e_s[:, :, None] + o_chain[:, :, None]
+        SE_GATE[bname] = (o_chain.abs().max() / G_chain.abs().max().clamp_min(1e-300)).item()
+        return gm64
+
+    SE_GATE.clear()
     stem = plan.stem
     imagenet = net.style == "imagenet"
     c1 = net.conv1
     img64 = rnd(nhwc(img.to(F64)))
     # ---- blocks, in reverse (the block-input gradient of block bi is what arrived at block bi - 1's last unit)
+    # (behind an SE block the last unit's record holds G, the gradient of the BN output: the block-output gradient is in the
+    # SE record)
     g_in = {}
     for bi, b in enumerate(plan.blocks):
         if bi > 0:
-            g_in[bi] = rec[id(plan.blocks[bi - 1]["units"][-1])]["gy"]
+            up_b = plan.blocks[bi - 1]
+            up_last = up_b["units"][-1]
+            g_in[bi] = rec[se_key(up_last)]["g"] if "se" in up_b else rec[id(up_last)]["gy"]
+    b0 = plan.blocks[0]
     if id(stem) in rec:
         g_in[0] = rec[id(stem)]["gy"]
+    elif "se" in b0 and "ds" in b0:
+        g_in[0] = rec[id(b0["ds"])]["out"]       # the shortcut's data gradient runs last there and adds the first unit's
     else:
-        g_in[0] = rec[id(plan.blocks[0]["units"][0])]["out"]
+        g_in[0] = rec[id(b0["units"][0])]["out"]
     for bi, b in enumerate(plan.blocks):
         units = b["units"]
         last = units[-1]
@@ -337,9 +512,15 @@ def check_step(net, img, cap):
             rres = shortcut_a_fwd(inp, b["blk"].out_planes)
         else:
             rres = inp
-        xr, st = forward(last, P(last.src), not unrounded_last, unrounded_last, res_t=rres)
+        se = "se" in b
+        xr, st = forward(last, P(last.src), not unrounded_last, unrounded_last, res_t=rres,
+                         gate=P(b["se"]["e"]) if se else None)
         xrs.append(xr)
         sts.append(st)
+        # an SE block: bn3 has no ReLU of its own, so G arrives at the last unit unmasked, and the identity path carries the
+        # masked block-output gradient (the shortcut unit's record holds it already masked)
+        gm = se_check(b, last, st) if se else None
+        last_mask = None if se else mask_of(last)
         # backward, last unit: x-hat of the route ("sums from P": the unrounded product, the producer that recomputes conv3's
         # tile: that tile rounded, stored units: the stored output)
         if alg and route.backward == "pure":
@@ -348,7 +529,9 @@ def check_step(net, img, cap):
             xsrc = rnd(xr)
         else:
             xsrc = P(last.x)
-        dx, gt = backward(last, P(last.src), P(lrec["gy"]), mask_of(last), xsrc, st, stored_dx=not alg)
+        dx, gt = backward(last, P(last.src), P(lrec["gy"]), last_mask, xsrc, st, stored_dx=not alg)
+        if se:
+            gt = gm
         dxs = {len(units) - 1: dx}
         d_res = None
         if du is not None:
@@ -356,7 +539,7 @@ def check_step(net, img, cap):
             # the shortcut's BN backward by algebra (not through _unit_backward) takes its sums from P = g~^T x_in: unrounded
             xs_d = P(du.x) if drec is not None else xr_d
             gy_d = P(drec["gy"]) if drec is not None else P(lrec["gy"])
-            dx_d, _ = backward(du, inp, gy_d, mask_of(last), xs_d, st_d, stored_dx=drec is not None)
+            dx_d, _ = backward(du, inp, gy_d, last_mask, xs_d, st_d, stored_dx=drec is not None)
             d_res = conv_dgrad(dx_d, weight(du.conv), inp.shape, du.conv.stride, du.conv.pad)
         elif "sc" in b:
             d_res = shortcut_a_bwd(gt, inp.shape)
@@ -374,7 +557,10 @@ def check_step(net, img, cap):
             dgrad_metric(names[id(cv)], rec[id(u)]["out"], d, mask_of(units[ui - 1]))
         f = units[0]
         d = conv_dgrad(dxs[0], weight(f.conv), f.src.shape, f.conv.stride, f.conv.pad, f.conv.groups) + d_res
-        up = plan.blocks[bi - 1]["units"][-1] if bi > 0 else None
+        # behind an SE or option-A block the engine stores the block-input gradient ungated (no upstream unit fused into the
+        # data gradient that completes it): compared ungated there
+        up_b = plan.blocks[bi - 1] if bi > 0 else None
+        up = up_b["units"][-1] if up_b is not None and "se" not in up_b and "sc" not in up_b else None
         dgrad_metric(names[id(f.conv)], g_in[bi], d, mask_of(up))
         del xrs, dxs
     # ---- stem
