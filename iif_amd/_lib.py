@@ -110,6 +110,9 @@ SIGNATURES = {
     "iif_class_accumulate": [_P, _P, _I, _I, _P, _P, _P],
     "iif_fasa_update": [_P, _P, _I, _I, _L, _I, _F, _P, _P, _P, _P],
     "iif_fasa_generate": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
+    "iif_fasa_update_rows": [_P, _P, _I, _I, _L, _I, _F, _P, _P, _P, _P, _P],
+    "iif_fasa_generate_padded": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P],
+    "iif_head_loss_cums_fwd": [_P, _I, _L, _P, _P, _P, _P, _L, _F, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "iif_conv_igemm_dgrad_bnbwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P],
     "iif_bn_backward_partials": [_P, _P, _P, _I, _L, _I, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P],
     "iif_maxpool_bn_forward": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],

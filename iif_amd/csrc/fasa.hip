@@ -8,6 +8,7 @@
 // The reference loops over torch.unique(labels) on the host (one sync per class).  Here every class is one
 // thread / one block that scans the labels in row order: no host round trip, deterministic sums.
 #include "common.h"
+#include "fasa_stats.h"
 
 namespace {
 
@@ -37,24 +38,13 @@ __global__ void __launch_bounds__(256) fasa_update_kernel(const float* emb, cons
     if (total == 0) return;                                  // block-uniform
     const bool seen = fused[c] > 0.f;
     __syncthreads();                                         // every thread has read fused[c] before thread 0 bumps it
+    // the arithmetic is fasa_stats.h's, shared with the padded-row kernel of fasa_head.hip
     for (int d = threadIdx.x; d < D; d += 256) {
-        float sum = 0.f;
-        for (int i = 0; i < n; ++i)
-            if (labels[i] == (int64_t)c) sum += emb[(int64_t)i * lde + d];
-        const float mean = sum / (float)total;
-        float ss = 0.f;
-        for (int i = 0; i < n; ++i)
-            if (labels[i] == (int64_t)c) { const float t = emb[(int64_t)i * lde + d] - mean; ss = fmaf(t, t, ss); }
-        // var(unbiased=False) * n/(n-1) for n > 1 (fasa_bbox_head.py:133-137)
-        const float var = total > 1 ? (ss / (float)total) * ((float)total / (float)(total - 1)) : ss / (float)total;
         const int64_t o = (int64_t)c * D + d;
-        if (seen) {
-            fmean[o] = decay * mean + (1.f - decay) * fmean[o];
-            fvar[o] = decay * var + (1.f - decay) * fvar[o];
-        } else {
-            fmean[o] = mean;
-            fvar[o] = var;
-        }
+        fasa_class_feature(emb + d, lde, total, seen, decay, fmean + o, fvar + o, [&](auto visit) {
+            for (int i = 0; i < n; ++i)
+                if (labels[i] == (int64_t)c) visit(i);
+        });
     }
     if (threadIdx.x == 0 && !seen) fused[c] += 1.f;
 }
@@ -68,7 +58,7 @@ __global__ void __launch_bounds__(256) fasa_select_kernel(const float* rnd, cons
     __syncthreads();
     for (int c0 = 0; c0 < C; c0 += 256) {
         const int c = c0 + threadIdx.x;
-        const int take = (c < C && rnd[c] < prob[c] && fused[c] > 0.f) ? 1 : 0;
+        const int take = (c < C && fasa_class_drawn(rnd, prob, fused, c)) ? 1 : 0;
         // exclusive prefix inside the block (wave scan + wave totals)
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
         int incl = take;
@@ -95,7 +85,7 @@ __global__ void __launch_bounds__(256) fasa_generate_kernel(const int* slot_clas
     const int c = slot_class[k];
     for (int d = threadIdx.x; d < D; d += 256) {
         const int64_t o = (int64_t)c * D + d;
-        out[(int64_t)k * D + d] = fmean[o] + sqrtf(fvar[o]) * normal[o];
+        out[(int64_t)k * D + d] = fasa_virtual_sample(fmean[o], fvar[o], normal[o]);
     }
     if (threadIdx.x == 0) out_labels[k] = c;
 }

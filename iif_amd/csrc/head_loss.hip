@@ -20,6 +20,11 @@
 // rows and of hits - into loss, acc and avg.  Thread t of the last block adds the partials of blocks t, t + 256, ... and a
 // halving tree folds the threads: a fixed order for a given N, integers exact, no float atomics, the same bits every call.
 // Only the ticket word has to be zero on entry, and it is zero again on exit.
+//
+// iif_head_loss_cums_fwd (FasaIIFLoss with open accumulators, losses/fasa_iif_loss.py:145-160) is the ROWS instance of the same
+// row loop - it also stores the row losses, counts the rows with w != 0 and returns their mean - followed by
+// class_accumulate_rows_kernel, a wave per class that adds the stored rows of its class in ascending row order.  The instances
+// of iif_head_loss_fwd are the ROWS = false ones: the same code as before the template parameter.
 #include "common.h"
 #include "head_math.h"
 #include "vec16.h"
@@ -44,6 +49,7 @@ struct HeadLossArgs {
     float* loss_out; float* acc_out; float* avg_out;
     int32_t* ws;                       // [0] ticket, [1..3] unused, then (float sum, int valid, int hits) per block
     int vec_in, vec_out;               // whole groups of x / dx are one vector access
+    float* rows_out;                   // ROWS instances only: the row losses [N]
 };
 
 // One group of 4 columns at c0 (a multiple of 4): a vector access if the row allows it.  Only the LAST group of a lane
@@ -66,7 +72,10 @@ __device__ __forceinline__ void store_group(T* row, int c0, int C, bool vec, con
 // NCH: groups per lane = ceil(C / 256).  Blocks of 4 waves; a wave walks rows wave, wave + n_waves, ...
 // (launch bound: no occupancy asked for - 8 groups are 32 row values per lane, and the compiler's own allocation keeps every
 // instance free of scratch; a tighter bound would only constrain it)
-template <typename T, int NCH>
+// ROWS (iif_head_loss_cums_fwd: FasaIIFLoss with open accumulators, reduction 'none' followed by .mean()): the row losses
+// loss_weight * w_i * nll_i are stored (0 for a row that is not read), the rows that count are those with w != 0 - in the
+// accuracy and in the divisor alike - and the loss is the sum of the stored rows over max(#{w != 0}, 1).
+template <typename T, int NCH, bool ROWS>
 __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
     __shared__ __attribute__((aligned(16))) float tab_s[NCH * 256];
     __shared__ float red_f[256];
@@ -92,8 +101,10 @@ __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
             live = in_range && l64 != a.ignore;
             l = live ? (int)l64 : 0;
         }
-        wave_v += w > 0.f;
+        const bool counts = ROWS ? w != 0.f : w > 0.f;
+        wave_v += counts;
         if (!live) {                               // wave-uniform: nothing of the row is read
+            if (ROWS && lane == 0) a.rows_out[row] = 0.f;
             if (dxr) {
                 const float zero[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -122,7 +133,7 @@ __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
             }
         }
         cnt = wave_sum_i(cnt);
-        wave_h += (w > 0.f) && cnt == 0;
+        wave_h += counts && cnt == 0;
         m = wave_max(m);
         // 2^((z - m) log2 e) with the difference formed first, so that the row maximum contributes exactly 1 (iif_head.hip's single
         // fma z log2 e - round(m log2 e) scales the whole row by 2^residual: harmless for its lse = m + ..., not here).
@@ -147,7 +158,13 @@ __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
         // (el underflows only for a target ~87 below the maximum: there log(sum) - dl has nothing to cancel)
         const float nll = el > 1e-30f ? log1pf(so / el) : kLn2 * fast_log2(sum) - dl;
         const float cw = a.clsw ? a.clsw[l] : 1.0f;
-        wave_loss += w * (cw * nll);
+        if (ROWS) {
+            const float r = a.loss_weight * (w * (cw * nll));
+            if (lane == 0) a.rows_out[row] = r;
+            wave_loss += r;
+        } else {
+            wave_loss += w * (cw * nll);
+        }
         if (dxr == nullptr) continue;
         const float coef = w * cw, gs = coef * inv_s, gl = -(so * gs);
 #pragma unroll
@@ -198,7 +215,7 @@ __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
     if (threadIdx.x == 0) {
         const int valid = red_v[0];
         const float avg = (float)(valid > 1 ? valid : 1);
-        *a.loss_out = a.loss_weight * (red_f[0] / avg);
+        *a.loss_out = ROWS ? red_f[0] / avg : a.loss_weight * (red_f[0] / avg);
         // accuracy.py:49: correct.float().sum() * (100.0 / rows), the factor a Python double rounded to float32
         *a.acc_out = valid > 0 ? (float)red_h[0] * (float)(100.0 / (double)avg) : 0.f;
         *a.avg_out = avg;
@@ -227,9 +244,32 @@ __global__ void __launch_bounds__(256) head_loss_scale_kernel(const T* u, int64_
     }
 }
 
+// wave = class c: cum_labels[c] += #{i: labels[i] == c, w_i != 0}, cum_losses[c] += the sum of rows[i] over those i in ASCENDING
+// row order (FasaIIFLoss.forward, losses/fasa_iif_loss.py:154-160).  The wave looks at 64 labels at a time; the rows of a ballot
+// are added one by one, lowest first, by every lane alike (plain adds, no atomics: the same bits every call).
+__global__ void __launch_bounds__(256) class_accumulate_rows_kernel(const float* rows, const int64_t* labels, const float* roww, int n,
+                                                                    int C, float* cum_losses, float* cum_labels) {
+    const int lane = threadIdx.x & 63;
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= C) return;                                      // wave-uniform
+    float s = 0.f;
+    int cnt = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const bool hit = i < n && labels[i] == (int64_t)c && (roww == nullptr || roww[i] != 0.f);
+        unsigned long long m = __ballot(hit);
+        cnt += __popcll(m);
+        while (m) {
+            s += rows[i0 + __builtin_ctzll(m)];
+            m &= m - 1;
+        }
+    }
+    if (cnt && lane == 0) { cum_losses[c] += s; cum_labels[c] += (float)cnt; }
+}
+
 inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
-template <typename T>
+template <typename T, bool ROWS>
 int launch_fwd(HeadLossArgs a, hipStream_t st) {
     a.vec_in = a.N > 0 && a.ldx % 4 == 0 && aligned(a.x, kVecBytes<T>);
     a.vec_out = a.dx != nullptr && a.lddx % 4 == 0 && aligned(a.dx, kVecBytes<T>);
@@ -238,14 +278,14 @@ int launch_fwd(HeadLossArgs a, hipStream_t st) {
     if (blocks > kMaxBlocks) blocks = kMaxBlocks;
     const dim3 grid(blocks), block(256);
     const int nch = (a.C + 255) / 256;
-    if (nch <= 1) hipLaunchKernelGGL((head_loss_kernel<T, 1>), grid, block, 0, st, a);            // COCO: 81
-    else if (nch <= 2) hipLaunchKernelGGL((head_loss_kernel<T, 2>), grid, block, 0, st, a);
-    else if (nch <= 3) hipLaunchKernelGGL((head_loss_kernel<T, 3>), grid, block, 0, st, a);
-    else if (nch <= 4) hipLaunchKernelGGL((head_loss_kernel<T, 4>), grid, block, 0, st, a);
-    else if (nch <= 5) hipLaunchKernelGGL((head_loss_kernel<T, 5>), grid, block, 0, st, a);       // LVIS: 1204, Seesaw-sized 1205
-    else if (nch <= 6) hipLaunchKernelGGL((head_loss_kernel<T, 6>), grid, block, 0, st, a);
-    else if (nch <= 7) hipLaunchKernelGGL((head_loss_kernel<T, 7>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((head_loss_kernel<T, 8>), grid, block, 0, st, a);
+    if (nch <= 1) hipLaunchKernelGGL((head_loss_kernel<T, 1, ROWS>), grid, block, 0, st, a);            // COCO: 81
+    else if (nch <= 2) hipLaunchKernelGGL((head_loss_kernel<T, 2, ROWS>), grid, block, 0, st, a);
+    else if (nch <= 3) hipLaunchKernelGGL((head_loss_kernel<T, 3, ROWS>), grid, block, 0, st, a);
+    else if (nch <= 4) hipLaunchKernelGGL((head_loss_kernel<T, 4, ROWS>), grid, block, 0, st, a);
+    else if (nch <= 5) hipLaunchKernelGGL((head_loss_kernel<T, 5, ROWS>), grid, block, 0, st, a);       // LVIS: 1204, Seesaw-sized 1205
+    else if (nch <= 6) hipLaunchKernelGGL((head_loss_kernel<T, 6, ROWS>), grid, block, 0, st, a);
+    else if (nch <= 7) hipLaunchKernelGGL((head_loss_kernel<T, 7, ROWS>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((head_loss_kernel<T, 8, ROWS>), grid, block, 0, st, a);
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }
@@ -266,8 +306,31 @@ int iif_head_loss_fwd(const void* scores, int dtype, int64_t ld_scores, const fl
     if (!aligned(scores, dtype == IIF_F32 ? 4 : 2) || !aligned(dscores, dtype == IIF_F32 ? 4 : 2)) return IIF_EINVAL;
     if (C > IIF_HEAD_LOSS_MAX_CLASSES) return IIF_EUNSUPPORTED;
     HeadLossArgs a{scores, ld_scores, table, labels, label_weights, class_weight, ignore_index, loss_weight, N, C,
-                   N > 0 ? dscores : nullptr, ld_dscores, d_status, loss_out, acc_out, avg_out, static_cast<int32_t*>(d_workspace), 0, 0};
-    return dtype == IIF_F32 ? launch_fwd<float>(a, as_stream(stream)) : launch_fwd<unsigned short>(a, as_stream(stream));
+                   N > 0 ? dscores : nullptr, ld_dscores, d_status, loss_out, acc_out, avg_out, static_cast<int32_t*>(d_workspace), 0, 0,
+                   nullptr};
+    return dtype == IIF_F32 ? launch_fwd<float, false>(a, as_stream(stream)) : launch_fwd<unsigned short, false>(a, as_stream(stream));
+}
+
+int iif_head_loss_cums_fwd(const void* scores, int dtype, int64_t ld_scores, const float* table, const int64_t* labels,
+                           const float* label_weights, const float* class_weight, int64_t ignore_index, float loss_weight, int N, int C,
+                           void* dscores, int64_t ld_dscores, float* rows_out, float* cum_losses, float* cum_labels, float* loss_out,
+                           float* acc_out, float* avg_out, int32_t* d_status, void* d_workspace, void* stream) {
+    if (N < 0 || N > IIF_HEAD_LOSS_MAX_ROWS || C < 2) return IIF_EINVAL;
+    if (dtype != IIF_F32 && dtype != IIF_BF16) return IIF_EINVAL;
+    if (!loss_out || !acc_out || !avg_out || !cum_losses || !cum_labels || !d_workspace || !aligned(d_workspace, 4)) return IIF_EINVAL;
+    if (N > 0 && (!scores || !labels || !rows_out)) return IIF_EINVAL;
+    if (N > 0 && (ld_scores < C || (dscores && ld_dscores < C))) return IIF_EINVAL;
+    if (!aligned(scores, dtype == IIF_F32 ? 4 : 2) || !aligned(dscores, dtype == IIF_F32 ? 4 : 2)) return IIF_EINVAL;
+    if (C > IIF_HEAD_LOSS_MAX_CLASSES) return IIF_EUNSUPPORTED;
+    HeadLossArgs a{scores, ld_scores, table, labels, label_weights, class_weight, ignore_index, loss_weight, N, C,
+                   N > 0 ? dscores : nullptr, ld_dscores, d_status, loss_out, acc_out, avg_out, static_cast<int32_t*>(d_workspace), 0, 0,
+                   rows_out};
+    const int rc = dtype == IIF_F32 ? launch_fwd<float, true>(a, as_stream(stream)) : launch_fwd<unsigned short, true>(a, as_stream(stream));
+    if (rc != IIF_OK || N == 0) return rc;
+    hipLaunchKernelGGL(class_accumulate_rows_kernel, dim3((C + 3) / 4), dim3(256), 0, as_stream(stream), rows_out, labels, label_weights,
+                       N, C, cum_losses, cum_labels);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
 }
 
 int iif_head_loss_bwd(const void* dscores, int dtype, int64_t n, const float* d_upstream, const float* d_avg, float loss_weight,

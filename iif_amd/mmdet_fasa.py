@@ -11,7 +11,8 @@ Mirrors, from instance_segmentation/mmdet:
 
 The reference walks ``torch.unique(labels)`` on the host (one device sync per class and step); here each of
 those is one launch with no host round trip, except the row count of ``fa_generate`` (one sync, as the
-reference's ``len(embedding_list)``).
+reference's ``len(embedding_list)``).  ``fa_update_rows`` and ``fa_generate_padded`` are the forms without any host read, for
+the padded pipeline (``mmdet_fasa_head_loss.fasa_bbox_head_loss``).
 """
 import torch
 import torch.nn as nn
@@ -130,6 +131,78 @@ class FasaFeatureBank(nn.Module):
         if k == 0:
             return [], []
         return out[:k], labels[:k]
+
+    # ---- the padded pipeline (mmdet_fasa_head_loss.fasa_bbox_head_loss): no host read
+    MAX_ROWS = 65535            # IIF_FASA_ROWS_MAX_ROWS
+    MAX_CLASSES = 4096          # IIF_FASA_ROWS_MAX_CLASSES
+
+    def fa_update_rows(self, embedding, labels):
+        """``fa_update(embedding[pos], labels[pos])`` with ``pos = (labels >= 0) & (labels < num_classes)`` selected on
+        the device (fasa_bbox_head.py:258-262 without its two boolean indexings): the padded rows of
+        ``roi_stage_targets_padded`` go in as they are.  ``feature_mean``, ``feature_std`` and ``feature_used`` end
+        with the bits ``fa_update`` gives on the compacted rows; the embedding of a row that is not positive is never
+        read; two launches, no atomics.  ``embedding`` [N, D] float32 with any row pitch >= D, ``labels`` [N].
+
+        Raises ``ValueError`` for more than 65535 rows or more than 4096 classes: compact the rows and call
+        ``fa_update``, which has no such limit."""
+        if embedding.dim() != 2 or embedding.shape[1] != self.feat_dim or labels.numel() != embedding.shape[0]:
+            raise ValueError("fa_update_rows: embedding [N, %d] and N labels expected, got %s and %d labels"
+                             % (self.feat_dim, tuple(embedding.shape), labels.numel()))
+        n = embedding.shape[0]
+        if n > self.MAX_ROWS or self.num_classes > self.MAX_CLASSES:
+            raise ValueError("fa_update_rows: at most %d rows and %d classes (got %d rows, %d classes); compact the positive "
+                             "rows and call fa_update instead" % (self.MAX_ROWS, self.MAX_CLASSES, n, self.num_classes))
+        if n == 0:
+            return
+        _lib.require_gpu(embedding, labels)
+        e = embedding.detach()
+        if e.dtype != torch.float32:
+            e = e.float()
+        if e.stride(1) != 1 or (n > 1 and e.stride(0) < e.shape[1]):
+            e = e.contiguous()
+        lb = labels.reshape(-1).to(torch.int64).contiguous()
+        if getattr(self, "_present", None) is None or self._present.device != e.device:
+            self._present = torch.zeros(self.num_classes, dtype=torch.int32, device=e.device)
+        _lib.check(_lib.lib().iif_fasa_update_rows(_lib.ptr(e), _lib.ptr(lb), n, e.shape[1], e.stride(0) if n > 1 else e.shape[1],
+                                                   self.num_classes, float(self.decay_ratio), _lib.ptr(self.feature_mean.data),
+                                                   _lib.ptr(self.feature_std.data), _lib.ptr(self.feature_used.data),
+                                                   _lib.ptr(self._present), _lib.stream_ptr()), "iif_fasa_update_rows")
+
+    def fa_generate_padded(self, rand=None, normal=None, capacity=None):
+        """``fa_generate`` with a fixed shape and no host read: ``(embedding [K, D] float32, labels [K] int64,
+        weights [K] float32, count)`` with ``K = capacity`` (default ``num_classes``) and ``count`` a 0-d int32 device
+        tensor.  Rows below ``count`` hold what ``fa_generate`` returns for the same draws - the same classes in
+        ascending order, the same bits - with weight ``loss_aug_weight``; the rows from ``count`` on hold zeros, label
+        ``num_classes`` and weight 0, which ``head_cls_loss`` does not read.  One launch (plus the two draws when
+        ``rand`` [C] / ``normal`` [C, D] are not given).
+
+        With ``capacity`` below the number of classes drawn the lowest ``capacity`` classes are kept, ``count ==
+        capacity``, and ``self.aug_dropped`` (0-d int32 device tensor, rewritten by every call) holds the number of
+        classes dropped; it is 0 otherwise, always so at the default capacity.  This is the one deliberate difference
+        from the reference.  ``capacity < 1`` raises ``ValueError``."""
+        K = self.num_classes if capacity is None else int(capacity)
+        if K < 1:
+            raise ValueError("fa_generate_padded: capacity must be at least 1, got %r" % (capacity,))
+        dev = self.feature_mean.device
+        if rand is None:
+            rand = torch.rand(self.num_classes, device=dev)
+        if normal is None:
+            normal = torch.randn(self.num_classes, self.feat_dim, device=dev)
+        if rand.numel() != self.num_classes or tuple(normal.shape) != (self.num_classes, self.feat_dim):
+            raise ValueError("fa_generate_padded: rand [%d] and normal [%d, %d] expected, got %s and %s"
+                             % (self.num_classes, self.num_classes, self.feat_dim, tuple(rand.shape), tuple(normal.shape)))
+        _lib.require_gpu(rand, normal, self.feature_mean)
+        out = torch.empty(K, self.feat_dim, device=dev)
+        labels = torch.empty(K, dtype=torch.int64, device=dev)
+        weights = torch.empty(K, device=dev)
+        count = torch.empty(2, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().iif_fasa_generate_padded(
+            _lib.ptr(rand.reshape(-1).float().contiguous()), _lib.ptr(self.prob_list.data), _lib.ptr(self.feature_used.data),
+            _lib.ptr(self.feature_mean.data), _lib.ptr(self.feature_std.data), _lib.ptr(normal.float().contiguous()),
+            self.num_classes, self.feat_dim, K, float(self.loss_aug_weight), _lib.ptr(out), _lib.ptr(labels), _lib.ptr(weights),
+            _lib.ptr(count), _lib.stream_ptr()), "iif_fasa_generate_padded")
+        self.aug_dropped = count[1]
+        return out, labels, weights, count[0]
 
     def dynamic_sampling(self, loss_cls, training=False):
         """fasa_bbox_head.py:174-215: once per epoch, in eval mode.  Host-side (AffinityPropagation)."""

@@ -1142,6 +1142,40 @@ int iif_fasa_generate(const float* rnd, const float* prob, const float* feature_
                       const float* feature_var, const float* normal, int c, int d, int* slot_class, int* count,
                       float* out, int64_t* out_labels, void* stream);
 
+/* FasaBBoxHead.loss without a host read (csrc/fasa_head.hip, csrc/head_loss.hip; ConvFCFASABBoxHead.loss,
+ * roi_heads/bbox_heads/fasa_bbox_head.py:217-300).
+ *   iif_fasa_update_rows      iif_fasa_update on the rows with 0 <= labels[i] < c of a PADDED batch, selected on the device:
+ *                             feature_mean / feature_var / feature_used end with the very bits iif_fasa_update gives on
+ *                             embedding[pos], labels[pos] (one shared __device__ function, sums in ascending row order).
+ *                             A row whose label is outside [0, c) is never dereferenced; no atomics; two launches (the
+ *                             statistics, then feature_used).  present: int32 [c] scratch.  n <= IIF_FASA_ROWS_MAX_ROWS and
+ *                             c <= IIF_FASA_ROWS_MAX_CLASSES, else IIF_EUNSUPPORTED; any d, any ld >= d.
+ *   iif_fasa_generate_padded  iif_fasa_generate with a fixed shape, ONE launch: out [capacity, d], out_labels [capacity],
+ *                             out_weights [capacity].  Row k below count[0] = min(#drawn, capacity) holds the k-th drawn
+ *                             class (ascending) exactly as iif_fasa_generate writes it, weight aug_weight; the rows from
+ *                             count[0] on hold zeros, label c and weight 0.  count: device int32 [2] = (rows written,
+ *                             drawn classes dropped because capacity was smaller).
+ *   iif_head_loss_cums_fwd    iif_head_loss_fwd for FasaIIFLoss with OPEN accumulators (reduction 'none', then .mean();
+ *                             losses/fasa_iif_loss.py:145-160): rows_out[i] = loss_weight * w_i * cw[l_i] * nll_i,
+ *                             *loss_out = sum_i rows_out[i] / avg with avg = max(#{w_i != 0}, 1), *acc_out the top-1
+ *                             accuracy over the rows with w_i != 0, and in a second launch cum_losses[l] += the sum of
+ *                             rows_out over the rows of label l in ascending row order, cum_labels[l] += their number.
+ *                             A row of weight 0 is not read and enters none of these.  dscores as iif_head_loss_fwd's,
+ *                             to be finished by iif_head_loss_bwd with loss_weight and *avg_out.  Arguments are checked
+ *                             as iif_head_loss_fwd's. */
+#define IIF_FASA_ROWS_MAX_ROWS 65535
+#define IIF_FASA_ROWS_MAX_CLASSES 4096
+int iif_fasa_update_rows(const float* embedding, const int64_t* labels, int n, int d, int64_t ld, int c, float decay,
+                         float* feature_mean, float* feature_var, float* feature_used, int32_t* present, void* stream);
+int iif_fasa_generate_padded(const float* rnd, const float* prob, const float* feature_used, const float* feature_mean,
+                             const float* feature_var, const float* normal, int c, int d, int capacity, float aug_weight,
+                             float* out, int64_t* out_labels, float* out_weights, int32_t* count, void* stream);
+int iif_head_loss_cums_fwd(const void* scores, int dtype, int64_t ld_scores, const float* table, const int64_t* labels,
+                           const float* label_weights, const float* class_weight, int64_t ignore_index, float loss_weight,
+                           int N, int C, void* dscores, int64_t ld_dscores, float* rows_out, float* cum_losses,
+                           float* cum_labels, float* loss_out, float* acc_out, float* avg_out, int32_t* d_status,
+                           void* d_workspace, void* stream);
+
 /* Data gradient that also emits the batch-norm BACKWARD partial sums of the upstream unit.  dst (= dL/dy of the
  * unit that produced this convolution's input) is gated by that unit's ReLU bits `up_bits` (nullable: no ReLU) and
  * reduced per pixel tile against its pre-normalisation output `up_x` (same shape as dst) and statistics
