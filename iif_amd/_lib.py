@@ -136,6 +136,9 @@ SIGNATURES = {
     "iif_bbox_reg_scatter_grad": [_P, _P, _I, _I, _I, _P, _P, _I, _L, _P],
     "iif_head_loss_fwd": [_P, _I, _L, _P, _P, _P, _P, _L, _F, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P],
     "iif_head_loss_bwd": [_P, _I, _L, _P, _P, _F, _P, _P],
+    "iif_head_bce_loss_fwd": [_P, _I, _L, _P, _P, _P, _L, _F, _I, _I, _P, _L, _P, _P, _P, _P, _P],
+    "iif_seesaw_head_fwd": [_P, _I, _L, _P, _P, _P, _F, _F, _F, _F, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P],
+    "iif_seesaw_head_bwd": [_P, _L, _I, _I, _P, _P, _P, _F, _P, _L, _P],
     "iif_bbox_overlaps": [_P, _L, _L, _P, _L, _L, _I, _I, _F, _P, _P],
     "iif_max_iou_assign": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _F, _F, _F, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
     "iif_bbox2delta": [_P, _L, _P, _L, _L, _P, _P, _P, _P],

@@ -62,21 +62,13 @@ __device__ __forceinline__ void load_row(const Args& a, int64_t i, float& wi, in
 // unscaled weighted loss l and d l / d x of one element.  DENSE: y / ew are its target and weight; else wi / t its row's.
 template <bool DENSE>
 __device__ __forceinline__ void one(const Args& a, float x, int c, float wi, int t, float y, float ew, float& l, float& d) {
-    const SigmoidElem p = sigmoid_elem(x);
     if constexpr (DENSE) {
+        const SigmoidElem p = sigmoid_elem(x);
         const float pw = a.cw ? a.cw[c] : 1.0f;
         l = ((1.0f - y) * p.spp + pw * y * p.spn) * ew;
         d = ((1.0f - y) * p.s - pw * y * p.q) * ew;
     } else {
-        l = p.spp;
-        d = p.s;
-        if (c == t) {
-            const float pw = a.cw ? a.cw[c] : 1.0f;
-            l = pw * p.spn;
-            d = -pw * p.q;
-        }
-        l *= wi;
-        d *= wi;
+        bce_label_elem(x, c, t, wi, a.cw, l, d);             // head_math.h
     }
 }
 

@@ -25,6 +25,9 @@
 // row loop - it also stores the row losses, counts the rows with w != 0 and returns their mean - followed by
 // class_accumulate_rows_kernel, a wave per class that adds the stored rows of its class in ascending row order.  The instances
 // of iif_head_loss_fwd are the ROWS = false ones: the same code as before the template parameter.
+//
+// iif_head_bce_loss_fwd (CrossEntropyLoss(use_sigmoid=True)) is the same frame around the sigmoid element of head_math.h that
+// bce_head.hip uses: head_bce_kernel, below head_loss_kernel.  Both end in reduce_three, the reduction described above.
 #include "common.h"
 #include "head_math.h"
 #include "vec16.h"
@@ -69,6 +72,52 @@ __device__ __forceinline__ void store_group(T* row, int c0, int C, bool vec, con
         if (!RAGGED || c0 + e < C) VT<T>::store1(row + c0 + e, v[e]);
 }
 
+// The block's three sums, then loss_reduce.h's protocol (see the head of the file).  Called by every thread of a 256-thread block
+// with its wave's sums (wave-uniform); true in thread 0 of the last block only, which gets the grid's totals and has to put the
+// ticket word ws[0] back to zero once it has written its results.
+__device__ __forceinline__ bool reduce_three(int32_t* ws, float wave_loss, int wave_v, int wave_h, float& sum, int& valid, int& hits) {
+    __shared__ float red_f[256];
+    __shared__ int red_v[256], red_h[256];
+    __shared__ int last;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) { red_f[wv] = wave_loss; red_v[wv] = wave_v; red_h[wv] = wave_h; }
+    __syncthreads();
+    int32_t* part = ws + 4;
+    if (threadIdx.x == 0) {
+        float f = 0.f;
+        int v = 0, h = 0;
+        for (int i = 0; i < 4; ++i) { f += red_f[i]; v += red_v[i]; h += red_h[i]; }
+        const float p0 = __hip_atomic_exchange(reinterpret_cast<float*>(part + 3 * blockIdx.x), f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int p1 = __hip_atomic_exchange(part + 3 * blockIdx.x + 1, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int p2 = __hip_atomic_exchange(part + 3 * blockIdx.x + 2, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" : : "v"(p0), "v"(p1), "v"(p2) : "memory");
+        const int t = __hip_atomic_fetch_add(ws, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = (t == (int)gridDim.x - 1);
+    }
+    __syncthreads();
+    if (!last) return false;
+    float f = 0.f;
+    int v = 0, h = 0;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
+        f += __hip_atomic_load(reinterpret_cast<float*>(part + 3 * i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v += __hip_atomic_load(part + 3 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        h += __hip_atomic_load(part + 3 * i + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    red_f[threadIdx.x] = f; red_v[threadIdx.x] = v; red_h[threadIdx.x] = h;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red_f[threadIdx.x] += red_f[threadIdx.x + o];
+            red_v[threadIdx.x] += red_v[threadIdx.x + o];
+            red_h[threadIdx.x] += red_h[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    sum = red_f[0]; valid = red_v[0]; hits = red_h[0];
+    return threadIdx.x == 0;
+}
+
 // NCH: groups per lane = ceil(C / 256).  Blocks of 4 waves; a wave walks rows wave, wave + n_waves, ...
 // (launch bound: no occupancy asked for - 8 groups are 32 row values per lane, and the compiler's own allocation keeps every
 // instance free of scratch; a tighter bound would only constrain it)
@@ -78,9 +127,6 @@ __device__ __forceinline__ void store_group(T* row, int c0, int C, bool vec, con
 template <typename T, int NCH, bool ROWS>
 __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
     __shared__ __attribute__((aligned(16))) float tab_s[NCH * 256];
-    __shared__ float red_f[256];
-    __shared__ int red_v[256], red_h[256];
-    __shared__ int last;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nwaves = gridDim.x * 4;
     const int C = a.C;
@@ -177,50 +223,83 @@ __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
             else store_group<T, true>(dxr, c0, C, a.vec_out, p);
         }
     }
-    // ---- the block's three sums, then loss_reduce.h's protocol
-    if (lane == 0) { red_f[wv] = wave_loss; red_v[wv] = wave_v; red_h[wv] = wave_h; }
-    __syncthreads();
-    int32_t* part = a.ws + 4;
-    if (threadIdx.x == 0) {
-        float f = 0.f;
-        int v = 0, h = 0;
-        for (int i = 0; i < 4; ++i) { f += red_f[i]; v += red_v[i]; h += red_h[i]; }
-        const float p0 = __hip_atomic_exchange(reinterpret_cast<float*>(part + 3 * blockIdx.x), f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int p1 = __hip_atomic_exchange(part + 3 * blockIdx.x + 1, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int p2 = __hip_atomic_exchange(part + 3 * blockIdx.x + 2, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" : : "v"(p0), "v"(p1), "v"(p2) : "memory");
-        const int t = __hip_atomic_fetch_add(a.ws, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!last) return;
-    float f = 0.f;
-    int v = 0, h = 0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
-        f += __hip_atomic_load(reinterpret_cast<float*>(part + 3 * i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v += __hip_atomic_load(part + 3 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        h += __hip_atomic_load(part + 3 * i + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    red_f[threadIdx.x] = f; red_v[threadIdx.x] = v; red_h[threadIdx.x] = h;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            red_f[threadIdx.x] += red_f[threadIdx.x + o];
-            red_v[threadIdx.x] += red_v[threadIdx.x + o];
-            red_h[threadIdx.x] += red_h[threadIdx.x + o];
+    float sum;
+    int valid, hits;
+    if (!reduce_three(a.ws, wave_loss, wave_v, wave_h, sum, valid, hits)) return;
+    const float avg = (float)(valid > 1 ? valid : 1);
+    *a.loss_out = ROWS ? sum / avg : a.loss_weight * (sum / avg);
+    // accuracy.py:49: correct.float().sum() * (100.0 / rows), the factor a Python double rounded to float32
+    *a.acc_out = valid > 0 ? (float)hits * (float)(100.0 / (double)avg) : 0.f;
+    *a.avg_out = avg;
+    __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The sigmoid head: mmdet's binary_cross_entropy with one class index per row (cross_entropy_loss.py:53-111, the element of
+// bce_head.hip) in the frame of head_loss_kernel - a wave per row, the weight read first, the row in registers, the three sums.
+// A label >= C that is valid is a background row (every column a negative), a label < 0 or equal to ignore_index turns the
+// row's weight into 0 but the row still counts in V when label_weights > 0, as in the reference; a hit needs a label in [0, C).
+template <typename T, int NCH>
+__global__ void __launch_bounds__(256) head_bce_kernel(HeadLossArgs a) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nwaves = gridDim.x * 4;
+    const int C = a.C;
+    float wave_loss = 0.f;
+    int wave_v = 0, wave_h = 0;                    // wave-uniform
+    for (int row = blockIdx.x * 4 + wv; row < a.N; row += nwaves) {
+        const float w = a.roww ? a.roww[row] : 1.0f;
+        T* dxr = a.dx ? static_cast<T*>(a.dx) + (int64_t)row * a.lddx : nullptr;
+        if (w == 0.f) {                            // wave-uniform: nothing of the row is read, its label included
+            if (dxr) {
+                const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < NCH - 1; ++j) store_group<T, false>(dxr, (j * 64 + lane) * 4, C, a.vec_out, zero);
+                store_group<T, true>(dxr, ((NCH - 1) * 64 + lane) * 4, C, a.vec_out, zero);
+            }
+            continue;
         }
-        __syncthreads();
+        const int64_t l64 = a.labels[row];
+        const bool valid = l64 >= 0 && l64 != a.ignore;
+        const bool in_range = l64 >= 0 && l64 < C;
+        const float wi = valid ? w : 0.0f;
+        const int t = (valid && in_range) ? (int)l64 : -1;
+        const T* xr = static_cast<const T*>(a.x) + (int64_t)row * a.ldx;
+        float z[NCH][4];
+#pragma unroll
+        for (int j = 0; j < NCH - 1; ++j) load_group<T, false>(xr, (j * 64 + lane) * 4, C, a.vec_in, z[j]);
+        load_group<T, true>(xr, ((NCH - 1) * 64 + lane) * 4, C, a.vec_in, z[NCH - 1]);
+        const int lh = in_range ? (int)l64 : 0;
+        const float xt = VT<T>::load1(xr + lh);
+        int cnt = 0;
+        float lsum = 0.f;
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const int c0 = (j * 64 + lane) * 4;
+            float d[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                // top-1 on the raw scores, iif_topk_hits' tie rule (columns that do not exist hold -inf and never outrank)
+                cnt += (z[j][e] > xt) || (z[j][e] == xt && c0 + e < lh);
+                float l;
+                bce_label_elem(z[j][e], c0 + e, t, wi, a.clsw, l, d[e]);
+                if (j < NCH - 1 || c0 + e < C) lsum += l;
+            }
+            if (dxr == nullptr) continue;
+            if (j < NCH - 1) store_group<T, false>(dxr, c0, C, a.vec_out, d);
+            else store_group<T, true>(dxr, c0, C, a.vec_out, d);
+        }
+        cnt = wave_sum_i(cnt);
+        wave_loss += wave_sum(lsum);
+        wave_v += w > 0.f;
+        wave_h += w > 0.f && in_range && cnt == 0;
     }
-    if (threadIdx.x == 0) {
-        const int valid = red_v[0];
-        const float avg = (float)(valid > 1 ? valid : 1);
-        *a.loss_out = ROWS ? red_f[0] / avg : a.loss_weight * (red_f[0] / avg);
-        // accuracy.py:49: correct.float().sum() * (100.0 / rows), the factor a Python double rounded to float32
-        *a.acc_out = valid > 0 ? (float)red_h[0] * (float)(100.0 / (double)avg) : 0.f;
-        *a.avg_out = avg;
-        __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    float sum;
+    int valid, hits;
+    if (!reduce_three(a.ws, wave_loss, wave_v, wave_h, sum, valid, hits)) return;
+    const float avg = (float)(valid > 1 ? valid : 1);
+    *a.loss_out = a.loss_weight * (sum / avg);
+    *a.acc_out = valid > 0 ? (float)hits * (float)(100.0 / (double)avg) : 0.f;
+    *a.avg_out = avg;
+    __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // out = u * (upstream * loss_weight / avg), the three factors read on the device
@@ -290,9 +369,46 @@ int launch_fwd(HeadLossArgs a, hipStream_t st) {
     return IIF_OK;
 }
 
+template <typename T>
+int launch_bce(HeadLossArgs a, hipStream_t st) {
+    a.vec_in = a.N > 0 && a.ldx % 4 == 0 && aligned(a.x, kVecBytes<T>);
+    a.vec_out = a.dx != nullptr && a.lddx % 4 == 0 && aligned(a.dx, kVecBytes<T>);
+    int blocks = (a.N + 3) / 4;
+    if (blocks < 1) blocks = 1;                   // N == 0: one block writes loss 0, acc 0, avg 1
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+    const dim3 grid(blocks), block(256);
+    const int nch = (a.C + 255) / 256;
+    if (nch <= 1) hipLaunchKernelGGL((head_bce_kernel<T, 1>), grid, block, 0, st, a);                   // COCO: 80
+    else if (nch <= 2) hipLaunchKernelGGL((head_bce_kernel<T, 2>), grid, block, 0, st, a);
+    else if (nch <= 3) hipLaunchKernelGGL((head_bce_kernel<T, 3>), grid, block, 0, st, a);
+    else if (nch <= 4) hipLaunchKernelGGL((head_bce_kernel<T, 4>), grid, block, 0, st, a);
+    else if (nch <= 5) hipLaunchKernelGGL((head_bce_kernel<T, 5>), grid, block, 0, st, a);              // LVIS: 1203
+    else if (nch <= 6) hipLaunchKernelGGL((head_bce_kernel<T, 6>), grid, block, 0, st, a);
+    else if (nch <= 7) hipLaunchKernelGGL((head_bce_kernel<T, 7>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((head_bce_kernel<T, 8>), grid, block, 0, st, a);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int iif_head_bce_loss_fwd(const void* scores, int dtype, int64_t ld_scores, const int64_t* labels, const float* label_weights,
+                          const float* class_weight, int64_t ignore_index, float loss_weight, int N, int C, void* dscores,
+                          int64_t ld_dscores, float* loss_out, float* acc_out, float* avg_out, void* d_workspace, void* stream) {
+    if (N < 0 || N > IIF_HEAD_LOSS_MAX_ROWS || C < 1) return IIF_EINVAL;
+    if (dtype != IIF_F32 && dtype != IIF_BF16) return IIF_EINVAL;
+    if (!loss_out || !acc_out || !avg_out || !d_workspace || !aligned(d_workspace, 4)) return IIF_EINVAL;
+    if (N > 0 && (!scores || !labels)) return IIF_EINVAL;
+    if (N > 0 && (ld_scores < C || (dscores && ld_dscores < C))) return IIF_EINVAL;
+    if (!aligned(scores, dtype == IIF_F32 ? 4 : 2) || !aligned(dscores, dtype == IIF_F32 ? 4 : 2)) return IIF_EINVAL;
+    if (C > IIF_HEAD_LOSS_MAX_CLASSES) return IIF_EUNSUPPORTED;
+    HeadLossArgs a{scores, ld_scores, nullptr, labels, label_weights, class_weight, ignore_index, loss_weight, N, C,
+                   N > 0 ? dscores : nullptr, ld_dscores, nullptr, loss_out, acc_out, avg_out, static_cast<int32_t*>(d_workspace), 0, 0,
+                   nullptr};
+    return dtype == IIF_F32 ? launch_bce<float>(a, as_stream(stream)) : launch_bce<unsigned short>(a, as_stream(stream));
+}
 
 int iif_head_loss_fwd(const void* scores, int dtype, int64_t ld_scores, const float* table, const int64_t* labels,
                       const float* label_weights, const float* class_weight, int64_t ignore_index, float loss_weight, int N, int C,

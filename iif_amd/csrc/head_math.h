@@ -32,4 +32,20 @@ __device__ __forceinline__ SigmoidElem sigmoid_elem(float x) {
     p.q = x >= 0.0f ? er : r;
     return p;
 }
+
+// mmdet's binary_cross_entropy with one class index per row (cross_entropy_loss.py:53-111): the weighted loss l and d l / d x of
+// the logit x in column c of a row whose target column is t (-1: a background row) and whose weight is wi (0 for an ignored
+// row); pw is torch's pos_weight [C] or nullptr, read at the target column only.  bce_head.hip and head_loss.hip share it.
+__device__ __forceinline__ void bce_label_elem(float x, int c, int t, float wi, const float* pw, float& l, float& d) {
+    const SigmoidElem p = sigmoid_elem(x);
+    l = p.spp;
+    d = p.s;
+    if (c == t) {
+        const float w = pw ? pw[c] : 1.0f;
+        l = w * p.spn;
+        d = -w * p.q;
+    }
+    l *= wi;
+    d *= wi;
+}
 }  // namespace

@@ -10,6 +10,8 @@
 // Lane l of chunk j owns column j * 64 + l: each wave instruction is a dword access over 256 contiguous bytes, whatever the
 // row's phase; only the last chunk is ragged (lanes beyond C hold -inf).  The kernels are latency / HBM bound: no GEMM, no MFMA.
 // Arithmetic: base-2 hardware transcendentals (v_exp_f32 / v_log_f32, ~1 ulp), as in iif_head.hip.
+// iif_seesaw_head_fwd (BBoxHead.loss without its host read) is the HEAD instance of the same two kernels: rows of weight 0 are
+// not read, avg_factor is counted by the first launch, both accuracies and the division leave the second.
 #include <math.h>
 
 #include "common.h"
@@ -28,18 +30,33 @@ constexpr int kMaxCountBlocks = 64;
 constexpr int kWsHist = 4;
 constexpr int kWsPartial = kWsHist + kMaxCols;
 static_assert(IIF_SEESAW_WORKSPACE_BYTES == 4 * (kWsPartial + 2 * kMaxLossBlocks), "header and kernel disagree on the workspace");
+// workspace of iif_seesaw_head_fwd: the same four words and histogram, then [kWsHeadV] rows with w > 0 and [kWsHeadV + 1] positive
+// rows with w > 0 of the last call, [kWsHeadV + 2 .. 3] their accumulators across count blocks (zero between calls), then per loss
+// block (float class sum, float objectness sum, int objectness hits, int class hits)
+constexpr int kWsHeadV = kWsHist + kMaxCols;
+constexpr int kWsHeadPartial = kWsHeadV + 4;
+static_assert(IIF_SEESAW_HEAD_WORKSPACE_BYTES == 4 * (kWsHeadPartial + 4 * kMaxLossBlocks), "header and kernel disagree on the workspace");
 
 // ------------------------------------------------------------------------------------------------ count
 // cum_samples[l] += (float)count(labels == l): the count is an integer, so the result does not depend on the order of
 // anything and stays exact above 2^24 (three +1.0f onto 16777216.0f would be lost, one +3 gives 16777220).
-__global__ void __launch_bounds__(kCountBlock) seesaw_count_kernel(const int64_t* labels, int N, int C, float* cum, int update,
-                                                                   int32_t* ws, int32_t* status) {
+//
+// HEAD (iif_seesaw_head_fwd): a row of weight 0 is not counted and its label is not read - the weight, read first, gates the
+// label's load, and such a row is handled as the rows past the end are.  The launch also counts V = #{w > 0} and the positive
+// rows among them (0 <= label < C), into ws[kWsHeadV] and ws[kWsHeadV + 1].  The HEAD = false instance is the code that it was
+// before the parameter.
+template <bool HEAD>
+__global__ void __launch_bounds__(kCountBlock) seesaw_count_kernel(const int64_t* labels, const float* roww, int N, int C, float* cum,
+                                                                   int update, int32_t* ws, int32_t* status) {
     __shared__ int h[kMaxCols];
     __shared__ int last, npos;
+    __shared__ int head_n[2];                      // HEAD: rows with w > 0, positive rows with w > 0
     const int nb = C + 1;
     for (int i = threadIdx.x; i < nb; i += blockDim.x) h[i] = 0;
     if (threadIdx.x == 0) npos = 0;
+    if (HEAD && threadIdx.x < 2) head_n[threadIdx.x] = 0;
     __syncthreads();
+    int nv = 0, npw = 0;                           // HEAD: this thread's share of the two
     // the background is most of a sampled batch (mmdet: three rows in four): counted per lane and added once per wave, so the
     // LDS atomics do not queue on one address
     bool bad = false;
@@ -49,22 +66,42 @@ __global__ void __launch_bounds__(kCountBlock) seesaw_count_kernel(const int64_t
     const int stride = gridDim.x * blockDim.x;
     for (int64_t i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < N; i0 += 8 * stride) {
         int64_t l[8];
+        float w[8];
+        if constexpr (HEAD) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int64_t i = i0 + (int64_t)k * stride;
+                w[k] = i < N ? (roww ? roww[i] : 1.0f) : 0.0f;
+                nv += w[k] > 0.f;
+            }
+        }
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int64_t i = i0 + (int64_t)k * stride;
-            l[k] = i < N ? labels[i] : (int64_t)C;         // past the end: a background label that is taken off again below
-            if (i >= N) --bg;
+            const bool there = HEAD ? w[k] != 0.f : i < N;
+            l[k] = there ? labels[i] : (int64_t)C;         // past the end: a background label that is taken off again below
+            if (!there) --bg;
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             if (l[k] == C) ++bg;
-            else if (l[k] >= 0 && l[k] < C) atomicAdd(&h[(int)l[k]], 1);
-            else bad = true;
+            else if (l[k] >= 0 && l[k] < C) {
+                atomicAdd(&h[(int)l[k]], 1);
+                if (HEAD) npw += w[k] > 0.f;
+            } else bad = true;
         }
     }
     bg = wave_sum_i(bg);
     if (bg != 0 && (threadIdx.x & 63) == 0) atomicAdd(&h[C], bg);
     if (bad && status) atomicExch(status, 1);
+    if constexpr (HEAD) {
+        nv = wave_sum_i(nv);
+        npw = wave_sum_i(npw);
+        if ((threadIdx.x & 63) == 0) {
+            if (nv != 0) atomicAdd(&head_n[0], nv);
+            if (npw != 0) atomicAdd(&head_n[1], npw);
+        }
+    }
     __syncthreads();
     if (gridDim.x > 1) {
         // integer global atomics (returning: complete when the value is back), then the ticket; the last block reads the
@@ -73,6 +110,8 @@ __global__ void __launch_bounds__(kCountBlock) seesaw_count_kernel(const int64_t
         int back = 0;
         for (int i = threadIdx.x; i < nb; i += blockDim.x)
             if (h[i] != 0) back += __hip_atomic_fetch_add(gh + i, h[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (HEAD && threadIdx.x < 2)               // the two row counts travel the same way, through ws[kWsHeadV + 2 .. 3]
+            back += __hip_atomic_fetch_add(ws + kWsHeadV + 2 + threadIdx.x, head_n[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" : : "v"(back) : "memory");
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -84,6 +123,10 @@ __global__ void __launch_bounds__(kCountBlock) seesaw_count_kernel(const int64_t
         for (int i = threadIdx.x; i < nb; i += blockDim.x) {
             h[i] = __hip_atomic_load(gh + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(gh + i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (HEAD && threadIdx.x < 2) {
+            head_n[threadIdx.x] = __hip_atomic_load(ws + kWsHeadV + 2 + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(ws + kWsHeadV + 2 + threadIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __syncthreads();
     }
@@ -97,6 +140,7 @@ __global__ void __launch_bounds__(kCountBlock) seesaw_count_kernel(const int64_t
     __syncthreads();
     if (threadIdx.x == 0) {
         ws[2] = npos;
+        if (HEAD) { ws[kWsHeadV] = head_n[0]; ws[kWsHeadV + 1] = head_n[1]; }
         if (gridDim.x > 1) __hip_atomic_store(ws + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -110,6 +154,7 @@ struct SeesawArgs {
     float* rows_cls; float* rows_obj; float* loss_out;
     float* dx; int64_t lddx;
     int32_t* status; int32_t* ws;
+    float loss_weight; float* acc_out; float* avg_out;          // HEAD instances only
 };
 
 // One row's class columns in NCH registers per lane (column j * 64 + lane) and one extra dword: lanes 0 / 1 the two objectness
@@ -130,7 +175,76 @@ __device__ __forceinline__ void seesaw_load_row(const float* xp, int C, int64_t 
     aux = xp[lane < 2 ? C + lane : tcol];
 }
 
-template <int NCH, bool EXACT>
+// The end of a HEAD launch: loss_reduce.h's ticket protocol (partials published with returning agent-scope exchanges, s_waitcnt,
+// ticket; no fence) for two float sums and two INTEGER hit counts, which ticketed_finish cannot carry.  Thread t of the last
+// block adds the partials of blocks t, t + 256, ... and a halving tree folds the threads: a fixed order for a given N, integers
+// exact, the same bits every call.  The last block then reads the two row counts of the count launch and writes the five results.
+__device__ __forceinline__ void seesaw_head_finish(const SeesawArgs& a, float wave_cls, float wave_obj, int wave_ho, int wave_hc) {
+    __shared__ float red_c[256], red_o[256];
+    __shared__ int red_ho[256], red_hc[256];
+    __shared__ int last;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) { red_c[wv] = wave_cls; red_o[wv] = wave_obj; red_ho[wv] = wave_ho; red_hc[wv] = wave_hc; }
+    __syncthreads();
+    int32_t* part = a.ws + kWsHeadPartial + 4 * blockIdx.x;
+    if (threadIdx.x == 0) {
+        float c = 0.f, o = 0.f;
+        int ho = 0, hc = 0;
+        for (int i = 0; i < 4; ++i) { c += red_c[i]; o += red_o[i]; ho += red_ho[i]; hc += red_hc[i]; }
+        const float p0 = __hip_atomic_exchange(reinterpret_cast<float*>(part), c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const float p1 = __hip_atomic_exchange(reinterpret_cast<float*>(part + 1), o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int p2 = __hip_atomic_exchange(part + 2, ho, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int p3 = __hip_atomic_exchange(part + 3, hc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" : : "v"(p0), "v"(p1), "v"(p2), "v"(p3) : "memory");
+        const int t = __hip_atomic_fetch_add(a.ws, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = (t == (int)gridDim.x - 1);
+    }
+    __syncthreads();
+    if (!last) return;
+    float c = 0.f, o = 0.f;
+    int ho = 0, hc = 0;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
+        const int32_t* q = a.ws + kWsHeadPartial + 4 * i;
+        c += __hip_atomic_load(reinterpret_cast<const float*>(q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        o += __hip_atomic_load(reinterpret_cast<const float*>(q + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ho += __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        hc += __hip_atomic_load(q + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    red_c[threadIdx.x] = c; red_o[threadIdx.x] = o; red_ho[threadIdx.x] = ho; red_hc[threadIdx.x] = hc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            red_c[threadIdx.x] += red_c[threadIdx.x + s];
+            red_o[threadIdx.x] += red_o[threadIdx.x + s];
+            red_ho[threadIdx.x] += red_ho[threadIdx.x + s];
+            red_hc[threadIdx.x] += red_hc[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const int valid = a.ws[kWsHeadV], npos = a.ws[kWsHeadV + 1];     // of the count launch, earlier on the stream
+        const float avg = (float)(valid > 1 ? valid : 1);
+        const float lc = a.loss_weight * (red_c[0] / avg), lo = a.loss_weight * (red_o[0] / avg);
+        a.loss_out[0] = lc;
+        a.loss_out[1] = lo;
+        a.loss_out[2] = lc + lo;                                          // return_dict=False: seesaw_loss.py:261
+        // accuracy.py:49-50: float32 hit count times the float32 value of the double 100 / rows; 0 for no rows
+        a.acc_out[0] = valid > 0 ? (float)red_ho[0] * (float)(100.0 / (double)avg) : 0.f;
+        a.acc_out[1] = npos > 0 ? (float)red_hc[0] * (float)(100.0 / (double)npos) : 0.f;
+        *a.avg_out = avg;
+        __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// HEAD (iif_seesaw_head_fwd, the classification half of BBoxHead.loss without its host read): the same row loop with the row's
+// WEIGHT prefetched first - a zero weight issues no further load for the row, whose gradient row is zeros and which enters
+// nothing; no row losses are stored; the objectness hits of the rows with w > 0 and the class hits of the positive rows with
+// w > 0 (seesaw_loss.py:177-197, iif_topk_hits' rank rule on the raw scores) are counted; and the last block divides by
+// avg = max(#{w > 0}, 1), which the count launch left in the workspace.  The two row losses are formed from the same exponentials
+// in the forms that do not cancel on a confident row (see the row loop); the gradient is untouched.  The entry passes scale_cls = scale_obj = 1 and
+// div_pos = 0, so dscore is at unit scale.  The HEAD = false instances are the code that they were before the parameter.
+template <int NCH, bool EXACT, bool HEAD>
 __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
     __shared__ float lc_s[NCH * 64];                   // log(max(cum, 1)); 0 beyond C
     const int lane = threadIdx.x & 63;
@@ -139,9 +253,13 @@ __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
     int row = __builtin_amdgcn_readfirstlane(blockIdx.x * wpb + (threadIdx.x >> 6));
     float xn[NCH], auxn = 0.f;
     int64_t labn = 0;
+    float wn = 0.f;                                    // HEAD: the weight of the row in xn
     if (row < a.N) {                                   // in flight while the table is staged
-        labn = a.labels[row];
-        seesaw_load_row<NCH, EXACT>(a.x + (int64_t)row * a.ldx, a.C, labn, lane, xn, auxn);
+        if (HEAD) wn = a.roww ? a.roww[row] : 1.0f;
+        if (!HEAD || wn != 0.f) {
+            labn = a.labels[row];
+            seesaw_load_row<NCH, EXACT>(a.x + (int64_t)row * a.ldx, a.C, labn, lane, xn, auxn);
+        }
     }
 #pragma unroll
     for (int k = 0; k < (NCH * 64 + 255) / 256; ++k) {
@@ -156,6 +274,7 @@ __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
     }
     __syncthreads();
     float wave_cls = 0.f, wave_obj = 0.f;
+    int wave_ho = 0, wave_hc = 0;                      // HEAD: objectness and class hits (wave-uniform)
     for (; row < a.N; row += nwaves) {
         asm volatile("" ::: "memory");                 // keep the table reads in LDS
         float z[NCH];
@@ -163,17 +282,31 @@ __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
         for (int j = 0; j < NCH; ++j) z[j] = seesaw_has_col<NCH, EXACT>(j, lane, a.C) ? xn[j] : -INFINITY;
         const float aux = auxn;
         const int64_t lab = labn;
+        const float wrow = wn;
         // the next row's loads go out before this row's stores (vmcnt retires in order)
         const int nrow = row + nwaves;
         if (nrow < a.N) {
-            labn = a.labels[nrow];
-            seesaw_load_row<NCH, EXACT>(a.x + (int64_t)nrow * a.ldx, a.C, labn, lane, xn, auxn);
+            if (HEAD) wn = a.roww ? a.roww[nrow] : 1.0f;
+            if (!HEAD || wn != 0.f) {
+                labn = a.labels[nrow];
+                seesaw_load_row<NCH, EXACT>(a.x + (int64_t)nrow * a.ldx, a.C, labn, lane, xn, auxn);
+            }
+        }
+        if (HEAD && wrow == 0.f) {                     // wave-uniform: nothing of the row was read
+            if (a.dx) {
+                float* dz = a.dx + (int64_t)row * a.lddx;
+#pragma unroll
+                for (int j = 0; j < NCH; ++j)
+                    if (seesaw_has_col<NCH, EXACT>(j, lane, a.C)) dz[j * 64 + lane] = 0.f;
+                if (lane < 2) dz[a.C + lane] = 0.f;
+            }
+            continue;
         }
         const bool valid = lab >= 0 && lab <= a.C;
         const bool pos = valid && lab < a.C;
         const int t = pos ? (int)lab : -1;
         if (!valid && a.status && lane == 0) atomicExch(a.status, 1);
-        const float w = valid ? (a.roww ? a.roww[row] : 1.0f) : 0.0f;      // an out-of-range label zeroes its row
+        const float w = valid ? (HEAD ? wrow : a.roww ? a.roww[row] : 1.0f) : 0.0f;      // an out-of-range label zeroes its row
         float* dx = a.dx ? a.dx + (int64_t)row * a.lddx : nullptr;
         // objectness: two columns, label (lab == C)
         {
@@ -182,9 +315,17 @@ __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
             const float e0 = fast_exp2((o0 - mo) * kLog2e), e1 = fast_exp2((o1 - mo) * kLog2e);
             const float so = e0 + e1;
             const bool neg = lab == a.C;
-            const float lo = valid ? w * (mo + kLn2 * fast_log2(so) - (neg ? o1 : o0)) : 0.f;
+            // HEAD: the two-column cross entropy is softplus(other - target), which does not cancel on a confident row
+            // (mo + log(so) - target is right only to ulp(mo), more than such a row's whole loss); the gradient is the same
+            const float lo = !valid ? 0.f
+                           : HEAD ? w * sigmoid_elem(neg ? o0 - o1 : o1 - o0).spp
+                                  : w * (mo + kLn2 * fast_log2(so) - (neg ? o1 : o0));
             wave_obj += lo;
-            if (lane == 0) a.rows_obj[row] = lo;
+            if (!HEAD && lane == 0) a.rows_obj[row] = lo;
+            if (HEAD) {                                // a hit: the other column neither greater nor equal at a lower index
+                const float ot = neg ? o1 : o0, oo = neg ? o0 : o1;
+                wave_ho += valid && wrow > 0.f && !((oo > ot) || (oo == ot && neg));
+            }
             if (dx && lane < 2) {
                 const float g = a.scale_obj * w;
                 const float pr = (lane == 0 ? e0 : e1) / so;
@@ -192,7 +333,7 @@ __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
             }
         }
         if (!pos) {                                    // wave-uniform: background rows have no class loss and no class gradient
-            if (lane == 0) a.rows_cls[row] = 0.f;
+            if (!HEAD && lane == 0) a.rows_cls[row] = 0.f;
             if (dx) {
 #pragma unroll
                 for (int j = 0; j < NCH; ++j)
@@ -202,6 +343,12 @@ __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
         }
         // first softmax: lse(z), for the compensation term
         const float zt = __shfl(aux, 2, 64);
+        if (HEAD && wrow > 0.f) {                      // wave-uniform; on the raw scores, before the seesaw terms go in
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) c += (z[j] > zt) || (z[j] == zt && j * 64 + lane < t);
+            wave_hc += wave_sum_i(c) == 0;
+        }
         float base = 0.f;
         if (a.q > 0.f) {
             float m = z[0];
@@ -236,9 +383,25 @@ __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
             s2 += z[j];
         }
         s2 = wave_sum(s2);
-        const float lc = w * (mm + kLn2 * fast_log2(s2) - zt);
+        float lc = w * (mm + kLn2 * fast_log2(s2) - zt);
+        if constexpr (HEAD) {
+            // the same value with the target's own term e_t kept out of the sum, as head_loss.hip does it:
+            // lse(z') - z_t = log1p(sum_{j != t} e_j / e_t), which has nothing to cancel on a confident hit.  Every e_j carries
+            // the same factor 2^(mm log2 e - mm2), which the quotient drops.  (e_t underflows only for a target ~87 below the
+            // maximum, where the form above has nothing to cancel either.)
+            float so = 0.f, et = 0.f;
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) {
+                const bool tgt = j * 64 + lane == t;
+                so += tgt ? 0.f : z[j];
+                et += tgt ? z[j] : 0.f;
+            }
+            so = wave_sum(so);
+            et = wave_sum(et);
+            if (et > 1e-30f) lc = w * log1pf(so / et);
+        }
         wave_cls += lc;
-        if (lane == 0) a.rows_cls[row] = lc;
+        if (!HEAD && lane == 0) a.rows_cls[row] = lc;
         if (dx) {
             const float g = sc * w, gs = g / s2;
 #pragma unroll
@@ -249,7 +412,11 @@ __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
         }
     }
     // both scalar losses out of the same launch (loss_reduce.h): ticket at ws[0], interleaved cls / obj partials
-    ticketed_finish<2>(a.ws, {wave_cls, wave_obj}, {sc, a.scale_obj}, {a.loss_out, a.loss_out + 1}, kWsPartial);
+    if constexpr (!HEAD) {
+        ticketed_finish<2>(a.ws, {wave_cls, wave_obj}, {sc, a.scale_obj}, {a.loss_out, a.loss_out + 1}, kWsPartial);
+    } else {
+        seesaw_head_finish(a, wave_cls, wave_obj, wave_ho, wave_hc);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ activation
@@ -360,6 +527,21 @@ __global__ void __launch_bounds__(256) seesaw_scale_grad_kernel(const float* d, 
     }
 }
 
+// backward of iif_seesaw_head_fwd: out = d * (g_cls * loss_weight / avg) on the class columns and d * (g_obj * loss_weight / avg)
+// on the two objectness columns, every factor a device scalar
+__global__ void __launch_bounds__(256) seesaw_head_scale_kernel(const float* d, int64_t ld, int N, int C, const float* g_cls,
+                                                                const float* g_obj, const float* avg, float loss_weight, float* out,
+                                                                int64_t ldo) {
+    const int lane = threadIdx.x & 63;
+    const int wpb = blockDim.x >> 6;
+    const float gc = (*g_cls * loss_weight) / *avg, go = (*g_obj * loss_weight) / *avg;
+    for (int row = blockIdx.x * wpb + (threadIdx.x >> 6); row < N; row += gridDim.x * wpb) {
+        const float* dr = d + (int64_t)row * ld;
+        float* o = out + (int64_t)row * ldo;
+        for (int col = lane; col < C + 2; col += 64) o[col] = dr[col] * (col < C ? gc : go);
+    }
+}
+
 inline unsigned row_grid(int N, unsigned maxb) {
     const unsigned g = (unsigned)((N + 3) / 4);
     return g < maxb ? g : maxb;
@@ -407,19 +589,66 @@ int iif_seesaw_fwd_bwd(const void* cls_score, int dtype, int64_t ld_score, const
     int32_t* ws = static_cast<int32_t*>(d_workspace);
     int cb = (N + kLabelsPerCountBlock - 1) / kLabelsPerCountBlock;
     if (cb > kMaxCountBlocks) cb = kMaxCountBlocks;
-    hipLaunchKernelGGL(seesaw_count_kernel, dim3(cb), dim3(kCountBlock), 0, st, labels, N, C, cum_samples, update_counts, ws,
-                       d_status);
+    hipLaunchKernelGGL(seesaw_count_kernel<false>, dim3(cb), dim3(kCountBlock), 0, st, labels, (const float*)nullptr, N, C, cum_samples,
+                       update_counts, ws, d_status);
     IIF_LAUNCH_CHECK();
     SeesawArgs a{static_cast<const float*>(cls_score), ld_score, labels, label_weights, cum_samples, p, q,
                  q > 0.f ? logf(eps) : 0.f, scale_cls, scale_obj, div_by_pos, N, C, loss_rows_cls, loss_rows_obj, loss_out,
-                 static_cast<float*>(dscore), ld_dscore, d_status, ws};
+                 static_cast<float*>(dscore), ld_dscore, d_status, ws, 0.f, nullptr, nullptr};
     // 512 blocks of four waves: beyond that a wave walks several rows (iif_head.hip measured the same grid for fp32 rows)
     const dim3 grid(row_grid(N, 512)), block(256);
     static_assert(512 <= kMaxLossBlocks, "one partial slot per block");
     const int nch = (C + 63) / 64;
-#define CALL(K, E) hipLaunchKernelGGL((seesaw_loss_kernel<K, E>), grid, block, 0, st, a)
+#define CALL(K, E) hipLaunchKernelGGL((seesaw_loss_kernel<K, E, false>), grid, block, 0, st, a)
     SEESAW_DISPATCH(nch, CALL);
 #undef CALL
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+int iif_seesaw_head_fwd(const void* cls_score, int dtype, int64_t ld_score, const int64_t* labels, const float* label_weights,
+                        float* cum_samples, float p, float q, float eps, float loss_weight, int N, int C, void* dscore,
+                        int64_t ld_dscore, float* loss_out, float* acc_out, float* avg_out, int32_t* d_status, void* d_workspace,
+                        void* stream) {
+    if (N < 0 || N > IIF_HEAD_LOSS_MAX_ROWS || C <= 0) return IIF_EINVAL;
+    if (dtype != IIF_F32) return IIF_EINVAL;
+    if (!(p >= 0.f) || !(q >= 0.f) || (q > 0.f && !(eps > 0.f))) return IIF_EINVAL;
+    if (!loss_out || !acc_out || !avg_out || !cum_samples || !d_workspace) return IIF_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 4 != 0 || reinterpret_cast<uintptr_t>(cls_score) % 4 != 0 ||
+        reinterpret_cast<uintptr_t>(dscore) % 4 != 0)
+        return IIF_EINVAL;
+    if (N > 0 && (!cls_score || !labels)) return IIF_EINVAL;
+    if (N > 0 && (ld_score < (int64_t)C + 2 || (dscore && ld_dscore < (int64_t)C + 2))) return IIF_EINVAL;
+    if ((int64_t)C + 2 > kMaxCols) return IIF_EUNSUPPORTED;
+    hipStream_t st = as_stream(stream);
+    int32_t* ws = static_cast<int32_t*>(d_workspace);
+    int cb = (N + kLabelsPerCountBlock - 1) / kLabelsPerCountBlock;
+    if (cb < 1) cb = 1;                                // N == 0: one block of each launch, for loss 0, acc 0, avg 1
+    hipLaunchKernelGGL(seesaw_count_kernel<true>, dim3(cb), dim3(kCountBlock), 0, st, labels, label_weights, N, C, cum_samples, 1, ws,
+                       d_status);
+    IIF_LAUNCH_CHECK();
+    SeesawArgs a{static_cast<const float*>(cls_score), ld_score, labels, label_weights, cum_samples, p, q,
+                 q > 0.f ? logf(eps) : 0.f, 1.0f, 1.0f, 0, N, C, nullptr, nullptr, loss_out,
+                 N > 0 ? static_cast<float*>(dscore) : nullptr, ld_dscore, d_status, ws, loss_weight, acc_out, avg_out};
+    unsigned g = row_grid(N, 512);
+    if (g < 1) g = 1;
+    const dim3 grid(g), block(256);
+    const int nch = (C + 63) / 64;
+#define CALL(K, E) hipLaunchKernelGGL((seesaw_loss_kernel<K, E, true>), grid, block, 0, st, a)
+    SEESAW_DISPATCH(nch, CALL);
+#undef CALL
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+int iif_seesaw_head_bwd(const float* dscore, int64_t ld_dscore, int N, int C, const float* d_g_cls, const float* d_g_obj,
+                        const float* d_avg, float loss_weight, float* out, int64_t ld_out, void* stream) {
+    if (N < 0 || C <= 0 || !d_g_cls || !d_g_obj || !d_avg) return IIF_EINVAL;
+    if (N == 0) return IIF_OK;
+    if (!dscore || !out || ld_dscore < (int64_t)C + 2 || ld_out < (int64_t)C + 2) return IIF_EINVAL;
+    if (reinterpret_cast<uintptr_t>(dscore) % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 4 != 0) return IIF_EINVAL;
+    hipLaunchKernelGGL(seesaw_head_scale_kernel, dim3(row_grid(N, 2048)), dim3(256), 0, as_stream(stream), dscore, ld_dscore, N, C,
+                       d_g_cls, d_g_obj, d_avg, loss_weight, out, ld_out);
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }

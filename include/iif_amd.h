@@ -234,6 +234,28 @@ int iif_head_loss_fwd(const void* scores, int dtype, int64_t ld_scores, const fl
 int iif_head_loss_bwd(const void* dscores, int dtype, int64_t n, const float* d_upstream, const float* d_avg, float loss_weight,
                       void* out, void* stream);
 
+/* iif_head_loss_fwd for the SIGMOID head, CrossEntropyLoss(use_sigmoid=True): mmdet's binary_cross_entropy with one class index
+ * per row (mmdet/models/losses/cross_entropy_loss.py:53-111, the element loss of iif_bce_det_fwd_bwd) in ONE launch and with NO
+ * host read (csrc/head_loss.hip).  scores [N, C], 1 <= C <= IIF_HEAD_LOSS_MAX_CLASSES, row pitch ld_scores >= C, IIF_F32 or
+ * IIF_BF16 (math is fp32), element-aligned; l_i = labels[i], w_i = label_weights[i] (NULL = ones), pw = class_weight (torch's
+ * pos_weight, NULL = ones); sp = softplus, s = sigmoid:
+ *   valid_i = l_i >= 0 and l_i != ignore_index,   y_ic = [l_i == c]   (a valid label >= C is a background row, not an error)
+ *   l_ic    = (1 - y_ic) sp(x_ic) + pw_c y_ic sp(-x_ic)
+ *   V       = #{ i : w_i > 0 },  avg = max(V, 1)
+ *   loss    = loss_weight * (sum_i w_i valid_i sum_c l_ic) / avg
+ *   hit_i   = l_i in [0, C) and no column of the RAW scores_i outranks column l_i (iif_topk_hits' tie rule)
+ *   acc     = float(sum_{w_i > 0} hit_i) * float(100.0 / avg)   0 when V == 0
+ *   dscores[i, c] = w_i valid_i ((1 - y_ic) s(x_ic) - pw_c y_ic (1 - s(x_ic)))       WITHOUT loss_weight / avg: iif_head_loss_bwd
+ * A row with w_i == 0 is NOT READ, its label included: its dscores row is zeros and it takes no part in loss, V or acc.  A row
+ * with w_i < 0 enters the loss but not V or acc.  dscores equals iif_bce_det_fwd_bwd's dpred at scale 1 bit for bit (fp32).
+ * loss_out, acc_out, avg_out, dscores, d_workspace (IIF_HEAD_LOSS_WORKSPACE_BYTES) and the order of the sums: as
+ * iif_head_loss_fwd's.  N == 0 writes loss 0, acc 0, avg 1 (one launch).
+ * Before anything is launched: IIF_EINVAL for N outside 0 .. IIF_HEAD_LOSS_MAX_ROWS, C < 1, an unknown dtype, a null or
+ * misaligned output / workspace / scores / labels, a pitch smaller than C; IIF_EUNSUPPORTED for C > IIF_HEAD_LOSS_MAX_CLASSES. */
+int iif_head_bce_loss_fwd(const void* scores, int dtype, int64_t ld_scores, const int64_t* labels, const float* label_weights,
+                          const float* class_weight, int64_t ignore_index, float loss_weight, int N, int C, void* dscores,
+                          int64_t ld_dscores, float* loss_out, float* acc_out, float* avg_out, void* d_workspace, void* stream);
+
 /* ---- Box overlaps and max-IoU assignment (csrc/assign.hip): mmdet/core/bbox/iou_calculators/iou2d_calculator.py:75-261 and
  * mmdet/core/bbox/assigners/max_iou_assigner.py:61-213 without the [G, N] overlap matrix.
  *
@@ -540,6 +562,45 @@ int iif_seesaw_fwd_bwd(const void* cls_score, int dtype, int64_t ld_score, const
                        int N, int C, float* loss_rows_cls, float* loss_rows_obj, float* loss_out,
                        void* dscore, int64_t ld_dscore, int32_t* d_status, void* d_workspace, void* stream);
 #define IIF_SEESAW_WORKSPACE_BYTES (4 * (4 + 2048 + 2 * 1024))
+
+/* iif_seesaw_fwd_bwd as the classification half of BBoxHead.loss (bbox_head.py:266-283 with SeesawLoss.forward and
+ * SeesawLoss.get_accuracy, seesaw_loss.py:177-262) with NO host read: avg_factor = max(#{label_weights > 0}, 1) is counted on
+ * the device and both accuracies leave the loss launch.  TWO launches.  cls_score [N, C + 2] fp32 (IIF_F32 only), C + 2 <= 2048,
+ * N <= IIF_HEAD_LOSS_MAX_ROWS, pitch ld_score >= C + 2; labels, label_weights (NULL = ones), cum_samples, p, q, eps as above.
+ *   launch 1   the histogram over the rows with w_i != 0 and a label in [0, C], added to cum_samples as one fp32 addition per
+ *              class; V = #{w_i > 0} and P = #{w_i > 0, label_i < C}, as integers
+ *   launch 2   the row arithmetic of iif_seesaw_fwd_bwd with the updated cum_samples; avg = max(V, 1)
+ *   loss_out[0] = loss_weight * (sum class loss_i) / avg       an exact 0 without a positive row
+ *   loss_out[1] = loss_weight * (sum objectness loss_i) / avg
+ *   loss_out[2] = loss_out[0] + loss_out[1]                     (return_dict=False)
+ *   acc_out[0]  = float(objectness hits over w_i > 0) * float(100 / avg)          0 when V == 0
+ *   acc_out[1]  = float(class hits over the positive rows with w_i > 0) * float(100 / P)          0 when P == 0
+ *   avg_out     = avg
+ *   dscore      = w_i * (softmax(z') - onehot_t | softmax(o) - onehot) at UNIT scale: iif_seesaw_fwd_bwd's at scale_cls =
+ *                 scale_obj = 1, div_by_pos = 0, bit for bit; iif_seesaw_head_bwd applies the rest
+ * A row with w_i == 0 is NOT READ, its label included: its dscore row is zeros and it enters neither the losses, V, the
+ * accuracies nor cum_samples (the padded rows of iif_roi_stage_targets; the reference counts every one of them into
+ * cum_samples[C]).  A row with w_i < 0 enters the losses and the histogram but not V or the accuracies.  A label outside [0, C]
+ * of a row with w_i != 0 zeroes the row, is not counted in the histogram, is never a hit and sets d_status, as above.
+ * loss_out float[3], acc_out float[2], avg_out float[1]: DEVICE memory, all required.  dscore [N, C + 2] or NULL.
+ * d_workspace: IIF_SEESAW_HEAD_WORKSPACE_BYTES, ZERO on first use; its tickets, histogram and accumulators are zero again on
+ * exit.  One per stream.  Integer counts, float sums in an order fixed by N: the same bits from call to call.
+ * N == 0 writes losses 0, accuracies 0, avg 1 (two launches) and leaves cum_samples alone.
+ * Before anything is launched: IIF_EINVAL for N outside 0 .. IIF_HEAD_LOSS_MAX_ROWS, C < 1, a dtype other than IIF_F32, p or q
+ * negative, eps <= 0 with q > 0, a null or misaligned output / cum_samples / workspace / cls_score / labels, a pitch smaller
+ * than C + 2; IIF_EUNSUPPORTED for C + 2 > 2048. */
+#define IIF_SEESAW_HEAD_WORKSPACE_BYTES (4 * (4 + 2048 + 4 + 4 * 1024))
+int iif_seesaw_head_fwd(const void* cls_score, int dtype, int64_t ld_score, const int64_t* labels, const float* label_weights,
+                        float* cum_samples, float p, float q, float eps, float loss_weight, int N, int C, void* dscore,
+                        int64_t ld_dscore, float* loss_out, float* acc_out, float* avg_out, int32_t* d_status, void* d_workspace,
+                        void* stream);
+
+/* Backward of iif_seesaw_head_fwd in ONE launch: out = dscore * (*d_g_cls * loss_weight / *d_avg) on the C class columns and
+ * dscore * (*d_g_obj * loss_weight / *d_avg) on the two objectness columns.  d_g_cls / d_g_obj (the gradients of loss_out[0] /
+ * loss_out[1]; the same pointer twice for loss_out[2]) and d_avg (avg_out) are DEVICE floats; dscore is left intact (backward
+ * may run twice).  N == 0 is a no-op.  IIF_EINVAL: N < 0, C < 1, a null or misaligned pointer, a pitch smaller than C + 2. */
+int iif_seesaw_head_bwd(const float* dscore, int64_t ld_dscore, int N, int C, const float* d_g_cls, const float* d_g_obj,
+                        const float* d_avg, float loss_weight, float* out, int64_t ld_out, void* stream);
 
 /* out[:, :C] = softmax(z) * softmax(o)[0], out[:, C] = softmax(o)[1]; out: [N, C + 1] fp32 with ld_out >= C + 1.
  * Replaces seesaw_loss.py:157-175 (get_activation).  One launch.  fp32 only, C + 2 <= 2048. */
