@@ -26,6 +26,7 @@ SIGNATURES = {
     "iif_build_table": [_P, _I, _I, _I, _P],
     "iif_set_cu_budget": [_I],
     "iif_get_cu_budget": [],
+    "iif_persistent_grid_blocks": [_I],
     "iif_ce_fwd_bwd": [_P, _I, _L, _P, _P, _P, _F, _P, _P, _L, _F, _I, _I, _P, _P, _P, _L, _P, _P, _P],
     "iif_sigmoid_focal_fwd_bwd": [_P, _I, _L, _P, _P, _F, _P, _F, _I, _F, _F, _I, _I, _P, _P, _P, _L, _P, _P, _P],
     "iif_scale_logits": [_P, _I, _L, _P, _I, _I, _P, _L, _P],

@@ -1764,6 +1764,14 @@ int iif_jpeg_decode(const uint8_t* data, int64_t data_bytes, const int64_t* rec,
  * iif_get_cu_budget: the count the next persistent launch will use. */
 int iif_set_cu_budget(int cus);
 int iif_get_cu_budget(void);
+/* Blocks of a persistent grid that is launched in whole units of `unit` blocks (8 * S: the S column slices of eight tile
+ * sequences, one sequence per XCD), before the layer's own tile and row counts bound it.  With n = the device's CUs and
+ * b = iif_get_cu_budget(): g = b / unit * unit, the largest whole-unit count within the budget - unless that rounding gives up
+ * more CUs than the reservation asked for, b - g > n - b, in which case the launch keeps the device's whole-unit grid,
+ * n / unit * unit.  (n = 256, b = 240: units of 8, 16, 32 give 240, 240, 224; units of 64 and 128 keep 256.)  The result may
+ * be 0 (b = 64, unit 128): such a launch takes the tile kernels.  unit <= 0: b.  A host function; no device is needed (256 CUs
+ * are assumed without one). */
+int iif_persistent_grid_blocks(int unit);
 
 #ifdef __cplusplus
 }

@@ -52,7 +52,14 @@ CONFIGS = {
     "r18_basic": ("resnet18", 365, 32, 128, BF16, {}),
     # exact-fp32 arithmetic for the SE conventions (gate, residual, masked identity path, ungated block-input gradient)
     "se_r50_fp32": ("se_resnet50", 1000, 8, 64, FP32, {}),
+    # the benchmark's mix of routes under a compute-unit budget (CU_BUDGET), forward and backward: the persistent kernels launch
+    # smaller grids - other tile sequences, other partial-row, column-sum and P / Gram slab counts - for the same plan
+    "r50_budget_240": ("resnet50", 1000, 32, 128, BF16, {"IIF_BN3_ALGEBRA_PURE_MIN_ELEMS": "5e7"}),
+    "r50_budget_64": ("resnet50", 1000, 32, 128, BF16, {"IIF_BN3_ALGEBRA_PURE_MIN_ELEMS": "5e7"}),
 }
+# iif_set_cu_budget around the whole configuration: 240 of 256 CUs is what a rank with an active gradient reducer sets, 64 the
+# smallest budget there is
+CU_BUDGET = {"r50_budget_240": 240, "r50_budget_64": 64}
 
 # The gate path must be visible.  At the oracle's initialisation every e is 0.5 +- 0.016 and the offset o = (dz1 W1) / HW is
 # 1e-4 .. 1.2e-2 of max |G| (se_resnet50, batch 32 / 128 x 128, the oracle in float64 on the CPU): a dropped o would hide
@@ -85,6 +92,8 @@ INVENTORY = {
     "se_r32_cifar": {"se": 15, "alg3": 0, "nostore": 0, "wg_stream": False, "ds_stream": False, "pool_fused_bwd": False},
     "r18_basic": {"se": 0, "alg3": 0, "nostore": 0, "ds_alg": 0, "pool_fused_bwd": True, "wg_stream": True, "ds_stream": True},
     "se_r50_fp32": {"se": 16, "alg3": 0, "rx": 0, "nostore": 0, "pg": 0, "pro": 0, "ds_alg": 0, "pool_fused_bwd": False},
+    "r50_budget_240": {"alg3": 13, "rx": 7, "nostore": 7, "pg": 3, "ds_alg": 1, "pool_fused_bwd": True, "wg_stream": True},
+    "r50_budget_64": {"alg3": 13, "rx": 7, "nostore": 7, "pg": 3, "ds_alg": 1, "pool_fused_bwd": True, "wg_stream": True},
 }
 
 # bf16 bounds: the measured worst case over the five bf16 configurations (MI355X; the step is bit-reproducible, so these are
@@ -185,10 +194,30 @@ def _check_inventory(name, inv):
         assert inv[k] == v, (name, k, inv[k], v, inv)
     if name == "r50_bench_mix":
         assert inv["pg"] >= 1 and inv["pro_rows"] >= 1 and inv["alg3_pure"] == 0
+    if name in CU_BUDGET:           # the routes whose launches a budget resizes: recomputing producer, its slabs, never-stored forward
+        assert inv["rx"] >= 1 and inv["pg"] >= 1 and inv["nostore"] >= 1, (name, inv)
+
+
+@pytest.fixture
+def cu_budget():
+    """set_(cus): iif_set_cu_budget for the rest of the test; budget 0 (the whole device) is restored whatever happens."""
+    from iif_amd import _lib
+    L = _lib.lib()
+
+    def set_(cus):
+        L.iif_set_cu_budget(0)
+        if L.iif_get_cu_budget() != 256:
+            pytest.skip("the budgets of CU_BUDGET are meant for 256 compute units")
+        _lib.check(L.iif_set_cu_budget(cus), "iif_set_cu_budget")
+        assert L.iif_get_cu_budget() == cus
+    try:
+        yield set_
+    finally:
+        L.iif_set_cu_budget(0)
 
 
 @pytest.mark.parametrize("name", [n for n in CONFIGS if CONFIGS[n][4] == BF16])
-def test_bf16_units_against_float64(name, monkeypatch):
+def test_bf16_units_against_float64(name, monkeypatch, cu_budget):
     """Measured worst cases per configuration (MI355X; dw: the pooled-stem units at 224 x 224; the stem's dw_rdx in brackets):
         r50_bench_mix    dgamma 2.0e-5  dw 3.1e-2  dw_rdx 3.2e-5 (1.2e-5)  dgrad 2.9e-3  invstd 2.9e-5  y 3.2e-3
         r50_sums_from_p  dgamma 2.2e-5  dw 6.9e-3  dw_rdx 4.9e-5 (2.1e-5)  dgrad 2.9e-3  invstd 6.3e-5  y 3.3e-3
@@ -198,6 +227,10 @@ def test_bf16_units_against_float64(name, monkeypatch):
         se_r50           dgamma 3.3e-7  dw 6.7e-3  dw_rdx 4.3e-5 (5.6e-6)  dgrad 2.9e-3  invstd 1.8e-4  y 3.4e-3
         se_r32_cifar     dgamma 1.4e-7  dw 1.5e-2  dw_rdx 2.1e-5 (2.1e-5)  dgrad 2.4e-3  invstd 6.5e-6  y 3.6e-3
         r18_basic        dgamma 3.0e-7  dw 5.7e-3  dw_rdx 1.7e-5 (1.6e-5)  dgrad 2.9e-3  invstd 1.3e-4  y 3.4e-3
+        r50_budget_240   dgamma 1.8e-5  dw 9.5e-3  dw_rdx 3.3e-5           dgrad 2.9e-3  invstd 8.2e-5  y 3.4e-3
+        r50_budget_64    dgamma 2.4e-5  dw 1.2e-2  dw_rdx 3.6e-5           dgrad 2.9e-3  invstd 6.4e-5  y 3.3e-3
+    (the two budget configurations: dw at layer1.0.conv1, a pooled-stem unit; dgrad_max 5.0e-3 / 6.5e-3, x 3.7e-3 / 3.5e-3,
+    mean 3.5e-5 / 4.2e-5, dbeta 4.0e-8 / 4.3e-8.)
     (invstd: layer4.0.downsample.0 of se_r50, layer4.1.conv2 of r18_basic, both 512 rows; the bound is 2e-4.)
     The SE metrics, measured worst case (bound), se_r50 / se_r32_cifar: se_sums 2.9e-2 / 1.5e-2 (1), se_s1 3.4e-2 / 1.2e-2 (1),
     se_s2 5.3e-2 / 3.0e-2 (1), se_q 8.1e-7 / 3.6e-7 (1e-5), se_h 1.0e-7 / 1.0e-7 (2e-5), se_e 2.2e-7 / 1.0e-7 (2e-6), se_dz2
@@ -205,6 +238,8 @@ def test_bf16_units_against_float64(name, monkeypatch):
     7.4e-3 (1), se_G 0 / 0 (2^-7: the reference's one rounding of g~ e + o is the kernel's), se_gmask and se_pad 0 / 0 (0).
     max |o| / max |G| from the float64 reference: se_r50 6e-3 .. 8e-3 in layer1, 1.9e-2 .. 2.4e-2 in layer2, 6.0e-2 .. 9.6e-2 in
     layer3, 0.22 .. 0.39 in layer4; se_r32_cifar 3.7e-2 .. 0.46."""
+    if name in CU_BUDGET:
+        cu_budget(CU_BUDGET[name])
     net, cap, inv, met, _ = run_config(name, monkeypatch)
     _check_inventory(name, inv)
     assert len(met) == len(net._saved.units) + _se_blocks(net), (len(met), len(net._saved.units))
