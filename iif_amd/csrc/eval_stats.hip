@@ -222,8 +222,6 @@ __global__ void __launch_bounds__(256) eval_stream_kernel(EvalArgs a) {
     block_end(a, s_acc);
 }
 
-inline bool aligned(const void* p, int n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; }
-
 template <typename T, int NCH>
 void launch_reg(const EvalArgs& a, dim3 grid, hipStream_t st) {
     if (a.tab) hipLaunchKernelGGL((eval_reg_kernel<T, NCH, true>), grid, dim3(64 * kWpb), 0, st, a);

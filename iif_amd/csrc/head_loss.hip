@@ -15,11 +15,10 @@
 // avg is known only when the last row is done, so the gradient is stored WITHOUT loss_weight / avg and iif_head_loss_bwd applies
 // upstream * loss_weight / avg from the device scalars in its one launch (normed_mask_predictor.hip's device-scalar pattern).
 //
-// Reduction: loss_reduce.h's ticket protocol (partials published with returning agent-scope exchanges, s_waitcnt, ticket; no
-// fence), restated here because the last block has to combine three sums - the float loss sum and the INTEGER count of valid
-// rows and of hits - into loss, acc and avg.  Thread t of the last block adds the partials of blocks t, t + 256, ... and a
-// halving tree folds the threads: a fixed order for a given N, integers exact, no float atomics, the same bits every call.
-// Only the ticket word has to be zero on entry, and it is zero again on exit.
+// Reduction: loss_reduce.h's ticketed_sums carries three sums - the float loss sum and the INTEGER count of valid rows and of
+// hits - to thread 0 of the last block, where head_loss_finish combines them into loss, acc and avg: a fixed order of
+// additions for a given N, integers exact, no float atomics, the same bits every call.  Only the ticket word has to be zero on
+// entry, and it is zero again on exit.
 //
 // iif_head_loss_cums_fwd (FasaIIFLoss with open accumulators, losses/fasa_iif_loss.py:145-160) is the ROWS instance of the same
 // row loop - it also stores the row losses, counts the rows with w != 0 and returns their mean - followed by
@@ -27,9 +26,10 @@
 // of iif_head_loss_fwd are the ROWS = false ones: the same code as before the template parameter.
 //
 // iif_head_bce_loss_fwd (CrossEntropyLoss(use_sigmoid=True)) is the same frame around the sigmoid element of head_math.h that
-// bce_head.hip uses: head_bce_kernel, below head_loss_kernel.  Both end in reduce_three, the reduction described above.
+// bce_head.hip uses: head_bce_kernel, below head_loss_kernel.  Both end in head_loss_finish, the reduction described above.
 #include "common.h"
 #include "head_math.h"
+#include "loss_reduce.h"
 #include "vec16.h"
 
 namespace {
@@ -38,6 +38,7 @@ constexpr int kMaxBlocks = (IIF_HEAD_LOSS_WORKSPACE_BYTES / 4 - 4) / 3;       //
 static_assert(IIF_HEAD_LOSS_WORKSPACE_BYTES == 4 * (4 + 3 * kMaxBlocks), "a 4-word header and whole (sum, valid, hits) triples");
 static_assert(IIF_HEAD_LOSS_WORKSPACE_BYTES <= IIF_CE_WORKSPACE_BYTES, "the per-stream CE workspace serves this head too");
 
+constexpr int kThreads = 256;            // the one block size of head_loss_kernel and head_bce_kernel: four waves, a row each
 template <typename T> constexpr int kVecBytes = 4 * (int)sizeof(T);      // a group of 4 columns
 
 struct HeadLossArgs {
@@ -72,50 +73,30 @@ __device__ __forceinline__ void store_group(T* row, int c0, int C, bool vec, con
         if (!RAGGED || c0 + e < C) VT<T>::store1(row + c0 + e, v[e]);
 }
 
-// The block's three sums, then loss_reduce.h's protocol (see the head of the file).  Called by every thread of a 256-thread block
-// with its wave's sums (wave-uniform); true in thread 0 of the last block only, which gets the grid's totals and has to put the
-// ticket word ws[0] back to zero once it has written its results.
-__device__ __forceinline__ bool reduce_three(int32_t* ws, float wave_loss, int wave_v, int wave_h, float& sum, int& valid, int& hits) {
-    __shared__ float red_f[256];
-    __shared__ int red_v[256], red_h[256];
-    __shared__ int last;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { red_f[wv] = wave_loss; red_v[wv] = wave_v; red_h[wv] = wave_h; }
-    __syncthreads();
-    int32_t* part = ws + 4;
-    if (threadIdx.x == 0) {
-        float f = 0.f;
-        int v = 0, h = 0;
-        for (int i = 0; i < 4; ++i) { f += red_f[i]; v += red_v[i]; h += red_h[i]; }
-        const float p0 = __hip_atomic_exchange(reinterpret_cast<float*>(part + 3 * blockIdx.x), f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int p1 = __hip_atomic_exchange(part + 3 * blockIdx.x + 1, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int p2 = __hip_atomic_exchange(part + 3 * blockIdx.x + 2, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" : : "v"(p0), "v"(p1), "v"(p2) : "memory");
-        const int t = __hip_atomic_fetch_add(ws, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!last) return false;
-    float f = 0.f;
-    int v = 0, h = 0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
-        f += __hip_atomic_load(reinterpret_cast<float*>(part + 3 * i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v += __hip_atomic_load(part + 3 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        h += __hip_atomic_load(part + 3 * i + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    red_f[threadIdx.x] = f; red_v[threadIdx.x] = v; red_h[threadIdx.x] = h;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            red_f[threadIdx.x] += red_f[threadIdx.x + o];
-            red_v[threadIdx.x] += red_v[threadIdx.x + o];
-            red_h[threadIdx.x] += red_h[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    sum = red_f[0]; valid = red_v[0]; hits = red_h[0];
-    return threadIdx.x == 0;
+// The gradient row of a row that is not read
+template <typename T, int NCH>
+__device__ __forceinline__ void store_zero_row(T* dxr, int lane, int C, bool vec) {
+    const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NCH - 1; ++j) store_group<T, false>(dxr, (j * 64 + lane) * 4, C, vec, zero);
+    store_group<T, true>(dxr, ((NCH - 1) * 64 + lane) * 4, C, vec, zero);
+}
+
+// The end of both kernels, called by every thread with its wave's sums (wave-uniform): the grid's (sum, valid, hits) reach thread
+// 0 of the last block (loss_reduce.h), which writes loss, acc and avg and puts the ticket word ws[0] back to zero.
+// ROWS: loss_weight is already in the row losses that were summed.
+template <bool ROWS>
+__device__ __forceinline__ void head_loss_finish(const HeadLossArgs& a, float wave_loss, int wave_v, int wave_h) {
+    float sum[1] = {wave_loss};
+    int n[2] = {wave_v, wave_h};
+    if (!ticketed_sums<1, 2, kThreads>(a.ws, a.ws + 4, sum, n)) return;
+    const int valid = n[0], hits = n[1];
+    const float avg = (float)(valid > 1 ? valid : 1);
+    *a.loss_out = ROWS ? sum[0] / avg : a.loss_weight * (sum[0] / avg);
+    // accuracy.py:49: correct.float().sum() * (100.0 / rows), the factor a Python double rounded to float32
+    *a.acc_out = valid > 0 ? (float)hits * (float)(100.0 / (double)avg) : 0.f;
+    *a.avg_out = avg;
+    __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // NCH: groups per lane = ceil(C / 256).  Blocks of 4 waves; a wave walks rows wave, wave + n_waves, ...
@@ -126,7 +107,9 @@ __device__ __forceinline__ bool reduce_three(int32_t* ws, float wave_loss, int w
 // accuracy and in the divisor alike - and the loss is the sum of the stored rows over max(#{w != 0}, 1).
 template <typename T, int NCH, bool ROWS>
 __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
-    __shared__ __attribute__((aligned(16))) float tab_s[NCH * 256];
+    // aligned(32), more than any other array of the block asks for, puts the table FIRST in LDS, where the row loop's reads of it
+    // need no base: behind the reduction's arrays <float, 2, *> takes 82 VGPRs for 74 and loses a wave per SIMD
+    __shared__ __attribute__((aligned(32))) float tab_s[NCH * 256];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nwaves = gridDim.x * 4;
     const int C = a.C;
@@ -151,12 +134,7 @@ __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
         wave_v += counts;
         if (!live) {                               // wave-uniform: nothing of the row is read
             if (ROWS && lane == 0) a.rows_out[row] = 0.f;
-            if (dxr) {
-                const float zero[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < NCH - 1; ++j) store_group<T, false>(dxr, (j * 64 + lane) * 4, C, a.vec_out, zero);
-                store_group<T, true>(dxr, ((NCH - 1) * 64 + lane) * 4, C, a.vec_out, zero);
-            }
+            if (dxr) store_zero_row<T, NCH>(dxr, lane, C, a.vec_out);
             continue;
         }
         const T* xr = static_cast<const T*>(a.x) + (int64_t)row * a.ldx;
@@ -223,15 +201,7 @@ __global__ void __launch_bounds__(256) head_loss_kernel(HeadLossArgs a) {
             else store_group<T, true>(dxr, c0, C, a.vec_out, p);
         }
     }
-    float sum;
-    int valid, hits;
-    if (!reduce_three(a.ws, wave_loss, wave_v, wave_h, sum, valid, hits)) return;
-    const float avg = (float)(valid > 1 ? valid : 1);
-    *a.loss_out = ROWS ? sum / avg : a.loss_weight * (sum / avg);
-    // accuracy.py:49: correct.float().sum() * (100.0 / rows), the factor a Python double rounded to float32
-    *a.acc_out = valid > 0 ? (float)hits * (float)(100.0 / (double)avg) : 0.f;
-    *a.avg_out = avg;
-    __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    head_loss_finish<ROWS>(a, wave_loss, wave_v, wave_h);
 }
 
 // The sigmoid head: mmdet's binary_cross_entropy with one class index per row (cross_entropy_loss.py:53-111, the element of
@@ -249,12 +219,7 @@ __global__ void __launch_bounds__(256) head_bce_kernel(HeadLossArgs a) {
         const float w = a.roww ? a.roww[row] : 1.0f;
         T* dxr = a.dx ? static_cast<T*>(a.dx) + (int64_t)row * a.lddx : nullptr;
         if (w == 0.f) {                            // wave-uniform: nothing of the row is read, its label included
-            if (dxr) {
-                const float zero[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < NCH - 1; ++j) store_group<T, false>(dxr, (j * 64 + lane) * 4, C, a.vec_out, zero);
-                store_group<T, true>(dxr, ((NCH - 1) * 64 + lane) * 4, C, a.vec_out, zero);
-            }
+            if (dxr) store_zero_row<T, NCH>(dxr, lane, C, a.vec_out);
             continue;
         }
         const int64_t l64 = a.labels[row];
@@ -292,14 +257,7 @@ __global__ void __launch_bounds__(256) head_bce_kernel(HeadLossArgs a) {
         wave_v += w > 0.f;
         wave_h += w > 0.f && in_range && cnt == 0;
     }
-    float sum;
-    int valid, hits;
-    if (!reduce_three(a.ws, wave_loss, wave_v, wave_h, sum, valid, hits)) return;
-    const float avg = (float)(valid > 1 ? valid : 1);
-    *a.loss_out = a.loss_weight * (sum / avg);
-    *a.acc_out = valid > 0 ? (float)hits * (float)(100.0 / (double)avg) : 0.f;
-    *a.avg_out = avg;
-    __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    head_loss_finish<false>(a, wave_loss, wave_v, wave_h);
 }
 
 // out = u * (upstream * loss_weight / avg), the three factors read on the device
@@ -346,47 +304,47 @@ __global__ void __launch_bounds__(256) class_accumulate_rows_kernel(const float*
     if (cnt && lane == 0) { cum_losses[c] += s; cum_labels[c] += (float)cnt; }
 }
 
-inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+// The two kernel families of the forward entries
+template <bool ROWS> struct SoftmaxKernels { template <typename T, int NCH> static constexpr auto kernel = head_loss_kernel<T, NCH, ROWS>; };
+struct SigmoidKernels { template <typename T, int NCH> static constexpr auto kernel = head_bce_kernel<T, NCH>; };
 
-template <typename T, bool ROWS>
-int launch_fwd(HeadLossArgs a, hipStream_t st) {
+template <typename F, typename T>
+int launch_rows(HeadLossArgs a, hipStream_t st) {
     a.vec_in = a.N > 0 && a.ldx % 4 == 0 && aligned(a.x, kVecBytes<T>);
     a.vec_out = a.dx != nullptr && a.lddx % 4 == 0 && aligned(a.dx, kVecBytes<T>);
     int blocks = (a.N + 3) / 4;
     if (blocks < 1) blocks = 1;                   // N == 0: one block writes loss 0, acc 0, avg 1
     if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-    const dim3 grid(blocks), block(256);
-    const int nch = (a.C + 255) / 256;
-    if (nch <= 1) hipLaunchKernelGGL((head_loss_kernel<T, 1, ROWS>), grid, block, 0, st, a);            // COCO: 81
-    else if (nch <= 2) hipLaunchKernelGGL((head_loss_kernel<T, 2, ROWS>), grid, block, 0, st, a);
-    else if (nch <= 3) hipLaunchKernelGGL((head_loss_kernel<T, 3, ROWS>), grid, block, 0, st, a);
-    else if (nch <= 4) hipLaunchKernelGGL((head_loss_kernel<T, 4, ROWS>), grid, block, 0, st, a);
-    else if (nch <= 5) hipLaunchKernelGGL((head_loss_kernel<T, 5, ROWS>), grid, block, 0, st, a);       // LVIS: 1204, Seesaw-sized 1205
-    else if (nch <= 6) hipLaunchKernelGGL((head_loss_kernel<T, 6, ROWS>), grid, block, 0, st, a);
-    else if (nch <= 7) hipLaunchKernelGGL((head_loss_kernel<T, 7, ROWS>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((head_loss_kernel<T, 8, ROWS>), grid, block, 0, st, a);
+    const dim3 grid(blocks), block(kThreads);
+    switch ((a.C + 255) / 256) {                  // 1 .. 8: the entries refuse C > 2048
+    case 1: hipLaunchKernelGGL((F::template kernel<T, 1>), grid, block, 0, st, a); break;      // COCO: 81, sigmoid 80
+    case 2: hipLaunchKernelGGL((F::template kernel<T, 2>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((F::template kernel<T, 3>), grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((F::template kernel<T, 4>), grid, block, 0, st, a); break;
+    case 5: hipLaunchKernelGGL((F::template kernel<T, 5>), grid, block, 0, st, a); break;      // LVIS: 1204, Seesaw-sized 1205, sigmoid 1203
+    case 6: hipLaunchKernelGGL((F::template kernel<T, 6>), grid, block, 0, st, a); break;
+    case 7: hipLaunchKernelGGL((F::template kernel<T, 7>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((F::template kernel<T, 8>), grid, block, 0, st, a); break;
+    }
     IIF_LAUNCH_CHECK();
     return IIF_OK;
 }
+template <typename F>
+int launch_rows(int dtype, const HeadLossArgs& a, void* stream) {
+    return dtype == IIF_F32 ? launch_rows<F, float>(a, as_stream(stream)) : launch_rows<F, unsigned short>(a, as_stream(stream));
+}
 
-template <typename T>
-int launch_bce(HeadLossArgs a, hipStream_t st) {
-    a.vec_in = a.N > 0 && a.ldx % 4 == 0 && aligned(a.x, kVecBytes<T>);
-    a.vec_out = a.dx != nullptr && a.lddx % 4 == 0 && aligned(a.dx, kVecBytes<T>);
-    int blocks = (a.N + 3) / 4;
-    if (blocks < 1) blocks = 1;                   // N == 0: one block writes loss 0, acc 0, avg 1
-    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-    const dim3 grid(blocks), block(256);
-    const int nch = (a.C + 255) / 256;
-    if (nch <= 1) hipLaunchKernelGGL((head_bce_kernel<T, 1>), grid, block, 0, st, a);                   // COCO: 80
-    else if (nch <= 2) hipLaunchKernelGGL((head_bce_kernel<T, 2>), grid, block, 0, st, a);
-    else if (nch <= 3) hipLaunchKernelGGL((head_bce_kernel<T, 3>), grid, block, 0, st, a);
-    else if (nch <= 4) hipLaunchKernelGGL((head_bce_kernel<T, 4>), grid, block, 0, st, a);
-    else if (nch <= 5) hipLaunchKernelGGL((head_bce_kernel<T, 5>), grid, block, 0, st, a);              // LVIS: 1203
-    else if (nch <= 6) hipLaunchKernelGGL((head_bce_kernel<T, 6>), grid, block, 0, st, a);
-    else if (nch <= 7) hipLaunchKernelGGL((head_bce_kernel<T, 7>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((head_bce_kernel<T, 8>), grid, block, 0, st, a);
-    IIF_LAUNCH_CHECK();
+// What the three forward entries ask of their arguments, IIF_EINVAL before IIF_EUNSUPPORTED.  outs: every result pointer of the
+// entry is there; ins: so is everything that N > 0 rows are read from or written to.
+int check_fwd(int dtype, int N, int C, int min_C, const void* scores, int64_t ld_scores, const void* dscores, int64_t ld_dscores, bool outs,
+              bool ins, const void* d_workspace) {
+    if (N < 0 || N > IIF_HEAD_LOSS_MAX_ROWS || C < min_C) return IIF_EINVAL;
+    if (dtype != IIF_F32 && dtype != IIF_BF16) return IIF_EINVAL;
+    if (!outs || !d_workspace || !aligned(d_workspace, 4)) return IIF_EINVAL;
+    if (N > 0 && !ins) return IIF_EINVAL;
+    if (N > 0 && (ld_scores < C || (dscores && ld_dscores < C))) return IIF_EINVAL;
+    if (!aligned(scores, dtype == IIF_F32 ? 4 : 2) || !aligned(dscores, dtype == IIF_F32 ? 4 : 2)) return IIF_EINVAL;
+    if (C > IIF_HEAD_LOSS_MAX_CLASSES) return IIF_EUNSUPPORTED;
     return IIF_OK;
 }
 
@@ -397,51 +355,39 @@ extern "C" {
 int iif_head_bce_loss_fwd(const void* scores, int dtype, int64_t ld_scores, const int64_t* labels, const float* label_weights,
                           const float* class_weight, int64_t ignore_index, float loss_weight, int N, int C, void* dscores,
                           int64_t ld_dscores, float* loss_out, float* acc_out, float* avg_out, void* d_workspace, void* stream) {
-    if (N < 0 || N > IIF_HEAD_LOSS_MAX_ROWS || C < 1) return IIF_EINVAL;
-    if (dtype != IIF_F32 && dtype != IIF_BF16) return IIF_EINVAL;
-    if (!loss_out || !acc_out || !avg_out || !d_workspace || !aligned(d_workspace, 4)) return IIF_EINVAL;
-    if (N > 0 && (!scores || !labels)) return IIF_EINVAL;
-    if (N > 0 && (ld_scores < C || (dscores && ld_dscores < C))) return IIF_EINVAL;
-    if (!aligned(scores, dtype == IIF_F32 ? 4 : 2) || !aligned(dscores, dtype == IIF_F32 ? 4 : 2)) return IIF_EINVAL;
-    if (C > IIF_HEAD_LOSS_MAX_CLASSES) return IIF_EUNSUPPORTED;
+    const int rc = check_fwd(dtype, N, C, 1, scores, ld_scores, dscores, ld_dscores, loss_out && acc_out && avg_out, scores && labels,
+                             d_workspace);
+    if (rc != IIF_OK) return rc;
     HeadLossArgs a{scores, ld_scores, nullptr, labels, label_weights, class_weight, ignore_index, loss_weight, N, C,
                    N > 0 ? dscores : nullptr, ld_dscores, nullptr, loss_out, acc_out, avg_out, static_cast<int32_t*>(d_workspace), 0, 0,
                    nullptr};
-    return dtype == IIF_F32 ? launch_bce<float>(a, as_stream(stream)) : launch_bce<unsigned short>(a, as_stream(stream));
+    return launch_rows<SigmoidKernels>(dtype, a, stream);
 }
 
 int iif_head_loss_fwd(const void* scores, int dtype, int64_t ld_scores, const float* table, const int64_t* labels,
                       const float* label_weights, const float* class_weight, int64_t ignore_index, float loss_weight, int N, int C,
                       void* dscores, int64_t ld_dscores, float* loss_out, float* acc_out, float* avg_out, int32_t* d_status,
                       void* d_workspace, void* stream) {
-    if (N < 0 || N > IIF_HEAD_LOSS_MAX_ROWS || C < 2) return IIF_EINVAL;
-    if (dtype != IIF_F32 && dtype != IIF_BF16) return IIF_EINVAL;
-    if (!loss_out || !acc_out || !avg_out || !d_workspace || !aligned(d_workspace, 4)) return IIF_EINVAL;
-    if (N > 0 && (!scores || !labels)) return IIF_EINVAL;
-    if (N > 0 && (ld_scores < C || (dscores && ld_dscores < C))) return IIF_EINVAL;
-    if (!aligned(scores, dtype == IIF_F32 ? 4 : 2) || !aligned(dscores, dtype == IIF_F32 ? 4 : 2)) return IIF_EINVAL;
-    if (C > IIF_HEAD_LOSS_MAX_CLASSES) return IIF_EUNSUPPORTED;
+    const int rc = check_fwd(dtype, N, C, 2, scores, ld_scores, dscores, ld_dscores, loss_out && acc_out && avg_out, scores && labels,
+                             d_workspace);
+    if (rc != IIF_OK) return rc;
     HeadLossArgs a{scores, ld_scores, table, labels, label_weights, class_weight, ignore_index, loss_weight, N, C,
                    N > 0 ? dscores : nullptr, ld_dscores, d_status, loss_out, acc_out, avg_out, static_cast<int32_t*>(d_workspace), 0, 0,
                    nullptr};
-    return dtype == IIF_F32 ? launch_fwd<float, false>(a, as_stream(stream)) : launch_fwd<unsigned short, false>(a, as_stream(stream));
+    return launch_rows<SoftmaxKernels<false>>(dtype, a, stream);
 }
 
 int iif_head_loss_cums_fwd(const void* scores, int dtype, int64_t ld_scores, const float* table, const int64_t* labels,
                            const float* label_weights, const float* class_weight, int64_t ignore_index, float loss_weight, int N, int C,
                            void* dscores, int64_t ld_dscores, float* rows_out, float* cum_losses, float* cum_labels, float* loss_out,
                            float* acc_out, float* avg_out, int32_t* d_status, void* d_workspace, void* stream) {
-    if (N < 0 || N > IIF_HEAD_LOSS_MAX_ROWS || C < 2) return IIF_EINVAL;
-    if (dtype != IIF_F32 && dtype != IIF_BF16) return IIF_EINVAL;
-    if (!loss_out || !acc_out || !avg_out || !cum_losses || !cum_labels || !d_workspace || !aligned(d_workspace, 4)) return IIF_EINVAL;
-    if (N > 0 && (!scores || !labels || !rows_out)) return IIF_EINVAL;
-    if (N > 0 && (ld_scores < C || (dscores && ld_dscores < C))) return IIF_EINVAL;
-    if (!aligned(scores, dtype == IIF_F32 ? 4 : 2) || !aligned(dscores, dtype == IIF_F32 ? 4 : 2)) return IIF_EINVAL;
-    if (C > IIF_HEAD_LOSS_MAX_CLASSES) return IIF_EUNSUPPORTED;
+    int rc = check_fwd(dtype, N, C, 2, scores, ld_scores, dscores, ld_dscores, loss_out && acc_out && avg_out && cum_losses && cum_labels,
+                       scores && labels && rows_out, d_workspace);
+    if (rc != IIF_OK) return rc;
     HeadLossArgs a{scores, ld_scores, table, labels, label_weights, class_weight, ignore_index, loss_weight, N, C,
                    N > 0 ? dscores : nullptr, ld_dscores, d_status, loss_out, acc_out, avg_out, static_cast<int32_t*>(d_workspace), 0, 0,
                    rows_out};
-    const int rc = dtype == IIF_F32 ? launch_fwd<float, true>(a, as_stream(stream)) : launch_fwd<unsigned short, true>(a, as_stream(stream));
+    rc = launch_rows<SoftmaxKernels<true>>(dtype, a, stream);
     if (rc != IIF_OK || N == 0) return rc;
     hipLaunchKernelGGL(class_accumulate_rows_kernel, dim3((C + 3) / 4), dim3(256), 0, as_stream(stream), rows_out, labels, label_weights,
                        N, C, cum_losses, cum_labels);

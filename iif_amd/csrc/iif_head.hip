@@ -332,8 +332,6 @@ __global__ void __launch_bounds__(256) scale_by_scalar_kernel(const T* x, int64_
         VT<T>::store1(out + i, VT<T>::load1(x + i) * f);
 }
 
-inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 // *inline_reduce (in/out): the caller wants the scalar loss reduced by this launch; cleared when the launch
 // configuration cannot do it (streaming kernel with more blocks than workspace slots).
 template <typename T, int MODE>

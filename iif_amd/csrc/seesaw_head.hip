@@ -22,6 +22,7 @@ namespace {
 
 constexpr int kMaxCols = 2048;              // C + 2 <= 2048: the row stays in registers (<= 32 values per lane)
 constexpr int kMaxLossBlocks = 1024;        // partial slots of the workspace
+constexpr int kHeadThreads = 256;           // the one block size iif_seesaw_head_fwd launches the loss kernel with
 constexpr int kCountBlock = 1024;           // threads of a count block
 constexpr int kLabelsPerCountBlock = 16384;   // one block: 3.4 us at 1024 labels; four blocks with their atomics and ticket: 9.2 us at 8192
 constexpr int kMaxCountBlocks = 64;
@@ -175,66 +176,24 @@ __device__ __forceinline__ void seesaw_load_row(const float* xp, int C, int64_t 
     aux = xp[lane < 2 ? C + lane : tcol];
 }
 
-// The end of a HEAD launch: loss_reduce.h's ticket protocol (partials published with returning agent-scope exchanges, s_waitcnt,
-// ticket; no fence) for two float sums and two INTEGER hit counts, which ticketed_finish cannot carry.  Thread t of the last
-// block adds the partials of blocks t, t + 256, ... and a halving tree folds the threads: a fixed order for a given N, integers
-// exact, the same bits every call.  The last block then reads the two row counts of the count launch and writes the five results.
+// The end of a HEAD launch, called by every thread with its wave's sums (wave-uniform): two float sums and two INTEGER hit counts
+// reach thread 0 of the last block (loss_reduce.h), which reads the two row counts of the count launch, writes the five results
+// and puts the ticket back to zero.
 __device__ __forceinline__ void seesaw_head_finish(const SeesawArgs& a, float wave_cls, float wave_obj, int wave_ho, int wave_hc) {
-    __shared__ float red_c[256], red_o[256];
-    __shared__ int red_ho[256], red_hc[256];
-    __shared__ int last;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { red_c[wv] = wave_cls; red_o[wv] = wave_obj; red_ho[wv] = wave_ho; red_hc[wv] = wave_hc; }
-    __syncthreads();
-    int32_t* part = a.ws + kWsHeadPartial + 4 * blockIdx.x;
-    if (threadIdx.x == 0) {
-        float c = 0.f, o = 0.f;
-        int ho = 0, hc = 0;
-        for (int i = 0; i < 4; ++i) { c += red_c[i]; o += red_o[i]; ho += red_ho[i]; hc += red_hc[i]; }
-        const float p0 = __hip_atomic_exchange(reinterpret_cast<float*>(part), c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const float p1 = __hip_atomic_exchange(reinterpret_cast<float*>(part + 1), o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int p2 = __hip_atomic_exchange(part + 2, ho, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int p3 = __hip_atomic_exchange(part + 3, hc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" : : "v"(p0), "v"(p1), "v"(p2), "v"(p3) : "memory");
-        const int t = __hip_atomic_fetch_add(a.ws, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!last) return;
-    float c = 0.f, o = 0.f;
-    int ho = 0, hc = 0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
-        const int32_t* q = a.ws + kWsHeadPartial + 4 * i;
-        c += __hip_atomic_load(reinterpret_cast<const float*>(q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        o += __hip_atomic_load(reinterpret_cast<const float*>(q + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ho += __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        hc += __hip_atomic_load(q + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    red_c[threadIdx.x] = c; red_o[threadIdx.x] = o; red_ho[threadIdx.x] = ho; red_hc[threadIdx.x] = hc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            red_c[threadIdx.x] += red_c[threadIdx.x + s];
-            red_o[threadIdx.x] += red_o[threadIdx.x + s];
-            red_ho[threadIdx.x] += red_ho[threadIdx.x + s];
-            red_hc[threadIdx.x] += red_hc[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const int valid = a.ws[kWsHeadV], npos = a.ws[kWsHeadV + 1];     // of the count launch, earlier on the stream
-        const float avg = (float)(valid > 1 ? valid : 1);
-        const float lc = a.loss_weight * (red_c[0] / avg), lo = a.loss_weight * (red_o[0] / avg);
-        a.loss_out[0] = lc;
-        a.loss_out[1] = lo;
-        a.loss_out[2] = lc + lo;                                          // return_dict=False: seesaw_loss.py:261
-        // accuracy.py:49-50: float32 hit count times the float32 value of the double 100 / rows; 0 for no rows
-        a.acc_out[0] = valid > 0 ? (float)red_ho[0] * (float)(100.0 / (double)avg) : 0.f;
-        a.acc_out[1] = npos > 0 ? (float)red_hc[0] * (float)(100.0 / (double)npos) : 0.f;
-        *a.avg_out = avg;
-        __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    float sum[2] = {wave_cls, wave_obj};
+    int hits[2] = {wave_ho, wave_hc};
+    if (!ticketed_sums<2, 2, kHeadThreads>(a.ws, a.ws + kWsHeadPartial, sum, hits)) return;
+    const int valid = a.ws[kWsHeadV], npos = a.ws[kWsHeadV + 1];         // of the count launch, earlier on the stream
+    const float avg = (float)(valid > 1 ? valid : 1);
+    const float lc = a.loss_weight * (sum[0] / avg), lo = a.loss_weight * (sum[1] / avg);
+    a.loss_out[0] = lc;
+    a.loss_out[1] = lo;
+    a.loss_out[2] = lc + lo;                                              // return_dict=False: seesaw_loss.py:261
+    // accuracy.py:49-50: float32 hit count times the float32 value of the double 100 / rows; 0 for no rows
+    a.acc_out[0] = valid > 0 ? (float)hits[0] * (float)(100.0 / (double)avg) : 0.f;
+    a.acc_out[1] = npos > 0 ? (float)hits[1] * (float)(100.0 / (double)npos) : 0.f;
+    *a.avg_out = avg;
+    __hip_atomic_store(a.ws, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // HEAD (iif_seesaw_head_fwd, the classification half of BBoxHead.loss without its host read): the same row loop with the row's
@@ -246,9 +205,11 @@ __device__ __forceinline__ void seesaw_head_finish(const SeesawArgs& a, float wa
 // div_pos = 0, so dscore is at unit scale.  The HEAD = false instances are the code that they were before the parameter.
 template <int NCH, bool EXACT, bool HEAD>
 __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
-    __shared__ float lc_s[NCH * 64];                   // log(max(cum, 1)); 0 beyond C
+    // log(max(cum, 1)); 0 beyond C.  aligned(32), more than any other array of the block asks for, puts it FIRST in LDS: behind the
+    // reduction's arrays <4, false, true> takes 65 VGPRs for 62 and loses a wave per SIMD
+    __shared__ __attribute__((aligned(32))) float lc_s[NCH * 64];
     const int lane = threadIdx.x & 63;
-    const int wpb = blockDim.x >> 6;
+    const int wpb = block_threads() >> 6;              // read here, it is at hand for the reduction at the end (loss_reduce.h)
     const int nwaves = gridDim.x * wpb;
     int row = __builtin_amdgcn_readfirstlane(blockIdx.x * wpb + (threadIdx.x >> 6));
     float xn[NCH], auxn = 0.f;
@@ -411,7 +372,8 @@ __global__ void __launch_bounds__(256) seesaw_loss_kernel(SeesawArgs a) {
             }
         }
     }
-    // both scalar losses out of the same launch (loss_reduce.h): ticket at ws[0], interleaved cls / obj partials
+    // both scalar losses out of the same launch (loss_reduce.h): ticket at ws[0], interleaved cls / obj partials, under HEAD
+    // with the two hit counts behind them
     if constexpr (!HEAD) {
         ticketed_finish<2>(a.ws, {wave_cls, wave_obj}, {sc, a.scale_obj}, {a.loss_out, a.loss_out + 1}, kWsPartial);
     } else {
@@ -632,7 +594,7 @@ int iif_seesaw_head_fwd(const void* cls_score, int dtype, int64_t ld_score, cons
                  N > 0 ? static_cast<float*>(dscore) : nullptr, ld_dscore, d_status, ws, loss_weight, acc_out, avg_out};
     unsigned g = row_grid(N, 512);
     if (g < 1) g = 1;
-    const dim3 grid(g), block(256);
+    const dim3 grid(g), block(kHeadThreads);
     const int nch = (C + 63) / 64;
 #define CALL(K, E) hipLaunchKernelGGL((seesaw_loss_kernel<K, E, true>), grid, block, 0, st, a)
     SEESAW_DISPATCH(nch, CALL);
