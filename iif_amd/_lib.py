@@ -171,6 +171,9 @@ SIGNATURES = {
     "iif_mask_predict_fwd": [_P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "iif_mask_predict_bwd_input": [_P, _P, _P, _L, _P, _I, _I, _I, _I, _P, _I, _P],
     "iif_mask_predict_bwd_weight": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    "iif_mask_predict_loss_fwd": [_P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "iif_mask_predict_loss_bwd_input": [_P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _P, _I, _P],
+    "iif_mask_predict_loss_bwd_weight": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "iif_normed_mask_predict_fwd": [_P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "iif_normed_mask_predict_bwd_input": [_P, _I, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _F, _P, _P],
     "iif_normed_mask_predict_bwd_weight": [_P, _I, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P],
@@ -180,6 +183,10 @@ SIGNATURES = {
     "iif_mask_tail_splits": [_I, _I, _I],
     "iif_mask_tail_bwd_params": [_P, _I, _P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "iif_mask_tail_bwd_classes": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "iif_mask_tail_loss_fwd": [_P, _I, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "iif_mask_tail_loss_bwd_rows": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "iif_mask_tail_loss_bwd_input": [_P, _P, _P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P],
+    "iif_mask_tail_loss_bwd_params": [_P, _I, _P, _P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "iif_nms": [_P, _L, _P, _P, _L, _I, _F, _I, _F, _L, _P, _P, _P, _P, _L, _P],
     "iif_rpn_proposals": [_P, _I, _I, _P, _I, _I, _F, _F, _I, _P, _P, _F, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P],
     "iif_multiclass_nms": [_P, _L, _I, _P, _L, _P, _P, _I, _L, _L, _F, _F, _I, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P],

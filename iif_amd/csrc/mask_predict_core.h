@@ -2,7 +2,8 @@
 // (normed_mask_predictor.hip) and the fused mask head tail (mask_tail.hip).  Each piece exists once, here:
 //   host    the argument checks and the (dtype, vector width) dispatch of the C entries
 //   loads   VTn<T, V> (vec16.h): V consecutive elements of a channel row as floats
-//   forward the weight-row staging, the group fold, the BCE term, the sigmoid and the fold of a tile's loss into its row partial
+//   forward the weight-row staging, the group fold, the BCE term, the sigmoid, the fold of a tile's loss into its row partial and
+//           the finishing kernel of the forwards whose divisor is a device scalar (row partials -> loss, valid-row count, 1 / divisor)
 //   dweight the per-RoI row kernel of the two 1x1 predictors, the ascending list of a class's RoIs and the ordered sum of the
 //           listed rows, the plain per-class kernel (scratch [n][cin + 1] -> dweight [C][cin], dbias [C])
 // Every sum here has ONE order, which the callers' outputs depend on to the bit.
@@ -91,27 +92,95 @@ template <int kWaves> __device__ __forceinline__ void store_tile_loss(float loss
     }
 }
 
-// Rows of the weight gradient of the 1x1 predictors: block (chunk, n) stages u g of its RoI once - kNormed: u g A, with
-// u = up * inv_div - 16 lanes per channel sum it against x over the contiguous pixels, a 16-lane butterfly folds them.
+// One block: the row partials summed in double in a fixed order, the divisor - n hw, or with valid_rows max(1, #{labels in
+// [0, C)}) hw counted here - *loss = sum / divisor and *inv_div = 1 / divisor, the device scalar every backward pass multiplies in.
+// hw: the pixels the loss averages over per RoI (the tail: 4 h w).
+__global__ void __launch_bounds__(256) mask_predict_finish_kernel(const float* __restrict__ rows, int nrows,
+                                                                  const int64_t* __restrict__ labels, int n, int C, int hw,
+                                                                  int valid_rows, float* __restrict__ loss,
+                                                                  float* __restrict__ inv_div) {
+    __shared__ double sh[256];
+    __shared__ int cnt[256];
+    double acc = 0;
+    int k = 0;
+    for (int i = threadIdx.x; i < nrows; i += 256) acc += (double)rows[i];
+    if (valid_rows)
+        for (int i = threadIdx.x; i < n; i += 256) k += (labels[i] >= 0 && labels[i] < C) ? 1 : 0;
+    sh[threadIdx.x] = acc;
+    cnt[threadIdx.x] = k;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            sh[threadIdx.x] += sh[threadIdx.x + o];
+            cnt[threadIdx.x] += cnt[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double rois = valid_rows ? (double)max(1, cnt[0]) : (double)n;
+        const double inv = 1.0 / (rois * (double)hw);
+        *loss = (float)(sh[0] * inv);
+        *inv_div = (float)inv;
+    }
+}
+
+// u = up * inv_div, the factor every backward kernel of the family applies to the stored gradient: two device scalars, either
+// may be absent (an absent one multiplies by 1.0f, which changes no bit).
+__device__ __forceinline__ float upstream_scale(const float* __restrict__ up, const float* __restrict__ inv_div) {
+    return (up ? *up : 1.0f) * (inv_div ? *inv_div : 1.0f);
+}
+
+// The RoI that block y of a (., n) grid works on when the RoIs with a label in [0, C) go first: the y-th of them in ascending
+// index or, for y >= K (their number), the RoI of rank n - 1 - y among the others - one pass, K is never needed.  What is computed
+// for a RoI does not depend on the block that computes it, so no result changes; but the blocks with work are then the first in
+// dispatch order and spread over the CUs as they do on compacted rows, where otherwise a CU may draw several of them and the
+// grid waits for it (profiles/mask_valid_rows.txt).  The labels pass 256 at a time, a ballot and a prefix count rank each one,
+// as in class_roi_list; exactly one RoI matches.  All 256 threads call it; slot: 5 ints of LDS of its own.
+__device__ __forceinline__ int valid_first_roi(const int64_t* __restrict__ labels, int n, int C, int y, int* slot) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int before = 0;                                      // valid labels of the earlier rounds (block-uniform)
+    if (tid == 0) slot[4] = -1;                          // (ordered before the matching thread's write by the round's barriers)
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        const bool in = i < n;
+        const int64_t lb = in ? labels[i] : -1;
+        const bool hit = in && lb >= 0 && lb < C;
+        const unsigned long long b = __ballot(hit);
+        __syncthreads();
+        if (lane == 0) slot[wv] = __popcll(b);
+        __syncthreads();
+        int rank = before;                               // valid labels before i
+        for (int w = 0; w < wv; ++w) rank += slot[w];
+        rank += __popcll(b & ((1ull << lane) - 1ull));
+        if (in && (hit ? rank == y : i - rank == n - 1 - y)) slot[4] = i;
+        before += slot[0] + slot[1] + slot[2] + slot[3];
+    }
+    __syncthreads();
+    return slot[4];
+}
+
+// Rows of the weight gradient of the 1x1 predictors: block (chunk, n) stages u g of its RoI once - kNormed: u g A - with
+// u = up * inv_div; 16 lanes per channel sum it against x over the contiguous pixels, a 16-lane butterfly folds them.
 // scratch[n, c] for c < cin; scratch[n, cin] = u sum_p g (without A: kNormed keeps that copy in a second LDS array), the bias
-// gradient's row.  ca and inv_div are read by kNormed only.
+// gradient's row.  ca is read by kNormed only.  valid_first: block y takes valid_first_roi(y) instead of RoI y.
 template <typename T, int V, bool kNormed>
 __global__ void __launch_bounds__(256) mask_predict_dw_rows_kernel(const T* __restrict__ x, const float* __restrict__ g,
                                                                    const float* __restrict__ ca, const float* __restrict__ up,
                                                                    const float* __restrict__ inv_div,
                                                                    const int64_t* __restrict__ labels, int C, int cin, int hw,
-                                                                   float* __restrict__ scratch) {
+                                                                   int valid_first, float* __restrict__ scratch) {
     __shared__ __attribute__((aligned(16))) float sg[kMaxHW];
+    __shared__ int slot[5];
     float* s0 = sg;                                      // what the bias column sums
     if constexpr (kNormed) {
         __shared__ float unscaled[kMaxHW];
         s0 = unscaled;
     }
-    const int n = blockIdx.y, c0 = blockIdx.x * kChunk, tid = threadIdx.x;
+    const int n = valid_first ? valid_first_roi(labels, gridDim.y, C, blockIdx.y, slot) : blockIdx.y;
+    const int c0 = blockIdx.x * kChunk, tid = threadIdx.x;
     const int64_t lb = labels[n];
     if (lb < 0 || lb >= C) return;                       // no class reads this RoI's row
-    float u = up ? *up : 1.0f;
-    if constexpr (kNormed) u = u * (inv_div ? *inv_div : 1.0f);
+    const float u = upstream_scale(up, inv_div);
     for (int p = tid; p < hw; p += 256) {
         const int64_t o = (int64_t)n * hw + p;
         const float gu = g[o] * u;

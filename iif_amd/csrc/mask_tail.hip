@@ -17,6 +17,9 @@
 //   dup       block (64 ci, 128 columns, RoI range): [Ci][pixels] x [pixels][4 Co] with the same generated operand, one partial
 //             per RoI range, summed in range order; dup_bias from the column sums of the generated operand
 // dweight / dbias: the per-class segment sum of mask_predict_core.h on the rows.  No float atomics: the same bits from call to call.
+// The iif_mask_tail_loss_* entries leave the divisor to the device: g = sigmoid(z) - t is stored undivided,
+// mask_predict_finish_kernel counts the valid rows and writes *inv_div, and rows / df / dup multiply by u = up * inv_div; in
+// their forward, rows and df grids block y takes the y-th valid RoI (valid_first_roi), so the blocks with work come first.
 #include "common.h"
 #include "loss_reduce.h"
 #include "mask_predict_core.h"
@@ -106,19 +109,22 @@ __global__ void __launch_bounds__(256, 2) mask_tail_fwd_kernel(const T* __restri
                                                             const float* __restrict__ upb, const float* __restrict__ weight,
                                                             int64_t ld_w, const float* __restrict__ bias,
                                                             const int64_t* __restrict__ labels, const float* __restrict__ target,
-                                                            int C, int ci, int co, int w, int hw, float inv, float* __restrict__ z,
-                                                            float* __restrict__ g0, float* __restrict__ row_loss, int* status) {
+                                                            int C, int ci, int co, int w, int hw, float inv, int valid_first,
+                                                            float* __restrict__ z, float* __restrict__ g0,
+                                                            float* __restrict__ row_loss, int* status) {
     __shared__ float sA[kSlab * 64];
     __shared__ float zs[4][kPix][4];
     __shared__ float wl[4];
-    const int n = blockIdx.y, p0 = blockIdx.x * kPix, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
+    __shared__ int slot[5];
+    const int n = valid_first ? valid_first_roi(labels, gridDim.y, C, blockIdx.y, slot) : blockIdx.y;
+    const int p0 = blockIdx.x * kPix, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
     const int64_t lb = labels[n];
     const int opx = tid >> 2, oab = tid & 3;             // the output this thread finishes
     const bool live = p0 + opx < hw;
     const int64_t o = live ? (int64_t)n * 4 * hw + out_pixel(p0 + opx, oab, w) : 0;
     if (lb < 0 || lb >= C) {                             // block-uniform
         if (tid == 0) {
-            atomicOr(status, 1);
+            if (status) atomicOr(status, 1);
             if (row_loss) row_loss[(int64_t)n * gridDim.x + blockIdx.x] = 0.f;
         }
         if (live) {
@@ -176,10 +182,10 @@ __global__ void __launch_bounds__(256, 2) mask_tail_fwd_kernel(const T* __restri
     if (row_loss) store_tile_loss<4>(loss, wl, row_loss + (int64_t)n * gridDim.x + blockIdx.x);
 }
 
-// g[n, :] * up of one RoI as sg[p][ab], zeros from pixel hw to pixel `fill`
-__device__ __forceinline__ void stage_g(const float* __restrict__ g, const float* __restrict__ up, int n, int w, int hw, int fill,
-                                        float* sg) {
-    const float u = up ? *up : 1.0f;
+// g[n, :] * u of one RoI as sg[p][ab], zeros from pixel hw to pixel `fill`; u = up * inv_div
+__device__ __forceinline__ void stage_g(const float* __restrict__ g, const float* __restrict__ up, const float* __restrict__ inv_div,
+                                        int n, int w, int hw, int fill, float* sg) {
+    const float u = upstream_scale(up, inv_div);
     for (int i = threadIdx.x; i < fill * 4; i += 256) {
         const int p = i >> 2;
         sg[i] = p < hw ? g[(int64_t)n * 4 * hw + out_pixel(p, i & 3, w)] * u : 0.f;
@@ -191,12 +197,15 @@ __device__ __forceinline__ void stage_g(const float* __restrict__ g, const float
 template <typename T>
 __global__ void __launch_bounds__(256, 2) mask_tail_rows_kernel(const T* __restrict__ f, const float* __restrict__ upw,
                                                              const float* __restrict__ upb, const float* __restrict__ g,
-                                                             const float* __restrict__ up, const int64_t* __restrict__ labels, int C,
-                                                             int ci, int co, int w, int hw, unsigned int* __restrict__ signs,
+                                                             const float* __restrict__ up, const float* __restrict__ inv_div,
+                                                             const int64_t* __restrict__ labels, int C, int ci, int co, int w,
+                                                             int hw, int valid_first, unsigned int* __restrict__ signs,
                                                              float* __restrict__ rows) {
     __shared__ float sA[kSlab * 64];
     __shared__ float sg[kMaxInHW * 4];
-    const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
+    __shared__ int slot[5];
+    const int n = valid_first ? valid_first_roi(labels, gridDim.y, C, blockIdx.y, slot) : blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
     const int64_t lb = labels[n];
     if (lb < 0 || lb >= C) return;                       // g counts as zero there: neither the bits nor the row are read
     const int ld = 4 * co, nsub32 = (hw + 31) / 32;
@@ -209,7 +218,7 @@ __global__ void __launch_bounds__(256, 2) mask_tail_rows_kernel(const T* __restr
         ub[c] = (cidx < co && upb) ? upb[cidx] : 0.f;
     }
     const T* fn = f + (int64_t)n * ci * hw;
-    stage_g(g, up, n, w, hw, hw, sg);                    // (tail_gemm's first barrier publishes it)
+    stage_g(g, up, inv_div, n, w, hw, hw, sg);           // (tail_gemm's first barrier publishes it)
     float stg[kSlab / 4];
     load_slab<T>(fn, ci, hw, 0, 0, stg);
     float rowacc[2] = {0.f, 0.f};
@@ -258,13 +267,16 @@ __global__ void __launch_bounds__(256, 2) mask_tail_rows_kernel(const T* __restr
 // co = 2 t + hf in step t, one MFMA per ab.
 template <typename T>
 __global__ void __launch_bounds__(256) mask_tail_df_kernel(const float* __restrict__ g, const float* __restrict__ up,
-                                                           const float* __restrict__ upw, const float* __restrict__ weight,
-                                                           int64_t ld_w, const int64_t* __restrict__ labels,
+                                                           const float* __restrict__ inv_div, const float* __restrict__ upw,
+                                                           const float* __restrict__ weight, int64_t ld_w,
+                                                           const int64_t* __restrict__ labels,
                                                            const unsigned int* __restrict__ signs, int C, int ci, int co, int w,
-                                                           int hw, T* __restrict__ df) {
+                                                           int hw, int valid_first, T* __restrict__ df) {
     __shared__ __attribute__((aligned(16))) unsigned int sbits[2][4 * kMaxC];
     __shared__ float sw[kMaxC];
-    const int n = blockIdx.y, p0 = blockIdx.x * kPix, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
+    __shared__ int slot[5];
+    const int n = valid_first ? valid_first_roi(labels, gridDim.y, C, blockIdx.y, slot) : blockIdx.y;
+    const int p0 = blockIdx.x * kPix, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
     const int li = lane & 31;
     const int64_t lb = labels[n];
     const int ld = 4 * co, nsub32 = (hw + 31) / 32, nsub = min(2, (hw - p0 + 31) / 32);
@@ -280,7 +292,7 @@ __global__ void __launch_bounds__(256) mask_tail_df_kernel(const float* __restri
     for (int s = 0; s < 2; ++s)
         for (int j = tid; j < fill; j += 256)
             sbits[s][j] = (s < nsub && j < ld) ? signs[((int64_t)n * nsub32 + (p0 >> 5) + s) * ld + j] : 0u;
-    const float u = up ? *up : 1.0f;
+    const float u = upstream_scale(up, inv_div);
     float g4[2][4];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -329,8 +341,9 @@ __global__ void __launch_bounds__(256) mask_tail_df_kernel(const float* __restri
 // partial [splits][ci][4 co], then colsum [splits][4 co]: the column sums of dpre, from which dup_bias follows.
 template <typename T>
 __global__ void __launch_bounds__(256) mask_tail_dup_kernel(const T* __restrict__ f, const float* __restrict__ g,
-                                                            const float* __restrict__ up, const float* __restrict__ weight,
-                                                            int64_t ld_w, const int64_t* __restrict__ labels,
+                                                            const float* __restrict__ up, const float* __restrict__ inv_div,
+                                                            const float* __restrict__ weight, int64_t ld_w,
+                                                            const int64_t* __restrict__ labels,
                                                             const unsigned int* __restrict__ signs, int N, int C, int ci, int co,
                                                             int w, int hw, int per, float* __restrict__ partial,
                                                             float* __restrict__ colsum) {
@@ -351,7 +364,8 @@ __global__ void __launch_bounds__(256) mask_tail_dup_kernel(const T* __restrict_
     auto load = [&](int it) {
         const int n = n0 + it / nslab, q0 = (it % nslab) * 64;
         const T* fn = f + ((int64_t)n * ci + ci0) * hw + q0 + spx;
-        const bool pok = q0 + spx < hw;
+        const int64_t lb = labels[n];
+        const bool pok = q0 + spx < hw && lb >= 0 && lb < C;     // f of an RoI outside is not read: its round is skipped below
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) {
             const int c = rr * 4 + sc0;
@@ -364,7 +378,7 @@ __global__ void __launch_bounds__(256) mask_tail_dup_kernel(const T* __restrict_
         const int64_t lb = labels[n];
         const bool valid = lb >= 0 && lb < C;            // block-uniform; an RoI outside contributes nothing
         __syncthreads();                                 // the previous round's reads of sA (and sg) are done
-        if (q0 == 0 && valid) stage_g(g, up, n, w, hw, nsub32 * 32, sg);
+        if (q0 == 0 && valid) stage_g(g, up, inv_div, n, w, hw, nsub32 * 32, sg);
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) sA[(rr * 4 + sc0) * 65 + spx] = stg[rr];
         __syncthreads();
@@ -423,6 +437,104 @@ inline bool geometry_ok(int n, int c, int ci, int co, int h, int w) {
     return rois_ok(n, c) && dim_ok(ci, kMaxC) && dim_ok(co, kMaxC) && h >= 1 && w >= 1 && (int64_t)h * w <= kMaxInHW;
 }
 
+// The forward of both entries.  inv_div == nullptr: the divisor 4 n hw is fixed here, g0 is stored divided and the row partials
+// go through rows_reduce_kernel; otherwise g0 is stored undivided and mask_predict_finish_kernel writes *loss and *inv_div.
+// The entries with a device divisor are the ones that meet padded rows: they (inv_div != nullptr, here and in the rows and df
+// launchers) put the valid RoIs first in the grid (valid_first_roi).
+int tail_fwd(const void* f, int dtype, const float* up_weight, const float* up_bias, const float* weight, int64_t ld_w,
+             const float* bias, const int64_t* labels, const float* target, int n, int c, int ci, int co, int h, int w, int valid_rows,
+             float* z, float* g0, float* row_loss, float* loss, float* inv_div, int* status, void* stream) {
+    hipStream_t st = as_stream(stream);
+    const int hw = h * w, tiles = (hw + kPix - 1) / kPix;
+    const dim3 grid(tiles, n);
+    const double invd = 1.0 / ((double)n * 4.0 * (double)hw);
+    const float inv = inv_div ? 1.0f : (float)invd;
+    float* rows = target ? row_loss : nullptr;
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_tail_fwd_kernel<T>), grid, dim3(256), 0, st, (const T*)f, up_weight, up_bias, weight, ld_w, bias,
+                           labels, target, c, ci, co, w, hw, inv, inv_div ? 1 : 0, z, g0, rows, status);
+    });
+    IIF_LAUNCH_CHECK();
+    if (!target) return IIF_OK;
+    if (inv_div)
+        hipLaunchKernelGGL(mask_predict_finish_kernel, dim3(1), dim3(256), 0, st, row_loss, n * tiles, labels, n, c, 4 * hw,
+                           valid_rows ? 1 : 0, loss, inv_div);
+    else
+        hipLaunchKernelGGL(rows_reduce_kernel<double>, dim3(1), dim3(256), 0, st, row_loss, n * tiles, invd, loss);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+int tail_bwd_rows(const void* f, int dtype, const float* up_weight, const float* up_bias, const float* g, const float* up,
+                  const float* inv_div, const int64_t* labels, int n, int c, int ci, int co, int h, int w, unsigned int* signs,
+                  float* rows, void* stream) {
+    if (!geometry_ok(n, c, ci, co, h, w) || !dtype_ok(dtype)) return IIF_EINVAL;
+    if (!f || !up_weight || !g || !labels || !signs) return IIF_EINVAL;
+    if (n == 0) return IIF_OK;
+    hipStream_t st = as_stream(stream);
+    const dim3 grid((4 * co + 2 * kCols - 1) / (2 * kCols), n);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_tail_rows_kernel<T>), grid, dim3(256), 0, st, (const T*)f, up_weight, up_bias, g, up, inv_div, labels,
+                           c, ci, co, w, h * w, inv_div ? 1 : 0, signs, rows);
+    });
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+int tail_bwd_input(const float* g, const float* up, const float* inv_div, const float* up_weight, const float* weight, int64_t ld_w,
+                   const int64_t* labels, const unsigned int* signs, int n, int c, int ci, int co, int h, int w, void* df, int dtype,
+                   void* stream) {
+    if (!geometry_ok(n, c, ci, co, h, w) || ld_w < co || !dtype_ok(dtype)) return IIF_EINVAL;
+    if (!g || !up_weight || !weight || !labels || !signs || !df) return IIF_EINVAL;
+    if ((uintptr_t)up_weight % 16) return IIF_EUNSUPPORTED;          // rows of 4 co floats are read 16 bytes at a time
+    if (n == 0) return IIF_OK;
+    hipStream_t st = as_stream(stream);
+    const int hw = h * w;
+    const dim3 grid((hw + kPix - 1) / kPix, n);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_tail_df_kernel<T>), grid, dim3(256), 0, st, g, up, inv_div, up_weight, weight, ld_w, labels, signs, c,
+                           ci, co, w, hw, inv_div ? 1 : 0, (T*)df);
+    });
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
+int tail_splits(int n, int ci, int co) {
+    if (n < 1 || ci < 1 || co < 1) return 0;
+    const int tiles = ((ci + 63) / 64) * ((4 * co + kCols - 1) / kCols);
+    int s = 512 / tiles;
+    s = s < 1 ? 1 : (s > 16 ? 16 : s);
+    s = s > n ? n : s;
+    const int per = (n + s - 1) / s;
+    return (n + per - 1) / per;
+}
+
+int tail_bwd_params(const void* f, int dtype, const float* g, const float* up, const float* inv_div, const float* weight, int64_t ld_w,
+                    const int64_t* labels, const unsigned int* signs, int n, int c, int ci, int co, int h, int w, float* partial,
+                    float* dup_weight, float* dup_bias, void* stream) {
+    if (!geometry_ok(n, c, ci, co, h, w) || ld_w < co || !dtype_ok(dtype)) return IIF_EINVAL;
+    if (!f || !g || !weight || !labels || !signs || !partial || (!dup_weight && !dup_bias)) return IIF_EINVAL;
+    if (n == 0) return IIF_OK;
+    hipStream_t st = as_stream(stream);
+    const int splits = tail_splits(n, ci, co), per = (n + splits - 1) / splits;
+    const dim3 grid((ci + 63) / 64, (4 * co + kCols - 1) / kCols, splits);
+    float* colsum = partial + (int64_t)splits * ci * 4 * co;
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mask_tail_dup_kernel<T>), grid, dim3(256), 0, st, (const T*)f, g, up, inv_div, weight, ld_w, labels, signs,
+                           n, c, ci, co, w, h * w, per, partial, colsum);
+    });
+    IIF_LAUNCH_CHECK();
+    const int64_t total = (int64_t)ci * 4 * co + co;
+    hipLaunchKernelGGL(mask_tail_dup_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, partial, colsum, splits, ci,
+                       co, dup_weight, dup_bias);
+    IIF_LAUNCH_CHECK();
+    return IIF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -434,91 +546,29 @@ int iif_mask_tail_fwd(const void* f, int dtype, const float* up_weight, const fl
     if (!f || !up_weight || !weight || !labels || !status || (!z && !target)) return IIF_EINVAL;
     if (target ? (!row_loss || !loss) : (g0 != nullptr)) return IIF_EINVAL;
     if (n == 0) return IIF_OK;
-    hipStream_t st = as_stream(stream);
-    const int hw = h * w, tiles = (hw + kPix - 1) / kPix;
-    const dim3 grid(tiles, n);
-    const double invd = 1.0 / ((double)n * 4.0 * (double)hw);
-    float* rows = target ? row_loss : nullptr;
-    dispatch_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((mask_tail_fwd_kernel<T>), grid, dim3(256), 0, st, (const T*)f, up_weight, up_bias, weight, ld_w, bias,
-                           labels, target, c, ci, co, w, hw, (float)invd, z, g0, rows, status);
-    });
-    IIF_LAUNCH_CHECK();
-    if (target) {
-        hipLaunchKernelGGL(rows_reduce_kernel<double>, dim3(1), dim3(256), 0, st, row_loss, n * tiles, invd, loss);
-        IIF_LAUNCH_CHECK();
-    }
-    return IIF_OK;
+    return tail_fwd(f, dtype, up_weight, up_bias, weight, ld_w, bias, labels, target, n, c, ci, co, h, w, 0, z, g0, row_loss, loss,
+                    nullptr, status, stream);
 }
 
 int iif_mask_tail_bwd_rows(const void* f, int dtype, const float* up_weight, const float* up_bias, const float* g, const float* up,
                            const int64_t* labels, int n, int c, int ci, int co, int h, int w, unsigned int* signs, float* rows,
                            void* stream) {
-    if (!geometry_ok(n, c, ci, co, h, w) || !dtype_ok(dtype)) return IIF_EINVAL;
-    if (!f || !up_weight || !g || !labels || !signs) return IIF_EINVAL;
-    if (n == 0) return IIF_OK;
-    hipStream_t st = as_stream(stream);
-    const dim3 grid((4 * co + 2 * kCols - 1) / (2 * kCols), n);
-    dispatch_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((mask_tail_rows_kernel<T>), grid, dim3(256), 0, st, (const T*)f, up_weight, up_bias, g, up, labels, c, ci,
-                           co, w, h * w, signs, rows);
-    });
-    IIF_LAUNCH_CHECK();
-    return IIF_OK;
+    return tail_bwd_rows(f, dtype, up_weight, up_bias, g, up, nullptr, labels, n, c, ci, co, h, w, signs, rows, stream);
 }
 
 int iif_mask_tail_bwd_input(const float* g, const float* up, const float* up_weight, const float* weight, int64_t ld_w,
                             const int64_t* labels, const unsigned int* signs, int n, int c, int ci, int co, int h, int w, void* df,
                             int dtype, void* stream) {
-    if (!geometry_ok(n, c, ci, co, h, w) || ld_w < co || !dtype_ok(dtype)) return IIF_EINVAL;
-    if (!g || !up_weight || !weight || !labels || !signs || !df) return IIF_EINVAL;
-    if ((uintptr_t)up_weight % 16) return IIF_EUNSUPPORTED;          // rows of 4 co floats are read 16 bytes at a time
-    if (n == 0) return IIF_OK;
-    hipStream_t st = as_stream(stream);
-    const int hw = h * w;
-    const dim3 grid((hw + kPix - 1) / kPix, n);
-    dispatch_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((mask_tail_df_kernel<T>), grid, dim3(256), 0, st, g, up, up_weight, weight, ld_w, labels, signs, c, ci, co,
-                           w, hw, (T*)df);
-    });
-    IIF_LAUNCH_CHECK();
-    return IIF_OK;
+    return tail_bwd_input(g, up, nullptr, up_weight, weight, ld_w, labels, signs, n, c, ci, co, h, w, df, dtype, stream);
 }
 
-int iif_mask_tail_splits(int n, int ci, int co) {
-    if (n < 1 || ci < 1 || co < 1) return 0;
-    const int tiles = ((ci + 63) / 64) * ((4 * co + kCols - 1) / kCols);
-    int s = 512 / tiles;
-    s = s < 1 ? 1 : (s > 16 ? 16 : s);
-    s = s > n ? n : s;
-    const int per = (n + s - 1) / s;
-    return (n + per - 1) / per;
-}
+int iif_mask_tail_splits(int n, int ci, int co) { return tail_splits(n, ci, co); }
 
 int iif_mask_tail_bwd_params(const void* f, int dtype, const float* g, const float* up, const float* weight, int64_t ld_w,
                              const int64_t* labels, const unsigned int* signs, int n, int c, int ci, int co, int h, int w,
                              float* partial, float* dup_weight, float* dup_bias, void* stream) {
-    if (!geometry_ok(n, c, ci, co, h, w) || ld_w < co || !dtype_ok(dtype)) return IIF_EINVAL;
-    if (!f || !g || !weight || !labels || !signs || !partial || (!dup_weight && !dup_bias)) return IIF_EINVAL;
-    if (n == 0) return IIF_OK;
-    hipStream_t st = as_stream(stream);
-    const int splits = iif_mask_tail_splits(n, ci, co), per = (n + splits - 1) / splits;
-    const dim3 grid((ci + 63) / 64, (4 * co + kCols - 1) / kCols, splits);
-    float* colsum = partial + (int64_t)splits * ci * 4 * co;
-    dispatch_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((mask_tail_dup_kernel<T>), grid, dim3(256), 0, st, (const T*)f, g, up, weight, ld_w, labels, signs, n, c,
-                           ci, co, w, h * w, per, partial, colsum);
-    });
-    IIF_LAUNCH_CHECK();
-    const int64_t total = (int64_t)ci * 4 * co + co;
-    hipLaunchKernelGGL(mask_tail_dup_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, partial, colsum, splits, ci,
-                       co, dup_weight, dup_bias);
-    IIF_LAUNCH_CHECK();
-    return IIF_OK;
+    return tail_bwd_params(f, dtype, g, up, nullptr, weight, ld_w, labels, signs, n, c, ci, co, h, w, partial, dup_weight, dup_bias,
+                           stream);
 }
 
 int iif_mask_tail_bwd_classes(const float* rows, const int64_t* labels, int n, int c, int co, float* dweight, float* dbias,
@@ -529,6 +579,35 @@ int iif_mask_tail_bwd_classes(const float* rows, const int64_t* labels, int n, i
     hipLaunchKernelGGL(mask_predict_dw_classes_kernel, dim3(c), dim3(256), 0, as_stream(stream), rows, labels, n, co, dweight, dbias);
     IIF_LAUNCH_CHECK();
     return IIF_OK;
+}
+
+int iif_mask_tail_loss_fwd(const void* f, int dtype, const float* up_weight, const float* up_bias, const float* weight, int64_t ld_w,
+                           const float* bias, const int64_t* labels, const float* target, int n, int c, int ci, int co, int h, int w,
+                           int valid_rows, float* g, float* row_loss, float* loss, float* inv_div, void* stream) {
+    if (!geometry_ok(n, c, ci, co, h, w) || ld_w < co || !dtype_ok(dtype)) return IIF_EINVAL;
+    if (!f || !up_weight || !weight || !labels || !target || !row_loss || !loss || !inv_div) return IIF_EINVAL;
+    if (n == 0) return IIF_OK;
+    return tail_fwd(f, dtype, up_weight, up_bias, weight, ld_w, bias, labels, target, n, c, ci, co, h, w, valid_rows, nullptr, g,
+                    row_loss, loss, inv_div, nullptr, stream);
+}
+
+int iif_mask_tail_loss_bwd_rows(const void* f, int dtype, const float* up_weight, const float* up_bias, const float* g,
+                                const float* up, const float* inv_div, const int64_t* labels, int n, int c, int ci, int co, int h,
+                                int w, unsigned int* signs, float* rows, void* stream) {
+    return tail_bwd_rows(f, dtype, up_weight, up_bias, g, up, inv_div, labels, n, c, ci, co, h, w, signs, rows, stream);
+}
+
+int iif_mask_tail_loss_bwd_input(const float* g, const float* up, const float* inv_div, const float* up_weight, const float* weight,
+                                 int64_t ld_w, const int64_t* labels, const unsigned int* signs, int n, int c, int ci, int co, int h,
+                                 int w, void* df, int dtype, void* stream) {
+    return tail_bwd_input(g, up, inv_div, up_weight, weight, ld_w, labels, signs, n, c, ci, co, h, w, df, dtype, stream);
+}
+
+int iif_mask_tail_loss_bwd_params(const void* f, int dtype, const float* g, const float* up, const float* inv_div,
+                                  const float* weight, int64_t ld_w, const int64_t* labels, const unsigned int* signs, int n, int c,
+                                  int ci, int co, int h, int w, float* partial, float* dup_weight, float* dup_bias, void* stream) {
+    return tail_bwd_params(f, dtype, g, up, inv_div, weight, ld_w, labels, signs, n, c, ci, co, h, w, partial, dup_weight, dup_bias,
+                           stream);
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 // class row is exactly zero and the [N, C, H, W] logits are never formed.  With l = labels[n], T = tempearture, q = power,
 //   r = |x[n, :, p]|_2, rho = |w[l, :]|_2, s_x = T / (r^q + eps), s_w = 1 / (rho^q + eps), what = w[l] s_w, d = <what, x[n, :, p]>
 //   forward   z[n, p] = s_x d + bias[l]; with targets the BCE rows, the loss, g = sigmoid(z) - t (UNSCALED: the divisor is a
-//             device scalar, see the finish kernel) and the two coefficients A = s_x, B = d T q r^(q-2) / (r^q + eps)^2 (0 at r = 0)
+//             device scalar, see mask_predict_finish_kernel) and the two coefficients A = s_x, B = d T q r^(q-2) / (r^q + eps)^2 (0 at r = 0)
 //   dx        g (A what[c] - B x[n, c, p]): reads x once, writes dx once
 //   dweight   per-RoI rows sum_p g A x (+ sum_p g) into a scratch [N, Cin + 1]; one block per class adds the rows of its RoIs in
 //             ascending RoI index and applies the backward of the row normalisation; EVERY row of dweight / dbias is written
@@ -100,36 +100,7 @@ __global__ void __launch_bounds__(256) normed_predict_fwd_kernel(const T* __rest
     if (row_loss) store_tile_loss<kTile / 64>(loss, wl, row_loss + (int64_t)n * gridDim.x + blockIdx.x);
 }
 
-// One block: the row partials summed in double in a fixed order, the divisor - n hw, or with valid_rows max(1, #{labels in
-// [0, C)}) hw counted here - *loss = sum / divisor and *inv_div = 1 / divisor, the device scalar both backward passes multiply in.
-__global__ void __launch_bounds__(256) normed_predict_finish_kernel(const float* __restrict__ rows, int nrows,
-                                                                    const int64_t* __restrict__ labels, int n, int C, int hw,
-                                                                    int valid_rows, float* __restrict__ loss,
-                                                                    float* __restrict__ inv_div) {
-    __shared__ double sh[256];
-    __shared__ int cnt[256];
-    double acc = 0;
-    int k = 0;
-    for (int i = threadIdx.x; i < nrows; i += 256) acc += (double)rows[i];
-    if (valid_rows)
-        for (int i = threadIdx.x; i < n; i += 256) k += (labels[i] >= 0 && labels[i] < C) ? 1 : 0;
-    sh[threadIdx.x] = acc;
-    cnt[threadIdx.x] = k;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            sh[threadIdx.x] += sh[threadIdx.x + o];
-            cnt[threadIdx.x] += cnt[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double rois = valid_rows ? (double)max(1, cnt[0]) : (double)n;
-        const double inv = 1.0 / (rois * (double)hw);
-        *loss = (float)(sh[0] * inv);
-        *inv_div = (float)inv;
-    }
-}
+// The loss, the valid-row count and the divisor: mask_predict_finish_kernel of mask_predict_core.h.
 
 // dx = u g (A what[c] - B x): block (chunk, n) reads and writes the contiguous kChunk * hw elements of channels
 // [c0, c0 + kChunk) of RoI n; u = up * inv_div (device scalars, either may be absent).  A RoI with a label outside [0, C) gets
@@ -158,7 +129,7 @@ __global__ void __launch_bounds__(256) normed_predict_dx_kernel(const T* __restr
         for (int i = tid; i < total; i += 256) VTn<T, V>::store(out + (int64_t)i * V, v);
         return;
     }
-    const float u = (up ? *up : 1.0f) * (inv_div ? *inv_div : 1.0f);
+    const float u = upstream_scale(up, inv_div);
     for (int p = tid; p < hw; p += 256) {
         const int64_t o = (int64_t)n * hw + p;
         const float gu = g[o] * u;
@@ -244,7 +215,7 @@ int iif_normed_mask_predict_fwd(const void* x, int dtype, const float* weight, i
     });
     IIF_LAUNCH_CHECK();
     if (target) {
-        hipLaunchKernelGGL(normed_predict_finish_kernel, dim3(1), dim3(256), 0, st, row_loss, n * tiles, labels, n, c, hw,
+        hipLaunchKernelGGL(mask_predict_finish_kernel, dim3(1), dim3(256), 0, st, row_loss, n * tiles, labels, n, c, hw,
                            valid_rows ? 1 : 0, loss, inv_div);
         IIF_LAUNCH_CHECK();
     }
@@ -281,7 +252,7 @@ int iif_normed_mask_predict_bwd_weight(const void* x, int dtype, const float* g,
     dispatch_row(dtype, wide_ok(x, dtype, hw), [&](auto t, auto v) {
         using T = decltype(t);
         hipLaunchKernelGGL((mask_predict_dw_rows_kernel<T, decltype(v)::value, true>), grid, dim3(256), 0, st, (const T*)x, g, coef_a,
-                           up, inv_div, labels, c, cin, hw, scratch);
+                           up, inv_div, labels, c, cin, hw, 0, scratch);
     });
     IIF_LAUNCH_CHECK();
     hipLaunchKernelGGL(normed_predict_dw_classes_kernel, dim3(c), dim3(256), 0, st, scratch, labels, weight, ld_w, n, cin, power, eps,

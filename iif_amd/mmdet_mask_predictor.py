@@ -10,6 +10,7 @@ The label is known before the mask head runs: ``pos_labels`` in ``_mask_forward_
 
   ``class_mask_logits(x, weight, bias, labels)``            the selected logits ``[N, 1, H, W]``, differentiable
   ``class_mask_loss(x, weight, bias, labels, targets)``     the predictor fused with ``mask_cross_entropy``, shape ``(1,)``
+                                                            (``valid_rows=True``: the padded RoI pipeline's divisor)
   ``ClassSelectedMaskPredictor``                            the module that stands where ``conv_logits`` stood
 
 Test end: the ``[N, 1, h, w]`` logits go into ``mmdet_mask_loss.paste_masks`` / ``get_seg_masks`` with ``class_agnostic=True``
@@ -18,8 +19,11 @@ Test end: the ``[N, 1, h, w]`` logits go into ``mmdet_mask_loss.paste_masks`` / 
 ``x`` is float32 or bfloat16 (``dx`` comes back in that dtype), ``weight`` / ``bias`` float32.  The kernels read ``x`` as
 NCHW-contiguous: a non-contiguous or ``channels_last`` ``x`` costs one layout copy.  ``weight`` rows are read through their
 stride (a row-strided view is read in place).  Every sum is fp32 in a fixed order without float atomics: the same bits from call
-to call.  A label outside ``[0, C)`` contributes zero loss, a zero ``dx`` slice and nothing to ``dweight`` / ``dbias``; the
-divisor stays ``N * H * W``.  Limits: ``Cin <= 2048``, ``H * W <= 4096``, ``N <= 65535``.
+to call.  A label outside ``[0, C)`` contributes zero loss, a zero ``dx`` slice and nothing to ``dweight`` / ``dbias``, and that
+RoI's ``x`` and targets are not read.  The divisor is ``N * H * W``; with ``valid_rows=True`` it is ``max(1, K) * H * W``, ``K``
+the number of RoIs with a label in ``[0, C)``, counted on the device: a padded row of the padded RoI pipeline (image index -1,
+label ``num_classes``) then neither adds a term nor dilutes the loss, and nothing is read back.  ``K = 0``: the loss is exactly 0
+and every gradient exact zeros.  Limits: ``Cin <= 2048``, ``H * W <= 4096``, ``N <= 65535``.
 
 Deliberately not offered: the full ``[N, C, H, W]`` logits (``to_conv()`` gives the convolution back), a ``predictor_cfg`` other
 than a plain convolution (``NormedConv2d``: mmdet_normed_mask_predictor.py), ``class_weight``, float16 and a native ``channels_last`` kernel.  The deconv + ReLU in front are fused
@@ -83,24 +87,35 @@ def _ld(weight):
     return weight.stride(0) if weight.size(0) > 1 else weight.size(1)
 
 
-def _backward(x, xmeta, weight, labels, g, up, n, c, cin, hw, need_x, need_w, need_b):
+def _backward(x, xmeta, weight, labels, g, up, n, c, cin, hw, need_x, need_w, need_b, inv=None):
     """The two backward entries on the compact gradient g [N, HW] (times the device scalar `up`, or 1).  xmeta: shape and dtype
-    of x, which itself is only there when dweight / dbias are asked for."""
+    of x, which itself is only there when dweight / dbias are asked for.  inv: the device scalar 1 / divisor of a forward that
+    stored g undivided (valid_rows); the kernels multiply it in."""
     L, st = _lib.lib(), _lib.stream_ptr()
     dx = dw = db = None
     if need_x:
         dx = torch.empty(xmeta[0], dtype=xmeta[1], device=g.device)
-        _lib.check(L.iif_mask_predict_bwd_input(_lib.ptr(g), _lib.ptr(up), _lib.ptr(weight), _ld(weight), _lib.ptr(labels), n, c, cin,
-                                                hw, _lib.ptr(dx), _lib.dtype_code(dx), st), "iif_mask_predict_bwd_input")
+        if inv is None:
+            _lib.check(L.iif_mask_predict_bwd_input(_lib.ptr(g), _lib.ptr(up), _lib.ptr(weight), _ld(weight), _lib.ptr(labels), n, c,
+                                                    cin, hw, _lib.ptr(dx), _lib.dtype_code(dx), st), "iif_mask_predict_bwd_input")
+        else:
+            _lib.check(L.iif_mask_predict_loss_bwd_input(_lib.ptr(g), _lib.ptr(up), _lib.ptr(inv), _lib.ptr(weight), _ld(weight),
+                                                         _lib.ptr(labels), n, c, cin, hw, _lib.ptr(dx), _lib.dtype_code(dx), st),
+                       "iif_mask_predict_loss_bwd_input")
     if need_w or need_b:
         scratch = torch.empty((n, cin + 1), dtype=torch.float32, device=g.device)
         if need_w:
             dw = torch.empty((c, cin), dtype=torch.float32, device=g.device)
         if need_b:
             db = torch.empty(c, dtype=torch.float32, device=g.device)
-        _lib.check(L.iif_mask_predict_bwd_weight(_lib.ptr(x), _lib.dtype_code(x), _lib.ptr(g), _lib.ptr(up), _lib.ptr(labels), n, c,
-                                                 cin, hw, _lib.ptr(scratch), _lib.ptr(dw), _lib.ptr(db), st),
-                   "iif_mask_predict_bwd_weight")
+        if inv is None:
+            _lib.check(L.iif_mask_predict_bwd_weight(_lib.ptr(x), _lib.dtype_code(x), _lib.ptr(g), _lib.ptr(up), _lib.ptr(labels), n,
+                                                     c, cin, hw, _lib.ptr(scratch), _lib.ptr(dw), _lib.ptr(db), st),
+                       "iif_mask_predict_bwd_weight")
+        else:
+            _lib.check(L.iif_mask_predict_loss_bwd_weight(_lib.ptr(x), _lib.dtype_code(x), _lib.ptr(g), _lib.ptr(up), _lib.ptr(inv),
+                                                          _lib.ptr(labels), n, c, cin, hw, _lib.ptr(scratch), _lib.ptr(dw),
+                                                          _lib.ptr(db), st), "iif_mask_predict_loss_bwd_weight")
     return dx, dw, db
 
 
@@ -167,7 +182,7 @@ class _Logits(torch.autograd.Function):
 
 class _Loss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, labels, targets, wshape):
+    def forward(ctx, x, weight, bias, labels, targets, wshape, valid_rows):
         xc, w2, b, lb, n, c, cin, hw = _prep(x.detach(), weight.detach(), None if bias is None else bias.detach(), labels)
         if targets.numel() != n * hw:
             raise ValueError("targets must be [N, H, W] (got %s for x %s)" % (tuple(targets.shape), tuple(x.shape)))
@@ -178,24 +193,32 @@ class _Loss(torch.autograd.Function):
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         rows = torch.empty(n * ((hw + _TILE - 1) // _TILE), dtype=torch.float32, device=dev)
         g0 = torch.empty((n, hw), dtype=torch.float32, device=dev) if need_x or need_w or need_b else None
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().iif_mask_predict_fwd(_lib.ptr(xc), _lib.dtype_code(xc), _lib.ptr(w2), _ld(w2), _lib.ptr(b), _lib.ptr(lb),
-                                                   _lib.ptr(t), n, c, cin, hw, 0, _lib.ptr(g0), _lib.ptr(rows), _lib.ptr(loss),
-                                                   _lib.ptr(status), _lib.stream_ptr()), "iif_mask_predict_fwd")
-        ctx.save_for_backward(xc if need_w or need_b else None, w2 if need_x else None, lb, g0)
+        inv = None
+        if valid_rows:                                   # g0 undivided; the divisor is the device scalar `inv`
+            inv = torch.empty(1, dtype=torch.float32, device=dev)
+            _lib.check(_lib.lib().iif_mask_predict_loss_fwd(_lib.ptr(xc), _lib.dtype_code(xc), _lib.ptr(w2), _ld(w2), _lib.ptr(b),
+                                                            _lib.ptr(lb), _lib.ptr(t), n, c, cin, hw, 1, _lib.ptr(g0), _lib.ptr(rows),
+                                                            _lib.ptr(loss), _lib.ptr(inv), _lib.stream_ptr()),
+                       "iif_mask_predict_loss_fwd")
+        else:
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            _lib.check(_lib.lib().iif_mask_predict_fwd(_lib.ptr(xc), _lib.dtype_code(xc), _lib.ptr(w2), _ld(w2), _lib.ptr(b),
+                                                       _lib.ptr(lb), _lib.ptr(t), n, c, cin, hw, 0, _lib.ptr(g0), _lib.ptr(rows),
+                                                       _lib.ptr(loss), _lib.ptr(status), _lib.stream_ptr()), "iif_mask_predict_fwd")
+        ctx.save_for_backward(xc if need_w or need_b else None, w2 if need_x else None, lb, g0, inv if g0 is not None else None)
         ctx.dims = (n, c, cin, hw, (tuple(x.shape), x.dtype), wshape)
         return loss
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gl):
-        xc, w2, lb, g0 = ctx.saved_tensors
+        xc, w2, lb, g0, inv = ctx.saved_tensors
         n, c, cin, hw, xmeta, wshape = ctx.dims
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         if g0 is None or not (need_x or need_w or need_b):
-            return None, None, None, None, None, None
-        dx, dw, db = _backward(xc, xmeta, w2, lb, g0, _up(gl), n, c, cin, hw, need_x, need_w, need_b)
-        return dx, None if dw is None else dw.reshape(wshape), db, None, None, None
+            return (None,) * 7
+        dx, dw, db = _backward(xc, xmeta, w2, lb, g0, _up(gl), n, c, cin, hw, need_x, need_w, need_b, inv)
+        return (dx, None if dw is None else dw.reshape(wshape), db) + (None,) * 4
 
 
 def class_mask_logits(x, weight, bias, labels):
@@ -209,17 +232,26 @@ def class_mask_logits(x, weight, bias, labels):
     return _Logits.apply(x, weight, bias, labels, tuple(weight.shape))
 
 
-def class_mask_loss(x, weight, bias, labels, targets):
+def class_mask_loss(x, weight, bias, labels, targets, valid_rows=False):
     """``mask_cross_entropy(conv_logits(x), targets, labels)`` (cross_entropy_loss.py:114-162) -> shape ``(1,)``, as ONE autograd
     node: the forward is one pass over ``x`` that leaves the loss and the compact gradient ``[N, H * W]``, the backward writes
     ``dx`` from it without reading ``x`` and sums ``dweight`` / ``dbias`` in a fixed order.  Only what ``requires_grad`` asks for
-    is computed and stored; the upstream gradient is applied on the device.  ``targets [N, H, W]``.  ``N == 0``: a zero connected
-    to ``x``, ``weight`` and ``bias`` (the reference's ``mask_pred.sum()``).  A non-contiguous or ``channels_last`` ``x`` costs one
-    layout copy."""
+    is computed and stored; the upstream gradient is applied on the device.  ``targets [N, H, W]``.  ``valid_rows``: divide by
+    ``max(1, #{n: 0 <= labels[n] < C}) * H * W`` instead of ``N * H * W``, the count taken on the device; the compact gradient is
+    then kept undivided and the backward kernels apply the divisor, in as many launches as without it.  ``N == 0``: a zero
+    connected to ``x``, ``weight`` and ``bias`` (the reference's ``mask_pred.sum()``).  A non-contiguous or ``channels_last`` ``x``
+    costs one layout copy."""
     if _is_empty(x):
         _prep(x, weight, bias, labels)
         return _empty_result(x, (weight, bias), (1,))
-    return _Loss.apply(x, weight, bias, labels, targets, tuple(weight.shape))
+    return _Loss.apply(x, weight, bias, labels, targets, tuple(weight.shape), bool(valid_rows))
+
+
+def _agnostic_labels(labels, num_classes, valid_rows):
+    """The label mapping of a ``class_agnostic`` head, shared with ``FusedMaskHeadTail``."""
+    if valid_rows:
+        return torch.where((labels >= 0) & (labels < num_classes), torch.zeros_like(labels), torch.full_like(labels, -1))
+    return torch.zeros_like(labels)
 
 
 class _SelectedPredictor(nn.Module):
@@ -239,9 +271,10 @@ class _SelectedPredictor(nn.Module):
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
         nn.init.constant_(self.bias, 0)
 
-    def _labels(self, labels):
-        """The weight row of each RoI: its label, or row 0 of a ``class_agnostic`` head."""
-        return torch.zeros_like(labels) if self.class_agnostic else labels
+    def _labels(self, labels, valid_rows=False):
+        """The weight row of each RoI: its label, or row 0 of a ``class_agnostic`` head.  With ``valid_rows`` a ``class_agnostic``
+        head keeps a padded row apart: row 0 for a label in ``[0, num_classes)``, the invalid -1 for any other."""
+        return _agnostic_labels(labels, self.num_classes, valid_rows) if self.class_agnostic else labels
 
     @classmethod
     def _from_conv(cls, conv, class_agnostic, **kwargs):
@@ -268,9 +301,10 @@ class ClassSelectedMaskPredictor(_SelectedPredictor):
         """The selected logits ``[N, 1, H, W]``: ``pos_labels`` in training, ``det_labels`` at test time."""
         return class_mask_logits(x, self.weight, self.bias, self._labels(labels))
 
-    def loss(self, x, labels, mask_targets):
-        """``FCNMaskHead.loss`` (fcn_mask_head.py:147-177) on the head's features instead of its logits."""
-        return dict(loss_mask=class_mask_loss(x, self.weight, self.bias, self._labels(labels), mask_targets))
+    def loss(self, x, labels, mask_targets, valid_rows=False):
+        """``FCNMaskHead.loss`` (fcn_mask_head.py:147-177) on the head's features instead of its logits.  ``valid_rows``: the
+        rows of the padded RoI pipeline (label ``num_classes`` = padding), divided by the device-counted number of real rows."""
+        return dict(loss_mask=class_mask_loss(x, self.weight, self.bias, self._labels(labels, valid_rows), mask_targets, valid_rows))
 
     @classmethod
     def from_conv(cls, conv, class_agnostic=None):

@@ -25,8 +25,11 @@ atomics: the same bits from call to call.
 
 ``f`` is float32 or bfloat16 (widened exactly; ``df`` comes back in that dtype), the parameters float32.  A non-contiguous or
 ``channels_last`` ``f`` costs one layout copy.  ``weight`` rows are read through their stride.  A label outside ``[0, C)``
-contributes zero loss, a zero ``df`` slice and nothing to any parameter gradient; the divisor stays ``N * 4hw``.  Limits: scale
-factor 2, ``1 <= Ci, Co <= 1024``, ``h * w <= 1024``, ``N <= 65535``.
+contributes zero loss, a zero ``df`` slice and nothing to any parameter gradient, and that RoI's ``f`` and targets are not read.
+The divisor is ``N * 4hw``; with ``valid_rows=True`` it is ``max(1, K) * 4hw``, ``K`` the number of RoIs with a label in
+``[0, C)``, counted on the device (the padded RoI pipeline: a padded row neither adds a term nor dilutes the loss, nothing is read
+back; ``K = 0`` gives exactly 0 and exact zero gradients).  Limits: scale factor 2, ``1 <= Ci, Co <= 1024``, ``h * w <= 1024``,
+``N <= 65535``.
 
 Not offered: the four 3x3 ``convs`` in front, ``nearest`` / ``bilinear`` / ``carafe`` upsampling, other scale factors, float16,
 bf16 MFMA arithmetic, ``class_weight``, a native ``channels_last`` kernel.
@@ -36,7 +39,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .mmdet_mask_predictor import _TILE, _copy_params, _empty_result, _is_empty, _is_plain_1x1, _ld, _needs, _up
+from .mmdet_mask_predictor import _TILE, _agnostic_labels, _copy_params, _empty_result, _is_empty, _is_plain_1x1, _ld, _needs, _up
 
 _MAX_C, _MAX_HW, _MAX_N = 1024, 1024, 65535
 
@@ -92,12 +95,12 @@ def _prep(f, up_weight, up_bias, weight, bias, labels):
     return f, up_weight, up_bias, weight, bias, labels, n, c, ci, co, h, w
 
 
-def _forward(f, up_weight, up_bias, weight, bias, labels, targets, need_g0):
-    """One forward launch.  targets None: returns z [N, 1, 2h, 2w]; else (loss (1,), g0 [N, 4hw] or None)."""
+def _forward(f, up_weight, up_bias, weight, bias, labels, targets, need_g0, valid_rows=False):
+    """One forward launch.  targets None: returns z [N, 1, 2h, 2w]; else (loss (1,), g0 [N, 4hw] or None).  valid_rows: g0 is
+    left undivided and the last result is the device scalar 1 / divisor (None otherwise)."""
     fc, uw, ub, w2, b, lb, n, c, ci, co, h, w = _prep(f, up_weight, up_bias, weight, bias, labels)
     dev, hw = fc.device, h * w
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    z = g0 = rows = loss = t = None
+    z = g0 = rows = loss = t = inv = None
     if targets is None:
         z = torch.empty((n, 1, 2 * h, 2 * w), dtype=torch.float32, device=dev)
     else:
@@ -108,15 +111,25 @@ def _forward(f, up_weight, up_bias, weight, bias, labels, targets, need_g0):
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         rows = torch.empty(n * ((hw + _TILE - 1) // _TILE), dtype=torch.float32, device=dev)
         g0 = torch.empty((n, 4 * hw), dtype=torch.float32, device=dev) if need_g0 else None
-    _lib.check(_lib.lib().iif_mask_tail_fwd(_lib.ptr(fc), _lib.dtype_code(fc), _lib.ptr(uw), _lib.ptr(ub), _lib.ptr(w2), _ld(w2),
-                                            _lib.ptr(b), _lib.ptr(lb), _lib.ptr(t), n, c, ci, co, h, w, _lib.ptr(z), _lib.ptr(g0),
-                                            _lib.ptr(rows), _lib.ptr(loss), _lib.ptr(status), _lib.stream_ptr()), "iif_mask_tail_fwd")
-    return (fc, uw, ub, w2, lb), (n, c, ci, co, h, w), (z if targets is None else loss), g0
+    if valid_rows and targets is not None:
+        inv = torch.empty(1, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().iif_mask_tail_loss_fwd(_lib.ptr(fc), _lib.dtype_code(fc), _lib.ptr(uw), _lib.ptr(ub), _lib.ptr(w2),
+                                                     _ld(w2), _lib.ptr(b), _lib.ptr(lb), _lib.ptr(t), n, c, ci, co, h, w, 1,
+                                                     _lib.ptr(g0), _lib.ptr(rows), _lib.ptr(loss), _lib.ptr(inv), _lib.stream_ptr()),
+                   "iif_mask_tail_loss_fwd")
+    else:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().iif_mask_tail_fwd(_lib.ptr(fc), _lib.dtype_code(fc), _lib.ptr(uw), _lib.ptr(ub), _lib.ptr(w2), _ld(w2),
+                                                _lib.ptr(b), _lib.ptr(lb), _lib.ptr(t), n, c, ci, co, h, w, _lib.ptr(z), _lib.ptr(g0),
+                                                _lib.ptr(rows), _lib.ptr(loss), _lib.ptr(status), _lib.stream_ptr()),
+                   "iif_mask_tail_fwd")
+    return (fc, uw, ub, w2, lb), (n, c, ci, co, h, w), (z if targets is None else loss), g0, inv
 
 
-def _backward(saved, dims, g, up, needs):
+def _backward(saved, dims, g, up, needs, inv=None):
     """The backward entries on the compact gradient g [N, 4hw] (times the device scalar `up`, or 1).  needs: f, up_weight, up_bias,
-    weight, bias.  Returns the five gradients (None where not asked for)."""
+    weight, bias.  inv: the device scalar 1 / divisor of a forward that stored g undivided (valid_rows); the kernels multiply
+    it in.  Returns the five gradients (None where not asked for)."""
     fc, uw, ub, w2, lb = saved
     n, c, ci, co, h, w = dims
     need_f, need_uw, need_ub, need_w, need_b = needs
@@ -124,8 +137,14 @@ def _backward(saved, dims, g, up, needs):
     df = duw = dub = dw = db = None
     signs = torch.empty((n, (hw + 31) // 32, 4 * co), dtype=torch.int32, device=dev)
     rows = torch.empty((n, co + 1), dtype=torch.float32, device=dev) if (need_w or need_b) else None
-    _lib.check(L.iif_mask_tail_bwd_rows(_lib.ptr(fc), _lib.dtype_code(fc), _lib.ptr(uw), _lib.ptr(ub), _lib.ptr(g), _lib.ptr(up),
-                                        _lib.ptr(lb), n, c, ci, co, h, w, _lib.ptr(signs), _lib.ptr(rows), st), "iif_mask_tail_bwd_rows")
+    if inv is None:
+        _lib.check(L.iif_mask_tail_bwd_rows(_lib.ptr(fc), _lib.dtype_code(fc), _lib.ptr(uw), _lib.ptr(ub), _lib.ptr(g), _lib.ptr(up),
+                                            _lib.ptr(lb), n, c, ci, co, h, w, _lib.ptr(signs), _lib.ptr(rows), st),
+                   "iif_mask_tail_bwd_rows")
+    else:
+        _lib.check(L.iif_mask_tail_loss_bwd_rows(_lib.ptr(fc), _lib.dtype_code(fc), _lib.ptr(uw), _lib.ptr(ub), _lib.ptr(g),
+                                                 _lib.ptr(up), _lib.ptr(inv), _lib.ptr(lb), n, c, ci, co, h, w, _lib.ptr(signs),
+                                                 _lib.ptr(rows), st), "iif_mask_tail_loss_bwd_rows")
     if rows is not None:
         if need_w:
             dw = torch.empty((c, co), dtype=torch.float32, device=dev)
@@ -135,9 +154,14 @@ def _backward(saved, dims, g, up, needs):
                    "iif_mask_tail_bwd_classes")
     if need_f:
         df = torch.empty((n, ci, h, w), dtype=fc.dtype, device=dev)
-        _lib.check(L.iif_mask_tail_bwd_input(_lib.ptr(g), _lib.ptr(up), _lib.ptr(uw), _lib.ptr(w2), _ld(w2), _lib.ptr(lb),
-                                             _lib.ptr(signs), n, c, ci, co, h, w, _lib.ptr(df), _lib.dtype_code(df), st),
-                   "iif_mask_tail_bwd_input")
+        if inv is None:
+            _lib.check(L.iif_mask_tail_bwd_input(_lib.ptr(g), _lib.ptr(up), _lib.ptr(uw), _lib.ptr(w2), _ld(w2), _lib.ptr(lb),
+                                                 _lib.ptr(signs), n, c, ci, co, h, w, _lib.ptr(df), _lib.dtype_code(df), st),
+                       "iif_mask_tail_bwd_input")
+        else:
+            _lib.check(L.iif_mask_tail_loss_bwd_input(_lib.ptr(g), _lib.ptr(up), _lib.ptr(inv), _lib.ptr(uw), _lib.ptr(w2), _ld(w2),
+                                                      _lib.ptr(lb), _lib.ptr(signs), n, c, ci, co, h, w, _lib.ptr(df),
+                                                      _lib.dtype_code(df), st), "iif_mask_tail_loss_bwd_input")
     if need_uw or need_ub:
         splits = L.iif_mask_tail_splits(n, ci, co)
         partial = torch.empty(splits * (ci + 1) * 4 * co, dtype=torch.float32, device=dev)
@@ -145,9 +169,15 @@ def _backward(saved, dims, g, up, needs):
             duw = torch.empty((ci, co, 2, 2), dtype=torch.float32, device=dev)
         if need_ub:
             dub = torch.empty(co, dtype=torch.float32, device=dev)
-        _lib.check(L.iif_mask_tail_bwd_params(_lib.ptr(fc), _lib.dtype_code(fc), _lib.ptr(g), _lib.ptr(up), _lib.ptr(w2), _ld(w2),
-                                              _lib.ptr(lb), _lib.ptr(signs), n, c, ci, co, h, w, _lib.ptr(partial), _lib.ptr(duw),
-                                              _lib.ptr(dub), st), "iif_mask_tail_bwd_params")
+        if inv is None:
+            _lib.check(L.iif_mask_tail_bwd_params(_lib.ptr(fc), _lib.dtype_code(fc), _lib.ptr(g), _lib.ptr(up), _lib.ptr(w2), _ld(w2),
+                                                  _lib.ptr(lb), _lib.ptr(signs), n, c, ci, co, h, w, _lib.ptr(partial),
+                                                  _lib.ptr(duw), _lib.ptr(dub), st), "iif_mask_tail_bwd_params")
+        else:
+            _lib.check(L.iif_mask_tail_loss_bwd_params(_lib.ptr(fc), _lib.dtype_code(fc), _lib.ptr(g), _lib.ptr(up), _lib.ptr(inv),
+                                                       _lib.ptr(w2), _ld(w2), _lib.ptr(lb), _lib.ptr(signs), n, c, ci, co, h, w,
+                                                       _lib.ptr(partial), _lib.ptr(duw), _lib.ptr(dub), st),
+                       "iif_mask_tail_loss_bwd_params")
     return df, duw, dub, dw, db
 
 
@@ -158,7 +188,7 @@ def _det(t):
 class _Logits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, f, up_weight, up_bias, weight, bias, labels, wshape):
-        saved, dims, z, _ = _forward(f.detach(), up_weight.detach(), _det(up_bias), weight.detach(), _det(bias), labels, None, False)
+        saved, dims, z, _, _ = _forward(f.detach(), up_weight.detach(), _det(up_bias), weight.detach(), _det(bias), labels, None, False)
         ctx.save_for_backward(*saved)
         ctx.meta = (dims, wshape)
         return z
@@ -178,12 +208,12 @@ class _Logits(torch.autograd.Function):
 
 class _Loss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, f, up_weight, up_bias, weight, bias, labels, targets, wshape):
+    def forward(ctx, f, up_weight, up_bias, weight, bias, labels, targets, wshape, valid_rows):
         need = any(_needs(f, up_weight, up_bias, weight, bias))
-        saved, dims, loss, g0 = _forward(f.detach(), up_weight.detach(), _det(up_bias), weight.detach(), _det(bias), labels, targets,
-                                         need)
+        saved, dims, loss, g0, inv = _forward(f.detach(), up_weight.detach(), _det(up_bias), weight.detach(), _det(bias), labels,
+                                              targets, need, valid_rows)
         if need:
-            ctx.save_for_backward(*saved, g0)
+            ctx.save_for_backward(*saved, g0, inv)
         ctx.meta = (dims, wshape, need)
         return loss
 
@@ -193,10 +223,10 @@ class _Loss(torch.autograd.Function):
         dims, wshape, need = ctx.meta
         needs = ctx.needs_input_grad[:5]                 # (False for a bias that is None)
         if not need or not any(needs):
-            return (None,) * 8
-        *saved, g0 = ctx.saved_tensors
-        df, duw, dub, dw, db = _backward(saved, dims, g0, _up(gl), needs)
-        return df, duw, dub, None if dw is None else dw.reshape(wshape), db, None, None, None
+            return (None,) * 9
+        *saved, g0, inv = ctx.saved_tensors
+        df, duw, dub, dw, db = _backward(saved, dims, g0, _up(gl), needs, inv)
+        return (df, duw, dub, None if dw is None else dw.reshape(wshape), db) + (None,) * 4
 
 
 def upsampled_class_mask_logits(f, up_weight, up_bias, weight, bias, labels):
@@ -210,14 +240,16 @@ def upsampled_class_mask_logits(f, up_weight, up_bias, weight, bias, labels):
     return _Logits.apply(f, up_weight, up_bias, weight, bias, labels, tuple(weight.shape))
 
 
-def upsampled_class_mask_loss(f, up_weight, up_bias, weight, bias, labels, targets):
+def upsampled_class_mask_loss(f, up_weight, up_bias, weight, bias, labels, targets, valid_rows=False):
     """``mask_cross_entropy(conv_logits(relu(upsample(f))), targets, labels)`` (cross_entropy_loss.py:114-162) -> shape ``(1,)``
     as ONE autograd node.  Only what ``requires_grad`` asks for is computed; the upstream gradient is applied on the device.
-    ``targets [N, 2h, 2w]``.  ``N == 0``: a zero connected to every input."""
+    ``targets [N, 2h, 2w]``.  ``valid_rows``: divide by ``max(1, #{n: 0 <= labels[n] < C}) * 4hw`` instead of ``N * 4hw``, the
+    count taken on the device; the backward kernels apply the divisor, in as many launches as without it.  ``N == 0``: a zero
+    connected to every input."""
     if _is_empty(f):
         _prep(f, up_weight, up_bias, weight, bias, labels)
         return _empty_result(f, (up_weight, up_bias, weight, bias), (1,))
-    return _Loss.apply(f, up_weight, up_bias, weight, bias, labels, targets, tuple(weight.shape))
+    return _Loss.apply(f, up_weight, up_bias, weight, bias, labels, targets, tuple(weight.shape), bool(valid_rows))
 
 
 class _Params(nn.Module):
@@ -250,8 +282,8 @@ class FusedMaskHeadTail(nn.Module):
             nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
             nn.init.constant_(m.bias, 0)
 
-    def _labels(self, labels):
-        return torch.zeros_like(labels) if self.class_agnostic else labels
+    def _labels(self, labels, valid_rows=False):
+        return _agnostic_labels(labels, self.num_classes, valid_rows) if self.class_agnostic else labels
 
     def _args(self):
         return self.upsample.weight, self.upsample.bias, self.conv_logits.weight, self.conv_logits.bias
@@ -260,9 +292,10 @@ class FusedMaskHeadTail(nn.Module):
         """The selected logits ``[N, 1, 2h, 2w]``: ``pos_labels`` in training, ``det_labels`` at test time."""
         return upsampled_class_mask_logits(f, *self._args(), self._labels(labels))
 
-    def loss(self, f, labels, mask_targets):
-        """``FCNMaskHead.loss`` (fcn_mask_head.py:147-177) on the input of ``upsample`` instead of the logits."""
-        return dict(loss_mask=upsampled_class_mask_loss(f, *self._args(), self._labels(labels), mask_targets))
+    def loss(self, f, labels, mask_targets, valid_rows=False):
+        """``FCNMaskHead.loss`` (fcn_mask_head.py:147-177) on the input of ``upsample`` instead of the logits.  ``valid_rows``: the
+        rows of the padded RoI pipeline (label ``num_classes`` = padding), divided by the device-counted number of real rows."""
+        return dict(loss_mask=upsampled_class_mask_loss(f, *self._args(), self._labels(labels, valid_rows), mask_targets, valid_rows))
 
     @classmethod
     def from_modules(cls, upsample, conv_logits, class_agnostic=None):

@@ -173,11 +173,6 @@ class ClassSelectedNormedMaskPredictor(_SelectedPredictor):
         super().__init__(in_channels, num_classes, class_agnostic)
         self.tempearture, self.power, self.eps, self.norm_over_kernel = tempearture, power, eps, bool(norm_over_kernel)
 
-    def _labels(self, labels, valid_rows=False):
-        if self.class_agnostic and valid_rows:           # channel 0 for a real class, still invalid for a padded row
-            return torch.where((labels >= 0) & (labels < self.num_classes), torch.zeros_like(labels), torch.full_like(labels, -1))
-        return super()._labels(labels)
-
     def forward(self, x, labels):
         """The selected logits ``[N, 1, H, W]``: ``pos_labels`` in training, ``det_labels`` at test time."""
         return normed_class_mask_logits(x, self.weight, self.bias, self._labels(labels), self.tempearture, self.power, self.eps)

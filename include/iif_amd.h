@@ -1469,6 +1469,28 @@ int iif_mask_predict_bwd_weight(const void* x, int dtype, const float* g, const 
                                 int n, int c, int cin, int hw, float* scratch, float* dweight /* nullable */,
                                 float* dbias /* nullable */, void* stream);
 
+/* The same predictor fused with the loss, the divisor left to the device (the padded RoI pipeline: rows with a label outside
+ * [0, c) are padding).  Operands, limits, errors and launch counts as for the three entries above, with these differences:
+ *
+ * iif_mask_predict_loss_fwd (two launches): target is required, no z.  g[i, p] = sigmoid(z) - target (fp32 [n][hw], nullable, NOT
+ *   divided), *loss = sum BCEWithLogits(z, target) / divisor and *inv_div = 1 / divisor, a device scalar for the backward
+ *   entries.  divisor = n * hw, or with valid_rows != 0 max(1, #{i : 0 <= labels[i] < c}) * hw, counted on the device (the
+ *   finishing kernel the normed family uses).  A RoI with a label outside [0, c) gets g = 0 and adds nothing to the loss;
+ *   its x and target are not read.  No status word.
+ * iif_mask_predict_loss_bwd_input / iif_mask_predict_loss_bwd_weight: iif_mask_predict_bwd_input / _bwd_weight with u = up *
+ *   inv_div (DEVICE scalars, each nullable = 1) in place of up; the product is formed inside the kernels.
+ * In the grids of these three entries block y works on the y-th RoI with a label in [0, c) (the others follow), so the blocks
+ * with work are dispatched first; every result is the one the RoI order would give, to the bit. */
+int iif_mask_predict_loss_fwd(const void* x, int dtype, const float* weight, int64_t ld_w, const float* bias /* nullable */,
+                              const int64_t* labels, const float* target, int n, int c, int cin, int hw, int valid_rows,
+                              float* g /* nullable */, float* row_loss, float* loss, float* inv_div, void* stream);
+int iif_mask_predict_loss_bwd_input(const float* g, const float* up /* nullable */, const float* inv_div /* nullable */,
+                                    const float* weight, int64_t ld_w, const int64_t* labels, int n, int c, int cin, int hw,
+                                    void* dx, int dtype, void* stream);
+int iif_mask_predict_loss_bwd_weight(const void* x, int dtype, const float* g, const float* up /* nullable */,
+                                     const float* inv_div /* nullable */, const int64_t* labels, int n, int c, int cin, int hw,
+                                     float* scratch, float* dweight /* nullable */, float* dbias /* nullable */, void* stream);
+
 /* The class-selected mask predictor of the cosine-norm heads (csrc/normed_mask_predictor.hip;
  * iif_amd/mmdet_normed_mask_predictor.py): predictor_cfg=dict(type='NormedConv2d', tempearture=20) - normed_predictor.py:104-124,
  * a 1x1 kernel - evaluated at each RoI's label channel only.  Operands as for iif_mask_predict_*.  With l = labels[i],
@@ -1558,6 +1580,33 @@ int iif_mask_tail_bwd_params(const void* f, int dtype, const float* g, const flo
                              void* stream);
 int iif_mask_tail_bwd_classes(const float* rows, const int64_t* labels, int n, int c, int co, float* dweight /* nullable */,
                               float* dbias /* nullable */, void* stream);
+
+/* The tail fused with the loss, the divisor left to the device, as iif_mask_predict_loss_* above.  Operands, limits, errors and
+ * launch counts as for the iif_mask_tail_* entries, with these differences:
+ *
+ * iif_mask_tail_loss_fwd (two launches): target is required, no z.  g = sigmoid(z) - target (fp32 [n][2h][2w], nullable, NOT
+ *   divided), *loss = sum BCEWithLogits(z, target) / divisor, *inv_div = 1 / divisor (device scalar).  divisor = 4 n h w, or with
+ *   valid_rows != 0 max(1, #{i : 0 <= labels[i] < c}) * 4 h w, counted on the device.  A RoI with a label outside [0, c) gets
+ *   g = 0 and adds nothing; its f and target are not read.  No status word.
+ * iif_mask_tail_loss_bwd_rows / _bwd_input / _bwd_params: the iif_mask_tail_bwd_* entries with u = up * inv_div (DEVICE scalars,
+ *   each nullable = 1) in place of up; the product is formed inside the kernels.  iif_mask_tail_bwd_classes and
+ *   iif_mask_tail_splits serve both.  Forward, rows and df put the RoIs with a label in [0, c) first in their grids, as above. */
+int iif_mask_tail_loss_fwd(const void* f, int dtype, const float* up_weight, const float* up_bias /* nullable */,
+                           const float* weight, int64_t ld_w, const float* bias /* nullable */, const int64_t* labels,
+                           const float* target, int n, int c, int ci, int co, int h, int w, int valid_rows, float* g /* nullable */,
+                           float* row_loss, float* loss, float* inv_div, void* stream);
+int iif_mask_tail_loss_bwd_rows(const void* f, int dtype, const float* up_weight, const float* up_bias /* nullable */,
+                                const float* g, const float* up /* nullable */, const float* inv_div /* nullable */,
+                                const int64_t* labels, int n, int c, int ci, int co, int h, int w, unsigned int* signs,
+                                float* rows /* nullable */, void* stream);
+int iif_mask_tail_loss_bwd_input(const float* g, const float* up /* nullable */, const float* inv_div /* nullable */,
+                                 const float* up_weight, const float* weight, int64_t ld_w, const int64_t* labels,
+                                 const unsigned int* signs, int n, int c, int ci, int co, int h, int w, void* df, int dtype,
+                                 void* stream);
+int iif_mask_tail_loss_bwd_params(const void* f, int dtype, const float* g, const float* up /* nullable */,
+                                  const float* inv_div /* nullable */, const float* weight, int64_t ld_w, const int64_t* labels,
+                                  const unsigned int* signs, int n, int c, int ci, int co, int h, int w, float* partial,
+                                  float* dup_weight /* nullable */, float* dup_bias /* nullable */, void* stream);
 
 /* Non-maximum suppression (mmcv 1.3.8 ops/nms.py nms / batched_nms; iif_amd/mmdet_nms.py) in 5 enqueued operations for any N and
  * any data: a 4 KiB clear, the sort keys, the rank, the suppression bit matrix, the greedy scan (csrc/nms.hip).
