@@ -87,6 +87,7 @@ SIGNATURES = {
     "iif_conv_fwdbn_ok": [_P],
     "iif_conv_affine_ok": [_P, _I, _I],
     "iif_conv_affine_route": [_P, _I, _I, _I],
+    "iif_conv_route": [_P, _c.c_uint, _I, _P, _I],
     "iif_conv_igemm_affine": [_P, _P, _P, _P, _P, _P, _P, _P, _P],
     "iif_bn_fold": [_P, _I, _F, _P],
     "iif_conv_igemm_stats_acc": [_P, _P, _P, _P, _L, _P, _P],

@@ -2354,6 +2354,36 @@ extern "C" int iif_conv_affine_route(const iif_conv_desc* d, int has_res, int ha
     return conv_select(d, &a, false, false, 1, &p) == IIF_OK ? p.r[0].family : IIF_ROUTE_NONE;
 }
 
+// The launches of ANY call of the entry, as a value: a ConvSel filled from operand bits instead of from a call's pointers
+// (what sel_of reads), through the conv_select the launch starts with.  Aligned operands, a partial buffer without an end.
+extern "C" int iif_conv_route(const iif_conv_desc* d, unsigned operands, int cs2, int32_t* out, int cap) {
+    if (!d || cap < 0 || (cap > 0 && !out)) return IIF_EINVAL;
+    // (the entries that take the residual's ReLU bits refuse a stride-2 data gradient before they get here)
+    if ((operands & IIF_CONV_OP_RES_BITS) && (!d->transposed || d->stride != 1)) return IIF_EUNSUPPORTED;
+    const auto has = [operands](unsigned bit) { return (operands & bit) != 0; };
+    ConvSel a{};
+    a.res = has(IIF_CONV_OP_RES) || has(IIF_CONV_OP_RES_IS_DST); a.res_is_dst = has(IIF_CONV_OP_RES_IS_DST);
+    a.res_bits = has(IIF_CONV_OP_RES_BITS); a.bias = has(IIF_CONV_OP_BIAS); a.bn_partial = has(IIF_CONV_OP_PARTIAL);
+    a.bw_x = a.bn_partial && has(IIF_CONV_OP_UP_X); a.bw_bits = a.bn_partial && has(IIF_CONV_OP_UP_BITS);
+    a.bw_stats = a.bn_partial && has(IIF_CONV_OP_UP_STATS);
+    a.src2 = has(IIF_CONV_OP_SRC2); a.sbias = has(IIF_CONV_OP_SRC_BIAS); a.mask_store = has(IIF_CONV_OP_GATED_STORE);
+    a.no_store = has(IIF_CONV_OP_NO_STORE_ACC) ? 2 : has(IIF_CONV_OP_NO_STORE) ? 1 : 0;
+    a.rx_src2 = a.rx_w3 = has(IIF_CONV_OP_RX); a.pro_stats = has(IIF_CONV_OP_PROLOGUE);
+    if (a.src2 || a.rx_src2) {
+        if (cs2 <= 0) return IIF_EINVAL;
+        a.Cs2 = a.src2 ? cs2 : 0; a.rx_k2 = a.rx_ldw3 = a.rx_src2 ? cs2 : 0;
+    }
+    a.bn_cap = 0x7fffffffffffffffLL;
+    ConvPlan p;
+    if (const int rc = conv_select(d, &a, false, false, 0, &p)) return rc;
+    for (int i = 0; i < p.n && (i + 1) * 9 <= cap; ++i) {
+        const ConvRoute& r = p.r[i];
+        const int32_t v[9] = {r.family, r.inst, r.cls, r.mtiles, r.ntiles, (int32_t)r.grid, (int32_t)r.grid_y, (int32_t)r.block, r.rows};
+        for (int k = 0; k < 9; ++k) out[i * 9 + k] = v[k];
+    }
+    return p.n;
+}
+
 // ---- launching entry points
 extern "C" int iif_conv_igemm_dgrad_bnbwd(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
                                           const unsigned char* res_bits, const void* up_x, const unsigned char* up_bits,

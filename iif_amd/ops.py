@@ -60,6 +60,31 @@ def conv_affine_route(n, hs, ws, cs, hd, wd, cd, r, s, stride, pad, ldw, groups=
     return AFFINE_ROUTES[lib().iif_conv_affine_route(ctypes.byref(d), int(has_res), int(has_res_affine), int(has_relu_bits))]
 
 
+CONV_ROUTES = AFFINE_ROUTES + ("stem", "tile_mc")
+# IIF_CONV_OP_* of include/iif_amd.h, by the name conv_route takes them under
+CONV_OPERANDS = {"res": 1, "res_is_dst": 2, "res_bits": 4, "bias": 8, "partial": 16, "up_x": 32, "up_bits": 64, "up_stats": 128,
+                 "src2": 256, "src_bias": 512, "gated_store": 1024, "no_store": 2048, "no_store_acc": 4096, "rx": 8192,
+                 "prologue": 16384}
+ConvLaunch = collections.namedtuple("ConvLaunch", "family inst cls mtiles ntiles grid grid_y block rows")
+
+
+def conv_route(n, hs, ws, cs, hd, wd, cd, r, s, stride, pad, transposed, ldw, operands=(), cs2=0, dtype=torch.bfloat16,
+               dst_dtype=None, groups=1, w_frag=None):
+    """The launches a call of the convolution entry makes for this descriptor (source grid first, as the C descriptor; cs / cd
+    per group) and these operands (names of CONV_OPERANDS): a list of ConvLaunch, family by name (iif_conv_route; host only,
+    nothing is launched).  A call the entry refuses raises IIFNativeError."""
+    code = lambda t: _lib.IIF_F32 if t == torch.float32 else _lib.IIF_BF16      # noqa: E731
+    d = _desc(n, hs, ws, cs, hd, wd, cd, r, s, stride, pad, int(transposed), ldw, code(dtype), code(dst_dtype or dtype), groups, w_frag)
+    bits = 0
+    for name in operands:
+        bits |= CONV_OPERANDS[name]
+    out = (ctypes.c_int32 * 36)()
+    rc = lib().iif_conv_route(ctypes.byref(d), bits, cs2, ctypes.addressof(out), 36)
+    if rc < 0:
+        check(rc, "iif_conv_route")
+    return [ConvLaunch(CONV_ROUTES[out[9 * i]], *out[9 * i + 1:9 * i + 9]) for i in range(rc)]
+
+
 def conv_forward_affine(x, w, r, s, stride, pad, out, affine, res=None, res_affine=None, relu_bits=None, groups=1, w_frag=None):
     """Inference forward of a conv + BN (+ residual) + ReLU unit in one launch (bf16):
     out = relu(affine[2] * bf16(conv) + affine[3] + r), r = res, or res_affine[2] * res + res_affine[3] (a raw convolutional

@@ -1091,6 +1091,23 @@ int iif_conv_affine_ok(const iif_conv_desc* d, int has_res, int has_res_affine);
  * kernels size themselves by the device's compute units (256 assumed where there is no device).  For tests and route
  * listings. */
 int iif_conv_affine_route(const iif_conv_desc* d, int has_res, int has_res_affine, int has_relu_bits);
+/* The same for every other call of the convolution entry (forward, statistics, data gradient, two-source ...): which launches
+ * it makes for this descriptor and this set of operands, answered by the selection step the launch starts with.  Host only: it
+ * touches no operand, launches nothing and needs no device.  `operands`: IIF_CONV_OP_* bits, one per operand or option the call
+ * would pass (d->transposed says forward or data gradient); cs2: channels of the second source (IIF_CONV_OP_SRC2) or of the
+ * recomputed upstream a2 (IIF_CONV_OP_RX), else ignored.  Operands count as 16-byte aligned and the partial buffer as large
+ * enough.  Returns the number of launches (1; up to 4 for a stride-2 data gradient launched class by class) and writes, for
+ * each launch that fits `cap` int32 of `out`, the nine values {family (as iif_conv_affine_route; 12 stem, 13 all parity
+ * classes in one grid), instance (columns per tile of the tile families, rows per tile of the halo kernel, slice width of the
+ * streaming kernel, index of the register-weight instance), parity class or -1, pixel tiles, column tiles, grid x, grid y,
+ * threads per block, partial rows written}.  A call the entry would refuse returns that negative status code. */
+enum { IIF_CONV_OP_RES = 1, IIF_CONV_OP_RES_IS_DST = 2 /* dst += ... */, IIF_CONV_OP_RES_BITS = 4 /* ReLU bits gate the residual */,
+       IIF_CONV_OP_BIAS = 8, IIF_CONV_OP_PARTIAL = 16 /* partial rows: forward statistics, or with UP_* the backward sums */,
+       IIF_CONV_OP_UP_X = 32, IIF_CONV_OP_UP_BITS = 64, IIF_CONV_OP_UP_STATS = 128, IIF_CONV_OP_SRC2 = 256,
+       IIF_CONV_OP_SRC_BIAS = 512, IIF_CONV_OP_GATED_STORE = 1024, IIF_CONV_OP_NO_STORE = 2048 /* iif_conv_igemm_stats_only */,
+       IIF_CONV_OP_NO_STORE_ACC = 4096 /* iif_conv_igemm_stats_acc */, IIF_CONV_OP_RX = 8192 /* ..._dgrad_masksum_rx */,
+       IIF_CONV_OP_PROLOGUE = 16384 /* iif_conv_igemm_bnstats_pro */ };
+int iif_conv_route(const iif_conv_desc* d, unsigned operands, int cs2, int32_t* out, int cap);
 int iif_conv_igemm_affine(const iif_conv_desc* d, const void* src, const void* wgt, void* dst, const void* res,
                           const float* res_affine, const float* affine, unsigned char* relu_bits, void* stream);
 int iif_conv_igemm_stats_acc(const iif_conv_desc* d, const void* src, const void* wgt, float* bn_partial,
