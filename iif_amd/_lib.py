@@ -159,6 +159,9 @@ SIGNATURES = {
     "iif_rpn_stage_dense": [_P, _I, _P, _P, _P, _P, _L, _L, _L, _F, _P, _P, _P, _P, _P],
     "iif_rpn_loss_fwd": [_P, _P, _I, _P, _P, _P, _P, _L, _L, _P, _F, _F, _F, _F, _P, _P, _P],
     "iif_rpn_loss_bwd": [_P, _P, _I, _P, _P, _P, _P, _L, _L, _P, _F, _F, _F, _F, _P, _P, _P],
+    "iif_rpn_sampled_pixels": [_P, _I, _P, _P, _P, _P, _L, _L, _P, _P, _P],
+    "iif_rpn_head_sampled_workspace_bytes": [_I, _I, _I, _I],
+    "iif_rpn_head_sampled_bwd": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P],
     "iif_roi_extract_forward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _P],
     "iif_roi_extract_backward": [_P, _I, _I, _I, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P, _I, _P, _L, _P],
     "iif_mask_targets": [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P],
@@ -256,6 +259,12 @@ class RpnLossLevel(ctypes.Structure):
         (k, ctypes.c_int64 * 4) for k in ("score_strides", "delta_strides", "grad_score_strides", "grad_delta_strides")]
 
 
+class RpnHeadLevel(ctypes.Structure):
+    """Mirror of ``iif_rpn_head_level`` (include/iif_amd.h)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("feat", "grad_feat", "grad_scores", "grad_deltas")] + [
+        (k, ctypes.c_int64 * 4) for k in ("feat_strides", "grad_feat_strides", "grad_score_strides", "grad_delta_strides")]
+
+
 class RpnLevel(ctypes.Structure):
     """Mirror of ``iif_rpn_level`` (include/iif_amd.h)."""
     _fields_ = [("scores", ctypes.c_void_p), ("deltas", ctypes.c_void_p), ("anchors", ctypes.c_void_p),
@@ -291,7 +300,7 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = argtypes
             fn.restype = _L if name in ("iif_bn_workspace_bytes", "iif_bn3_algebra_prep_scratch_floats", "iif_rle_workspace_bytes",
-                                         "iif_rpn_stage_workspace_bytes") else _I
+                                         "iif_rpn_stage_workspace_bytes", "iif_rpn_head_sampled_workspace_bytes") else _I
         _lib = l
     return _lib
 

@@ -31,6 +31,7 @@
 //   iif_rpn_loss_bwd     one launch: plain stores at the sampled positions of a gradient arena the caller cleared.
 #include "common.h"
 #include "assign_common.h"
+#include "rpn_grid.h"
 #include "sample_core.h"
 
 namespace {
@@ -38,59 +39,14 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kChunk = kAssignChunk;
 static_assert(kThreads == kAssignChunk, "assign_pass1_chunks / step4_stage_chunk stage one box per thread");
-constexpr int kMaxImages = 16;
-constexpr int kMaxLevels = 8;
-constexpr int kMaxBase = 16;
-constexpr int kMaxNum = 1024;
 constexpr int kPass2MaxBlocks = 512;
 constexpr int kSelMaxBlocks = 64;
-
-struct Lvl { int start, W, H, nb, sx, sy; };
-struct Grid { int L, A; Lvl lv[kMaxLevels]; };
-struct Bases { float b[kMaxLevels][kMaxBase][4]; };
-
-struct Cell { int l, x, y, a, r; };
-
-__device__ __forceinline__ Cell locate(const Grid& g, int i) {
-    Cell c;
-    c.l = 0;
-    for (int k = 1; k < g.L; ++k)
-        if (i >= g.lv[k].start) c.l = k;
-    const Lvl& v = g.lv[c.l];
-    c.r = i - v.start;
-    c.a = c.r % v.nb;
-    const int cell = c.r / v.nb;
-    c.x = cell % v.W;
-    c.y = cell / v.W;
-    return c;
-}
 
 __device__ __forceinline__ Box make_anchor(const Grid& g, const Bases& bs, const Cell& c) {
     const float sx = (float)(c.x * g.lv[c.l].sx), sy = (float)(c.y * g.lv[c.l].sy);
     const float* b = bs.b[c.l][c.a];
     return Box{b[0] + sx, b[1] + sy, b[2] + sx, b[3] + sy};
 }
-
-bool fill_grid(const iif_rpn_grid* in, Grid* g, Bases* bs) {
-    if (!in || in->num_levels < 1 || in->num_levels > kMaxLevels) return false;
-    int64_t at = 0;
-    g->L = in->num_levels;
-    for (int l = 0; l < in->num_levels; ++l) {
-        const int W = in->W[l], H = in->H[l], nb = in->num_base[l];
-        if (W < 0 || H < 0 || W > 65535 || H > 65535 || nb < 1 || nb > kMaxBase || in->stride_w[l] < 1 || in->stride_h[l] < 1) return false;
-        if ((int64_t)W * in->stride_w[l] >= (1 << 24) || (int64_t)H * in->stride_h[l] >= (1 << 24)) return false;   // exact as float32
-        g->lv[l] = Lvl{(int)at, W > 0 ? W : 1, H, nb, in->stride_w[l], in->stride_h[l]};
-        at += (int64_t)W * H * nb;
-        if (at >= INT32_MAX - 4) return false;
-        if (bs)
-            for (int a = 0; a < nb; ++a)
-                for (int j = 0; j < 4; ++j) bs->b[l][a][j] = in->base[l][a][j];
-    }
-    g->A = (int)at;
-    return true;
-}
-
-bool aligned_to(const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
 
 // ------------------------------------------------------------------------------------------------ generator
 struct GenArgs { Grid g; Bases bs; float* anchors; uint8_t* flags; int vw[kMaxLevels], vh[kMaxLevels]; };
@@ -255,10 +211,6 @@ __global__ void __launch_bounds__(64) rpn_total_kernel(const int64_t* counts, in
 }
 
 // ------------------------------------------------------------------------------------------------ the sampled lists, shared
-struct Lists { const int64_t* pos_inds; const int64_t* neg_inds; const int64_t* counts; const float* pos_bt; int nep, num, B; };
-
-__device__ __forceinline__ int clampi(int64_t v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
-
 // position of `i` in the ascending list[0 .. n), -1 if absent
 __device__ __forceinline__ int find_in(const int64_t* list, int n, int64_t i) {
     int lo = 0, hi = n;
@@ -310,18 +262,6 @@ struct LossArgs {
     float* out_cls; float* out_box;                                  // forward: [L] each
     const float* go_cls; const float* go_box;                        // backward: the gradients of those
 };
-
-// entry e of the B (nep + num) slots: the flat anchor index, or -1 for an unused slot
-__device__ __forceinline__ int64_t entry_of(const Lists& s, int e, int& b, bool& pos, int& slot) {
-    const int per = s.nep + s.num;
-    b = e / per;
-    const int r = e - b * per;
-    pos = r < s.nep;
-    slot = pos ? r : r - s.nep;
-    const int kp = clampi(s.counts[2 * b], s.nep), kn = clampi(s.counts[2 * b + 1], s.num);
-    if (slot >= (pos ? kp : kn)) return -1;
-    return pos ? s.pos_inds[(int64_t)b * s.nep + slot] : s.neg_inds[(int64_t)b * s.num + slot];
-}
 
 __device__ __forceinline__ double block_sum_ordered(double v, double* s_w) {
 #pragma unroll
@@ -411,16 +351,6 @@ int64_t cleared_bytes(int B, int64_t total_G) {
     n = (n + 15) / 16 * 16;                                 // the histograms are read in 16-byte pieces
     n += 4 * (int64_t)B * 2 * kBins + 4 * (int64_t)B;
     return (n + 15) / 16 * 16;
-}
-
-bool fill_lists(Lists* s, int B, const int64_t* pos_inds, const int64_t* neg_inds, const int64_t* counts, const float* pos_bt,
-                int64_t nep, int64_t num) {
-    if (B < 1 || B > kMaxImages || num < 0 || num > kMaxNum || nep < 0 || nep > num || !counts) return false;
-    if ((nep > 0 && (!pos_inds || !pos_bt)) || (num > 0 && !neg_inds)) return false;
-    if (!aligned_to(pos_inds, 8) || !aligned_to(neg_inds, 8) || !aligned_to(counts, 8) || !aligned_to(pos_bt, 16)) return false;
-    s->pos_inds = pos_inds; s->neg_inds = neg_inds; s->counts = counts; s->pos_bt = pos_bt;
-    s->nep = (int)nep; s->num = (int)num; s->B = B;
-    return true;
 }
 
 bool fill_loss(LossArgs* a, const iif_rpn_grid* grid, const iif_rpn_loss_level* levels, int B, bool backward) {

@@ -490,6 +490,51 @@ int iif_rpn_loss_bwd(const iif_rpn_grid* grid, const iif_rpn_loss_level* levels,
                      int64_t num, const float* num_total_samples, float pos_weight, float cls_loss_weight, float bbox_loss_weight,
                      float beta, const float* grad_loss_cls, const float* grad_loss_bbox, void* stream);
 
+/* ---- The RPN head's backward at the sampled pixels only (csrc/rpn_head_sampled.hip).  RPNHead.forward_single
+ * (dense_heads/rpn_head.py:38-44) is relu(rpn_conv(x)) followed by the 1x1 convolutions rpn_cls and rpn_reg; the gradient that
+ * iif_rpn_loss_bwd leaves in the maps is zero outside the pixels of the sampled anchors, so the three convolutions' backward is
+ * formed from those pixels alone.
+ *
+ * iif_rpn_sampled_pixels: slot e of the B (num_expected_pos + num) entries of the lists above -> its pixel.
+ *   owner [B, P] int32, P = sum_l H_l W_l, pixel (l, y, x) of image b at b P + sum_{l' < l} H_l' W_l' + y W_l + x: the lowest slot
+ *   index whose anchor lies on the pixel (flat index -> pixel: (i - start_l) / num_base[l]), -1 where nothing was sampled.
+ *   slots [B (num_expected_pos + num), 4] int32: <image, level, y, x> of a slot that owns its pixel, level -1 for every other slot
+ *   (unused, or a second sampled anchor of a pixel).  THREE enqueued operations whatever the data: the clear of owner, an integer
+ *   atomicMin per entry, the slot records. */
+int iif_rpn_sampled_pixels(const iif_rpn_grid* grid, int B, const int64_t* pos_inds, const int64_t* neg_inds, const int64_t* counts,
+                           const float* pos_bbox_targets, int64_t num_expected_pos, int64_t num, int32_t* owner, int32_t* slots,
+                           void* stream);
+
+/* One level of the head's backward: the float32 feature map [B, Ci, H, W] the head read, the gradient map of the same shape THE
+ * CALLER HAS CLEARED (NULL on every level: the features' gradient is not wanted), and the gradients of the score map
+ * [B, A, H, W] and delta map [B, 4 A, H, W]; each with its element strides (any memory format). */
+typedef struct iif_rpn_head_level {
+    const float* feat;
+    float* grad_feat;
+    const float* grad_scores;
+    const float* grad_deltas;
+    int64_t feat_strides[4], grad_feat_strides[4], grad_score_strides[4], grad_delta_strides[4];
+} iif_rpn_head_level;
+
+/* The gradients of rpn_conv [Co, Ci, 3, 3] (stride 1, pad 1; b_conv nullable), rpn_cls [A, Co] and rpn_reg [4 A, Co] and of the
+ * features, from the `slots` records of iif_rpn_sampled_pixels.  CONTRACT: grad_scores / grad_deltas are zero outside the pixels
+ * of the active slots (they are read nowhere else).
+ *   d_w_conv [Co, Ci, 3, 3], d_b_conv [Co], d_w_cls [A, Co], d_b_cls [A], d_w_reg [4 A, Co], d_b_reg [4 A]: each nullable, every
+ *   element written (a product none of whose results is wanted is not launched).  grad_feat: every pixel within the 3x3 neighbourhood of an active slot's pixel written once (all Ci
+ *   channels); nothing else is touched.
+ *   d_workspace: iif_rpn_head_sampled_workspace_bytes(slots, ci, co, A) on a 16-byte boundary (the patches, the hidden rows and
+ *   their gradients, the per-range partials); it belongs to the call until the stream has run it.
+ * Exact float32 products on v_mfma_f32_32x32x2_f32, fixed summation order (the slots in at most 16 ranges, partials added in range
+ * order), no float atomics: the same bits from call to call.  NINE launches whatever the data (seven without grad_feat).
+ * IIF_EINVAL before any launch: a required pointer NULL or misaligned, B outside 1 .. 16, slots < 1, ci or co < 1, a negative
+ * stride, a workspace too small.  IIF_EUNSUPPORTED: ci or co not a multiple of 8 or above 2048, slots > 32768, levels with
+ * different num_base, w_conv or d_workspace not 16-byte aligned. */
+int64_t iif_rpn_head_sampled_workspace_bytes(int slots, int ci, int co, int num_base);
+int iif_rpn_head_sampled_bwd(const iif_rpn_grid* grid, const iif_rpn_head_level* levels, int B, int slots_n, const int32_t* owner,
+                             const int32_t* slots, const float* w_conv, const float* b_conv, const float* w_cls, const float* w_reg,
+                             int ci, int co, float* d_w_conv, float* d_b_conv, float* d_w_cls, float* d_b_cls, float* d_w_reg,
+                             float* d_b_reg, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* out = logits * table. Replaces classification/custom.py:37-39 (infer=True). */
 int iif_scale_logits(const void* logits, int dtype, int64_t ld_logits, const float* table,
                      int B, int C, void* out, int64_t ld_out, void* stream);
