@@ -59,6 +59,7 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+static inline bool aligned_to(const void* p, unsigned n) { return aligned(p, (int)n); }     // the head-side entries' spelling
 
 // ---- The convolution entry in two steps (conv_igemm.hip; continuations in conv_regw.hip and conv_stem.hip): SELECT maps a
 // ConvSel - the geometry and WHICH operands a call has, no addresses - to a ConvRoute or a status code on the host alone;

@@ -288,8 +288,6 @@ __global__ void __launch_bounds__(kThreads) paste_masks_kernel(PasteArgs a) {
     }
 }
 
-bool aligned_to(const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
-
 }  // namespace
 
 extern "C" {

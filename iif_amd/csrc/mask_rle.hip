@@ -214,8 +214,6 @@ __global__ void __launch_bounds__(kThreads) rle_diff_kernel(RleArgs a, int64_t t
     a.runs[k] = k == a.offsets[lo] ? p : p - a.pos[k - 1];
 }
 
-bool aligned_to(const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
-
 int64_t seg_count(int H) { return cdiv64(H, kSegRows); }
 
 // the item arrays of N masks, then offsets [N + 1] as int64 on an 8-byte boundary

@@ -22,19 +22,19 @@
 //   class walk (per class)  one workgroup of 256 threads per (image, class): returns at once on an empty segment, else ranks
 //              the segment's keys in LDS and walks them on the same shifted boxes.  Appends the kept keys to the image's kept
 //              list through an integer counter.
-//   select x 6 (per class)  the cap largest keys of the kept list: the radix select of the RPN path (five digit histograms,
-//              then the gather).  With at most cap kept keys the histograms are skipped on the device.
+//   select x 6 (per class)  the cap largest keys of the kept list: the radix select of nms_common.h (select_pass_core), one
+//              segment per image.  With at most cap kept keys the histograms are skipped on the device.
 //   finish     one workgroup per image ranks the at most cap selected keys in LDS and writes dets (the UNSHIFTED box and the
 //              ranked score, recomputed from the inputs), labels, inds, the padding, counts and num_candidates.
 //
 // The walk (both regimes) holds no matrix.  Thread t keeps the shifted boxes of ranks t, t + T, ... in registers and one alive
 // bit each.  Per block of 64 ranks: the owners publish their boxes to LDS; wave 0 tests the 64 x 64 pairs of the block itself
-// (lane = row, one 64-bit word per lane) and resolves them in order from registers (v_readlane), as nms_scan_kernel does; then
+// (lane = row, one 64-bit word per lane) and resolves them in order with resolve_block64 (nms_common.h); then
 // every thread tests its later boxes that are still alive against the boxes just kept.  Two barriers per 64 ranks (the LDS
 // block is double-buffered), kept x m overlap tests in all, and the walk ends as soon as cap boxes are kept.  This is the
 // only design that was measured (profiles/multiclass_nms.txt); the 128 KiB LDS bit matrix was not built.
 //
-// The overlap test is nms.hip's (nms_common.h), compiled with -ffp-contract=off.  Integer atomics only.
+// The sort key, both forms of the overlap test (-ffp-contract=off) and the counting ranks are nms_common.h's.  Integer atomics only.
 #include "nms_common.h"
 
 namespace {
@@ -44,7 +44,6 @@ constexpr int kFilterItems = 8;               // candidates per thread of the fi
 constexpr int kFlatCap = IIF_NMS_MAX_BOXES;   // all pairs: M < split_thr <= kFlatCap, or M <= R C <= kFlatCap
 constexpr int kFlatThreads = 1024, kFlatPer = kFlatCap / kFlatThreads;
 constexpr int kClassThreads = 256, kClassPer = IIF_MULTICLASS_NMS_MAX_ROWS / kClassThreads;
-constexpr int kSelBlocks = 16;
 constexpr int kFinishThreads = 1024;
 constexpr int kMaxImages = 16;
 constexpr int kHeaderBytes = 4096;
@@ -72,17 +71,6 @@ struct McArgs {
 };
 
 __device__ __forceinline__ bool all_pairs(int M, int split) { return M > 0 && M < split; }
-
-// nms_suppresses with the quotient left out where it cannot decide: inter is >= 0 or NaN, and with inter == 0 (or NaN) the quotient
-// is 0, -0 or NaN, none of them above a threshold >= 0.  The same result, bit for bit; most pairs of a walk do not meet.
-__device__ __forceinline__ bool suppresses_quick(const f32x4 p, float sp, const f32x4 q, float off, float thr) {
-    const float left = fmaxf(p.x, q.x), right = fminf(p.z, q.z);
-    const float top = fmaxf(p.y, q.y), bottom = fminf(p.w, q.w);
-    const float w = fmaxf(right - left + off, 0.0f), h = fmaxf(bottom - top + off, 0.0f);
-    const float inter = w * h;
-    if (thr >= 0.0f && !(inter > 0.0f)) return false;
-    return inter / (sp + nms_area(q, off) - inter) > thr;
-}
 
 __device__ __forceinline__ const float* box_of(const McArgs& a, int b, int r, int c) {
     return a.boxes + ((int64_t)b * a.R + r) * a.ldb + (a.per_class ? 4 * c : 0);
@@ -118,9 +106,9 @@ __global__ void __launch_bounds__(kThreads) mc_filter_kernel(McArgs a) {
                 if (s > a.score_thr) {
                     v = true;
                     if (a.factors) s = s * a.factors[(int64_t)b * a.R + r];
-                    key[k] = ((u64)fkey(s) << 24) | (u64)(kIndexMask - (u32)f);
+                    key[k] = sort_key(fkey(s), f);
                     const float* p = box_of(a, b, r, c);
-                    mk = max(mk, fkey(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3]))));
+                    mk = max(mk, box_max_key(p[0], p[1], p[2], p[3]));
                     const u32 slot = atomicAdd(a.ccnt + (int64_t)b * a.ccnt_ld + c, 1u);
                     if ((int)slot < a.R) a.seg[((int64_t)b * a.C + c) * a.R + slot] = key[k];
                 }
@@ -153,25 +141,14 @@ __global__ void __launch_bounds__(kThreads) mc_filter_kernel(McArgs a) {
 }
 
 __global__ void __launch_bounds__(kThreads) mc_flat_rank_kernel(McArgs a) {
-    __shared__ u64 s_tile[1024];
+    __shared__ u64 s_tile[kRankTile];
     const int tid = threadIdx.x, b = blockIdx.y;
     const int M = (int)a.hdr[b * kHdrWords + kHdrM];
     if (!all_pairs(M, a.split) || blockIdx.x * kThreads >= M) return;
     const u64* keys = a.list + (int64_t)b * a.n;
     const int i = blockIdx.x * kThreads + tid;
     const u64 my = i < M ? keys[i] : 0ull;
-    int rank = 0;
-    for (int j0 = 0; j0 < M; j0 += 1024) {
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 1024 / kThreads; ++q) {
-            const int j = j0 + q * kThreads + tid;
-            s_tile[q * kThreads + tid] = j < M ? keys[j] : 0ull;               // 0 is greater than no key
-        }
-        __syncthreads();
-        const int cn = min(1024, (M - j0 + 3) & ~3);
-        for (int j = 0; j < cn; j += 4) rank += (s_tile[j] > my) + (s_tile[j + 1] > my) + (s_tile[j + 2] > my) + (s_tile[j + 3] > my);
-    }
+    const int rank = count_greater_tiled<kThreads>(keys, M, my, s_tile);
     if (i < M) a.ranked[(int64_t)b * kFlatCap + rank] = my;
 }
 
@@ -195,7 +172,7 @@ __device__ __forceinline__ void walk(const McArgs& a, int b, const u64* rk, int 
         const int j = k * T + tid;
         box[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         if (j < m) {
-            const int f = (int)(kIndexMask - ((u32)rk[j] & kIndexMask));
+            const int f = key_index(rk[j]);
             const int r = f / a.C, c = f - r * a.C;
             const float* p = box_of(a, b, r, c);
             // batched_nms: offsets = idxs.to(boxes) * (boxes.max() + 1); boxes_for_nms = boxes + offsets[:, None]
@@ -229,18 +206,7 @@ __device__ __forceinline__ void walk(const McArgs& a, int b, const u64* rk, int 
                 const bool hit = nms_suppresses(me, sa, q, nms_area(q, off), off, thr) && c > tid;
                 word |= hit ? (1ull << c) : 0ull;
             }
-            u64 rem = ~__ballot(mykey != 0ull);
-            const u32 dlo = (u32)word, dhi = (u32)(word >> 32);
-            u64 kept = 0ull;
-#pragma unroll
-            for (int i = 0; i < 64; ++i) {
-                const u64 di = (u64)(u32)__builtin_amdgcn_readlane((int)dlo, i) | ((u64)(u32)__builtin_amdgcn_readlane((int)dhi, i) << 32);
-                const bool k = !((rem >> i) & 1ull);
-                kept |= k ? (1ull << i) : 0ull;
-                rem |= k ? di : 0ull;
-            }
-            const int room = a.cap - total;
-            while (__popcll(kept) > room) kept &= ~(1ull << (63 - __clzll((long long)kept)));
+            const u64 kept = resolve_block64(word, ~__ballot(mykey != 0ull), a.cap - total);
             const int nk = __popcll(kept);
             u32 base = (u32)total;
             if (!FLAT && nk > 0) {
@@ -265,7 +231,7 @@ __device__ __forceinline__ void walk(const McArgs& a, int b, const u64* rk, int 
                 const float sq = nms_area(q, off);
 #pragma unroll
                 for (int k = 0; k < P; ++k) {
-                    if (k * T + tid >= j0 + 64 && ((alive >> k) & 1u) && suppresses_quick(q, sq, box[k], off, thr))
+                    if (k * T + tid >= j0 + 64 && ((alive >> k) & 1u) && nms_suppresses_quick(q, sq, box[k], off, thr))
                         alive &= ~(1u << k);
                 }
             }
@@ -299,13 +265,7 @@ __global__ void __launch_bounds__(kClassThreads) mc_class_walk_kernel(McArgs a) 
     }
     __syncthreads();
     int rank[kClassPer];
-#pragma unroll
-    for (int k = 0; k < kClassPer; ++k) rank[k] = 0;
-    for (int j = 0; j < m; ++j) {
-        const u64 o = s_in[j];
-#pragma unroll
-        for (int k = 0; k < kClassPer; ++k) rank[k] += o > my[k];
-    }
+    count_greater_lds(s_in, m, my, rank);
 #pragma unroll
     for (int k = 0; k < kClassPer; ++k)
         if (k * kClassThreads + tid < m) s_rk[rank[k]] = my[k];
@@ -313,61 +273,31 @@ __global__ void __launch_bounds__(kClassThreads) mc_class_walk_kernel(McArgs a) 
     walk<kClassThreads, kClassPer, false>(a, b, s_rk, m);
 }
 
-// Pass p = 0 .. 4 histograms digit p of the kept keys; pass 5 gathers.  rpn_select_kernel's scheme with one segment per image
-// and k = cap; with at most cap kept keys everything is taken and the histogram passes return at once.
+// select_pass_core's policy for image b: the cap largest of the K kept keys, the keys themselves as numbers; with at most cap
+// kept keys everything is taken and the histogram passes return at once.
+struct McSelect {
+    struct Item { u64 number; };
+    const McArgs& a; int seg, n, k; bool all;
+    u32* hist; SelState* state; u32* hdr; const u64* keys;
+    __device__ __forceinline__ McSelect(const McArgs& a_, int b, u32* hdr_, int K)
+        : a(a_), seg(b), n(K), k(a_.cap), all(K <= a_.cap), hist(a_.hist), state(a_.state), hdr(hdr_), keys(a_.list + (int64_t)b * a_.n) {}
+    __device__ __forceinline__ Item load(int i) const { return Item{keys[i]}; }
+    __device__ __forceinline__ void take(int, const Item& it) const {
+        const u32 slot = atomicAdd(hdr + kHdrSlot, 1u);
+        if ((int)slot < k) a.sel[(int64_t)seg * k + slot] = it.number;
+    }
+    __device__ __forceinline__ void finish() const {}
+};
+
 __global__ void __launch_bounds__(kSelThreads) mc_select_kernel(McArgs a, int p) {
-    __shared__ u32 s_h[kBins];
-    __shared__ u32 s_scan[kSelThreads / 64 + 1];
-    __shared__ u32 s_bin, s_rem;
-    const int tid = threadIdx.x, b = blockIdx.y;
+    const int b = blockIdx.y;
     u32* hdr = a.hdr + b * kHdrWords;
     const int M = (int)hdr[kHdrM];
     if (M == 0 || all_pairs(M, a.split)) return;
     const int K = min((int)hdr[kHdrKept], a.n);
-    const bool gather = p == kPasses, all = K <= a.cap;
-    if (K == 0 || (all && !gather)) return;
-    SelState st;
-    st.prefix = 0ull; st.rem = (u32)a.cap; st.pad = 0u;
-    if (!all && p >= 1) {
-        if (p >= 2) st = a.state[b * kPasses + p - 2];
-        const u32x4 h = reinterpret_cast<const u32x4*>(a.hist + ((int64_t)b * kPasses + p - 1) * kBins)[tid];
-        const u32 hv[4] = {h.x, h.y, h.z, h.w};
-        if (tid == 0) { s_bin = 0u; s_rem = 1u; }
-        u32 cum = block_scan_excl(h.x + h.y + h.z + h.w, s_scan);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (cum < st.rem && st.rem <= cum + hv[j]) { s_bin = 4u * tid + j; s_rem = st.rem - cum; }
-            cum += hv[j];
-        }
-        __syncthreads();
-        const int bits = digit_bits(p - 1);
-        st.prefix = (st.prefix << bits) | (u64)(((1u << bits) - 1u) - s_bin);      // bins run from the largest digit down
-        st.rem = s_rem;
-        if (blockIdx.x == 0 && tid == 0) a.state[b * kPasses + p - 1] = st;
-    }
-    if (!gather) {
-        for (int i = tid; i < kBins; i += kSelThreads) s_h[i] = 0u;
-        __syncthreads();
-    }
-    const int shift = gather ? 0 : digit_shift(p);
-    const u32 dmask = gather ? 0u : (1u << digit_bits(p)) - 1u;
-    const int pshift = p >= 1 ? digit_shift(p - 1) : 0;
-    const u64* keys = a.list + (int64_t)b * a.n;
-    for (int i = blockIdx.x * kSelThreads + tid; i < K; i += kSelBlocks * kSelThreads) {
-        const u64 cmp = keys[i];
-        if (!gather) {
-            if (p == 0 || (cmp >> pshift) == st.prefix) atomicAdd(&s_h[dmask - ((u32)(cmp >> shift) & dmask)], 1u);
-        } else if (all || cmp >= st.prefix) {
-            const u32 slot = atomicAdd(hdr + kHdrSlot, 1u);
-            if ((int)slot < a.cap) a.sel[(int64_t)b * a.cap + slot] = cmp;
-        }
-    }
-    if (!gather) {
-        __syncthreads();
-        u32* hist = a.hist + ((int64_t)b * kPasses + p) * kBins;
-        for (int i = tid; i < kBins; i += kSelThreads)
-            if (s_h[i] != 0u) atomicAdd(hist + i, s_h[i]);
-    }
+    McSelect s(a, b, hdr, K);
+    if (K == 0 || (s.all && p != kPasses)) return;
+    select_pass_core(s, p);
 }
 
 __global__ void __launch_bounds__(kFinishThreads) mc_finish_kernel(McArgs a) {
@@ -381,13 +311,13 @@ __global__ void __launch_bounds__(kFinishThreads) mc_finish_kernel(McArgs a) {
     for (int i = tid; i < n; i += kFinishThreads) s_key[i] = sel[i];
     __syncthreads();
     for (int i = tid; i < n; i += kFinishThreads) {
-        const u64 my = s_key[i];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) rank += s_key[j] > my;
-        const int f = (int)(kIndexMask - ((u32)my & kIndexMask));
+        const u64 my[1] = {s_key[i]};
+        int rank[1];
+        count_greater_lds(s_key, n, my, rank);
+        const int f = key_index(my[0]);
         const int r = f / a.C, c = f - r * a.C;
         const float* p = box_of(a, b, r, c);
-        const int64_t o = (int64_t)b * a.cap + rank;
+        const int64_t o = (int64_t)b * a.cap + rank[0];
         float* d = a.dets + o * 5;
         d[0] = p[0]; d[1] = p[1]; d[2] = p[2]; d[3] = p[3];
         d[4] = ranked_score(a, b, r, c);
@@ -396,8 +326,7 @@ __global__ void __launch_bounds__(kFinishThreads) mc_finish_kernel(McArgs a) {
     }
     for (int i = n + tid; i < a.cap; i += kFinishThreads) {
         const int64_t o = (int64_t)b * a.cap + i;
-        float* d = a.dets + o * 5;
-        d[0] = 0.0f; d[1] = 0.0f; d[2] = 0.0f; d[3] = 0.0f; d[4] = 0.0f;
+        zero_det_row(a.dets + o * 5);
         a.labels[o] = -1;
         a.inds[o] = -1;
     }
@@ -406,8 +335,6 @@ __global__ void __launch_bounds__(kFinishThreads) mc_finish_kernel(McArgs a) {
         if (a.ncand) a.ncand[b] = M;
     }
 }
-
-bool aligned_to(const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
 
 }  // namespace
 

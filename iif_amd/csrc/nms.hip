@@ -18,22 +18,18 @@
 //               never waits a memory round trip per kept box.  Writes keep, dets, the count and the padding; stops at max_num.
 //   iif_rpn_proposals   10 enqueued operations for any B <= 16, any number of levels <= 8 and any data:
 //     clear     header, histograms.
-//     select    x 5: the nms_pre largest (logit, lower flattened index first) of every (image, level) at once, as a radix select
-//               on the 56-bit number key << 24 | ~index in digits of 12, 12, 12, 12 and 8 bits: each pass histograms its digit
-//               among the elements that match the digits found so far (LDS atomics, flushed with integer global atomics); the
-//               next pass scans the histogram for the threshold digit.  The numbers are distinct, so five digits give the exact
-//               threshold: no boundary pass, no ordered sweep.  Scores and deltas are read in place through element strides.
-//     gather    takes the elements at or above the threshold, decodes them with the coder's shared device function
+//     select    x 5: the nms_pre largest (logit, lower flattened index first) of every (image, level) at once: the radix select
+//               of nms_common.h (select_pass_core) on the number logit bits << 24 | ~index.  No boundary pass, no ordered
+//               sweep.  Scores and deltas are read in place through element strides.
+//     gather    its sixth launch takes the elements at or above the threshold, decodes them with the coder's shared device function
 //               (box_coder.h), computes the sigmoid, the min-size flag and the per-image coordinate maximum over the valid ones.
 //               A candidate's slot within its level comes from an integer counter; the rank step orders them, so the
 //               result does not depend on arrival order.
 //     rank, matrix, scan   as above, for all images at once, with the level as id (id_mode 1) and the key built from the LOGIT
 //               and the index into the concatenated anchors.
 //
-// Overlap test (mmcv nms_cuda_kernel.cuh), each step one IEEE float32 operation in this order (-ffp-contract=off):
-//     left = max(a.x1, b.x1), right = min(a.x2, b.x2), ...;  w = max(right - left + offset, 0), h likewise;  inter = w * h
-//     Sa = (a.x2 - a.x1 + offset) * (a.y2 - a.y1 + offset);  suppressed: inter / (Sa + Sb - inter) > iou_threshold (NaN: no)
-// Integer atomics only.  Nothing is allocated, nothing is read back.
+// The sort key, the overlap test (mmcv nms_cuda_kernel.cuh, each step one IEEE float32 operation, -ffp-contract=off), the
+// counting rank and the 64-rank resolve of the scan are nms_common.h's.  Integer atomics only.  Nothing is allocated, nothing is read back.
 #include "nms_common.h"
 #include "box_coder.h"
 
@@ -41,8 +37,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kScanThreads = 1024;            // the scan: 256 word columns x 4 groups of 16 rows
-constexpr int kSegBlocks = 16;                // blocks per (image, level) in a selection pass
-constexpr int kRankTile = 1024;
 constexpr int kMaxLevels = 8, kMaxImages = 16;
 constexpr int kHeaderBytes = 4096;            // u32 words: [0, 16) coordinate maxima, [16, 144) level counters, [144, 160) valid counts
 constexpr int kHdrCount = 16, kHdrValid = 144;
@@ -101,11 +95,11 @@ __global__ void __launch_bounds__(kThreads) nms_prepare_kernel(PrepArgs a) {
     if (i < a.N) {
         const float s = a.scores[i];
         const bool valid = !(a.score_thr > 0.0f) || s > a.score_thr;       // NMSop.forward: filters only for a threshold > 0
-        a.sk[i] = ((u64)(valid ? 1u : 0u) << 56) | ((u64)fkey(s) << 24) | (u64)(kIndexMask - (u32)i);
+        a.sk[i] = sort_key(fkey(s), i, valid);
         if (a.ids) a.wid[i] = (int)a.ids[i];
         if (a.want_max) {
             const float* p = a.boxes + (int64_t)i * a.ldb;
-            mk = fkey(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])));
+            mk = box_max_key(p[0], p[1], p[2], p[3]);
         }
     }
     if (a.want_max) {
@@ -124,21 +118,8 @@ __global__ void __launch_bounds__(kThreads) nms_rank_kernel(NmsArgs a) {
     const bool live = i < a.N;
     const u64 my = live ? sk[i] : 0ull;
     if (tid == 0) s_nv = 0;
-    int rank = 0;
-    for (int j0 = 0; j0 < a.N; j0 += kRankTile) {
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < kRankTile / kThreads; ++q) {
-            const int j = j0 + q * kThreads + tid;
-            s_tile[q * kThreads + tid] = j < a.N ? sk[j] : 0ull;           // 0 is greater than no key
-        }
-        __syncthreads();
-        const int cn = min(kRankTile, (a.N - j0 + 3) & ~3);
-        for (int j = 0; j < cn; j += 4) {
-            rank += (s_tile[j] > my) + (s_tile[j + 1] > my) + (s_tile[j + 2] > my) + (s_tile[j + 3] > my);
-        }
-    }
-    const bool valid = live && ((my >> 56) & 1ull);
+    const int rank = count_greater_tiled<kThreads>(sk, a.N, my, s_tile);
+    const bool valid = live && key_valid(my);
     const u64 vm = __ballot(valid);
     if ((tid & 63) == 0 && vm) atomicAdd(&s_nv, __popcll(vm));
     __syncthreads();
@@ -182,14 +163,14 @@ __global__ void __launch_bounds__(64) nms_matrix_kernel(NmsArgs a) {
     if (j < nv) {
         const f32x4 q = a.w.sbox[row0 + j];
         s_box[lane] = q;
-        s_area[lane] = (q.z - q.x + off) * (q.w - q.y + off);
+        s_area[lane] = nms_area(q, off);
         s_id[lane] = a.w.sid[row0 + j];
     }
     __syncthreads();
     const int i = rb * 64 + lane;
     if (i >= nv) return;
     const f32x4 p = a.w.sbox[row0 + i];
-    const float sa = (p.z - p.x + off) * (p.w - p.y + off);
+    const float sa = nms_area(p, off);
     const int id = a.w.sid[row0 + i];
     const bool same_id_only = a.id_mode == 2;
     const int cn = min(64, nv - cb * 64);
@@ -242,19 +223,7 @@ __global__ void __launch_bounds__(kScanThreads) nms_scan_kernel(NmsArgs a) {
         __syncthreads();                                    // s_removed[r] is final
         if (tid < 64) {
             const int rows = min(64, nv - r * 64);
-            u64 rem = s_removed[r] | (rows == 64 ? 0ull : ~0ull << rows);
-            const u32 dlo = (u32)dcur, dhi = (u32)(dcur >> 32);
-            u64 kept = 0ull;
-#pragma unroll
-            for (int i = 0; i < 64; ++i) {
-                const u64 di = (u64)(u32)__builtin_amdgcn_readlane((int)dlo, i) |
-                               ((u64)(u32)__builtin_amdgcn_readlane((int)dhi, i) << 32);
-                const bool k = !((rem >> i) & 1ull);
-                kept |= k ? (1ull << i) : 0ull;
-                rem |= k ? di : 0ull;
-            }
-            const int64_t room = cap - total;
-            while ((int64_t)__popcll(kept) > room) kept &= ~(1ull << (63 - __clzll((long long)kept)));
+            const u64 kept = resolve_block64(dcur, s_removed[r] | (rows == 64 ? 0ull : ~0ull << rows), (int)(cap - total));
             if ((kept >> tid) & 1ull) {
                 const int64_t pos = total + __popcll(kept & ((1ull << tid) - 1ull));
                 const int o = a.w.sorig[row0 + r * 64 + tid];
@@ -285,10 +254,7 @@ __global__ void __launch_bounds__(kScanThreads) nms_scan_kernel(NmsArgs a) {
     }
     for (int64_t pos = total + tid; pos < cap; pos += kScanThreads) {
         if (a.keep) a.keep[(int64_t)b * cap + pos] = -1;
-        if (a.dets) {
-            float* d = a.dets + ((int64_t)b * cap + pos) * 5;
-            d[0] = 0.0f; d[1] = 0.0f; d[2] = 0.0f; d[3] = 0.0f; d[4] = 0.0f;
-        }
+        if (a.dets) zero_det_row(a.dets + ((int64_t)b * cap + pos) * 5);
     }
     if (tid == 0) a.count[b] = total;
 }
@@ -313,89 +279,56 @@ struct RpnArgs {
     Ws w;
 };
 
-// Pass p = 0 .. 4 histograms digit p; pass 5 gathers and decodes.  Every pass p >= 1 first turns the histogram of pass p - 1 into
-// the threshold digit (every block for itself; block 0 of the segment leaves the state for the next launch).
-__global__ void __launch_bounds__(kSelThreads) rpn_select_kernel(RpnArgs a, int p) {
-    __shared__ u32 s_h[kBins];
-    __shared__ u32 s_scan[kSelThreads / 64 + 1];
-    __shared__ u32 s_bin, s_rem;
-    const int tid = threadIdx.x;
-    const int seg = blockIdx.y, b = seg / a.L, l = seg - b * a.L;
-    const iif_rpn_level& lv = a.lv[l];
-    const int n = a.n[l], k = a.k[l];
-    SelState st;
-    st.prefix = 0ull; st.rem = (u32)k; st.pad = 0u;
-    if (p >= 1) {
-        if (p >= 2) st = a.w.state[seg * kPasses + p - 2];
-        const u32x4 h = reinterpret_cast<const u32x4*>(a.w.hist + ((int64_t)seg * kPasses + p - 1) * kBins)[tid];
-        const u32 hv[4] = {h.x, h.y, h.z, h.w};
-        if (tid == 0) { s_bin = 0u; s_rem = 1u; }
-        u32 cum = block_scan_excl(h.x + h.y + h.z + h.w, s_scan);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (cum < st.rem && st.rem <= cum + hv[j]) { s_bin = 4u * tid + j; s_rem = st.rem - cum; }
-            cum += hv[j];
-        }
-        __syncthreads();
-        const int bits = digit_bits(p - 1);
-        st.prefix = (st.prefix << bits) | (u64)(((1u << bits) - 1u) - s_bin);      // bins run from the largest digit down
-        st.rem = s_rem;
-        if (blockIdx.x == 0 && tid == 0) a.w.state[seg * kPasses + p - 1] = st;
+// select_pass_core's policy for segment (image b, level l): the number is logit bits << 24 | ~flattened index, read in place
+// through the element strides; taking an element decodes it into the next slot of its level.
+struct RpnSelect {
+    struct Item { u64 number; float logit; int an, x, y; };
+    static constexpr bool all = false;
+    const RpnArgs& a; const iif_rpn_level& lv;
+    int seg, b, l, n, k;
+    u32* hist; SelState* state;
+    u32 mk = 0u;                                            // the coordinate maximum over the valid boxes this thread took
+    __device__ __forceinline__ RpnSelect(const RpnArgs& a_, int seg_)
+        : a(a_), lv(a_.lv[seg_ % a_.L]), seg(seg_), b(seg_ / a_.L), l(seg_ % a_.L), hist(a_.w.hist), state(a_.w.state) {
+        n = a.n[l]; k = a.k[l];
     }
-    const bool gather = p == kPasses;
-    if (!gather) {
-        for (int i = tid; i < kBins; i += kSelThreads) s_h[i] = 0u;
-        __syncthreads();
+    __device__ __forceinline__ Item load(int f) const {     // f = (h * W + w) * A + anchor
+        Item it;
+        it.an = f % lv.A;
+        const int hw = f / lv.A;
+        it.x = hw % lv.W; it.y = hw / lv.W;
+        const float* sp = lv.scores + (int64_t)b * lv.score_strides[0];
+        it.logit = sp[it.an * lv.score_strides[1] + it.y * lv.score_strides[2] + it.x * lv.score_strides[3]];
+        it.number = sort_key(fkey(it.logit), f);
+        return it;
     }
-    const int shift = gather ? 0 : digit_shift(p);
-    const u32 dmask = gather ? 0u : (1u << digit_bits(p)) - 1u;
-    const int pshift = p >= 1 ? digit_shift(p - 1) : 0;
-    const float* sp = lv.scores + (int64_t)b * lv.score_strides[0];
-    const float* dp = lv.deltas + (int64_t)b * lv.delta_strides[0];
-    const int64_t row0 = (int64_t)b * a.Np;
-    u32 mk = 0u;
-    for (int base = blockIdx.x * kSelThreads; base < n; base += kSegBlocks * kSelThreads) {
-        const int f = base + tid;                           // flattened index (h * W + w) * A + anchor
-        if (f < n) {
-            const int an = f % lv.A, hw = f / lv.A;
-            const int x = hw % lv.W, y = hw / lv.W;
-            const float logit = sp[an * lv.score_strides[1] + y * lv.score_strides[2] + x * lv.score_strides[3]];
-            const u32 key = fkey(logit);
-            const u64 cmp = ((u64)key << 24) | (u64)(kIndexMask - (u32)f);
-            if (!gather) {
-                if (p == 0 || (cmp >> pshift) == st.prefix) atomicAdd(&s_h[dmask - ((u32)(cmp >> shift) & dmask)], 1u);
-            } else if (cmp >= st.prefix) {
-                const u32 slot = atomicAdd(a.w.hdr + kHdrCount + seg, 1u);
-                if ((int)slot < k) {
-                    const Box anc = load_box(lv.anchors + (int64_t)f * lv.ld_anchors, a.vec_anchor[l] != 0);
-                    const float* d = dp + (int64_t)(4 * an) * lv.delta_strides[1] + y * lv.delta_strides[2] + x * lv.delta_strides[3];
-                    const Box t = {d[0], d[lv.delta_strides[1]], d[2 * lv.delta_strides[1]], d[3 * lv.delta_strides[1]]};
-                    const f32x4 o = decode_box(anc, t, a.nm, a.max_ratio, a.add_ctr_clamp, a.ctr_clamp, a.clip, a.max_h[b], a.max_w[b]);
-                    const bool valid = a.min_size < 0.0f || ((o.z - o.x) > a.min_size && (o.w - o.y) > a.min_size);
-                    const int cidx = a.anchor_off[l] + f;
-                    const int64_t at = row0 + a.cand_off[l] + slot;
-                    a.w.cbox[at] = o;
-                    a.w.cscore[at] = 1.0f / (1.0f + expf(-logit));
-                    a.w.ccidx[at] = cidx;
-                    a.w.clevel[at] = l;
-                    a.w.sk[at] = ((u64)(valid ? 1u : 0u) << 56) | ((u64)key << 24) | (u64)(kIndexMask - (u32)cidx);
-                    if (valid) mk = max(mk, fkey(fmaxf(fmaxf(o.x, o.y), fmaxf(o.z, o.w))));
-                }
-            }
-        }
+    __device__ __forceinline__ void take(int f, const Item& it) {
+        const u32 slot = atomicAdd(a.w.hdr + kHdrCount + seg, 1u);
+        if ((int)slot >= k) return;
+        const Box anc = load_box(lv.anchors + (int64_t)f * lv.ld_anchors, a.vec_anchor[l] != 0);
+        const float* d = lv.deltas + (int64_t)b * lv.delta_strides[0] + (int64_t)(4 * it.an) * lv.delta_strides[1] + it.y * lv.delta_strides[2] + it.x * lv.delta_strides[3];
+        const Box t = {d[0], d[lv.delta_strides[1]], d[2 * lv.delta_strides[1]], d[3 * lv.delta_strides[1]]};
+        const f32x4 o = decode_box(anc, t, a.nm, a.max_ratio, a.add_ctr_clamp, a.ctr_clamp, a.clip, a.max_h[b], a.max_w[b]);
+        const bool valid = a.min_size < 0.0f || ((o.z - o.x) > a.min_size && (o.w - o.y) > a.min_size);
+        const int cidx = a.anchor_off[l] + f;
+        const int64_t at = (int64_t)b * a.Np + a.cand_off[l] + slot;
+        a.w.cbox[at] = o;
+        a.w.cscore[at] = 1.0f / (1.0f + expf(-it.logit));
+        a.w.ccidx[at] = cidx;
+        a.w.clevel[at] = l;
+        a.w.sk[at] = sort_key((u32)(it.number >> 24), cidx, valid);
+        if (valid) mk = max(mk, box_max_key(o.x, o.y, o.z, o.w));
     }
-    if (gather) {
-        mk = wave_max_u(mk);
-        if ((tid & 63) == 0 && mk != 0u) atomicMax(a.w.hdr + b, mk);
-    } else {
-        __syncthreads();
-        u32* hist = a.w.hist + ((int64_t)seg * kPasses + p) * kBins;
-        for (int i = tid; i < kBins; i += kSelThreads)
-            if (s_h[i] != 0u) atomicAdd(hist + i, s_h[i]);
+    __device__ __forceinline__ void finish() const {
+        const u32 m = wave_max_u(mk);
+        if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(a.w.hdr + b, m);
     }
-}
+};
 
-bool aligned_to(const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
+__global__ void __launch_bounds__(kSelThreads) rpn_select_kernel(RpnArgs a, int p) {
+    RpnSelect s(a, blockIdx.y);
+    select_pass_core(s, p);
+}
 
 }  // namespace
 
@@ -482,7 +415,7 @@ int iif_rpn_proposals(const iif_rpn_level* levels, int num_levels, int B, const 
     hipStream_t st = as_stream(stream);
     if (hipMemsetAsync(d_workspace, 0, (size_t)(kHeaderBytes + (int64_t)B * kHistBytes), st) != hipSuccess) return IIF_ELAUNCH;
     for (int p = 0; p <= kPasses; ++p) {
-        hipLaunchKernelGGL(rpn_select_kernel, dim3(kSegBlocks, (unsigned)(B * num_levels)), dim3(kSelThreads), 0, st, r, p);
+        hipLaunchKernelGGL(rpn_select_kernel, dim3(kSelBlocks, (unsigned)(B * num_levels)), dim3(kSelThreads), 0, st, r, p);
         IIF_LAUNCH_CHECK();
     }
     return launch_nms_stage(a, st);

@@ -224,10 +224,10 @@ __global__ void __launch_bounds__(kThreads) roi_stage_kernel(StageArgs a) {
             else if (key[k] == K[cl]) kind = 2;
         }
         u64 tot;
-        const u64 rank = block_scan_excl(kind == 2 ? one_of(cl) : 0ull, s_scan, tot) + run_eq;
+        const u64 rank = block_scan_excl(kind == 2 ? one_of(cl) : 0ull, s_scan, &tot) + run_eq;
         run_eq += tot;
         if (kind == 2) kind = half_of(rank, cl) < r3[cl] ? 1 : 0;
-        const u64 at = block_scan_excl(kind == 1 ? one_of(cl) : 0ull, s_scan, tot) + run_sel;
+        const u64 at = block_scan_excl(kind == 1 ? one_of(cl) : 0ull, s_scan, &tot) + run_sel;
         run_sel += tot;
         if (kind != 1) continue;
         const int slot = (int)half_of(at, cl);
@@ -318,7 +318,7 @@ __global__ void __launch_bounds__(kThreads) refine_bboxes_kernel(RefineArgs a) {
             o = decode_box(p, t, a.nm, a.max_ratio, a.add_ctr_clamp, a.ctr_clamp, a.clip, max_h, max_w);
         }
         u64 tot;
-        const u64 at = block_scan_excl(keep ? 1ull : 0ull, s_scan, tot) + run;
+        const u64 at = block_scan_excl(keep ? 1ull : 0ull, s_scan, &tot) + run;
         run += tot;
         if (keep) *reinterpret_cast<f32x4*>(a.out + 4 * (row0 + (int64_t)at)) = o;
     }
@@ -326,8 +326,6 @@ __global__ void __launch_bounds__(kThreads) refine_bboxes_kernel(RefineArgs a) {
     for (int r = (int)run + tid; r < a.num; r += kThreads) *reinterpret_cast<f32x4*>(a.out + 4 * (row0 + r)) = z;
     if (tid == 0) a.out_counts[b] = (int64_t)run;
 }
-
-bool aligned_to(const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
 
 }  // namespace
 

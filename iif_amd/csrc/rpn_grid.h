@@ -50,8 +50,6 @@ bool fill_grid(const iif_rpn_grid* in, Grid* g, Bases* bs) {
     return true;
 }
 
-bool aligned_to(const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
-
 // ------------------------------------------------------------------------------------------------ the sampled lists
 struct Lists { const int64_t* pos_inds; const int64_t* neg_inds; const int64_t* counts; const float* pos_bt; int nep, num, B; };
 

@@ -1,16 +1,13 @@
-// The random sampler (base_sampler.py:35-102 + random_sampler.py:32-82), once: the budget rule, the packed block scan, the
-// histogram of the top 12 key bits per class and the whole select step.  targets.hip (iif_random_sample) and rpn_stage.hip
-// (iif_rpn_stage_targets) run sample_select_core, each through a policy; roi_stage.hip keeps its own in-register radix select
-// and takes the budgets and the scan from here.  The rule: a class (0 positive, 1 negative) with more members than its budget k
+// The random sampler (base_sampler.py:35-102 + random_sampler.py:32-82), once: the budget rule, the histogram of the top
+// 12 key bits per class and the whole select step, on the packed block scan of block_scan.h.  targets.hip (iif_random_sample)
+// and rpn_stage.hip (iif_rpn_stage_targets) run sample_select_core, each through a policy; roi_stage.hip keeps its own
+// in-register radix select and takes the budgets from here.  The rule: a class (0 positive, 1 negative) with more members than its budget k
 // keeps the k SMALLEST (key, index) pairs - equal keys go to the lower index.
 #pragma once
-#include "common.h"
+#include "block_scan.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int kSelThreads = 1024;             // the block size block_scan_excl and the select's last block are written for
 constexpr int kBins = 4096;                   // top 12 of the 31 key bits
 constexpr int kLowBits = 19;
 constexpr unsigned kLowMask = (1u << kLowBits) - 1u;
@@ -30,36 +27,6 @@ __device__ __forceinline__ Budgets sample_budgets(long long P, long long Q, int 
         if (capd < (double)budget) budget = (long long)capd;          // int(): truncation
     }
     return Budgets{kp, Q < budget ? Q : budget};
-}
-
-// Exclusive prefix sums over the block's kSelThreads threads of two 32-bit counts packed in one word (neither half reaches
-// 2^31); `total` is the block's sum.  s_w: 17 words of LDS; reusable after the call returns.
-__device__ __forceinline__ u64 block_scan_excl(u64 v, u64* s_w, u64& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    if (wv == 0) {
-        const u64 x = lane < kSelThreads / 64 ? s_w[lane] : 0ull;
-        u64 xi = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const u64 t = __shfl_up(xi, o, 64);
-            if (lane >= o) xi += t;
-        }
-        if (lane < kSelThreads / 64) s_w[lane] = xi - x;
-        if (lane == 63) s_w[kSelThreads / 64] = xi;
-    }
-    __syncthreads();
-    const u64 res = s_w[wv] + inc - v;
-    total = s_w[kSelThreads / 64];
-    __syncthreads();
-    return res;
 }
 
 // The histogram of the top 12 key bits per class, 2 x kBins counters in LDS: clear (the caller synchronises), add, and the
@@ -139,7 +106,7 @@ __device__ __forceinline__ void sample_select_core(const P& p) {
     const u32x4 h1 = reinterpret_cast<const u32x4*>(p.hist + kBins)[tid];
     const unsigned c0 = h0.x + h0.y + h0.z + h0.w, c1 = h1.x + h1.y + h1.z + h1.w;
     u64 total;
-    const u64 ex = block_scan_excl((u64)c0 | ((u64)c1 << 32), s_scan, total);
+    const u64 ex = block_scan_excl((u64)c0 | ((u64)c1 << 32), s_scan, &total);
     const long long M[2] = {(unsigned)total, (unsigned)(total >> 32)};
     const Budgets bu = sample_budgets(M[0], M[1], p.nep, p.num, p.ub);
     const int kp = __builtin_amdgcn_readfirstlane((int)bu.kp);         // the same in every lane, and 0 <= k <= num < 2^31:
@@ -215,7 +182,7 @@ __device__ __forceinline__ void sample_select_core(const P& p) {
         __syncthreads();
         const u64 mine = (u64)s_h[tid] | ((u64)s_h[1024 + tid] << 32);
         u64 tot;
-        const u64 ex2 = block_scan_excl(mine, s_scan, tot);
+        const u64 ex2 = block_scan_excl(mine, s_scan, &tot);
         find_bin(mine, ex2, r, s_T2, s_r2);
         __syncthreads();
         const int T2[2] = {s_T2[0], s_T2[1]};
@@ -235,7 +202,7 @@ __device__ __forceinline__ void sample_select_core(const P& p) {
         }
         __syncthreads();
         const u64 mine3 = tid < 512 ? ((u64)s_h[tid] | ((u64)s_h[512 + tid] << 32)) : 0ull;
-        const u64 ex3 = block_scan_excl(mine3, s_scan, tot);
+        const u64 ex3 = block_scan_excl(mine3, s_scan, &tot);
         find_bin(mine3, ex3, r2, s_T3, s_r3);
         __syncthreads();
     }
@@ -268,7 +235,7 @@ __device__ __forceinline__ void sample_select_core(const P& p) {
             }
         }
         u64 tot;
-        u64 rank = block_scan_excl(eq, s_scan, tot) + run_eq;
+        u64 rank = block_scan_excl(eq, s_scan, &tot) + run_eq;
         run_eq += tot;
         u64 sel = 0ull;
 #pragma unroll
@@ -279,7 +246,7 @@ __device__ __forceinline__ void sample_select_core(const P& p) {
             }
             if (kind4[j] == 1) sel += one_of(cls4[j]);
         }
-        u64 at = block_scan_excl(sel, s_scan, tot) + run_sel;
+        u64 at = block_scan_excl(sel, s_scan, &tot) + run_sel;
         run_sel += tot;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {

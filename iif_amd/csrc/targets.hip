@@ -190,7 +190,6 @@ __global__ void __launch_bounds__(kThreads) roi_targets_kernel(RoiArgs a) {
     a.pos_gt[r] = pg;
 }
 
-bool aligned_to(const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
 bool rows_are_16_bytes(const void* p, int64_t ld) { return aligned_to(p, 16) && ld % 4 == 0; }
 
 bool set_norm(Norm* nm, const float* means, const float* stds) {

@@ -41,7 +41,7 @@ def _t(dev, *arrays):
 
 
 def _call(mm, dev, name, **kw):
-    c = mc.CASES[name]
+    c = mc.case(name)
     boxes, scores, factors = _t(dev, *mc.inputs(name))
     rc = torch.tensor([c["rows"]], dtype=torch.int64, device=dev) if c["rows"] is not None else None
     return mm.multiclass_nms_padded(boxes, scores, c["score_thr"], mc.nms_cfg(name), c["max_num"], score_factors=factors,
@@ -69,6 +69,16 @@ def test_padded_result_is_exact(dev, g, mm, name):
     dets, labels, inds, counts, ncand = _call(mm, dev, name)
     assert counts.shape == (1,) and ncand.shape == (1,)
     _check(g, name, dets, labels, inds, counts[0].item(), ncand[0].item())
+
+
+def test_select_takes_two_full_stride_steps(dev, mm):
+    """32 768 kept keys in the per-class regime, cut to 100 among equal scores: the padded result against the restatement."""
+    name = "long_kept"
+    dets, labels, inds, M = mc.run(name)
+    want = {name + "_inds": inds, name + "_labels": labels, name + "_M": M, name + "_count": inds.size}
+    assert M == 32768 >= mc.split_thr(name) and inds.size == mc.cap(name) == 100
+    got = _call(mm, dev, name)
+    _check(want, name, got[0], got[1], got[2], got[3][0].item(), got[4][0].item())
 
 
 @pytest.mark.parametrize("name", ["n130_c3", "n130_c80_split", "none", "none_split", "factors"])

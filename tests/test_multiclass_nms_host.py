@@ -64,6 +64,19 @@ def test_fixture_cases_say_what_they_should(g):
         assert int(g[name + "_count"]) == mc.cap(name)
 
 
+def test_long_kept_case_says_what_it_should():
+    """Without the cut every one of the 64 * 512 candidates is kept (the per-class regime), and the cut at 100 falls between two
+    equal scores, so the flat index decides it."""
+    name = "long_kept"
+    c = mc.LONG_CASES[name]
+    dets, labels, inds, M = mc.run(name, max_num=-1)
+    assert M == 32768 >= mc.split_thr(name) and inds.size == 32768 == 2 * 16 * 1024
+    assert c["max_num"] == mc.cap(name) == 100 and dets[99, 4] == dets[100, 4]
+    assert inds[99] < inds[100]
+    cut = mc.run(name)
+    assert np.array_equal(cut[2], inds[:100]) and np.array_equal(mc.bits(cut[0]), mc.bits(dets[:100]))
+
+
 def test_workspace_formula_matches_the_header():
     text = open(os.path.join(ROOT, "include", "iif_amd.h")).read()
     m = re.search(r"#define IIF_MULTICLASS_NMS_WORKSPACE_BYTES\(B, R, C, cap\) (.+)", text)

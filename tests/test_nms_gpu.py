@@ -109,7 +109,7 @@ def _run(mn, dev, name, workspace=None):
     """(inputs, dets [B, max_per_img, 5], counts [B], candidates as numpy): computed once per case and shared."""
     if name in _runs and workspace is None:
         return _runs[name]
-    c = nc.RPN_CASES[name]
+    c = nc.rpn_case(name)
     cls, reg, anchors = nc.rpn_inputs(name)
     tcls = [torch.from_numpy(x).to(dev) for x in cls]
     treg = [torch.from_numpy(x).to(dev) for x in reg]
@@ -154,11 +154,9 @@ def test_rpn_candidates(dev, g, mn, name):
         assert serr <= 2 * sig
 
 
-@pytest.mark.parametrize("name", list(nc.RPN_CASES))
-def test_rpn_result_follows_from_the_returned_candidates(dev, mn, name):
-    """Exact, no margin: the restatement of the NMS stage on the device's own ranked candidates."""
+def _check_result_follows(mn, dev, name):
     _, dets, counts, cand = _run(mn, dev, name)
-    c = nc.RPN_CASES[name]
+    c = nc.rpn_case(name)
     for b in range(len(c["shapes"])):
         v = cand.valid[b]
         nv = int(v.sum())
@@ -169,6 +167,26 @@ def test_rpn_result_follows_from_the_returned_candidates(dev, mn, name):
         assert np.array_equal(nc.bits(dets[b, :keep.size]), nc.bits(want))
         assert not nc.bits(dets[b, keep.size:]).any()
         assert dets.shape[1] == c["max_per_img"]
+
+
+@pytest.mark.parametrize("name", list(nc.RPN_CASES))
+def test_rpn_result_follows_from_the_returned_candidates(dev, mn, name):
+    """Exact, no margin: the restatement of the NMS stage on the device's own ranked candidates."""
+    _check_result_follows(mn, dev, name)
+
+
+@pytest.mark.parametrize("name", list(nc.RPN_LONG_CASES))
+def test_rpn_select_takes_a_second_stride_step(dev, mn, name):
+    """A level of 17 280 anchors beside one of 288: identities and levels equal the restatement's (every candidate is valid, so
+    the rank is by logit and index alone and no exp enters), and the result follows from the candidates, exactly."""
+    (cls, reg, anchors), dets, counts, cand = _run(mn, dev, name)
+    for b in range(len(nc.rpn_case(name)["shapes"])):
+        idx, lvl, logits, _, _ = nc.rpn_candidates_np(name, b, cls, reg, anchors)
+        order = nc.rpn_rank_np(idx, logits, np.ones(idx.size, dtype=bool))
+        assert idx.size == 512 and cand.valid[b].all()
+        assert np.array_equal(cand.index[b], idx[order])
+        assert np.array_equal(cand.level[b], lvl[order])
+    _check_result_follows(mn, dev, name)
 
 
 @pytest.mark.parametrize("name", [k for k in nc.RPN_CASES if k not in nc.RPN_TIE_CASES])

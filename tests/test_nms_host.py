@@ -59,6 +59,20 @@ def test_restatement_reproduces_rpn_case(g, name):
             assert nc.sigmoid_ulps(r["scores"][k], r["logits"][k]) <= 2 * float(g["ref_sigmoid_ulps"])
 
 
+def test_long_rpn_cases_say_what_they_should():
+    """The first level is longer than one grid-stride step of the select, both levels are cut, and the tie variant's cut at
+    nms_pre splits a run of equal logits (the distinct variant's does not)."""
+    for name, c in nc.RPN_LONG_CASES.items():
+        cls, reg, _ = nc.rpn_inputs(name)
+        assert c["min_size"] < 0 and c["nms_pre"] == 256
+        for b in range(len(c["shapes"])):
+            (x0, _), (x1, _) = nc.rpn_flat(cls, reg, b)
+            assert x0.size == 17280 > 16 * 1024 and x0.size - 16 * 1024 == 896 and x1.size == 288
+            top = np.sort(x0)[::-1]
+            assert (top[c["nms_pre"] - 1] == top[c["nms_pre"]]) == c["tie"]
+            assert np.unique(x1).size == x1.size
+
+
 def test_chain_and_zero_area_cases_say_what_they_should(g):
     assert g["p_chain_keep"].tolist() == [0, 2]                       # c survives: only the suppressed b overlaps it
     assert {3, 5} <= set(g["p_zero_area_keep"].tolist())              # 0 / 0 does not suppress
